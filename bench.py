@@ -63,7 +63,27 @@ def parse():
                    help="N>1, strong scaling: rank 0 takes this fraction of an equal share and the other ranks split the rest "
                         "(rank 0 also decodes the gathered column: profiles/r5_root_rehearsal.txt).  A DEVIATION from the reference's "
                         "partition (split_offsets, strsim.rs:21-39), off by default (1.0) and named in the JSON line when used")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the last timed step computed as DIR/<measure>.npy (f64), with the frame rows "
+                        "they hold as DIR/row_index.npy: every row when it fits in 64 MB, else a fixed, seeded sample of rows")
+    a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
+    return a
+
+
+DUMP_BYTES = 64_000_000  # --dump-outputs: everything written, .npy headers included
+DUMP_SEED = 20240607
+
+
+def dump_rows(total_rows, ncols):
+    """The frame rows --dump-outputs writes: all of them when `ncols` f64 columns plus the row index fit in DUMP_BYTES, else a sorted,
+    seeded sample that does (the same rows in every run with the same arguments)."""
+    import numpy as np
+    k = (DUMP_BYTES - 1024 * (ncols + 1)) // (8 * (ncols + 1))
+    if total_rows <= k:
+        return np.arange(total_rows, dtype=np.int64)
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, total_rows, size=k, dtype=np.int64))
 
 
 def cpu_baseline(measure, cfg, rows_total):
@@ -435,8 +455,41 @@ def main():
         got = sh.result()
         return all(int(got[o:o + ln].view(torch.int64).sum().item()) == int(sums[r].item()) for r, (o, ln) in enumerate(shards))
 
+    def dump_outputs(nsteps):
+        """--dump-outputs, outside any timed region and before anything else reuses the output buffers: the last timed step's column of
+        every measure at the rows of dump_rows(), assembled on rank 0 from every rank's shard (each row from the rank that owns it).
+        Collective; the files are written by rank 0."""
+        import numpy as np
+        idx = dump_rows(total_rows, len(measures))
+        starts = np.array([o for o, _ln in shards], dtype=np.int64)
+        owner = np.searchsorted(starts, idx, side="right") - 1
+        mine = np.nonzero(owner == rank)[0]
+        pos = torch.from_numpy(mine).to(dev)
+        local = torch.from_numpy(idx[mine] - row_base).to(dev)
+        cdev = dev if a.backend == "nccl" else "cpu"
+        cols = []
+        for o in out[((nsteps - 1) & 1) * len(measures):((nsteps - 1) & 1) * len(measures) + len(measures)]:
+            col = torch.zeros(len(idx), dtype=torch.float64, device=dev)
+            col[pos] = o.index_select(0, local)
+            if world > 1:
+                col = col.to(cdev)
+                cols_r = [torch.zeros_like(col) for _ in range(world)]
+                dist.all_gather(cols_r, col)
+                col = torch.stack(cols_r).to(dev)[torch.from_numpy(owner).to(dev), torch.arange(len(idx), device=dev)]
+            cols.append(col.cpu().numpy())
+        if rank != 0:
+            return None
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        files = {m: c for m, c in zip(measures, cols)}
+        files["row_index"] = idx.astype(np.float64)
+        for name, arr in files.items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
+        return {"dir": a.dump_outputs, "files": sorted(n + ".npy" for n in files), "rows": int(len(idx)),
+                "sampled": bool(len(idx) < total_rows), "dtype": "float64"}
+
     dt = max_over_ranks(dt)
     gather_ok = verify_gather(shipper, a.steps) if (world > 1 and gather) else None
+    dumped = dump_outputs(a.steps) if a.dump_outputs else None
     call_mode_timed = "stream_ordered (ABI default)" if ctx.stream_ordered else "one_launch (opt-in, strsim_ctx_set_stream_ordered(ctx, 0))"
     gather_impl = None if not gather else ("abi: strsim_gather_f64_ranges (grouped RCCL send/recv into the root's column)" if shipper.impl == "abi"
                                            else "torch.distributed.gather (shards padded to the longest)")
@@ -526,16 +579,17 @@ def main():
             dom_name = ("whole pass: k_lane_stage<%s> + " + ("k_wave_pairs" if (a.config == "cfg5" or hi > 128) else "k_lane_wide (+ k_lane_utf8, k_wave_pairs)")) % measures[0]
         achieved = read_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
         res = {
-            "metric": "M string-pairs/s, %s, %d M rows%s (+ achieved HBM GB/s in roofline)%s" %
-                      (measure, (total_rows if a.scaling == "strong" else rows) // 1_000_000, " per GPU" if a.scaling == "weak" else "",
-                       "; %d untimed preheat steps before the %d warm-up steps (--preheat-ms %g)" % (preheat_steps, a.warmup, a.preheat_ms) if preheat_steps else ""),
+            # the metric names what is measured (measure, frame) and nothing that varies with the run: the preheat step count is sized
+            # by a timed step, so it is reported in config (preheat_steps, preheat_ms), like the step counts in steps / warmup
+            "metric": "M string-pairs/s, %s, %d M rows%s (+ achieved HBM GB/s in roofline)" %
+                      (measure, (total_rows if a.scaling == "strong" else rows) // 1_000_000, " per GPU" if a.scaling == "weak" else ""),
             "passes_per_step": len(measures),
             "value": value, "unit": "M string-pairs/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": a.scaling, "vs_baseline": None,
             "dtype": "u8/u32 bit-parallel, f64 epilogue", "data": "synthetic",
             "config": {"workload": f"{a.config}: {measure}, {total_rows} rows ({a.scaling} scaling: {rows} on rank 0), lengths "
                                    f"{'U' if law == W.UNIFORM else 'Zipf'}{{{lo}..{hi}}} bytes, a-z, seed {seed}",
-                       "rows_total": total_rows, "rows_rank0": rows, "preheat_steps": preheat_steps,
+                       "rows_total": total_rows, "rows_rank0": rows, "preheat_steps": preheat_steps, "preheat_ms": a.preheat_ms,
                        # how the calls were enqueued: one-launch calls (strsim_ctx_set_stream_ordered(ctx, 0), the ABI's opt-in mode:
                        # a call is its first kernel alone unless the context's last call left slow rows) when nothing is gathered,
                        # the default stream-ordered mode (every kernel of the chain up front) under the gather
@@ -564,6 +618,8 @@ def main():
             "the headline ran in the default mode" if ctx.stream_ordered or gather else None)
         res["cold_first_call_ms"] = None if cold_first_call_ms is None else round(cold_first_call_ms, 3)
         res["idle_gpu_call_ms"] = None if idle_gpu_call_ms is None else round(idle_gpu_call_ms, 3)
+        if dumped is not None:
+            res["dumped_outputs"] = dumped
         if a.config == "cfg5" or hi > 128:
             cells = 0.0
             for _r0, _r1, oa, _va, ob, _vb in parts:

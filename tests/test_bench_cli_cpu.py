@@ -29,3 +29,8 @@ def test_ranks_are_started_as_children_and_their_exit_code_is_relayed():
     r = _bench("--gpus", "2", "--same-device", "--backend", "gloo", "--rows", "1000", "--steps", "1", "--warmup", "0", "--no-cpu-baseline")
     assert "starting 2 ranks" in r.stderr and "torch.distributed.run" in r.stderr
     assert r.returncode != 0 and "bench.py needs a GPU" in r.stderr  # what each rank said; the launcher's code came back
+
+
+def test_fewer_than_one_timed_step_is_refused():
+    r = _bench("--steps", "0", "--rows", "1000", "--no-cpu-baseline")
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr
