@@ -98,6 +98,17 @@ POLARS_PLUGIN_DECLARE(jaro_winkler)
 POLARS_PLUGIN_DECLARE(jaccard)
 POLARS_PLUGIN_DECLARE(sorensen_dice)
 
+/* Best match (not in the reference): input 0 = the query column (N rows), input 1 = the candidate column (any number of rows; the
+ * length rule of the functions above does not apply).  Output: N rows of an Arrow struct {index: UInt32, score: Float64} named after
+ * input 0 -- the candidate with the highest score (ties to the lower index; the index is its row in input 1), as
+ * strsim_best_match_host with k = 1.  Null where the query is null or there is no (non-null) candidate; null candidates are never
+ * matched.  No kwargs. */
+POLARS_PLUGIN_DECLARE(best_match_levenshtein)
+POLARS_PLUGIN_DECLARE(best_match_jaro)
+POLARS_PLUGIN_DECLARE(best_match_jaro_winkler)
+POLARS_PLUGIN_DECLARE(best_match_jaccard)
+POLARS_PLUGIN_DECLARE(best_match_sorensen_dice)
+
 /* ---- diagnostics of this implementation (not part of the polars-ffi contract; the engine never calls them) ----
  * The plugin's staging -- pinned host memory and its device mirrors, per pipeline set -- is leased per call from one process-wide
  * pool under POLARS_STRSIM_STAGING_BUDGET_MB (csrc/plugin_pack.h: StagingPool; reference counterpart: the per-call scratch of

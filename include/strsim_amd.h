@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define STRSIM_ABI_VERSION 0x00010006u /* major<<16 | minor; 1.1: strsim_pairs_device_small, strsim_codec_patch_indirect; 1.2: strsim_ctx_retire_oldest, strsim_offsets_from_lengths; 1.3: one-launch calls (strsim_ctx_set_stream_ordered, strsim_ctx_last_late_rows); 1.4: one-launch calls are OPT-IN -- a new context completes rows in stream order, as in 1.2; 1.5: strsim_column_from_views_bounded, strsim_codec_decode_gathered_from, strsim_gather_*, STRSIM_ERR_EARLIER_CALL; 1.6: strsim_gather_f64_ranges, strsim_gather_comm_count, strsim_ctx_get_stream_ordered */
+#define STRSIM_ABI_VERSION 0x00010007u /* major<<16 | minor; 1.1: strsim_pairs_device_small, strsim_codec_patch_indirect; 1.2: strsim_ctx_retire_oldest, strsim_offsets_from_lengths; 1.3: one-launch calls (strsim_ctx_set_stream_ordered, strsim_ctx_last_late_rows); 1.4: one-launch calls are OPT-IN -- a new context completes rows in stream order, as in 1.2; 1.5: strsim_column_from_views_bounded, strsim_codec_decode_gathered_from, strsim_gather_*, STRSIM_ERR_EARLIER_CALL; 1.6: strsim_gather_f64_ranges, strsim_gather_comm_count, strsim_ctx_get_stream_ordered; 1.7: strsim_best_match_device, strsim_best_match_host */
 
 #if defined(__GNUC__)
 #define STRSIM_API __attribute__((visibility("default")))
@@ -165,6 +165,38 @@ STRSIM_API int strsim_pairs_host(strsim_ctx_t *ctx, int measure,
                       const uint32_t *a_offsets, const uint8_t *a_values, uint64_t a_rows,
                       const uint32_t *b_offsets, const uint8_t *b_values, uint64_t b_rows,
                       double *out, uint64_t out_rows);
+
+/*
+ * Best match (ABI 1.7): for every query row i, the k candidates j with the highest score(i, j), where score(i, j) is bit for bit
+ * what strsim_pairs_device(measure, queries[i], candidates[j]) returns.  Row-major outputs of q_rows x k: out_index (uint32)
+ * and out_score (double).  A query's slots are in descending order of the score; ties go to the lower candidate index.  A
+ * candidate with score < min_score is never reported (-INFINITY or 0.0 reports every candidate).  Slots left empty (k > c_rows,
+ * or too few candidates pass min_score) hold index 0xFFFFFFFF and score NaN.
+ *
+ * 1 <= k <= STRSIM_BEST_MATCH_MAX_K, q_rows <= 2^32 - 1, c_rows <= 2^32 - 2; c_rows == 0 is allowed (every slot empty) and
+ * q_rows == 0 is a no-op.  A NaN min_score, a NULL buffer of a non-empty side or output, a bad measure or k: STRSIM_ERR_ARG.
+ * The arguments are checked first, the context last (a NULL ctx is STRSIM_ERR_ARG too): no argument error needs a device.
+ * Nulls are not seen here (as in strsim_pairs_device): a caller drops null candidates and maps the indices back.
+ *
+ * Device-resident: the same column layout as strsim_pairs_device.  Reads beyond the strings: none by the kernels of this call
+ * (each string is read byte by byte within its offsets); pairs with a string longer than STRSIM_LANE_PATH_MAX_BYTES or a
+ * non-ASCII one go through strsim_pairs_device (one side as the literal) and read what it documents.
+ * The call waits once for the stream (a read-back of how many strings fall outside the one-pair-per-lane class).  Without such
+ * strings it then returns with the search enqueued: results are complete after strsim_ctx_synchronize(), or in stream order.
+ * With them it runs those pairs through strsim_pairs_device batch by batch and synchronises the context (strsim_ctx_synchronize)
+ * after each batch, so everything enqueued on the context before the call is complete when it returns.
+ */
+#define STRSIM_BEST_MATCH_MAX_K 16u
+STRSIM_API int strsim_best_match_device(strsim_ctx_t *ctx, int measure,
+                                        const uint32_t *q_offsets, const uint8_t *q_values, uint64_t q_rows,
+                                        const uint32_t *c_offsets, const uint8_t *c_values, uint64_t c_rows,
+                                        uint32_t k, double min_score, uint32_t *out_index, double *out_score);
+
+/* The same with HOST-RESIDENT buffers (the column layout of strsim_pairs_host); synchronous. */
+STRSIM_API int strsim_best_match_host(strsim_ctx_t *ctx, int measure,
+                                      const uint32_t *q_offsets, const uint8_t *q_values, uint64_t q_rows,
+                                      const uint32_t *c_offsets, const uint8_t *c_values, uint64_t c_rows,
+                                      uint32_t k, double min_score, uint32_t *out_index, double *out_score);
 
 /* Row partition used to shard a column over `n` GPUs/ranks: the reference's split_offsets
  * (strsim.rs:21-39).  Writes n (offset,len) pairs into out_offset_len[2*n]. */

@@ -56,6 +56,7 @@ struct PluginError {
 #include "plugin_arrow.h"
 #include "plugin_pack.h"
 #include "plugin_pipeline.h"
+#include "plugin_match.h"
 
 void run(int measure, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret, bool engine_parallel)
 {
@@ -195,6 +196,17 @@ void _polars_plugin_strsim_coalesce_stats(uint64_t out[4]) { if (out) combiner()
     void _polars_plugin_field_##name(ArrowSchema *input_fields, size_t n_fields, ArrowSchema *return_value)     \
     {                                                                                                           \
         field_entry(input_fields, n_fields, return_value);                                                      \
+    }
+
+#define POLARS_PLUGIN_DEFINE_MATCH(name, id)                                                                    \
+    void _polars_plugin_best_match_##name(SeriesExport *inputs, size_t n_inputs, const uint8_t *, size_t,       \
+                                          SeriesExport *return_value, CallerContext *)                          \
+    {                                                                                                           \
+        best_match_entry(id, inputs, n_inputs, return_value);                                                   \
+    }                                                                                                           \
+    void _polars_plugin_field_best_match_##name(ArrowSchema *input_fields, size_t n_fields, ArrowSchema *return_value) \
+    {                                                                                                           \
+        best_match_field_entry(input_fields, n_fields, return_value);                                           \
     }
 
 #ifdef STRSIM_TEST_HOOKS
@@ -423,5 +435,10 @@ POLARS_PLUGIN_DEFINE(jaro, STRSIM_JARO)
 POLARS_PLUGIN_DEFINE(jaro_winkler, STRSIM_JARO_WINKLER)
 POLARS_PLUGIN_DEFINE(jaccard, STRSIM_JACCARD)
 POLARS_PLUGIN_DEFINE(sorensen_dice, STRSIM_SORENSEN_DICE)
+POLARS_PLUGIN_DEFINE_MATCH(levenshtein, STRSIM_LEVENSHTEIN)
+POLARS_PLUGIN_DEFINE_MATCH(jaro, STRSIM_JARO)
+POLARS_PLUGIN_DEFINE_MATCH(jaro_winkler, STRSIM_JARO_WINKLER)
+POLARS_PLUGIN_DEFINE_MATCH(jaccard, STRSIM_JACCARD)
+POLARS_PLUGIN_DEFINE_MATCH(sorensen_dice, STRSIM_SORENSEN_DICE)
 
 } // extern "C"

@@ -123,6 +123,13 @@ struct strsim_ctx {
     // STRSIM_ERR_EARLIER_CALL and the "a slot is retired whatever fails" rule without breaking the device
     uint64_t fault_retire_at = 0;      // STRSIM_FAULT_RETIRE_AT (0 = never)
     uint64_t retired = 0;
+    // best match (strsim_best_match_device): packed strings + slow lists + partial lists, the fallback's score batches, and a
+    // pinned word pair for the two slow counts (all grow-only)
+    void *match_ws = nullptr;
+    size_t match_ws_cap = 0;
+    void *match_scratch = nullptr;
+    size_t match_scratch_cap = 0;
+    uint32_t *match_counts_host = nullptr;
 };
 
 static int ctx_set_device(strsim_ctx *c) { HIP_TRY(hipSetDevice(c->device)); return STRSIM_OK; }
@@ -401,6 +408,9 @@ void strsim_ctx_destroy(strsim_ctx_t *c)
     if (c->sched) (void)hipFree(c->sched);
     if (c->huge_ws) (void)hipFree(c->huge_ws);
     if (c->scan_ws) (void)hipFree(c->scan_ws);
+    if (c->match_ws) (void)hipFree(c->match_ws);
+    if (c->match_scratch) (void)hipFree(c->match_scratch);
+    if (c->match_counts_host) (void)hipHostFree(c->match_counts_host);
     if (c->lev_ws) (void)hipFree(c->lev_ws);
     if (c->status) (void)hipFree(c->status);
     if (c->status_host) (void)hipHostFree(c->status_host);
@@ -769,3 +779,173 @@ int strsim_ctx_set_stream_ordered(strsim_ctx_t *c, int enable)
 int strsim_ctx_get_stream_ordered(strsim_ctx_t *c) { return c ? (c->stream_ordered ? 1 : 0) : 1; }
 
 } // extern "C"
+
+// ---- best match (strsim_match.h) ----
+
+// Candidate splits of k_match_lane for nq queries x nc candidates: about eight workgroups of four waves per CU in all (a
+// frame of few queries spreads its candidates over more workgroups), at least MATCH_MIN_PER_SPLIT candidates per split (a
+// split writes a partial list per query that the merge reads back), and the partial lists within MATCH_MAX_PARTIAL entries.
+static constexpr uint64_t MATCH_MIN_PER_SPLIT = 512;
+static constexpr uint64_t MATCH_MAX_PARTIAL = (uint64_t)1 << 24;
+static uint32_t match_splits(uint64_t nq, uint64_t nc, uint32_t kp, int num_cu)
+{
+    const uint64_t qblocks = (nq + 255) / 256;
+    const uint64_t target = 8u * (uint64_t)(num_cu > 0 ? num_cu : 256);
+    uint64_t s = (target + qblocks - 1) / qblocks;
+    const uint64_t by_m = (nc + MATCH_MIN_PER_SPLIT - 1) / MATCH_MIN_PER_SPLIT;
+    if (s > by_m) s = by_m;
+    const uint64_t by_mem = MATCH_MAX_PARTIAL / (nq * kp);
+    if (s > by_mem) s = by_mem;
+    if (s > 65535u) s = 65535u;
+    return s ? (uint32_t)s : 1u;
+}
+
+// fallback: scores of up to MATCH_FALLBACK_CALLS literal calls per batch, at most MATCH_FALLBACK_SCORES doubles
+static constexpr uint64_t MATCH_FALLBACK_CALLS = 16;
+static constexpr uint64_t MATCH_FALLBACK_SCORES = (uint64_t)1 << 24;
+
+static int best_match_check(const char *who, strsim_ctx_t *c, int measure, const uint32_t *q_off, const uint8_t *q_val,
+                            uint64_t q_rows, const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, uint32_t k,
+                            double min_score, const void *out_index, const void *out_score)
+{
+    if (measure < 0 || measure >= STRSIM_NUM_MEASURES) { set_error("%s: unknown measure %d", who, measure); return STRSIM_ERR_ARG; }
+    if (k < 1u || k > STRSIM_BEST_MATCH_MAX_K) { set_error("%s: k=%u is outside 1..%u", who, k, STRSIM_BEST_MATCH_MAX_K); return STRSIM_ERR_ARG; }
+    if (min_score != min_score) { set_error("%s: min_score is NaN", who); return STRSIM_ERR_ARG; }
+    if (q_rows > 0xFFFFFFFFull) { set_error("%s: %llu queries (at most 2^32 - 1)", who, (unsigned long long)q_rows); return STRSIM_ERR_ARG; }
+    if (c_rows > 0xFFFFFFFEull) { set_error("%s: %llu candidates (at most 2^32 - 2)", who, (unsigned long long)c_rows); return STRSIM_ERR_ARG; }
+    if (q_rows && (!q_off || !q_val || !out_index || !out_score)) { set_error("%s: NULL query or output buffer", who); return STRSIM_ERR_ARG; }
+    if (c_rows && (!c_off || !c_val)) { set_error("%s: NULL candidate buffer", who); return STRSIM_ERR_ARG; }
+    if (!c) { set_error("%s: ctx is NULL", who); return STRSIM_ERR_ARG; }
+    return STRSIM_OK;
+}
+
+extern "C" {
+
+int strsim_best_match_device(strsim_ctx_t *c, int measure, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows,
+                             const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, uint32_t k, double min_score,
+                             uint32_t *out_index, double *out_score)
+{
+    int rc = best_match_check("strsim_best_match_device", c, measure, q_off, q_val, q_rows, c_off, c_val, c_rows, k, min_score,
+                              out_index, out_score);
+    if (rc || q_rows == 0) return rc;
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    const uint32_t nq = (uint32_t)q_rows, nc = (uint32_t)c_rows, kp = (uint32_t)match_lane_k(k);
+    const uint32_t splits = nc ? match_splits(nq, nc, kp, c->num_cu) : 0u;
+    const uint32_t per = splits ? (uint32_t)(((uint64_t)nc + splits - 1) / splits) : 0u;
+    const uint32_t nsplit = splits ? (uint32_t)(((uint64_t)nc + per - 1) / per) : 0u;
+    // workspace: strings (32-byte words + meta), slow lists + counts, (nsplit + 1) lists of kp per query (the last: fallback)
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t nl = (size_t)nsplit + 1, lists = nl * nq * kp;
+    const size_t o_qw = 0, o_qm = o_qw + up((size_t)nq * 32), o_cw = o_qm + up((size_t)nq * 4), o_cm = o_cw + up((size_t)nc * 32),
+                 o_qs = o_cm + up((size_t)nc * 4), o_cs = o_qs + up((size_t)nq * 4), o_cnt = o_cs + up((size_t)nc * 4),
+                 o_ls = o_cnt + 256, o_li = o_ls + up(lists * 8), total = o_li + up(lists * 4);
+    rc = ctx_reserve(&c->match_ws, &c->match_ws_cap, total);
+    if (rc) return rc;
+    if (!c->match_counts_host) HIP_TRY(hipHostMalloc((void **)&c->match_counts_host, 64, hipHostMallocDefault));
+    uint8_t *const ws = static_cast<uint8_t *>(c->match_ws);
+    uint32_t *const qw = (uint32_t *)(ws + o_qw), *const qm = (uint32_t *)(ws + o_qm), *const cw = (uint32_t *)(ws + o_cw),
+                   *const cm = (uint32_t *)(ws + o_cm), *const qs = (uint32_t *)(ws + o_qs), *const cs = (uint32_t *)(ws + o_cs),
+                   *const cnt = (uint32_t *)(ws + o_cnt), *const lidx = (uint32_t *)(ws + o_li);
+    double *const lscore = (double *)(ws + o_ls);
+    hipStream_t st = c->stream;
+    HIP_TRY(hipMemsetAsync(cnt, 0, 8, st));
+    HIP_TRY(launch_match_pack(q_off, q_val, nq, qw, qm, qs, cnt, st));
+    HIP_TRY(launch_match_pack(c_off, c_val, nc, cw, cm, cs, cnt + 1, st));
+    // the sizes of the two slow classes decide what runs: one small read-back (the only wait of a call without slow strings)
+    HIP_TRY(hipMemcpyAsync(c->match_counts_host, cnt, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint32_t q_slow = c->match_counts_host[0], c_slow = c->match_counts_host[1];
+    // fast x fast: lists 0 .. nsplit - 1
+    uint32_t used = 0;
+    if (nsplit && q_slow < nq && c_slow < nc) {
+        MatchLaneArgs a{qw, qm, nq, cw, cm, nc, nsplit, per, k, c->qtab, min_score, lscore, lidx, st};
+        HIP_TRY(launch_match_lane(measure, a));
+        used = nsplit;
+    }
+    // every pair with a slow side: strsim_pairs_device with that side as the literal, batch by batch, folded into list `used`
+    if (nc && (q_slow || c_slow)) {
+        double *const fs = lscore + (size_t)used * nq * kp;
+        uint32_t *const fi = lidx + (size_t)used * nq * kp;
+        HIP_TRY(launch_match_clear(fs, fi, (uint64_t)nq * kp, st));
+        const uint64_t longest = nq > nc ? nq : nc;
+        uint64_t calls = MATCH_FALLBACK_SCORES / longest;
+        if (calls > MATCH_FALLBACK_CALLS) calls = MATCH_FALLBACK_CALLS;
+        if (calls < 1) calls = 1;
+        rc = ctx_reserve(&c->match_scratch, &c->match_scratch_cap, (size_t)(calls * longest * 8));
+        if (rc) return rc;
+        double *const scratch = static_cast<double *>(c->match_scratch);
+        uint32_t *host_list = static_cast<uint32_t *>(malloc(((size_t)q_slow + c_slow + 1) * 4));
+        if (!host_list) { set_error("strsim_best_match_device: out of host memory"); return STRSIM_ERR_OOM; }
+        auto run = [&]() -> int {
+            if (q_slow) HIP_TRY(hipMemcpyAsync(host_list, qs, (size_t)q_slow * 4, hipMemcpyDeviceToHost, st));
+            if (c_slow) HIP_TRY(hipMemcpyAsync(host_list + q_slow, cs, (size_t)c_slow * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            for (uint32_t b0 = 0; b0 < q_slow; b0 += (uint32_t)calls) { // a slow query against every candidate
+                const uint32_t nb = (uint32_t)(q_slow - b0 < calls ? q_slow - b0 : calls);
+                for (uint32_t b = 0; b < nb; ++b) {
+                    int r = strsim_pairs_device(c, measure, q_off + host_list[b0 + b], q_val, 1, c_off, c_val, nc, scratch + (size_t)b * nc, nc);
+                    if (r) return r;
+                }
+                int r = strsim_ctx_synchronize(c);
+                if (r) return r;
+                HIP_TRY(launch_match_fold_cols(k, scratch, qs + b0, nb, nc, min_score, fs, fi, st));
+            }
+            for (uint32_t b0 = 0; b0 < c_slow; b0 += (uint32_t)calls) { // a slow candidate against every query (the fast ones are kept)
+                const uint32_t nb = (uint32_t)(c_slow - b0 < calls ? c_slow - b0 : calls);
+                for (uint32_t b = 0; b < nb; ++b) {
+                    const uint32_t j = host_list[q_slow + b0 + b];
+                    int r = strsim_pairs_device(c, measure, c_off + j, c_val, 1, q_off, q_val, nq, scratch + (size_t)b * nq, nq);
+                    if (r) return r;
+                }
+                int r = strsim_ctx_synchronize(c);
+                if (r) return r;
+                HIP_TRY(launch_match_fold_rows(k, scratch, cs + b0, nb, qm, nq, min_score, fs, fi, st));
+            }
+            return STRSIM_OK;
+        };
+        rc = run();
+        free(host_list);
+        if (rc) return rc;
+        ++used;
+    }
+    HIP_TRY(launch_match_merge(k, lscore, lidx, used, nq, out_index, out_score, st));
+    return STRSIM_OK;
+}
+
+int strsim_best_match_host(strsim_ctx_t *c, int measure, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows,
+                           const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, uint32_t k, double min_score,
+                           uint32_t *out_index, double *out_score)
+{
+    int rc = best_match_check("strsim_best_match_host", c, measure, q_off, q_val, q_rows, c_off, c_val, c_rows, k, min_score,
+                              out_index, out_score);
+    if (rc || q_rows == 0) return rc;
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    // (as strsim_pairs_host's copy path: the caller's offset base is kept and the values go up from byte 0)
+    const size_t ob = q_rows * (size_t)k;
+    const size_t need[5] = {(q_rows + 1) * 4, (size_t)q_off[q_rows] + 1, (c_rows + 1) * 4, (c_rows ? (size_t)c_off[c_rows] : 0) + 1,
+                            ob * 12 + 256};
+    for (int i = 0; i < 5; ++i) {
+        rc = ctx_reserve(&c->stage[i], &c->stage_cap[i], need[i]);
+        if (rc) return rc;
+    }
+    hipStream_t st = c->stream;
+    HIP_TRY(hipMemcpyAsync(c->stage[0], q_off, (q_rows + 1) * 4, hipMemcpyHostToDevice, st));
+    if (q_off[q_rows]) HIP_TRY(hipMemcpyAsync(c->stage[1], q_val, q_off[q_rows], hipMemcpyHostToDevice, st));
+    if (c_rows) {
+        HIP_TRY(hipMemcpyAsync(c->stage[2], c_off, (c_rows + 1) * 4, hipMemcpyHostToDevice, st));
+        if (c_off[c_rows]) HIP_TRY(hipMemcpyAsync(c->stage[3], c_val, c_off[c_rows], hipMemcpyHostToDevice, st));
+    }
+    double *const d_score = static_cast<double *>(c->stage[4]);
+    uint32_t *const d_index = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(c->stage[4]) + ((ob * 8 + 255) & ~(size_t)255));
+    rc = strsim_best_match_device(c, measure, (const uint32_t *)c->stage[0], (const uint8_t *)c->stage[1], q_rows,
+                                  (const uint32_t *)c->stage[2], (const uint8_t *)c->stage[3], c_rows, k, min_score, d_index, d_score);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out_score, d_score, ob * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out_index, d_index, ob * 4, hipMemcpyDeviceToHost, st));
+    return strsim_ctx_synchronize(c);
+}
+
+} // extern "C"
+

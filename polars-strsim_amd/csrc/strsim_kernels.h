@@ -93,4 +93,29 @@ hipError_t launch_huge(int measure, const LaunchArgs &a, uint32_t *ws, uint32_t 
 // copies one DevStatus to host-mapped pinned memory from the device side (no copy-engine hand-over)
 hipError_t launch_publish_status(const DevStatus *src, DevStatus *dst_mapped, uint32_t ticket, hipStream_t stream);
 
+// Best match (strsim_match.h).  The lane kernel's top-K is instantiated at K = 1, 4, 16: match_lane_k(k) is the K a call with k
+// slots runs at (its lists are K long; the merge writes the first k).
+int match_lane_k(uint32_t k);
+struct MatchLaneArgs {
+    const uint32_t *qwords, *qmeta; uint32_t nq; // queries: eight words + meta per string (k_match_pack)
+    const uint32_t *cwords, *cmeta; uint32_t nc; // candidates
+    uint32_t splits, per;                         // grid.y and candidates per split
+    uint32_t k;
+    const double *qtab;
+    double min_score;
+    double *pscore; uint32_t *pidx;               // splits x nq x match_lane_k(k) partial lists
+    hipStream_t stream;
+};
+hipError_t launch_match_pack(const uint32_t *off, const uint8_t *val, uint32_t rows, uint32_t *words, uint32_t *meta,
+                             uint32_t *slow_list, uint32_t *slow_count, hipStream_t stream);
+hipError_t launch_match_lane(int measure, const MatchLaneArgs &a);
+hipError_t launch_match_clear(double *score, uint32_t *idx, uint64_t n, hipStream_t stream);
+hipError_t launch_match_fold_cols(uint32_t k, const double *scores, const uint32_t *qlist, uint32_t nb, uint32_t nc, double min_score,
+                                  double *fscore, uint32_t *fidx, hipStream_t stream);
+hipError_t launch_match_fold_rows(uint32_t k, const double *scores, const uint32_t *clist, uint32_t nb, const uint32_t *qmeta, uint32_t nq,
+                                  double min_score, double *fscore, uint32_t *fidx, hipStream_t stream);
+hipError_t launch_match_merge(uint32_t k, const double *pscore, const uint32_t *pidx, uint32_t nl, uint32_t nq, uint32_t *out_index,
+                              double *out_score, hipStream_t stream);
+
 } // namespace strsim
+

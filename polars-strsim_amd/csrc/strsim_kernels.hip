@@ -53,6 +53,7 @@ struct OutPtrs {
 #include "strsim_lane_stage_pc.h" // lab only: the producer / consumer form of k_lane_stage (round 6's experiment)
 #endif
 #include "strsim_lane_lit.h"
+#include "strsim_match.h"
 
 #include "strsim_kernel_wide.h"
 #include "strsim_kernel_utf8.h"
@@ -349,6 +350,91 @@ __global__ void k_publish_status(const DevStatus *__restrict__ src, DevStatus *_
 hipError_t launch_publish_status(const DevStatus *src, DevStatus *dst_mapped, uint32_t ticket, hipStream_t stream)
 {
     hipLaunchKernelGGL(k_publish_status, dim3(1), dim3(64), 0, stream, src, dst_mapped, ticket);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// best match (strsim_match.h)
+// ------------------------------------------------------------------------------------------------
+int match_lane_k(uint32_t k) { return k <= 1u ? 1 : (k <= 4u ? 4 : 16); }
+
+static unsigned match_grid(uint64_t n) { return (unsigned)((n + MATCH_BLOCK - 1) / MATCH_BLOCK); }
+
+hipError_t launch_match_pack(const uint32_t *off, const uint8_t *val, uint32_t rows, uint32_t *words, uint32_t *meta,
+                             uint32_t *slow_list, uint32_t *slow_count, hipStream_t stream)
+{
+    if (rows == 0u) return hipSuccess;
+    hipLaunchKernelGGL(k_match_pack, dim3(match_grid(rows)), dim3(MATCH_BLOCK), 0, stream, off, val, rows, words, meta, slow_list, slow_count);
+    return hipGetLastError();
+}
+
+template <int M, int K>
+static void launch_match_lane_t(const MatchLaneArgs &a)
+{
+    hipLaunchKernelGGL((k_match_lane<M, K>), dim3(match_grid(a.nq), a.splits), dim3(MATCH_BLOCK), 0, a.stream, a.qwords, a.qmeta, a.nq,
+                       a.cwords, a.cmeta, a.nc, a.per, a.qtab, a.min_score, a.pscore, a.pidx);
+}
+
+template <int M>
+static void launch_match_lane_m(const MatchLaneArgs &a)
+{
+    const int K = match_lane_k(a.k);
+    if (K == 1) launch_match_lane_t<M, 1>(a);
+    else if (K == 4) launch_match_lane_t<M, 4>(a);
+    else launch_match_lane_t<M, 16>(a);
+}
+
+hipError_t launch_match_lane(int measure, const MatchLaneArgs &a)
+{
+    switch (measure) {
+    case LEVENSHTEIN: launch_match_lane_m<LEVENSHTEIN>(a); break;
+    case JARO: launch_match_lane_m<JARO>(a); break;
+    case JARO_WINKLER: launch_match_lane_m<JARO_WINKLER>(a); break;
+    case JACCARD: launch_match_lane_m<JACCARD>(a); break;
+    default: launch_match_lane_m<SORENSEN_DICE>(a); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_match_clear(double *score, uint32_t *idx, uint64_t n, hipStream_t stream)
+{
+    if (n == 0u) return hipSuccess;
+    hipLaunchKernelGGL(k_match_clear, dim3(match_grid(n)), dim3(MATCH_BLOCK), 0, stream, score, idx, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_match_fold_cols(uint32_t k, const double *scores, const uint32_t *qlist, uint32_t nb, uint32_t nc, double min_score,
+                                  double *fscore, uint32_t *fidx, hipStream_t stream)
+{
+    if (nb == 0u) return hipSuccess;
+    const int K = match_lane_k(k);
+    if (K == 1) hipLaunchKernelGGL(k_match_fold_cols<1>, dim3(nb), dim3(MATCH_BLOCK), 0, stream, scores, qlist, nc, min_score, fscore, fidx);
+    else if (K == 4) hipLaunchKernelGGL(k_match_fold_cols<4>, dim3(nb), dim3(MATCH_BLOCK), 0, stream, scores, qlist, nc, min_score, fscore, fidx);
+    else hipLaunchKernelGGL(k_match_fold_cols<16>, dim3(nb), dim3(MATCH_BLOCK), 0, stream, scores, qlist, nc, min_score, fscore, fidx);
+    return hipGetLastError();
+}
+
+hipError_t launch_match_fold_rows(uint32_t k, const double *scores, const uint32_t *clist, uint32_t nb, const uint32_t *qmeta, uint32_t nq,
+                                  double min_score, double *fscore, uint32_t *fidx, hipStream_t stream)
+{
+    if (nb == 0u || nq == 0u) return hipSuccess;
+    const int K = match_lane_k(k);
+    const dim3 g(match_grid(nq)), b(MATCH_BLOCK);
+    if (K == 1) hipLaunchKernelGGL(k_match_fold_rows<1>, g, b, 0, stream, scores, clist, nb, qmeta, nq, min_score, fscore, fidx);
+    else if (K == 4) hipLaunchKernelGGL(k_match_fold_rows<4>, g, b, 0, stream, scores, clist, nb, qmeta, nq, min_score, fscore, fidx);
+    else hipLaunchKernelGGL(k_match_fold_rows<16>, g, b, 0, stream, scores, clist, nb, qmeta, nq, min_score, fscore, fidx);
+    return hipGetLastError();
+}
+
+hipError_t launch_match_merge(uint32_t k, const double *pscore, const uint32_t *pidx, uint32_t nl, uint32_t nq, uint32_t *out_index,
+                              double *out_score, hipStream_t stream)
+{
+    if (nq == 0u) return hipSuccess;
+    const int K = match_lane_k(k);
+    const dim3 g(match_grid(nq)), b(MATCH_BLOCK);
+    if (K == 1) hipLaunchKernelGGL(k_match_merge<1>, g, b, 0, stream, pscore, pidx, nl, nq, k, out_index, out_score);
+    else if (K == 4) hipLaunchKernelGGL(k_match_merge<4>, g, b, 0, stream, pscore, pidx, nl, nq, k, out_index, out_score);
+    else hipLaunchKernelGGL(k_match_merge<16>, g, b, 0, stream, pscore, pidx, nl, nq, k, out_index, out_score);
     return hipGetLastError();
 }
 

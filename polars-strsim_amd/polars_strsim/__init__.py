@@ -79,9 +79,27 @@ def sorensen_dice(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
 
 
 __all__ = [
+    "best_match",
     "levenshtein",
     "jaro",
     "jaro_winkler",
     "jaccard",
     "sorensen_dice",
 ]
+
+
+_BEST_MATCH_MEASURES = ("levenshtein", "jaro", "jaro_winkler", "jaccard", "sorensen_dice")
+
+
+def best_match(expr: IntoExpr, candidates: IntoExpr, measure: str = "jaro_winkler") -> pl.Expr:
+    """The best candidate of every row of `expr` among all rows of `candidates` (any length), by `measure`: a struct
+    {index: UInt32, score: Float64}, null where the row is null or no candidate is; ties go to the lower candidate index."""
+    if measure not in _BEST_MATCH_MEASURES:
+        raise ValueError(f"unknown measure {measure!r}; expected one of {_BEST_MATCH_MEASURES}")
+    return register_plugin_function(
+        plugin_path=_PLUGIN_DIR,
+        function_name="best_match_" + measure,
+        args=[parse_into_expr(expr, dtype=pl.Utf8), parse_into_expr(candidates, dtype=pl.Utf8)],
+        is_elementwise=False,
+    )
+

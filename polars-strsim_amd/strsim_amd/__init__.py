@@ -67,5 +67,26 @@ def sorensen_dice(a, b, ctx=None):
     return similarity("sorensen_dice", a, b, ctx)
 
 
-__all__ = ["Codec", "Context", "device_count", "pack_strings", "split_offsets", "similarity", "levenshtein", "jaro",
+def best_match(measure, queries, candidates, k=1, min_score=None, ctx=None):
+    """For every query, its k best candidates by `measure`: (index int64 [N, k], score f64 [N, k]).  Slots in descending order
+    of the score, ties to the lower candidate index; a candidate below min_score is not reported.  Empty slots -- and every slot
+    of a null query -- are (-1, NaN).  Null candidates are never matched; indices refer to the caller's candidate positions."""
+    ctx = ctx or default_context()
+    Q, vq = _as_column(queries)
+    cand = list(candidates)
+    keep = np.array([c is not None for c in cand], dtype=bool)
+    pos = np.flatnonzero(keep)
+    qo, qv = pack_strings(Q)
+    co, cv = pack_strings([cand[j] for j in pos])
+    idx, score = ctx.best_match(measure, qo, qv, co, cv, k, min_score)
+    empty = idx == 0xFFFFFFFF
+    out = np.full(idx.shape, -1, dtype=np.int64)
+    out[~empty] = pos[idx[~empty].astype(np.int64)]
+    if vq is not None:
+        out[~vq] = -1
+        score[~vq] = np.nan
+    return out, score
+
+
+__all__ = ["best_match", "Codec", "Context", "device_count", "pack_strings", "split_offsets", "similarity", "levenshtein", "jaro",
            "jaro_winkler", "jaccard", "sorensen_dice", "MEASURES", "MEASURE_ID", "STATUS", "ShapeMismatch", "StrsimError"]

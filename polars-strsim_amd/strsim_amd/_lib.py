@@ -84,6 +84,10 @@ def lib():
         f = getattr(L, name)
         f.restype = i32
         f.argtypes = [vp, i32, vp, vp, u64, vp, vp, u64, vp, u64]
+    for name in ("strsim_best_match_device", "strsim_best_match_host"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, i32, vp, vp, u64, vp, vp, u64, C.c_uint32, C.c_double, vp, vp]
     L.strsim_pairs_device_all.restype = i32
     L.strsim_pairs_device_all.argtypes = [vp, vp, vp, u64, vp, vp, u64, C.POINTER(vp), u64]
     L.strsim_codec_create.restype = i32

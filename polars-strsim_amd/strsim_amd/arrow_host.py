@@ -104,9 +104,11 @@ def _chunks(x, layout):
     return out, dtype
 
 
-def call_plugin(name, a, b, layout="vu", names=("a", "b"), parallel=False, _probe=None):
+def call_plugin(name, a, b, layout="vu", names=("a", "b"), parallel=False, _probe=None, out_type=None):
     """Evaluate plugin expression `name` over two columns (lists / pyarrow arrays / a single literal).
-    Returns a pyarrow ChunkedArray of float64.  `layout` picks the Arrow string layout sent to the plugin."""
+    Returns a pyarrow ChunkedArray of float64 (or of `out_type`: the best_match_* functions return a struct).  `layout` picks
+    the Arrow string layout sent to the plugin."""
+    out_type = pa.float64() if out_type is None else out_type
     L = _load()
     fn = getattr(L, "_polars_plugin_" + name)
     fn.restype = None
@@ -132,11 +134,11 @@ def call_plugin(name, a, b, layout="vu", names=("a", "b"), parallel=False, _prob
         out = []
         fld = pa.Field._import_from_c(C.addressof(ret.field.contents)) if False else None
         for i in range(ret.len):
-            out.append(pa.Array._import_from_c(C.addressof(ret.arrays[i].contents), pa.float64()))
+            out.append(pa.Array._import_from_c(C.addressof(ret.arrays[i].contents), out_type))
         name_out = ret.field.contents.name.decode() if ret.field.contents.name else ""
     finally:
         ret.release(C.byref(ret))
-    res = pa.chunked_array(out, type=pa.float64())
+    res = pa.chunked_array(out, type=out_type)
     if _probe is not None:
         _probe["name"] = name_out
     return res

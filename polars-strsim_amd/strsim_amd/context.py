@@ -190,6 +190,27 @@ class Context:
         return out
 
 
+    def best_match(self, measure, q_offsets, q_values, c_offsets, c_values, k=1, min_score=None):
+        """Synchronous best match (strsim_best_match_host, ABI 1.7): numpy uint32 offsets + uint8 values of the queries and the
+        candidates -> (index uint32 [rows, k], score f64 [rows, k]), each query's k best candidates by descending score, ties to the
+        lower index; empty slots are (0xFFFFFFFF, NaN).  min_score=None reports every candidate."""
+        qo = np.ascontiguousarray(q_offsets, dtype=np.uint32)
+        co = np.ascontiguousarray(c_offsets, dtype=np.uint32)
+        qv = np.ascontiguousarray(q_values, dtype=np.uint8)
+        cv = np.ascontiguousarray(c_values, dtype=np.uint8)
+        if qv.size == 0:
+            qv = np.zeros(1, dtype=np.uint8)
+        if cv.size == 0:
+            cv = np.zeros(1, dtype=np.uint8)
+        nq, nc = qo.size - 1, co.size - 1
+        index = np.empty((nq, int(k)), dtype=np.uint32)
+        score = np.empty((nq, int(k)), dtype=np.float64)
+        ms = -np.inf if min_score is None else float(min_score)
+        check(lib().strsim_best_match_host(self._h, measure_id(measure), qo.ctypes.data, qv.ctypes.data, nq,
+                                           co.ctypes.data, cv.ctypes.data, nc, int(k), ms, index.ctypes.data, score.ctypes.data))
+        return index, score
+
+
 class Codec:
     """Lossless 16-bit transport codec for one measure's result column (include/strsim_amd.h: strsim_codec_*)."""
     EXC_CAP = 1 << 20
