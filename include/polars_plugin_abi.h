@@ -97,6 +97,10 @@ POLARS_PLUGIN_DECLARE(jaro)
 POLARS_PLUGIN_DECLARE(jaro_winkler)
 POLARS_PLUGIN_DECLARE(jaccard)
 POLARS_PLUGIN_DECLARE(sorensen_dice)
+/* Not in the reference: optimal string alignment -- the restricted Damerau-Levenshtein similarity (adjacent transpositions count
+ * one edit, no substring is edited twice), STRSIM_OSA of strsim_amd.h.  Same inputs, output (Float64 named after input 0), nulls
+ * and literal broadcast as the five above. */
+POLARS_PLUGIN_DECLARE(osa)
 
 /* Best match (not in the reference): input 0 = the query column (N rows), input 1 = the candidate column (any number of rows; the
  * length rule of the functions above does not apply).  Output: N rows of an Arrow struct {index: UInt32, score: Float64} named after

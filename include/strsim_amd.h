@@ -44,8 +44,19 @@ typedef enum strsim_measure {
     STRSIM_JARO_WINKLER  = 2, /* strsim.rs:257-272 */
     STRSIM_JACCARD       = 3, /* character-multiset Jaccard, strsim.rs:286-308 */
     STRSIM_SORENSEN_DICE = 4, /* character-multiset Sorensen-Dice, strsim.rs:322-345 */
-    STRSIM_NUM_MEASURES  = 5
+    STRSIM_NUM_MEASURES  = 5, /* the reference's five; the value 5 itself is not a measure */
+    STRSIM_OSA           = 6  /* optimal string alignment (restricted Damerau-Levenshtein: no substring is edited twice), normalised
+                                 like STRSIM_LEVENSHTEIN: 1.0 when a == b or both are empty, else 1.0 - d / max(|a|, |b|) over Unicode
+                                 scalar values.  Pairwise entry points only (strsim_pairs_device, _small, strsim_pairs_host);
+                                 not a measure of the reference */
 } strsim_measure_t;
+
+/* Entry points of strsim_measure_supported(). */
+typedef enum strsim_entry_point {
+    STRSIM_ENTRY_PAIRWISE   = 0, /* strsim_pairs_device, strsim_pairs_device_small, strsim_pairs_host */
+    STRSIM_ENTRY_BEST_MATCH = 1, /* strsim_best_match_device, strsim_best_match_host */
+    STRSIM_ENTRY_CODEC      = 2  /* strsim_codec_create */
+} strsim_entry_point_t;
 
 typedef enum strsim_status {
     STRSIM_OK              = 0,
@@ -68,6 +79,11 @@ STRSIM_API uint32_t strsim_abi_version(void);
 /* NUL-terminated description of the last error raised on the calling thread ("" if none). */
 STRSIM_API const char *strsim_last_error_message(void);
 
+/* 1 if `entry_point` (strsim_entry_point_t) accepts `measure`, else 0 -- answered from the tables the argument checks of those
+ * entry points use, without a device or a context.  The way to detect a measure: the ABI version does not move for one (STRSIM_OSA
+ * came within 1.7), and the compute calls test for a NULL context before they look at the measure.  Unknown entry points: 0. */
+STRSIM_API uint32_t strsim_measure_supported(int measure, int entry_point);
+
 /* Number of usable HIP devices (0 when there is none; never fails). */
 STRSIM_API int strsim_device_count(void);
 
@@ -89,6 +105,13 @@ STRSIM_API void *strsim_ctx_stream(strsim_ctx_t *ctx);
  * `out` = double[out_rows] on the same device, out_rows = max(a_rows, b_rows).
  * Nulls are not seen here: like the reference's arity helpers the kernels compute on the bytes under
  * every slot; validity is combined by the caller (the plugin layer does it).
+ *
+ * STRSIM_OSA: rows where both strings are ASCII and at most 64 bytes are one pair per lane, every other row one pair per wave
+ * (any length: patterns beyond 2048 scalar values use a scratch buffer the context grows).  All rows are complete in stream
+ * order (strsim_ctx_last_long_rows / _last_late_rows report 0 for such a call), but the call waits once for the stream after
+ * its first kernel (a read-back of how many rows need the second kernel and how long their patterns are), so everything
+ * enqueued on the context's stream before it has completed when it returns.  Its kernels read only the bytes the offsets
+ * describe.  strsim_ctx_set_stream_ordered(ctx, 0) does not change an OSA call.
  *
  * Reads beyond the strings: the kernels copy the values of a block of rows in whole 16-byte chunks, from the
  * 16-byte-aligned address at or below the block's first byte (a_values + a_offsets[first row]) up to the chunk that

@@ -435,6 +435,7 @@ POLARS_PLUGIN_DEFINE(jaro, STRSIM_JARO)
 POLARS_PLUGIN_DEFINE(jaro_winkler, STRSIM_JARO_WINKLER)
 POLARS_PLUGIN_DEFINE(jaccard, STRSIM_JACCARD)
 POLARS_PLUGIN_DEFINE(sorensen_dice, STRSIM_SORENSEN_DICE)
+POLARS_PLUGIN_DEFINE(osa, STRSIM_OSA)
 POLARS_PLUGIN_DEFINE_MATCH(levenshtein, STRSIM_LEVENSHTEIN)
 POLARS_PLUGIN_DEFINE_MATCH(jaro, STRSIM_JARO)
 POLARS_PLUGIN_DEFINE_MATCH(jaro_winkler, STRSIM_JARO_WINKLER)

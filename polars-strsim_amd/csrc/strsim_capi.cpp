@@ -16,6 +16,8 @@
 #include "strsim_amd.h"
 #include "strsim_internal.h"
 #include "strsim_kernels.h"
+#define STRSIM_OSA_NO_KERNELS // (constants and sizes only: the kernels are compiled in strsim_kernels.hip)
+#include "strsim_osa.h"
 
 namespace strsim {
 
@@ -130,6 +132,11 @@ struct strsim_ctx {
     void *match_scratch = nullptr;
     size_t match_scratch_cap = 0;
     uint32_t *match_counts_host = nullptr;
+    // optimal string alignment (pairs_osa): the work list of k_osa_wave (one word per row) and its scratch for long patterns
+    uint32_t *osa_list = nullptr;
+    size_t osa_list_cap = 0;
+    uint32_t *osa_scratch = nullptr;
+    size_t osa_scratch_cap = 0;
 };
 
 static int ctx_set_device(strsim_ctx *c) { HIP_TRY(hipSetDevice(c->device)); return STRSIM_OK; }
@@ -237,7 +244,9 @@ static int ctx_retire_slot(strsim_ctx *c, int s)
         set_error("fault injected at retirement %llu of this context (STRSIM_FAULT_RETIRE_AT)", (unsigned long long)c->retired);
         return STRSIM_ERR_INTERNAL;
     }
-    const uint32_t left = *reinterpret_cast<const volatile uint32_t *>(&c->status_host[s].lane_left);
+    // (an OSA call has no lane_left: it says nothing about what the next call of the other measures leaves behind)
+    const uint32_t left = c->slot_measure[s] == STRSIM_OSA ? LANE_LEFT_UNKNOWN
+                                                           : *reinterpret_cast<const volatile uint32_t *>(&c->status_host[s].lane_left);
     if (left != LANE_LEFT_UNKNOWN) { // what the next call on this context is enqueued for
         c->expect_slow = left != 0u;
         c->long_rows = (uint64_t)left * 16u > c->slot_args[s].n;
@@ -307,6 +316,8 @@ static int ctx_reserve(void **p, size_t *cap, size_t bytes)
 extern "C" {
 
 uint32_t strsim_abi_version(void) { return STRSIM_ABI_VERSION; }
+
+uint32_t strsim_measure_supported(int measure, int entry_point) { return measure_accepted(measure, entry_point) ? 1u : 0u; }
 
 const char *strsim_last_error_message(void) { return g_last_error.c_str(); }
 
@@ -411,6 +422,8 @@ void strsim_ctx_destroy(strsim_ctx_t *c)
     if (c->match_ws) (void)hipFree(c->match_ws);
     if (c->match_scratch) (void)hipFree(c->match_scratch);
     if (c->match_counts_host) (void)hipHostFree(c->match_counts_host);
+    if (c->osa_list) (void)hipFree(c->osa_list);
+    if (c->osa_scratch) (void)hipFree(c->osa_scratch);
     if (c->lev_ws) (void)hipFree(c->lev_ws);
     if (c->status) (void)hipFree(c->status);
     if (c->status_host) (void)hipHostFree(c->status_host);
@@ -433,13 +446,64 @@ void strsim_split_offsets(uint64_t len, uint64_t n, uint64_t *out)
     }
 }
 
+// Optimal string alignment (strsim_osa.h): k_osa_lane over every row, a read-back of what it left for k_osa_wave (how many rows,
+// how long their patterns can be), then k_osa_wave sized for that.  Every row is complete in stream order; the call occupies a ring
+// slot like any other (its status block carries the ticket and the work-list count) and has nothing to do at retirement.
+static constexpr size_t OSA_SCRATCH_BUDGET = (size_t)1 << 30; // k_osa_wave runs fewer waves rather than use more scratch
+static int pairs_osa(strsim_ctx *c, int slot, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
+                     const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t n)
+{
+    int rc = ctx_reserve((void **)&c->osa_list, &c->osa_list_cap, n * sizeof(uint32_t));
+    if (rc) return rc;
+    if (++c->ticket_seq == 0u) c->ticket_seq = 1u;
+    c->slot_ticket[slot] = c->ticket_seq;
+    memset(&c->status_host[slot], 0, sizeof(DevStatus)); // (the slot is not pending: nothing on the device writes this block now)
+    LaunchArgs la{};
+    la.offA = a_off; la.valA = a_val; la.rowsA = a_rows;
+    la.offB = b_off; la.valB = b_val; la.rowsB = b_rows;
+    la.out = out; la.n = n;
+    la.status = c->status + slot; la.stream = c->stream;
+    HIP_TRY(hipMemsetAsync(la.status, 0, sizeof(DevStatus), c->stream));
+    hipError_t e = launch_osa_lane(la, c->osa_list);
+    if (e != hipSuccess) return hip_fail(e, "kernel launch (k_osa_lane)");
+    HIP_TRY(launch_publish_status(c->status + slot, c->status_host_dev + slot, c->slot_ticket[slot], c->stream));
+    c->enqueued_ops += 3u;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const uint32_t rows = c->status_host[slot].wave_rows, max_pat = c->status_host[slot].max_len;
+    if (rows != 0u) {
+        int grid = c->num_cu * 16;
+        if ((uint64_t)grid > rows) grid = (int)rows;
+        uint32_t *scratch = nullptr;
+        uint64_t slot_words = 0;
+        if (max_pat > OSA_WAVE_LDS_CPS) { // (max_pat bounds the pattern in scalar values: it is a byte length)
+            slot_words = osa_wave_slot_words(max_pat);
+            const size_t per = (size_t)slot_words * sizeof(uint32_t);
+            if ((size_t)grid * per > OSA_SCRATCH_BUDGET) grid = (int)std::max<size_t>(1, OSA_SCRATCH_BUDGET / per);
+            rc = ctx_reserve((void **)&c->osa_scratch, &c->osa_scratch_cap, (size_t)grid * per);
+            if (rc) return rc;
+            scratch = c->osa_scratch;
+        }
+        e = launch_osa_wave(la, c->osa_list, grid, scratch, slot_words);
+        if (e != hipSuccess) return hip_fail(e, "kernel launch (k_osa_wave)");
+        c->enqueued_ops += 1u;
+    }
+    c->slot_timed[slot] = false;
+    c->slot_deferred[slot] = false;
+    c->slot_args[slot] = la;
+    c->slot_measure[slot] = STRSIM_OSA;
+    for (int q = 0; q < STRSIM_NUM_MEASURES; ++q) c->slot_outs[slot][q] = nullptr;
+    c->slot_pending[slot] = true;
+    c->head = (slot + 1) % strsim_ctx::RING;
+    return STRSIM_OK;
+}
+
 static int pairs_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
                              const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, double *const *outs,
                              uint64_t out_rows, bool eager = false)
 {
     const bool all = measure == STRSIM_NUM_MEASURES;
     if (!c) { set_error("strsim_pairs_device: ctx is NULL"); return STRSIM_ERR_ARG; }
-    if (measure < 0 || measure > STRSIM_NUM_MEASURES) {
+    if (!all && !measure_accepted(measure, STRSIM_ENTRY_PAIRWISE)) {
         set_error("strsim_pairs_device: unknown measure %d", measure);
         return STRSIM_ERR_ARG;
     }
@@ -479,6 +543,7 @@ static int pairs_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_off
             return STRSIM_ERR_EARLIER_CALL;
         }
     }
+    if (measure == STRSIM_OSA) return pairs_osa(c, slot, a_off, a_val, a_rows, b_off, b_val, b_rows, outs[0], n);
     const uint64_t nchunks = (n + 63) >> 6;
     // One launch (the lane kernel alone, the rest at retirement if it turns out to be needed) when the caller has opted in and the
     // context's last retired call left nothing behind its lane kernel.  Such a call owns a mask buffer until it is retired (there
@@ -808,7 +873,7 @@ static int best_match_check(const char *who, strsim_ctx_t *c, int measure, const
                             uint64_t q_rows, const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, uint32_t k,
                             double min_score, const void *out_index, const void *out_score)
 {
-    if (measure < 0 || measure >= STRSIM_NUM_MEASURES) { set_error("%s: unknown measure %d", who, measure); return STRSIM_ERR_ARG; }
+    if (!measure_accepted(measure, STRSIM_ENTRY_BEST_MATCH)) { set_error("%s: unknown measure %d", who, measure); return STRSIM_ERR_ARG; }
     if (k < 1u || k > STRSIM_BEST_MATCH_MAX_K) { set_error("%s: k=%u is outside 1..%u", who, k, STRSIM_BEST_MATCH_MAX_K); return STRSIM_ERR_ARG; }
     if (min_score != min_score) { set_error("%s: min_score is NaN", who); return STRSIM_ERR_ARG; }
     if (q_rows > 0xFFFFFFFFull) { set_error("%s: %llu queries (at most 2^32 - 1)", who, (unsigned long long)q_rows); return STRSIM_ERR_ARG; }

@@ -536,7 +536,7 @@ int strsim_codec_create(strsim_ctx_t *ctx, int measure, uint32_t max_chars, strs
 {
     if (!ctx || !out) { set_error("strsim_codec_create: NULL argument"); return STRSIM_ERR_ARG; }
     *out = nullptr;
-    if (measure < 0 || measure >= STRSIM_NUM_MEASURES || max_chars == 0 || max_chars > 255) {
+    if (!measure_accepted(measure, STRSIM_ENTRY_CODEC) || max_chars == 0 || max_chars > 255) {
         set_error("strsim_codec_create: bad measure/max_chars");
         return STRSIM_ERR_ARG;
     }

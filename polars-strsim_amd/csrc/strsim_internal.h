@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "strsim_amd.h"
+
 namespace strsim {
 
 void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
@@ -9,6 +11,18 @@ int hip_fail(hipError_t e, const char *what);
 
 // 64 KB of device scratch owned by the context (strsim_capi.cpp), for strsim_offsets_from_lengths' block sums
 constexpr size_t SCAN_WS_WORDS = 16384;
+
+// Which measures each entry point accepts (strsim_measure_supported answers from here; so do the argument checks).
+inline bool measure_accepted(int measure, int entry_point)
+{
+    const bool reference_five = measure >= 0 && measure < STRSIM_NUM_MEASURES;
+    switch (entry_point) {
+    case STRSIM_ENTRY_PAIRWISE: return reference_five || measure == STRSIM_OSA;
+    case STRSIM_ENTRY_BEST_MATCH: return reference_five;
+    case STRSIM_ENTRY_CODEC: return reference_five;
+    default: return false;
+    }
+}
 
 } // namespace strsim
 

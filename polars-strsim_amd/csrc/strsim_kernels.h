@@ -117,5 +117,12 @@ hipError_t launch_match_fold_rows(uint32_t k, const double *scores, const uint32
 hipError_t launch_match_merge(uint32_t k, const double *pscore, const uint32_t *pidx, uint32_t nl, uint32_t nq, uint32_t *out_index,
                               double *out_score, hipStream_t stream);
 
+// Optimal string alignment (strsim_osa.h), measure id 6.  k_osa_lane over all a.n rows: the rows it cannot take go to `worklist`
+// (a.n words), counted in a.status->wave_rows, with a.status->max_len a bound of their pattern lengths; the caller zeroes the
+// status block first.  k_osa_wave then finishes the work list on `grid` waves, each with slot_words words of `scratch` (patterns
+// longer than OSA_WAVE_LDS_CPS scalar values; nullptr when there are none).
+hipError_t launch_osa_lane(const LaunchArgs &a, uint32_t *worklist);
+hipError_t launch_osa_wave(const LaunchArgs &a, const uint32_t *worklist, int grid, uint32_t *scratch, uint64_t slot_words);
+
 } // namespace strsim
 

@@ -21,6 +21,8 @@
 //                     lane, DPP hand-off), match masks from a per-lane LDS table, texts in a global arena; on bytes
 //                     (ASCII) or on 16-bit scalar values (the reference works on `char`s, strsim.rs:133,189,297).
 //                     Other measures: one pair per wave, scalar values in LDS, ballot matching / histograms.
+//   k_osa_lane / k_osa_wave  optimal string alignment (measure 6, strsim_osa.h): one pair per lane for ASCII strings of up
+//                     to 64 bytes, one pair per wave for the rest; both in stream order, no second pass.
 //   k_huge_pairs<M>   strings beyond WAVE_CAP, scratch in global memory, launched from strsim_ctx_synchronize() only
 //                     when such rows were counted; Levenshtein: the block step in stripes of 64 blocks, any length.
 //
@@ -39,6 +41,7 @@
 #include "strsim_lane_sym.h"
 #include "strsim_kernels.h"
 #include "strsim_lane_common.h"
+#include "strsim_osa.h"
 
 namespace strsim {
 
@@ -435,6 +438,26 @@ hipError_t launch_match_merge(uint32_t k, const double *pscore, const uint32_t *
     if (K == 1) hipLaunchKernelGGL(k_match_merge<1>, g, b, 0, stream, pscore, pidx, nl, nq, k, out_index, out_score);
     else if (K == 4) hipLaunchKernelGGL(k_match_merge<4>, g, b, 0, stream, pscore, pidx, nl, nq, k, out_index, out_score);
     else hipLaunchKernelGGL(k_match_merge<16>, g, b, 0, stream, pscore, pidx, nl, nq, k, out_index, out_score);
+    return hipGetLastError();
+}
+
+hipError_t launch_osa_lane(const LaunchArgs &a, uint32_t *worklist)
+{
+    const unsigned grid = (unsigned)((a.n + 255u) / 256u);
+    const int lit = a.rowsA == a.rowsB ? 0 : (a.rowsA == 1 ? 1 : 2);
+    if (lit == 1)
+        hipLaunchKernelGGL(k_osa_lane<1>, dim3(grid), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, a.out, worklist, a.status);
+    else if (lit == 2)
+        hipLaunchKernelGGL(k_osa_lane<2>, dim3(grid), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, a.out, worklist, a.status);
+    else
+        hipLaunchKernelGGL(k_osa_lane<0>, dim3(grid), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, a.out, worklist, a.status);
+    return hipGetLastError();
+}
+
+hipError_t launch_osa_wave(const LaunchArgs &a, const uint32_t *worklist, int grid, uint32_t *scratch, uint64_t slot_words)
+{
+    hipLaunchKernelGGL(k_osa_wave, dim3((unsigned)grid), dim3(64), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB, a.rowsB,
+                       a.out, worklist, a.status, scratch, slot_words);
     return hipGetLastError();
 }
 

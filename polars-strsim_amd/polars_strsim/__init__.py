@@ -78,8 +78,20 @@ def sorensen_dice(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
     return _similarity("sorensen_dice", expr, other)
 
 
+def osa(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
+    """Optimal string alignment: the restricted Damerau-Levenshtein (OSA) similarity.
+
+    Levenshtein with one more edit: a swap of two adjacent characters costs 1 ("jonh" / "john" is 0.75, not 0.5).  Restricted:
+    no substring is edited twice, so ("ca", "abc") is 3 edits, where the unrestricted Damerau-Levenshtein distance is 2.
+    Normalised like levenshtein: 1 - distance / max(len), over characters; 1.0 when both strings are empty.  Not a measure of
+    the upstream polars-strsim.
+    """
+    return _similarity("osa", expr, other)
+
+
 __all__ = [
     "best_match",
+    "osa",
     "levenshtein",
     "jaro",
     "jaro_winkler",

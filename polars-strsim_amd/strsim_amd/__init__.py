@@ -8,7 +8,7 @@ validity mask), as in README.md:69-70.
 """
 import numpy as np
 
-from ._lib import MEASURES, MEASURE_ID, LIB_PATH, STATUS, ShapeMismatch, StrsimError, lib
+from ._lib import ENTRY_POINT_ID, EXTRA_MEASURES, MEASURES, MEASURE_ID, LIB_PATH, STATUS, ShapeMismatch, StrsimError, lib
 from .context import Codec, Context, device_count, pack_strings, split_offsets
 
 _default_ctx = None
@@ -67,6 +67,19 @@ def sorensen_dice(a, b, ctx=None):
     return similarity("sorensen_dice", a, b, ctx)
 
 
+def osa(a, b, ctx=None):
+    """Optimal string alignment: the restricted Damerau-Levenshtein similarity.  Like levenshtein, with a swap of two adjacent
+    characters counted as one edit; no substring is edited twice (("ca", "abc") is 3 edits, not the unrestricted variant's 2).
+    1.0 - d / max(len(a), len(b)) over characters, 1.0 when both are empty."""
+    return similarity("osa", a, b, ctx)
+
+
+def measure_supported(measure, entry_point="pairwise"):
+    """True if the library's `entry_point` ("pairwise", "best_match" or "codec") accepts `measure`; needs no device."""
+    from ._lib import measure_id
+    return bool(lib().strsim_measure_supported(measure_id(measure), ENTRY_POINT_ID[entry_point]))
+
+
 def best_match(measure, queries, candidates, k=1, min_score=None, ctx=None):
     """For every query, its k best candidates by `measure`: (index int64 [N, k], score f64 [N, k]).  Slots in descending order
     of the score, ties to the lower candidate index; a candidate below min_score is not reported.  Empty slots -- and every slot
@@ -89,4 +102,4 @@ def best_match(measure, queries, candidates, k=1, min_score=None, ctx=None):
 
 
 __all__ = ["best_match", "Codec", "Context", "device_count", "pack_strings", "split_offsets", "similarity", "levenshtein", "jaro",
-           "jaro_winkler", "jaccard", "sorensen_dice", "MEASURES", "MEASURE_ID", "STATUS", "ShapeMismatch", "StrsimError"]
+           "jaro_winkler", "jaccard", "sorensen_dice", "osa", "measure_supported", "MEASURES", "EXTRA_MEASURES", "MEASURE_ID", "STATUS", "ShapeMismatch", "StrsimError"]

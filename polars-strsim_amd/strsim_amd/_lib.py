@@ -12,7 +12,12 @@ PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("STRSIM_AMD_LIB") or os.path.join(PKG_DIR, "polars_strsim", "libpolars_strsim_amd.so")
 
 MEASURES = ("levenshtein", "jaro", "jaro_winkler", "jaccard", "sorensen_dice")  # strsim.rs:9-15
+# Measures beyond the reference's five (pairwise entry points only): optimal string alignment = STRSIM_OSA = 6.  MEASURES stays the
+# reference's five, the list smoke() and the oracle helpers enumerate.
+EXTRA_MEASURES = ("osa",)
 MEASURE_ID = {m: i for i, m in enumerate(MEASURES)}
+MEASURE_ID["osa"] = 6
+ENTRY_POINT_ID = {"pairwise": 0, "best_match": 1, "codec": 2}  # strsim_entry_point_t
 
 STATUS = {0: "OK", 1: "ERR_SHAPE", 2: "ERR_ARG", 3: "ERR_NO_DEVICE", 4: "ERR_HIP", 5: "ERR_OOM", 6: "ERR_DTYPE",
           7: "ERR_INTERNAL", 8: "ERR_EARLIER_CALL"}
@@ -88,6 +93,8 @@ def lib():
         f = getattr(L, name)
         f.restype = i32
         f.argtypes = [vp, i32, vp, vp, u64, vp, vp, u64, C.c_uint32, C.c_double, vp, vp]
+    L.strsim_measure_supported.restype = C.c_uint32
+    L.strsim_measure_supported.argtypes = [i32, i32]
     L.strsim_pairs_device_all.restype = i32
     L.strsim_pairs_device_all.argtypes = [vp, vp, vp, u64, vp, vp, u64, C.POINTER(vp), u64]
     L.strsim_codec_create.restype = i32
