@@ -101,6 +101,12 @@ POLARS_PLUGIN_DECLARE(sorensen_dice)
  * one edit, no substring is edited twice), STRSIM_OSA of strsim_amd.h.  Same inputs, output (Float64 named after input 0), nulls
  * and literal broadcast as the five above. */
 POLARS_PLUGIN_DECLARE(osa)
+/* Not in the reference: bounded integer edit distances (strsim_distance_host of strsim_amd.h), Levenshtein and OSA.  Inputs 0 and 1
+ * as above (shape rule, literal broadcast, nulls); an optional input 2 is max_distance, a length-1 non-null UInt32 series (rows with
+ * a larger distance hold max_distance + 1).  Output: one UInt32 chunk named after input 0.  These calls bypass the small-call
+ * combiner. */
+POLARS_PLUGIN_DECLARE(levenshtein_distance)
+POLARS_PLUGIN_DECLARE(osa_distance)
 
 /* Best match (not in the reference): input 0 = the query column (N rows), input 1 = the candidate column (any number of rows; the
  * length rule of the functions above does not apply).  Output: N rows of an Arrow struct {index: UInt32, score: Float64} named after

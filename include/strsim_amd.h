@@ -221,6 +221,32 @@ STRSIM_API int strsim_best_match_host(strsim_ctx_t *ctx, int measure,
                                       const uint32_t *c_offsets, const uint8_t *c_values, uint64_t c_rows,
                                       uint32_t k, double min_score, uint32_t *out_index, double *out_score);
 
+/*
+ * Bounded edit distances as integers (found by dlsym, like strsim_measure_supported: the ABI version stays 1.7).  `measure` is
+ * STRSIM_LEVENSHTEIN (0: insert, delete, substitute) or STRSIM_OSA (6: plus the restricted swap of two adjacent characters); any
+ * other id is STRSIM_ERR_ARG (strsim_measure_supported does not describe these two entry points).  d is over Unicode scalar values.
+ * out[i] = d when d <= max_distance, else max_distance + 1 (rapidfuzz's score_cutoff convention); STRSIM_DISTANCE_UNBOUNDED is
+ * no cutoff and max_distance = 0 an equality test.  With no cutoff, 1.0 - d / max(|a|, |b|) (1.0 when both are empty) is bit for
+ * bit what strsim_pairs_device returns for the same measure.
+ *
+ * Shape rule, literal broadcast and out_rows as strsim_pairs_device; zero rows is a no-op.  The arguments are checked first and
+ * the context last (a NULL ctx is STRSIM_ERR_ARG too): no argument error needs a device.  Rows where both strings are ASCII and
+ * at most 64 bytes are one pair per lane, every other row one pair per wave (any length; patterns beyond 2048 scalar values use
+ * a scratch buffer the context grows).  Every row is complete in stream order; the call waits once for the stream after its
+ * first kernel (to size the second), so everything enqueued before it has completed when it returns.  It is not a pending call
+ * of strsim_ctx_synchronize and adds nothing to strsim_ctx_last_long_rows / _last_late_rows.  Its kernels read only the bytes
+ * the offsets describe.  The host variant stages the columns (strsim_pairs_host's copy path) and is synchronous.
+ */
+#define STRSIM_DISTANCE_UNBOUNDED 0xFFFFFFFFu
+STRSIM_API int strsim_distance_device(strsim_ctx_t *ctx, int measure,
+                                      const uint32_t *a_offsets, const uint8_t *a_values, uint64_t a_rows,
+                                      const uint32_t *b_offsets, const uint8_t *b_values, uint64_t b_rows,
+                                      uint32_t max_distance, uint32_t *out, uint64_t out_rows);
+STRSIM_API int strsim_distance_host(strsim_ctx_t *ctx, int measure,
+                                    const uint32_t *a_offsets, const uint8_t *a_values, uint64_t a_rows,
+                                    const uint32_t *b_offsets, const uint8_t *b_values, uint64_t b_rows,
+                                    uint32_t max_distance, uint32_t *out, uint64_t out_rows);
+
 /* Row partition used to shard a column over `n` GPUs/ranks: the reference's split_offsets
  * (strsim.rs:21-39).  Writes n (offset,len) pairs into out_offset_len[2*n]. */
 STRSIM_API void strsim_split_offsets(uint64_t len, uint64_t n, uint64_t *out_offset_len);

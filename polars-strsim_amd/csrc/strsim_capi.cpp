@@ -18,6 +18,7 @@
 #include "strsim_kernels.h"
 #define STRSIM_OSA_NO_KERNELS // (constants and sizes only: the kernels are compiled in strsim_kernels.hip)
 #include "strsim_osa.h"
+#include "strsim_distance.h"
 
 namespace strsim {
 
@@ -137,6 +138,10 @@ struct strsim_ctx {
     size_t osa_list_cap = 0;
     uint32_t *osa_scratch = nullptr;
     size_t osa_scratch_cap = 0;
+    // bounded distances (strsim_distance_device): the status block of k_dist_lane and its pinned read-back (the work list and
+    // the scratch are the OSA buffers above)
+    DevStatus *dist_status = nullptr;
+    DevStatus *dist_status_host = nullptr;
 };
 
 static int ctx_set_device(strsim_ctx *c) { HIP_TRY(hipSetDevice(c->device)); return STRSIM_OK; }
@@ -424,6 +429,8 @@ void strsim_ctx_destroy(strsim_ctx_t *c)
     if (c->match_counts_host) (void)hipHostFree(c->match_counts_host);
     if (c->osa_list) (void)hipFree(c->osa_list);
     if (c->osa_scratch) (void)hipFree(c->osa_scratch);
+    if (c->dist_status) (void)hipFree(c->dist_status);
+    if (c->dist_status_host) (void)hipHostFree(c->dist_status_host);
     if (c->lev_ws) (void)hipFree(c->lev_ws);
     if (c->status) (void)hipFree(c->status);
     if (c->status_host) (void)hipHostFree(c->status_host);
@@ -1014,3 +1021,113 @@ int strsim_best_match_host(strsim_ctx_t *c, int measure, const uint32_t *q_off, 
 
 } // extern "C"
 
+// ---- bounded distances (strsim_distance.h) ----
+
+static int distance_check(const char *who, strsim_ctx_t *c, int measure, const uint32_t *a_off, const uint8_t *a_val,
+                          uint64_t a_rows, const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, const uint32_t *out,
+                          uint64_t out_rows)
+{
+    if (measure != STRSIM_LEVENSHTEIN && measure != STRSIM_OSA) {
+        set_error("%s: measure %d has no distance (STRSIM_LEVENSHTEIN or STRSIM_OSA)", who, measure);
+        return STRSIM_ERR_ARG;
+    }
+    if (a_rows != b_rows && a_rows != 1 && b_rows != 1) { // strsim.rs:48-52
+        set_error("Inputs must have the same length, or one of them must be a Utf8 literal.");
+        return STRSIM_ERR_SHAPE;
+    }
+    const uint64_t n = (a_rows == 1) ? b_rows : a_rows;
+    if (out_rows != n) {
+        set_error("%s: out_rows=%llu but the inputs produce %llu rows", who, (unsigned long long)out_rows, (unsigned long long)n);
+        return STRSIM_ERR_ARG;
+    }
+    if (n > 0xFFFFFFFFull) {
+        set_error("%s: %llu rows in one call; split the column (at most 2^32 - 1 rows per call)", who, (unsigned long long)n);
+        return STRSIM_ERR_ARG;
+    }
+    if (n && (!a_off || !a_val || !b_off || !b_val || !out)) { set_error("%s: NULL buffer", who); return STRSIM_ERR_ARG; }
+    if (!c) { set_error("%s: ctx is NULL", who); return STRSIM_ERR_ARG; }
+    return STRSIM_OK;
+}
+
+// k_dist_lane over every row, a read-back of what it left for k_dist_wave, then k_dist_wave sized for that (as pairs_osa).
+static int distance_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
+                                const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, uint32_t k, uint32_t *out, uint64_t n)
+{
+    int rc = ctx_set_device(c);
+    if (rc) return rc;
+    rc = ctx_reserve((void **)&c->osa_list, &c->osa_list_cap, n * sizeof(uint32_t));
+    if (rc) return rc;
+    if (!c->dist_status) HIP_TRY(hipMalloc((void **)&c->dist_status, sizeof(DevStatus)));
+    if (!c->dist_status_host) HIP_TRY(hipHostMalloc((void **)&c->dist_status_host, sizeof(DevStatus), hipHostMallocDefault));
+    LaunchArgs la{};
+    la.offA = a_off; la.valA = a_val; la.rowsA = a_rows;
+    la.offB = b_off; la.valB = b_val; la.rowsB = b_rows;
+    la.n = n;
+    la.status = c->dist_status; la.stream = c->stream;
+    HIP_TRY(hipMemsetAsync(la.status, 0, sizeof(DevStatus), c->stream));
+    hipError_t e = launch_dist_lane(measure, la, k, out, c->osa_list);
+    if (e != hipSuccess) return hip_fail(e, "kernel launch (k_dist_lane)");
+    HIP_TRY(hipMemcpyAsync(c->dist_status_host, c->dist_status, sizeof(DevStatus), hipMemcpyDeviceToHost, c->stream));
+    c->enqueued_ops += 3u;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const uint32_t rows = c->dist_status_host->wave_rows, max_pat = c->dist_status_host->max_len;
+    if (rows == 0u) return STRSIM_OK;
+    int grid = c->num_cu * 16;
+    if ((uint64_t)grid > rows) grid = (int)rows;
+    uint32_t *scratch = nullptr;
+    uint64_t slot_words = 0;
+    if (max_pat > OSA_WAVE_LDS_CPS) { // (a byte length: it bounds the pattern in scalar values)
+        slot_words = dist_wave_slot_words(max_pat);
+        const size_t per = (size_t)slot_words * sizeof(uint32_t);
+        if ((size_t)grid * per > OSA_SCRATCH_BUDGET) grid = (int)std::max<size_t>(1, OSA_SCRATCH_BUDGET / per);
+        rc = ctx_reserve((void **)&c->osa_scratch, &c->osa_scratch_cap, (size_t)grid * per);
+        if (rc) return rc;
+        scratch = c->osa_scratch;
+    }
+    e = launch_dist_wave(measure, la, k, out, c->osa_list, grid, scratch, slot_words);
+    if (e != hipSuccess) return hip_fail(e, "kernel launch (k_dist_wave)");
+    c->enqueued_ops += 1u;
+    return STRSIM_OK;
+}
+
+extern "C" {
+
+int strsim_distance_device(strsim_ctx_t *c, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
+                           const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, uint32_t max_distance, uint32_t *out,
+                           uint64_t out_rows)
+{
+    int rc = distance_check("strsim_distance_device", c, measure, a_off, a_val, a_rows, b_off, b_val, b_rows, out, out_rows);
+    if (rc || out_rows == 0) return rc;
+    return distance_device_impl(c, measure, a_off, a_val, a_rows, b_off, b_val, b_rows, max_distance, out, out_rows);
+}
+
+int strsim_distance_host(strsim_ctx_t *c, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
+                         const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, uint32_t max_distance, uint32_t *out,
+                         uint64_t out_rows)
+{
+    int rc = distance_check("strsim_distance_host", c, measure, a_off, a_val, a_rows, b_off, b_val, b_rows, out, out_rows);
+    if (rc || out_rows == 0) return rc;
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    const uint64_t n = out_rows;
+    // (as strsim_pairs_host's copy path: the caller's offset base is kept and the values go up from byte 0)
+    const size_t need[5] = {(a_rows + 1) * 4, (size_t)a_off[a_rows] + 1, (b_rows + 1) * 4, (size_t)b_off[b_rows] + 1, n * 4};
+    for (int i = 0; i < 5; ++i) {
+        rc = ctx_reserve(&c->stage[i], &c->stage_cap[i], need[i]);
+        if (rc) return rc;
+    }
+    hipStream_t st = c->stream;
+    HIP_TRY(hipMemcpyAsync(c->stage[0], a_off, (a_rows + 1) * 4, hipMemcpyHostToDevice, st));
+    if (a_off[a_rows]) HIP_TRY(hipMemcpyAsync(c->stage[1], a_val, a_off[a_rows], hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c->stage[2], b_off, (b_rows + 1) * 4, hipMemcpyHostToDevice, st));
+    if (b_off[b_rows]) HIP_TRY(hipMemcpyAsync(c->stage[3], b_val, b_off[b_rows], hipMemcpyHostToDevice, st));
+    rc = distance_device_impl(c, measure, (const uint32_t *)c->stage[0], (const uint8_t *)c->stage[1], a_rows,
+                              (const uint32_t *)c->stage[2], (const uint8_t *)c->stage[3], b_rows, max_distance,
+                              (uint32_t *)c->stage[4], n);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->stage[4], n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return STRSIM_OK;
+}
+
+} // extern "C"

@@ -124,5 +124,11 @@ hipError_t launch_match_merge(uint32_t k, const double *pscore, const uint32_t *
 hipError_t launch_osa_lane(const LaunchArgs &a, uint32_t *worklist);
 hipError_t launch_osa_wave(const LaunchArgs &a, const uint32_t *worklist, int grid, uint32_t *scratch, uint64_t slot_words);
 
+// Bounded edit distances (strsim_distance.h): measure 0 (Levenshtein) or 6 (OSA), uint32 outputs (a.out is not used).  The same
+// two-kernel protocol as the OSA launches above: k_dist_lane over all a.n rows, then k_dist_wave over its work list.
+hipError_t launch_dist_lane(int measure, const LaunchArgs &a, uint32_t k, uint32_t *out, uint32_t *worklist);
+hipError_t launch_dist_wave(int measure, const LaunchArgs &a, uint32_t k, uint32_t *out, const uint32_t *worklist, int grid,
+                            uint32_t *scratch, uint64_t slot_words);
+
 } // namespace strsim
 

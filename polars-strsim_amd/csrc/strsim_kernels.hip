@@ -23,6 +23,8 @@
 //                     Other measures: one pair per wave, scalar values in LDS, ballot matching / histograms.
 //   k_osa_lane / k_osa_wave  optimal string alignment (measure 6, strsim_osa.h): one pair per lane for ASCII strings of up
 //                     to 64 bytes, one pair per wave for the rest; both in stream order, no second pass.
+//   k_dist_lane / k_dist_wave  bounded integer edit distances (Levenshtein, OSA; strsim_distance.h): the same two tiers, uint32
+//                     outputs, a length prefilter and, in the wave tier, the block cutoff of Myers / Ukkonen.
 //   k_huge_pairs<M>   strings beyond WAVE_CAP, scratch in global memory, launched from strsim_ctx_synchronize() only
 //                     when such rows were counted; Levenshtein: the block step in stripes of 64 blocks, any length.
 //
@@ -42,6 +44,7 @@
 #include "strsim_kernels.h"
 #include "strsim_lane_common.h"
 #include "strsim_osa.h"
+#include "strsim_distance.h"
 
 namespace strsim {
 
@@ -458,6 +461,38 @@ hipError_t launch_osa_wave(const LaunchArgs &a, const uint32_t *worklist, int gr
 {
     hipLaunchKernelGGL(k_osa_wave, dim3((unsigned)grid), dim3(64), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB, a.rowsB,
                        a.out, worklist, a.status, scratch, slot_words);
+    return hipGetLastError();
+}
+
+template <bool TR>
+static void launch_dist_lane_tr(const LaunchArgs &a, uint32_t k, uint32_t *out, uint32_t *worklist)
+{
+    const unsigned grid = (unsigned)((a.n + 255u) / 256u);
+    const int lit = a.rowsA == a.rowsB ? 0 : (a.rowsA == 1 ? 1 : 2);
+    if (lit == 1)
+        hipLaunchKernelGGL((k_dist_lane<TR, 1>), dim3(grid), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, k, out, worklist, a.status);
+    else if (lit == 2)
+        hipLaunchKernelGGL((k_dist_lane<TR, 2>), dim3(grid), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, k, out, worklist, a.status);
+    else
+        hipLaunchKernelGGL((k_dist_lane<TR, 0>), dim3(grid), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, k, out, worklist, a.status);
+}
+
+hipError_t launch_dist_lane(int measure, const LaunchArgs &a, uint32_t k, uint32_t *out, uint32_t *worklist)
+{
+    if (measure == OSA) launch_dist_lane_tr<true>(a, k, out, worklist);
+    else launch_dist_lane_tr<false>(a, k, out, worklist);
+    return hipGetLastError();
+}
+
+hipError_t launch_dist_wave(int measure, const LaunchArgs &a, uint32_t k, uint32_t *out, const uint32_t *worklist, int grid,
+                            uint32_t *scratch, uint64_t slot_words)
+{
+    if (measure == OSA)
+        hipLaunchKernelGGL(k_dist_wave<true>, dim3((unsigned)grid), dim3(64), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB,
+                           a.rowsB, k, out, worklist, a.status, scratch, slot_words);
+    else
+        hipLaunchKernelGGL(k_dist_wave<false>, dim3((unsigned)grid), dim3(64), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB,
+                           a.rowsB, k, out, worklist, a.status, scratch, slot_words);
     return hipGetLastError();
 }
 

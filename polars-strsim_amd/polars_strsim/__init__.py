@@ -89,8 +89,37 @@ def osa(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
     return _similarity("osa", expr, other)
 
 
+def _distance(function_name: str, expr: IntoExpr, other: IntoExpr, max_distance: int | None) -> pl.Expr:
+    args = [parse_into_expr(expr), other]
+    if max_distance is not None:
+        args.append(pl.lit(max_distance, dtype=pl.UInt32))
+    return register_plugin_function(
+        plugin_path=_PLUGIN_DIR,
+        function_name=function_name,
+        args=args,
+        is_elementwise=True,
+    )
+
+
+def levenshtein_distance(expr: IntoExpr, other: IntoExpr, max_distance: int | None = None) -> pl.Expr:
+    """Levenshtein distance (insert, delete, substitute, each 1) over characters, as UInt32.
+
+    With max_distance=k a row is the distance when it is at most k and k + 1 otherwise (rapidfuzz's score_cutoff), which the GPU
+    decides early: `levenshtein_distance(a, b, max_distance=2) <= 2` is "at most two typos".  Not in the upstream polars-strsim.
+    """
+    return _distance("levenshtein_distance", expr, other, max_distance)
+
+
+def osa_distance(expr: IntoExpr, other: IntoExpr, max_distance: int | None = None) -> pl.Expr:
+    """Optimal string alignment distance: levenshtein_distance plus a swap of two adjacent characters costing 1, no substring
+    edited twice.  max_distance as in levenshtein_distance.  Not in the upstream polars-strsim."""
+    return _distance("osa_distance", expr, other, max_distance)
+
+
 __all__ = [
     "best_match",
+    "levenshtein_distance",
+    "osa_distance",
     "osa",
     "levenshtein",
     "jaro",

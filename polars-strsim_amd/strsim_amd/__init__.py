@@ -8,7 +8,7 @@ validity mask), as in README.md:69-70.
 """
 import numpy as np
 
-from ._lib import ENTRY_POINT_ID, EXTRA_MEASURES, MEASURES, MEASURE_ID, LIB_PATH, STATUS, ShapeMismatch, StrsimError, lib
+from ._lib import DISTANCE_MEASURES, DISTANCE_UNBOUNDED, ENTRY_POINT_ID, EXTRA_MEASURES, MEASURES, MEASURE_ID, LIB_PATH, STATUS, ShapeMismatch, StrsimError, lib
 from .context import Codec, Context, device_count, pack_strings, split_offsets
 
 _default_ctx = None
@@ -80,6 +80,36 @@ def measure_supported(measure, entry_point="pairwise"):
     return bool(lib().strsim_measure_supported(measure_id(measure), ENTRY_POINT_ID[entry_point]))
 
 
+def distance(measure, a, b, max_distance=None, ctx=None):
+    """Integer edit distance ("levenshtein" or "osa", DISTANCE_MEASURES) over characters, for two columns / a column and a
+    literal -> numpy.ma.MaskedArray of uint32, masked where either input is null.  With max_distance=k a row is d when d <= k and
+    k + 1 otherwise (rapidfuzz's score_cutoff convention); None is no cutoff."""
+    if measure not in DISTANCE_MEASURES:
+        raise ValueError(f"no distance for measure {measure!r} (one of {DISTANCE_MEASURES})")
+    ctx = ctx or default_context()
+    A, va = _as_column(a)
+    B, vb = _as_column(b)
+    ao, av = pack_strings(A)
+    bo, bv = pack_strings(B)
+    out = ctx.distance_host(measure, ao, av, bo, bv, max_distance)
+    n = out.size
+    mask = np.zeros(n, dtype=bool)
+    for v in (va, vb):
+        if v is not None:
+            mask |= ~(np.broadcast_to(v, (n,)) if v.size == 1 else v)
+    return np.ma.MaskedArray(out, mask=mask)
+
+
+def levenshtein_distance(a, b, max_distance=None, ctx=None):
+    """Levenshtein distance (insert, delete, substitute) over characters; see distance()."""
+    return distance("levenshtein", a, b, max_distance, ctx)
+
+
+def osa_distance(a, b, max_distance=None, ctx=None):
+    """Optimal string alignment distance (Levenshtein plus the restricted swap of two adjacent characters); see distance()."""
+    return distance("osa", a, b, max_distance, ctx)
+
+
 def best_match(measure, queries, candidates, k=1, min_score=None, ctx=None):
     """For every query, its k best candidates by `measure`: (index int64 [N, k], score f64 [N, k]).  Slots in descending order
     of the score, ties to the lower candidate index; a candidate below min_score is not reported.  Empty slots -- and every slot
@@ -102,4 +132,5 @@ def best_match(measure, queries, candidates, k=1, min_score=None, ctx=None):
 
 
 __all__ = ["best_match", "Codec", "Context", "device_count", "pack_strings", "split_offsets", "similarity", "levenshtein", "jaro",
-           "jaro_winkler", "jaccard", "sorensen_dice", "osa", "measure_supported", "MEASURES", "EXTRA_MEASURES", "MEASURE_ID", "STATUS", "ShapeMismatch", "StrsimError"]
+           "jaro_winkler", "jaccard", "sorensen_dice", "osa", "measure_supported", "distance", "levenshtein_distance", "osa_distance",
+           "DISTANCE_MEASURES", "DISTANCE_UNBOUNDED", "MEASURES", "EXTRA_MEASURES", "MEASURE_ID", "STATUS", "ShapeMismatch", "StrsimError"]

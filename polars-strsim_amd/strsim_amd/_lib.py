@@ -18,6 +18,9 @@ EXTRA_MEASURES = ("osa",)
 MEASURE_ID = {m: i for i, m in enumerate(MEASURES)}
 MEASURE_ID["osa"] = 6
 ENTRY_POINT_ID = {"pairwise": 0, "best_match": 1, "codec": 2}  # strsim_entry_point_t
+# The measures strsim_distance_device / _host accept (integer edit distances), with their ids; STRSIM_DISTANCE_UNBOUNDED = no cutoff.
+DISTANCE_MEASURES = ("levenshtein", "osa")
+DISTANCE_UNBOUNDED = 0xFFFFFFFF
 
 STATUS = {0: "OK", 1: "ERR_SHAPE", 2: "ERR_ARG", 3: "ERR_NO_DEVICE", 4: "ERR_HIP", 5: "ERR_OOM", 6: "ERR_DTYPE",
           7: "ERR_INTERNAL", 8: "ERR_EARLIER_CALL"}
@@ -93,6 +96,10 @@ def lib():
         f = getattr(L, name)
         f.restype = i32
         f.argtypes = [vp, i32, vp, vp, u64, vp, vp, u64, C.c_uint32, C.c_double, vp, vp]
+    for name in ("strsim_distance_device", "strsim_distance_host"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, i32, vp, vp, u64, vp, vp, u64, C.c_uint32, vp, u64]
     L.strsim_measure_supported.restype = C.c_uint32
     L.strsim_measure_supported.argtypes = [i32, i32]
     L.strsim_pairs_device_all.restype = i32

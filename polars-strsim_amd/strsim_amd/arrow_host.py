@@ -104,10 +104,11 @@ def _chunks(x, layout):
     return out, dtype
 
 
-def call_plugin(name, a, b, layout="vu", names=("a", "b"), parallel=False, _probe=None, out_type=None):
+def call_plugin(name, a, b, layout="vu", names=("a", "b"), parallel=False, _probe=None, out_type=None, *, extra=()):
     """Evaluate plugin expression `name` over two columns (lists / pyarrow arrays / a single literal).
     Returns a pyarrow ChunkedArray of float64 (or of `out_type`: the best_match_* functions return a struct).  `layout` picks
-    the Arrow string layout sent to the plugin."""
+    the Arrow string layout sent to the plugin.  `extra`: further inputs after the two columns, pyarrow arrays exported as they
+    are (the *_distance functions take max_distance as a one-row UInt32 array)."""
     out_type = pa.float64() if out_type is None else out_type
     L = _load()
     fn = getattr(L, "_polars_plugin_" + name)
@@ -116,15 +117,20 @@ def call_plugin(name, a, b, layout="vu", names=("a", "b"), parallel=False, _prob
                    C.POINTER(CallerContext)]
     L._polars_plugin_get_last_error_message.restype = C.c_char_p
     exported = []
-    inputs = (SeriesExport * 2)()
+    inputs = (SeriesExport * (2 + len(extra)))()
     for i, x in enumerate((a, b)):
         chunks, dtype = _chunks(x, layout if isinstance(layout, str) else layout[i])
         ex = _Exported(names[i], chunks, dtype)
         ex.fill(inputs[i])
         exported.append(ex)
+    for i, x in enumerate(extra):
+        chunks = list(x.chunks) if isinstance(x, pa.ChunkedArray) else [x]
+        ex = _Exported("extra%d" % i, chunks, chunks[0].type)
+        ex.fill(inputs[2 + i])
+        exported.append(ex)
     ret = SeriesExport()  # SeriesExport::empty()
     ctx = CallerContext(1 if parallel else 0)
-    fn(inputs, 2, None, 0, C.byref(ret), C.byref(ctx))
+    fn(inputs, len(inputs), None, 0, C.byref(ret), C.byref(ctx))
     if _probe is not None:
         _probe["series_released"] = [e.released for e in exported]
         _probe["arrays_released"] = [e.arrays_released() for e in exported]

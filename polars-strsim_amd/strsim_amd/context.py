@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check, lib, measure_id
+from ._lib import DISTANCE_UNBOUNDED, check, lib, measure_id
 
 
 def split_offsets(length, n):
@@ -169,6 +169,26 @@ class Context:
                                             b_offsets.data_ptr(), b_values.data_ptr(), rb, arr, n))
         return outs
 
+    def distance_device(self, measure, a_offsets, a_values, b_offsets, b_values, max_distance=None, out=None):
+        """Bounded edit distances (strsim_distance_device) of device tensors laid out as for pairs_device -> uint32 values in an
+        int32 tensor (torch has no uint32 arithmetic; read it with .view or & 0xFFFFFFFF).  measure: "levenshtein" or "osa";
+        max_distance=None is no cutoff, else rows beyond it hold max_distance + 1.  Complete in stream order."""
+        import torch
+        ra, rb = a_offsets.numel() - 1, b_offsets.numel() - 1
+        n = rb if ra == 1 else ra
+        for t in (a_offsets, b_offsets):
+            assert t.is_cuda and t.element_size() == 4 and t.is_contiguous()
+        for t in (a_values, b_values):
+            assert t.is_cuda and t.element_size() == 1 and t.is_contiguous()
+        if out is None:
+            out = torch.empty(n if (ra == rb or ra == 1 or rb == 1) else 0, dtype=torch.int32, device=a_offsets.device)
+        assert out.is_cuda and out.device == a_offsets.device and out.element_size() == 4 and out.is_contiguous() \
+            and not out.is_floating_point(), "out must be a contiguous 4-byte integer tensor on the inputs' device"
+        check(lib().strsim_distance_device(self._h, measure_id(measure), a_offsets.data_ptr(), a_values.data_ptr(), ra,
+                                           b_offsets.data_ptr(), b_values.data_ptr(), rb, _max_distance(max_distance),
+                                           out.data_ptr(), out.numel()))
+        return out
+
     # ---- host-resident (numpy) ---------------------------------------------------------------------
     def pairs_host(self, measure, a_offsets, a_values, b_offsets, b_values):
         """Synchronous: numpy uint32 offsets + uint8 values in, numpy f64 out."""
@@ -189,6 +209,25 @@ class Context:
                                       bo.ctypes.data, bv.ctypes.data, rb, out.ctypes.data, n))
         return out
 
+
+    def distance_host(self, measure, a_offsets, a_values, b_offsets, b_values, max_distance=None):
+        """Synchronous bounded edit distances (strsim_distance_host): numpy uint32 offsets + uint8 values in, numpy uint32 out."""
+        ao = np.ascontiguousarray(a_offsets, dtype=np.uint32)
+        bo = np.ascontiguousarray(b_offsets, dtype=np.uint32)
+        av = np.ascontiguousarray(a_values, dtype=np.uint8)
+        bv = np.ascontiguousarray(b_values, dtype=np.uint8)
+        if av.size == 0:
+            av = np.zeros(1, dtype=np.uint8)
+        if bv.size == 0:
+            bv = np.zeros(1, dtype=np.uint8)
+        ra, rb = ao.size - 1, bo.size - 1
+        n = rb if ra == 1 else ra
+        if ra != rb and ra != 1 and rb != 1:
+            n = 0
+        out = np.empty(n, dtype=np.uint32)
+        check(lib().strsim_distance_host(self._h, measure_id(measure), ao.ctypes.data, av.ctypes.data, ra,
+                                         bo.ctypes.data, bv.ctypes.data, rb, _max_distance(max_distance), out.ctypes.data, n))
+        return out
 
     def best_match(self, measure, q_offsets, q_values, c_offsets, c_values, k=1, min_score=None):
         """Synchronous best match (strsim_best_match_host, ABI 1.7): numpy uint32 offsets + uint8 values of the queries and the
@@ -315,6 +354,16 @@ class Codec:
         ctx = ctx or self.ctx
         check(lib().strsim_codec_patch(ctx._h, out.data_ptr(), int(row_base), exc_rows.data_ptr(), exc_vals.data_ptr(),
                                        int(count)))
+
+
+def _max_distance(k):
+    """None -> STRSIM_DISTANCE_UNBOUNDED; else an int in 0 .. 2^32 - 1."""
+    if k is None:
+        return DISTANCE_UNBOUNDED
+    k = int(k)
+    if not 0 <= k <= DISTANCE_UNBOUNDED:
+        raise ValueError(f"max_distance={k} is outside 0 .. {DISTANCE_UNBOUNDED}")
+    return k
 
 
 def pack_strings(strings):
