@@ -1,12 +1,17 @@
 #!/bin/bash
 # Registers / LDS / scratch of the kernels in csrc/strsim_kernels.hip (device-only compile, then the code object's metadata).
-#   bash bench_support/kernel_resources.sh [name-filter-regex] [EXTRA flags]
+#   bash bench_support/kernel_resources.sh [name-filter-regex | group] [EXTRA flags]
+# groups: nearest -- the kernels of strsim_nearest_device (its own and the best-match kernels it reuses)
 ROOT=$(cd "$(dirname "$0")/.." && pwd); OUT=${TMPDIR:-/tmp}/strsim_co; mkdir -p $OUT
+case "$1" in
+    nearest) FILTER='k_nearest_|k_match_pack|k_match_clear|k_match_fold|k_match_merge' ;;
+    *) FILTER=${1:-.} ;;
+esac
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I$ROOT/include -I$ROOT/polars-strsim_amd/csrc $2 \
   --cuda-device-only -c -x hip $ROOT/polars-strsim_amd/csrc/strsim_kernels.hip -o $OUT/k.co 2>/dev/null || { echo "compile failed"; exit 1; }
 /opt/rocm/lib/llvm/bin/clang-offload-bundler --unbundle --type=o --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --input=$OUT/k.co --output=$OUT/k.elf
 /opt/rocm/lib/llvm/bin/llvm-readelf --notes $OUT/k.elf > $OUT/notes.txt
-python3 - "$OUT/notes.txt" "${1:-.}" <<'PY'
+python3 - "$OUT/notes.txt" "$FILTER" <<'PY'
 import re, subprocess, sys
 t = open(sys.argv[1]).read()
 for e in re.split(r'\n\s+- \.agpr_count:', t)[1:]:

@@ -119,6 +119,14 @@ POLARS_PLUGIN_DECLARE(best_match_jaro_winkler)
 POLARS_PLUGIN_DECLARE(best_match_jaccard)
 POLARS_PLUGIN_DECLARE(best_match_sorensen_dice)
 
+/* Nearest match by bounded edit distance (not in the reference): inputs 0 and 1 as best match (queries, candidates of any length),
+ * an optional input 2 is max_distance, parsed as the *_distance functions parse it.  Output: N rows of an Arrow struct
+ * {index: UInt32, distance: UInt32} named after input 0 -- the candidate with the smallest Levenshtein / OSA distance within
+ * max_distance (ties to the lower index; the index is its row in input 1), as strsim_nearest_host with k = 1.  Null where the query
+ * is null or no non-null candidate is within max_distance; null candidates are never matched. */
+POLARS_PLUGIN_DECLARE(nearest_levenshtein)
+POLARS_PLUGIN_DECLARE(nearest_osa)
+
 /* ---- diagnostics of this implementation (not part of the polars-ffi contract; the engine never calls them) ----
  * The plugin's staging -- pinned host memory and its device mirrors, per pipeline set -- is leased per call from one process-wide
  * pool under POLARS_STRSIM_STAGING_BUDGET_MB (csrc/plugin_pack.h: StagingPool; reference counterpart: the per-call scratch of

@@ -247,6 +247,41 @@ STRSIM_API int strsim_distance_host(strsim_ctx_t *ctx, int measure,
                                     const uint32_t *b_offsets, const uint8_t *b_values, uint64_t b_rows,
                                     uint32_t max_distance, uint32_t *out, uint64_t out_rows);
 
+/*
+ * Nearest match by bounded edit distance (found by dlsym, like the distance calls: the ABI version stays 1.7, and
+ * strsim_measure_supported does not describe these two entry points).  `measure` is STRSIM_LEVENSHTEIN or STRSIM_OSA; any other
+ * id is STRSIM_ERR_ARG.  d(i, j) is exactly what strsim_distance_device(measure, queries[i], candidates[j],
+ * STRSIM_DISTANCE_UNBOUNDED) returns: the edit distance over Unicode scalar values.  Row-major outputs of q_rows x k (uint32):
+ * query i gets the (up to) k candidates j with the smallest d(i, j) <= max_distance, in ascending order of d, ties to the lower
+ * candidate index -- one total order, so the result does not depend on the order in which candidates are visited.  Slots left
+ * empty hold index 0xFFFFFFFF and distance 0xFFFFFFFF.  STRSIM_DISTANCE_UNBOUNDED is no cutoff; max_distance = 0 reports exact
+ * matches only.
+ *
+ * 1 <= k <= STRSIM_NEAREST_MAX_K, q_rows <= 2^32 - 1, c_rows <= 2^32 - 2; c_rows == 0 is allowed (every slot empty) and
+ * q_rows == 0 is a no-op.  A NULL buffer of a non-empty side or output, a bad measure or k: STRSIM_ERR_ARG.  The arguments are
+ * checked first, the context last (a NULL ctx is STRSIM_ERR_ARG too): no argument error needs a device.  Nulls are not seen here:
+ * a caller drops null candidates and maps the indices back.
+ *
+ * Device-resident: the same column layout as strsim_pairs_device.  Reads beyond the strings: none by the kernels of this call
+ * (each string is read byte by byte within its offsets).  Strings of at most 32 ASCII bytes are searched one query per lane, in
+ * length order, visiting only candidate lengths that can still enter a list; every pair with a longer or non-ASCII side goes
+ * through strsim_distance_device (that string as the literal, max_distance passed on) and reads what it documents.
+ * The call waits once for the stream (a read-back of how many strings fall outside the one-query-per-lane class).  Without such
+ * strings it then returns with the search enqueued: results are complete after strsim_ctx_synchronize(), or in stream order.
+ * With them it runs those pairs through strsim_distance_device batch by batch, each of which waits for the stream.
+ */
+#define STRSIM_NEAREST_MAX_K 16u
+STRSIM_API int strsim_nearest_device(strsim_ctx_t *ctx, int measure,
+                                     const uint32_t *q_offsets, const uint8_t *q_values, uint64_t q_rows,
+                                     const uint32_t *c_offsets, const uint8_t *c_values, uint64_t c_rows,
+                                     uint32_t k, uint32_t max_distance, uint32_t *out_index, uint32_t *out_distance);
+
+/* The same with HOST-RESIDENT buffers (the column layout of strsim_pairs_host); synchronous. */
+STRSIM_API int strsim_nearest_host(strsim_ctx_t *ctx, int measure,
+                                   const uint32_t *q_offsets, const uint8_t *q_values, uint64_t q_rows,
+                                   const uint32_t *c_offsets, const uint8_t *c_values, uint64_t c_rows,
+                                   uint32_t k, uint32_t max_distance, uint32_t *out_index, uint32_t *out_distance);
+
 /* Row partition used to shard a column over `n` GPUs/ranks: the reference's split_offsets
  * (strsim.rs:21-39).  Writes n (offset,len) pairs into out_offset_len[2*n]. */
 STRSIM_API void strsim_split_offsets(uint64_t len, uint64_t n, uint64_t *out_offset_len);

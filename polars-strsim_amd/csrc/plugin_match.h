@@ -69,8 +69,8 @@ void fill_named_schema(ArrowSchema *s, const char *format, const char *name)
     s->format = format;
 }
 
-// {index: UInt32, score: Float64}, nullable, named `name`
-void fill_match_schema(ArrowSchema *s, const char *name)
+// {index: UInt32, <second>: <format>}, nullable, named `name` (best match: {index: UInt32, score: Float64})
+void fill_match_schema(ArrowSchema *s, const char *name, const char *second = "score", const char *format = "g")
 {
     memset(s, 0, sizeof *s);
     std::unique_ptr<StructSchemaPriv> p(new StructSchemaPriv{nullptr, {nullptr, nullptr}, {nullptr, nullptr}});
@@ -83,7 +83,7 @@ void fill_match_schema(ArrowSchema *s, const char *name)
         p->child[i] = static_cast<ArrowSchema *>(calloc(1, sizeof(ArrowSchema)));
         if (!p->child[i]) break;
         try {
-            fill_named_schema(p->child[i], i == 0 ? "I" : "g", i == 0 ? "index" : "score");
+            fill_named_schema(p->child[i], i == 0 ? "I" : format, i == 0 ? "index" : second);
         } catch (...) {
             undo();
             throw;
@@ -128,52 +128,29 @@ void pack_column(const Column &c, bool valid_only, std::vector<uint32_t> &off, s
     }
 }
 
-void run_best_match(int measure, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret)
-{
-    if (n_inputs != 2) fail("best_match: expected 2 input series (queries, candidates), got " + std::to_string(n_inputs));
-    Column q, c;
-    describe(inputs[0], q);
-    describe(inputs[1], c);
-    if (q.rows > 0xFFFFFFFFull) fail("best_match: more than 2^32 - 1 queries");
-    if (c.rows > 0xFFFFFFFEull) fail("best_match: more than 2^32 - 2 candidates");
-    const uint64_t n = q.rows;
-    std::vector<uint32_t> qo, co, pos;
-    std::vector<uint8_t> qv, cv;
-    pack_column(q, false, qo, qv, nullptr);
-    pack_column(c, true, co, cv, &pos);
-    const uint64_t m = pos.size();
+// Every buffer and box of a struct result, allocated before any of it is handed over; until then the destructor frees them.
+// buf: index (4 bytes a row), the second child (`width` bytes a row), the struct validity, the two child validities.
+struct MatchOwned {
+    void *buf[5] = {};
+    void *box[4] = {}; // two child arrays, the struct array, the schema
+    MatchOwned(uint64_t n, size_t width)
+    {
+        const size_t vbytes = (n + 63) / 64 * 8;
+        for (int b = 0; b < 5; ++b) buf[b] = alloc64(b == 0 ? n * 4 : (b == 1 ? n * width : vbytes));
+        for (int b = 0; b < 3; ++b)
+            if (!(box[b] = calloc(1, sizeof(ArrowArray)))) throw std::bad_alloc();
+        if (!(box[3] = calloc(1, sizeof(ArrowSchema)))) throw std::bad_alloc();
+    }
+    ~MatchOwned() { for (void *x : buf) free(x); for (void *x : box) free(x); }
+};
 
-    // every buffer and box of the result is allocated before any of it is handed over; until then `own` frees them
+// Hands the buffers of `own` to `ret` as one struct chunk {index: UInt32, <second>: <format>} of n rows named `name`.  The
+// caller has filled in the struct validity (own.buf[2], `nulls` rows clear); it is copied to both children here.
+void export_match_struct(MatchOwned &own, uint64_t n, int64_t nulls, const char *name, const char *second, const char *format,
+                         SeriesExport *ret)
+{
     const size_t vbytes = (n + 63) / 64 * 8;
-    struct Owned {
-        void *buf[5] = {};        // index, score, struct validity, child validities
-        void *box[4] = {};        // two child arrays, the struct array, the schema
-        ~Owned() { for (void *x : buf) free(x); for (void *x : box) free(x); }
-    } own;
-    for (int b = 0; b < 5; ++b) own.buf[b] = alloc64(b == 0 ? n * 4 : (b == 1 ? n * 8 : vbytes));
-    for (int b = 0; b < 3; ++b)
-        if (!(own.box[b] = calloc(1, sizeof(ArrowArray)))) throw std::bad_alloc();
-    if (!(own.box[3] = calloc(1, sizeof(ArrowSchema)))) throw std::bad_alloc();
-    uint32_t *const idx = static_cast<uint32_t *>(own.buf[0]);
-    double *const score = static_cast<double *>(own.buf[1]);
     uint8_t *const valid = static_cast<uint8_t *>(own.buf[2]);
-    if (n) {
-        // the lease is for its context: this call's device memory is the context's staging and search workspace (strsim_capi.cpp),
-        // reserved here against the staging budget at its size -- strings, offsets, outputs, packed strings and partial lists
-        const uint64_t lists = std::min<uint64_t>((uint64_t)1 << 24, n * 65535u) + n;
-        const uint64_t need = 2 * (qv.size() + cv.size() + 4 * (n + m + 2)) + 12 * n + 44 * (n + m) + 12 * lists;
-        PipeLease lease(need);
-        strsim_ctx_t *ctx = lease.set->at(0).open(plugin_devices()[0]);
-        if (strsim_best_match_host(ctx, measure, qo.data(), qv.data(), n, co.data(), cv.data(), m, 1, -__builtin_inf(), idx, score) != STRSIM_OK)
-            fail(strsim_last_error_message());
-    }
-    int64_t nulls = 0;
-    memset(valid, 0, vbytes);
-    for (uint64_t r = 0; r < n; ++r) {
-        const bool ok = idx[r] != 0xFFFFFFFFu && row_valid(q, r);
-        if (ok) { valid[r >> 3] |= (uint8_t)(1u << (r & 7)); idx[r] = pos[idx[r]]; }
-        else { ++nulls; idx[r] = 0; score[r] = 0.0; }
-    }
     memcpy(own.buf[3], valid, vbytes);
     memcpy(own.buf[4], valid, vbytes);
 
@@ -185,7 +162,7 @@ void run_best_match(int measure, SeriesExport *inputs, size_t n_inputs, SeriesEx
     spr->arrays = static_cast<ArrowArray **>(calloc(1, sizeof(ArrowArray *)));
     if (!spr->arrays) throw std::bad_alloc();
     try {
-        fill_match_schema(schema, q.name.c_str()); // (the last step that may throw)
+        fill_match_schema(schema, name, second, format); // (the last step that may throw)
     } catch (...) {
         free(spr->arrays);
         throw;
@@ -218,6 +195,48 @@ void run_best_match(int measure, SeriesExport *inputs, size_t n_inputs, SeriesEx
     ret->len = 1;
     ret->release = release_series;
     ret->private_data = spr.release();
+}
+
+
+void run_best_match(int measure, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret)
+{
+    if (n_inputs != 2) fail("best_match: expected 2 input series (queries, candidates), got " + std::to_string(n_inputs));
+    Column q, c;
+    describe(inputs[0], q);
+    describe(inputs[1], c);
+    if (q.rows > 0xFFFFFFFFull) fail("best_match: more than 2^32 - 1 queries");
+    if (c.rows > 0xFFFFFFFEull) fail("best_match: more than 2^32 - 2 candidates");
+    const uint64_t n = q.rows;
+    std::vector<uint32_t> qo, co, pos;
+    std::vector<uint8_t> qv, cv;
+    pack_column(q, false, qo, qv, nullptr);
+    pack_column(c, true, co, cv, &pos);
+    const uint64_t m = pos.size();
+
+    // every buffer and box of the result is allocated before any of it is handed over; until then `own` frees them
+    const size_t vbytes = (n + 63) / 64 * 8;
+    MatchOwned own(n, 8);
+    uint32_t *const idx = static_cast<uint32_t *>(own.buf[0]);
+    double *const score = static_cast<double *>(own.buf[1]);
+    uint8_t *const valid = static_cast<uint8_t *>(own.buf[2]);
+    if (n) {
+        // the lease is for its context: this call's device memory is the context's staging and search workspace (strsim_capi.cpp),
+        // reserved here against the staging budget at its size -- strings, offsets, outputs, packed strings and partial lists
+        const uint64_t lists = std::min<uint64_t>((uint64_t)1 << 24, n * 65535u) + n;
+        const uint64_t need = 2 * (qv.size() + cv.size() + 4 * (n + m + 2)) + 12 * n + 44 * (n + m) + 12 * lists;
+        PipeLease lease(need);
+        strsim_ctx_t *ctx = lease.set->at(0).open(plugin_devices()[0]);
+        if (strsim_best_match_host(ctx, measure, qo.data(), qv.data(), n, co.data(), cv.data(), m, 1, -__builtin_inf(), idx, score) != STRSIM_OK)
+            fail(strsim_last_error_message());
+    }
+    int64_t nulls = 0;
+    memset(valid, 0, vbytes);
+    for (uint64_t r = 0; r < n; ++r) {
+        const bool ok = idx[r] != 0xFFFFFFFFu && row_valid(q, r);
+        if (ok) { valid[r >> 3] |= (uint8_t)(1u << (r & 7)); idx[r] = pos[idx[r]]; }
+        else { ++nulls; idx[r] = 0; score[r] = 0.0; }
+    }
+    export_match_struct(own, n, nulls, q.name.c_str(), "score", "g", ret);
 }
 
 void best_match_entry(int measure, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret)

@@ -58,6 +58,7 @@ struct PluginError {
 #include "plugin_pipeline.h"
 #include "plugin_match.h"
 #include "plugin_distance.h"
+#include "plugin_nearest.h"
 
 void run(int measure, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret, bool engine_parallel)
 {
@@ -208,6 +209,17 @@ void _polars_plugin_strsim_coalesce_stats(uint64_t out[4]) { if (out) combiner()
     void _polars_plugin_field_##name##_distance(ArrowSchema *input_fields, size_t n_fields, ArrowSchema *return_value) \
     {                                                                                                           \
         distance_field_entry(input_fields, n_fields, return_value);                                             \
+    }
+
+#define POLARS_PLUGIN_DEFINE_NEAREST(name, id)                                                                  \
+    void _polars_plugin_nearest_##name(SeriesExport *inputs, size_t n_inputs, const uint8_t *, size_t,          \
+                                       SeriesExport *return_value, CallerContext *)                             \
+    {                                                                                                           \
+        nearest_entry(id, inputs, n_inputs, return_value);                                                      \
+    }                                                                                                           \
+    void _polars_plugin_field_nearest_##name(ArrowSchema *input_fields, size_t n_fields, ArrowSchema *return_value) \
+    {                                                                                                           \
+        nearest_field_entry(input_fields, n_fields, return_value);                                              \
     }
 
 #define POLARS_PLUGIN_DEFINE_MATCH(name, id)                                                                    \
@@ -450,6 +462,8 @@ POLARS_PLUGIN_DEFINE(sorensen_dice, STRSIM_SORENSEN_DICE)
 POLARS_PLUGIN_DEFINE(osa, STRSIM_OSA)
 POLARS_PLUGIN_DEFINE_DISTANCE(levenshtein, STRSIM_LEVENSHTEIN)
 POLARS_PLUGIN_DEFINE_DISTANCE(osa, STRSIM_OSA)
+POLARS_PLUGIN_DEFINE_NEAREST(levenshtein, STRSIM_LEVENSHTEIN)
+POLARS_PLUGIN_DEFINE_NEAREST(osa, STRSIM_OSA)
 POLARS_PLUGIN_DEFINE_MATCH(levenshtein, STRSIM_LEVENSHTEIN)
 POLARS_PLUGIN_DEFINE_MATCH(jaro, STRSIM_JARO)
 POLARS_PLUGIN_DEFINE_MATCH(jaro_winkler, STRSIM_JARO_WINKLER)

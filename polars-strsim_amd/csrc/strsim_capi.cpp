@@ -19,6 +19,7 @@
 #define STRSIM_OSA_NO_KERNELS // (constants and sizes only: the kernels are compiled in strsim_kernels.hip)
 #include "strsim_osa.h"
 #include "strsim_distance.h"
+#include "strsim_nearest.h"
 
 namespace strsim {
 
@@ -142,6 +143,12 @@ struct strsim_ctx {
     // the scratch are the OSA buffers above)
     DevStatus *dist_status = nullptr;
     DevStatus *dist_status_host = nullptr;
+    // nearest match (strsim_nearest_device): packed strings, their length order, partial lists and the merged scores, and the
+    // fallback's distance and score batches (grow-only; the slow counts come back through match_counts_host)
+    void *nearest_ws = nullptr;
+    size_t nearest_ws_cap = 0;
+    void *nearest_scratch = nullptr;
+    size_t nearest_scratch_cap = 0;
 };
 
 static int ctx_set_device(strsim_ctx *c) { HIP_TRY(hipSetDevice(c->device)); return STRSIM_OK; }
@@ -431,6 +438,8 @@ void strsim_ctx_destroy(strsim_ctx_t *c)
     if (c->osa_scratch) (void)hipFree(c->osa_scratch);
     if (c->dist_status) (void)hipFree(c->dist_status);
     if (c->dist_status_host) (void)hipHostFree(c->dist_status_host);
+    if (c->nearest_ws) (void)hipFree(c->nearest_ws);
+    if (c->nearest_scratch) (void)hipFree(c->nearest_scratch);
     if (c->lev_ws) (void)hipFree(c->lev_ws);
     if (c->status) (void)hipFree(c->status);
     if (c->status_host) (void)hipHostFree(c->status_host);
@@ -1126,6 +1135,166 @@ int strsim_distance_host(strsim_ctx_t *c, int measure, const uint32_t *a_off, co
                               (uint32_t *)c->stage[4], n);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(out, c->stage[4], n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return STRSIM_OK;
+}
+
+} // extern "C"
+
+// ---- nearest match (strsim_nearest.h, strsim_nearest_kernels.h) ----
+
+static int nearest_check(const char *who, strsim_ctx_t *c, int measure, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows,
+                         const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, uint32_t k, const void *out_index,
+                         const void *out_distance)
+{
+    if (measure != STRSIM_LEVENSHTEIN && measure != STRSIM_OSA) {
+        set_error("%s: measure %d has no distance (STRSIM_LEVENSHTEIN or STRSIM_OSA)", who, measure);
+        return STRSIM_ERR_ARG;
+    }
+    if (k < 1u || k > STRSIM_NEAREST_MAX_K) { set_error("%s: k=%u is outside 1..%u", who, k, STRSIM_NEAREST_MAX_K); return STRSIM_ERR_ARG; }
+    if (q_rows > 0xFFFFFFFFull) { set_error("%s: %llu queries (at most 2^32 - 1)", who, (unsigned long long)q_rows); return STRSIM_ERR_ARG; }
+    if (c_rows > 0xFFFFFFFEull) { set_error("%s: %llu candidates (at most 2^32 - 2)", who, (unsigned long long)c_rows); return STRSIM_ERR_ARG; }
+    if (q_rows && (!q_off || !q_val || !out_index || !out_distance)) { set_error("%s: NULL query or output buffer", who); return STRSIM_ERR_ARG; }
+    if (c_rows && (!c_off || !c_val)) { set_error("%s: NULL candidate buffer", who); return STRSIM_ERR_ARG; }
+    if (!c) { set_error("%s: ctx is NULL", who); return STRSIM_ERR_ARG; }
+    return STRSIM_OK;
+}
+
+extern "C" {
+
+int strsim_nearest_device(strsim_ctx_t *c, int measure, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows,
+                          const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, uint32_t k, uint32_t max_distance,
+                          uint32_t *out_index, uint32_t *out_distance)
+{
+    int rc = nearest_check("strsim_nearest_device", c, measure, q_off, q_val, q_rows, c_off, c_val, c_rows, k, out_index, out_distance);
+    if (rc || q_rows == 0) return rc;
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    const uint32_t nq = (uint32_t)q_rows, nc = (uint32_t)c_rows, kp = (uint32_t)match_lane_k(k);
+    const uint32_t splits = nc ? match_splits(nq, nc, kp, c->num_cu) : 0u;
+    // workspace: both sides packed (32-byte words + meta) and their slow lists, the small block (slow counts, histograms, bucket
+    // starts, cursors), the query permutation, the candidates in length order, (splits + 1) lists of kp per query (the last: the
+    // fallback) and the merged scores
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t nl = (size_t)splits + 1, lists = nl * nq * kp, ob = (size_t)nq * k;
+    const size_t o_qw = 0, o_qm = o_qw + up((size_t)nq * 32), o_cw = o_qm + up((size_t)nq * 4), o_cm = o_cw + up((size_t)nc * 32),
+                 o_qs = o_cm + up((size_t)nc * 4), o_cs = o_qs + up((size_t)nq * 4), o_small = o_cs + up((size_t)nc * 4),
+                 o_qp = o_small + 1024, o_sw = o_qp + up((size_t)nq * 4), o_sm = o_sw + up((size_t)nc * 32),
+                 o_si = o_sm + up((size_t)nc * 4), o_ls = o_si + up((size_t)nc * 4), o_li = o_ls + up(lists * 8),
+                 o_ms = o_li + up(lists * 4), total = o_ms + up(ob * 8);
+    rc = ctx_reserve(&c->nearest_ws, &c->nearest_ws_cap, total);
+    if (rc) return rc;
+    if (!c->match_counts_host) HIP_TRY(hipHostMalloc((void **)&c->match_counts_host, 64, hipHostMallocDefault));
+    uint8_t *const ws = static_cast<uint8_t *>(c->nearest_ws);
+    uint32_t *const qw = (uint32_t *)(ws + o_qw), *const qm = (uint32_t *)(ws + o_qm), *const cw = (uint32_t *)(ws + o_cw),
+                   *const cm = (uint32_t *)(ws + o_cm), *const qs = (uint32_t *)(ws + o_qs), *const cs = (uint32_t *)(ws + o_cs),
+                   *const small = (uint32_t *)(ws + o_small), *const lidx = (uint32_t *)(ws + o_li);
+    double *const lscore = (double *)(ws + o_ls), *const mscore = (double *)(ws + o_ms);
+    // the small block: slow counts [0, 2), histograms, bucket starts, cursors (the counts and histograms are zeroed)
+    uint32_t *const cnt = small, *const qhist = small + 8, *const chist = qhist + 40, *const qstart = chist + 40,
+                   *const cstart = qstart + 40, *const qcur = cstart + 40, *const ccur = qcur + 40;
+    hipStream_t st = c->stream;
+    HIP_TRY(hipMemsetAsync(small, 0, 4 * 88, st));
+    HIP_TRY(launch_match_pack(q_off, q_val, nq, qw, qm, qs, cnt, st));
+    HIP_TRY(launch_match_pack(c_off, c_val, nc, cw, cm, cs, cnt + 1, st));
+    // the sizes of the two slow classes decide what runs: one small read-back (the only wait of a call without slow strings)
+    HIP_TRY(hipMemcpyAsync(c->match_counts_host, cnt, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint32_t q_slow = c->match_counts_host[0], c_slow = c->match_counts_host[1];
+    // fast x fast: length order on the device, then lists 0 .. splits - 1
+    uint32_t used = 0;
+    if (splits && q_slow < nq && c_slow < nc) {
+        uint32_t *const qperm = (uint32_t *)(ws + o_qp), *const sw = (uint32_t *)(ws + o_sw), *const sm = (uint32_t *)(ws + o_sm),
+                       *const si = (uint32_t *)(ws + o_si);
+        NearestOrderArgs oa{qm, nq, cw, cm, nc, qhist, chist, qstart, cstart, qcur, ccur, qperm, sw, sm, si, st};
+        HIP_TRY(launch_nearest_order(oa));
+        NearestLaneArgs a{qw, qm, qperm, qstart, nq, sw, sm, si, cstart, splits, k, max_distance, lscore, lidx, st};
+        HIP_TRY(launch_nearest_lane(measure, a));
+        used = splits;
+    }
+    // every pair with a slow side: strsim_distance_device with that side as the literal (its length prefilter and block cutoff
+    // apply), batch by batch, folded into list `used` as the scores -(double)d
+    if (nc && (q_slow || c_slow)) {
+        double *const fs = lscore + (size_t)used * nq * kp;
+        uint32_t *const fi = lidx + (size_t)used * nq * kp;
+        const double min_score = -(double)max_distance; // (a cut pair comes back as max_distance + 1)
+        HIP_TRY(launch_match_clear(fs, fi, (uint64_t)nq * kp, st));
+        const uint64_t longest = nq > nc ? nq : nc;
+        uint64_t calls = MATCH_FALLBACK_SCORES / longest;
+        if (calls > MATCH_FALLBACK_CALLS) calls = MATCH_FALLBACK_CALLS;
+        if (calls < 1) calls = 1;
+        rc = ctx_reserve(&c->nearest_scratch, &c->nearest_scratch_cap, (size_t)(calls * longest * 12));
+        if (rc) return rc;
+        double *const scores = static_cast<double *>(c->nearest_scratch);
+        uint32_t *const dist = reinterpret_cast<uint32_t *>(scores + calls * longest);
+        uint32_t *host_list = static_cast<uint32_t *>(malloc(((size_t)q_slow + c_slow + 1) * 4));
+        if (!host_list) { set_error("strsim_nearest_device: out of host memory"); return STRSIM_ERR_OOM; }
+        auto run = [&]() -> int {
+            if (q_slow) HIP_TRY(hipMemcpyAsync(host_list, qs, (size_t)q_slow * 4, hipMemcpyDeviceToHost, st));
+            if (c_slow) HIP_TRY(hipMemcpyAsync(host_list + q_slow, cs, (size_t)c_slow * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            for (uint32_t b0 = 0; b0 < q_slow; b0 += (uint32_t)calls) { // a slow query against every candidate
+                const uint32_t nb = (uint32_t)(q_slow - b0 < calls ? q_slow - b0 : calls);
+                for (uint32_t b = 0; b < nb; ++b) {
+                    int r = strsim_distance_device(c, measure, q_off + host_list[b0 + b], q_val, 1, c_off, c_val, nc, max_distance,
+                                                   dist + (size_t)b * nc, nc);
+                    if (r) return r;
+                }
+                HIP_TRY(launch_nearest_scores(dist, (uint64_t)nb * nc, scores, st));
+                HIP_TRY(launch_match_fold_cols(k, scores, qs + b0, nb, nc, min_score, fs, fi, st));
+            }
+            for (uint32_t b0 = 0; b0 < c_slow; b0 += (uint32_t)calls) { // a slow candidate against every query (the fast ones are kept)
+                const uint32_t nb = (uint32_t)(c_slow - b0 < calls ? c_slow - b0 : calls);
+                for (uint32_t b = 0; b < nb; ++b) {
+                    const uint32_t j = host_list[q_slow + b0 + b];
+                    int r = strsim_distance_device(c, measure, c_off + j, c_val, 1, q_off, q_val, nq, max_distance, dist + (size_t)b * nq, nq);
+                    if (r) return r;
+                }
+                HIP_TRY(launch_nearest_scores(dist, (uint64_t)nb * nq, scores, st));
+                HIP_TRY(launch_match_fold_rows(k, scores, cs + b0, nb, qm, nq, min_score, fs, fi, st));
+            }
+            return STRSIM_OK;
+        };
+        rc = run();
+        free(host_list);
+        if (rc) return rc;
+        ++used;
+    }
+    HIP_TRY(launch_match_merge(k, lscore, lidx, used, nq, out_index, mscore, st));
+    HIP_TRY(launch_nearest_finish(mscore, out_index, ob, out_distance, st));
+    return STRSIM_OK;
+}
+
+int strsim_nearest_host(strsim_ctx_t *c, int measure, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows,
+                        const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, uint32_t k, uint32_t max_distance,
+                        uint32_t *out_index, uint32_t *out_distance)
+{
+    int rc = nearest_check("strsim_nearest_host", c, measure, q_off, q_val, q_rows, c_off, c_val, c_rows, k, out_index, out_distance);
+    if (rc || q_rows == 0) return rc;
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    // (as strsim_best_match_host: the caller's offset base is kept and the values go up from byte 0)
+    const size_t ob = q_rows * (size_t)k;
+    const size_t need[5] = {(q_rows + 1) * 4, (size_t)q_off[q_rows] + 1, (c_rows + 1) * 4, (c_rows ? (size_t)c_off[c_rows] : 0) + 1,
+                            ob * 8 + 256};
+    for (int i = 0; i < 5; ++i) {
+        rc = ctx_reserve(&c->stage[i], &c->stage_cap[i], need[i]);
+        if (rc) return rc;
+    }
+    hipStream_t st = c->stream;
+    HIP_TRY(hipMemcpyAsync(c->stage[0], q_off, (q_rows + 1) * 4, hipMemcpyHostToDevice, st));
+    if (q_off[q_rows]) HIP_TRY(hipMemcpyAsync(c->stage[1], q_val, q_off[q_rows], hipMemcpyHostToDevice, st));
+    if (c_rows) {
+        HIP_TRY(hipMemcpyAsync(c->stage[2], c_off, (c_rows + 1) * 4, hipMemcpyHostToDevice, st));
+        if (c_off[c_rows]) HIP_TRY(hipMemcpyAsync(c->stage[3], c_val, c_off[c_rows], hipMemcpyHostToDevice, st));
+    }
+    uint32_t *const d_index = static_cast<uint32_t *>(c->stage[4]);
+    uint32_t *const d_dist = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(c->stage[4]) + ((ob * 4 + 255) & ~(size_t)255));
+    rc = strsim_nearest_device(c, measure, (const uint32_t *)c->stage[0], (const uint8_t *)c->stage[1], q_rows,
+                               (const uint32_t *)c->stage[2], (const uint8_t *)c->stage[3], c_rows, k, max_distance, d_index, d_dist);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out_index, d_index, ob * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out_distance, d_dist, ob * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return STRSIM_OK;
 }

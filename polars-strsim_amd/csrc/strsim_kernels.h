@@ -130,5 +130,34 @@ hipError_t launch_dist_lane(int measure, const LaunchArgs &a, uint32_t k, uint32
 hipError_t launch_dist_wave(int measure, const LaunchArgs &a, uint32_t k, uint32_t *out, const uint32_t *worklist, int grid,
                             uint32_t *scratch, uint64_t slot_words);
 
+
+// Nearest match by bounded edit distance (strsim_nearest_kernels.h), measure 0 (Levenshtein) or 6 (OSA).  The strings of both
+// sides are packed by launch_match_pack first; launch_nearest_order then puts them in length order on the device (histograms,
+// scan, scatter; the histograms must be zeroed), and launch_nearest_lane writes splits x nq x match_lane_k(k) partial lists in
+// the encoding of k_match_merge (score -(double)d).
+struct NearestOrderArgs {
+    const uint32_t *qmeta; uint32_t nq;                // queries (k_match_pack)
+    const uint32_t *cwords, *cmeta; uint32_t nc;       // candidates
+    uint32_t *qhist, *chist;                           // NEAREST_BUCKETS words each, zeroed
+    uint32_t *qstart, *cstart;                         // NEAREST_BUCKETS + 1 words each
+    uint32_t *qcur, *ccur;                             // NEAREST_BUCKETS words each
+    uint32_t *qperm;                                   // nq: the queries in length order, the slow ones last
+    uint32_t *swords, *smeta, *sidx;                   // the fast candidates in length order: 8 words, meta, original index
+    hipStream_t stream;
+};
+hipError_t launch_nearest_order(const NearestOrderArgs &a);
+struct NearestLaneArgs {
+    const uint32_t *qwords, *qmeta, *qperm, *qstart; uint32_t nq;
+    const uint32_t *swords, *smeta, *sidx, *cstart;
+    uint32_t splits, k, max_distance;
+    double *pscore; uint32_t *pidx;
+    hipStream_t stream;
+};
+hipError_t launch_nearest_lane(int measure, const NearestLaneArgs &a);
+// fallback distances -> scores -(double)d for launch_match_fold_cols / _rows; the merged scores -> distances (0xFFFFFFFF where the
+// index is empty)
+hipError_t launch_nearest_scores(const uint32_t *dist, uint64_t n, double *score, hipStream_t stream);
+hipError_t launch_nearest_finish(const double *score, const uint32_t *index, uint64_t n, uint32_t *dist, hipStream_t stream);
+
 } // namespace strsim
 

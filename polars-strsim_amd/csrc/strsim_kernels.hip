@@ -25,6 +25,8 @@
 //                     to 64 bytes, one pair per wave for the rest; both in stream order, no second pass.
 //   k_dist_lane / k_dist_wave  bounded integer edit distances (Levenshtein, OSA; strsim_distance.h): the same two tiers, uint32
 //                     outputs, a length prefilter and, in the wave tier, the block cutoff of Myers / Ukkonen.
+//   k_nearest_lane<TR, K>  nearest match by bounded edit distance (strsim_nearest_kernels.h): one query per lane in length
+//                     order against wave-uniform candidates, a candidate length window and a running bound per lane.
 //   k_huge_pairs<M>   strings beyond WAVE_CAP, scratch in global memory, launched from strsim_ctx_synchronize() only
 //                     when such rows were counted; Levenshtein: the block step in stripes of 64 blocks, any length.
 //
@@ -45,6 +47,7 @@
 #include "strsim_lane_common.h"
 #include "strsim_osa.h"
 #include "strsim_distance.h"
+#include "strsim_nearest.h"
 
 namespace strsim {
 
@@ -60,6 +63,7 @@ struct OutPtrs {
 #endif
 #include "strsim_lane_lit.h"
 #include "strsim_match.h"
+#include "strsim_nearest_kernels.h"
 
 #include "strsim_kernel_wide.h"
 #include "strsim_kernel_utf8.h"
@@ -441,6 +445,60 @@ hipError_t launch_match_merge(uint32_t k, const double *pscore, const uint32_t *
     if (K == 1) hipLaunchKernelGGL(k_match_merge<1>, g, b, 0, stream, pscore, pidx, nl, nq, k, out_index, out_score);
     else if (K == 4) hipLaunchKernelGGL(k_match_merge<4>, g, b, 0, stream, pscore, pidx, nl, nq, k, out_index, out_score);
     else hipLaunchKernelGGL(k_match_merge<16>, g, b, 0, stream, pscore, pidx, nl, nq, k, out_index, out_score);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// nearest match (strsim_nearest_kernels.h)
+// ------------------------------------------------------------------------------------------------
+hipError_t launch_nearest_order(const NearestOrderArgs &a)
+{
+    if (a.nq) hipLaunchKernelGGL(k_nearest_hist, dim3(match_grid(a.nq)), dim3(MATCH_BLOCK), 0, a.stream, a.qmeta, a.nq, a.qhist);
+    if (a.nc) hipLaunchKernelGGL(k_nearest_hist, dim3(match_grid(a.nc)), dim3(MATCH_BLOCK), 0, a.stream, a.cmeta, a.nc, a.chist);
+    hipLaunchKernelGGL(k_nearest_scan, dim3(1), dim3(64), 0, a.stream, a.qhist, a.chist, a.qstart, a.cstart, a.qcur, a.ccur);
+    if (a.nq)
+        hipLaunchKernelGGL(k_nearest_scatter<0>, dim3(match_grid(a.nq)), dim3(MATCH_BLOCK), 0, a.stream, (const uint32_t *)nullptr, a.qmeta,
+                           a.nq, a.qcur, a.qperm, (uint32_t *)nullptr, (uint32_t *)nullptr);
+    if (a.nc)
+        hipLaunchKernelGGL(k_nearest_scatter<1>, dim3(match_grid(a.nc)), dim3(MATCH_BLOCK), 0, a.stream, a.cwords, a.cmeta, a.nc, a.ccur,
+                           a.sidx, a.swords, a.smeta);
+    return hipGetLastError();
+}
+
+template <bool TR, int K>
+static void launch_nearest_lane_t(const NearestLaneArgs &a)
+{
+    hipLaunchKernelGGL((k_nearest_lane<TR, K>), dim3(match_grid(a.nq), a.splits), dim3(MATCH_BLOCK), 0, a.stream, a.qwords, a.qmeta,
+                       a.qperm, a.qstart, a.nq, a.swords, a.smeta, a.sidx, a.cstart, a.max_distance, a.pscore, a.pidx);
+}
+
+template <bool TR>
+static void launch_nearest_lane_tr(const NearestLaneArgs &a)
+{
+    const int K = match_lane_k(a.k);
+    if (K == 1) launch_nearest_lane_t<TR, 1>(a);
+    else if (K == 4) launch_nearest_lane_t<TR, 4>(a);
+    else launch_nearest_lane_t<TR, 16>(a);
+}
+
+hipError_t launch_nearest_lane(int measure, const NearestLaneArgs &a)
+{
+    if (measure == OSA) launch_nearest_lane_tr<true>(a);
+    else launch_nearest_lane_tr<false>(a);
+    return hipGetLastError();
+}
+
+hipError_t launch_nearest_scores(const uint32_t *dist, uint64_t n, double *score, hipStream_t stream)
+{
+    if (n == 0u) return hipSuccess;
+    hipLaunchKernelGGL(k_nearest_scores, dim3(match_grid(n)), dim3(MATCH_BLOCK), 0, stream, dist, n, score);
+    return hipGetLastError();
+}
+
+hipError_t launch_nearest_finish(const double *score, const uint32_t *index, uint64_t n, uint32_t *dist, hipStream_t stream)
+{
+    if (n == 0u) return hipSuccess;
+    hipLaunchKernelGGL(k_nearest_finish, dim3(match_grid(n)), dim3(MATCH_BLOCK), 0, stream, score, index, n, dist);
     return hipGetLastError();
 }
 

@@ -118,6 +118,7 @@ def osa_distance(expr: IntoExpr, other: IntoExpr, max_distance: int | None = Non
 
 __all__ = [
     "best_match",
+    "nearest",
     "levenshtein_distance",
     "osa_distance",
     "osa",
@@ -144,3 +145,23 @@ def best_match(expr: IntoExpr, candidates: IntoExpr, measure: str = "jaro_winkle
         is_elementwise=False,
     )
 
+
+_NEAREST_MEASURES = ("levenshtein", "osa")
+
+
+def nearest(expr: IntoExpr, candidates: IntoExpr, measure: str = "levenshtein", max_distance: int | None = None) -> pl.Expr:
+    """The nearest candidate of every row of `expr` among all rows of `candidates` (any length) by edit distance ("levenshtein"
+    or "osa"): a struct {index: UInt32, distance: UInt32}, null where the row is null or no candidate is within max_distance
+    (None: no cutoff); ties go to the lower candidate index.  rapidfuzz's process.extractOne with a distance scorer and
+    score_cutoff.  Not in the upstream polars-strsim."""
+    if measure not in _NEAREST_MEASURES:
+        raise ValueError(f"unknown measure {measure!r}; expected one of {_NEAREST_MEASURES}")
+    args = [parse_into_expr(expr, dtype=pl.Utf8), parse_into_expr(candidates, dtype=pl.Utf8)]
+    if max_distance is not None:
+        args.append(pl.lit(max_distance, dtype=pl.UInt32))
+    return register_plugin_function(
+        plugin_path=_PLUGIN_DIR,
+        function_name="nearest_" + measure,
+        args=args,
+        is_elementwise=False,
+    )

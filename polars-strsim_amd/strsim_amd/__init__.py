@@ -131,6 +131,32 @@ def best_match(measure, queries, candidates, k=1, min_score=None, ctx=None):
     return out, score
 
 
-__all__ = ["best_match", "Codec", "Context", "device_count", "pack_strings", "split_offsets", "similarity", "levenshtein", "jaro",
+def nearest(measure, queries, candidates, k=1, max_distance=None, ctx=None):
+    """For every query, its k nearest candidates by edit distance ("levenshtein" or "osa", DISTANCE_MEASURES):
+    (index int64 [N, k], distance int64 [N, k]).  Slots in ascending order of the distance, ties to the lower candidate index;
+    only candidates within max_distance are reported (None: no cutoff, 0: exact matches).  Empty slots -- and every slot of a
+    null query -- are (-1, -1).  Null candidates are never matched; indices refer to the caller's candidate positions.
+    rapidfuzz: process.extract(q, candidates, scorer=Levenshtein.distance, score_cutoff=max_distance, limit=k)."""
+    if measure not in DISTANCE_MEASURES:
+        raise ValueError(f"no distance for measure {measure!r} (one of {DISTANCE_MEASURES})")
+    ctx = ctx or default_context()
+    Q, vq = _as_column(queries)
+    cand = list(candidates)
+    keep = np.array([c is not None for c in cand], dtype=bool)
+    pos = np.flatnonzero(keep)
+    qo, qv = pack_strings(Q)
+    co, cv = pack_strings([cand[j] for j in pos])
+    idx, dist = ctx.nearest(measure, qo, qv, co, cv, k, max_distance)
+    empty = idx == 0xFFFFFFFF
+    out = np.full(idx.shape, -1, dtype=np.int64)
+    out[~empty] = pos[idx[~empty].astype(np.int64)]
+    d = np.where(empty, -1, dist.astype(np.int64))
+    if vq is not None:
+        out[~vq] = -1
+        d[~vq] = -1
+    return out, d
+
+
+__all__ = ["best_match", "nearest", "Codec", "Context", "device_count", "pack_strings", "split_offsets", "similarity", "levenshtein", "jaro",
            "jaro_winkler", "jaccard", "sorensen_dice", "osa", "measure_supported", "distance", "levenshtein_distance", "osa_distance",
            "DISTANCE_MEASURES", "DISTANCE_UNBOUNDED", "MEASURES", "EXTRA_MEASURES", "MEASURE_ID", "STATUS", "ShapeMismatch", "StrsimError"]

@@ -249,6 +249,27 @@ class Context:
                                            co.ctypes.data, cv.ctypes.data, nc, int(k), ms, index.ctypes.data, score.ctypes.data))
         return index, score
 
+    def nearest(self, measure, q_offsets, q_values, c_offsets, c_values, k=1, max_distance=None):
+        """Synchronous nearest match (strsim_nearest_host): numpy uint32 offsets + uint8 values of the queries and the candidates ->
+        (index uint32 [rows, k], distance uint32 [rows, k]), each query's k nearest candidates by edit distance ("levenshtein" or
+        "osa"), ascending, ties to the lower index; only d <= max_distance is reported (None: no cutoff).  Empty slots are
+        (0xFFFFFFFF, 0xFFFFFFFF)."""
+        qo = np.ascontiguousarray(q_offsets, dtype=np.uint32)
+        co = np.ascontiguousarray(c_offsets, dtype=np.uint32)
+        qv = np.ascontiguousarray(q_values, dtype=np.uint8)
+        cv = np.ascontiguousarray(c_values, dtype=np.uint8)
+        if qv.size == 0:
+            qv = np.zeros(1, dtype=np.uint8)
+        if cv.size == 0:
+            cv = np.zeros(1, dtype=np.uint8)
+        nq, nc = qo.size - 1, co.size - 1
+        index = np.empty((nq, int(k)), dtype=np.uint32)
+        dist = np.empty((nq, int(k)), dtype=np.uint32)
+        check(lib().strsim_nearest_host(self._h, measure_id(measure), qo.ctypes.data, qv.ctypes.data, nq,
+                                        co.ctypes.data, cv.ctypes.data, nc, int(k), _max_distance(max_distance),
+                                        index.ctypes.data, dist.ctypes.data))
+        return index, dist
+
 
 class Codec:
     """Lossless 16-bit transport codec for one measure's result column (include/strsim_amd.h: strsim_codec_*)."""
