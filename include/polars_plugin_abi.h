@@ -107,6 +107,11 @@ POLARS_PLUGIN_DECLARE(osa)
  * combiner. */
 POLARS_PLUGIN_DECLARE(levenshtein_distance)
 POLARS_PLUGIN_DECLARE(osa_distance)
+/* Not in the reference: the Indel similarity (STRSIM_INDEL of strsim_amd.h: 1 - (|a| + |b| - 2 LCS) / (|a| + |b|), rapidfuzz's
+ * fuzz.ratio / 100), Float64 named after input 0 like the similarities above, and its integer distance |a| + |b| - 2 LCS (a
+ * substitution costs 2), UInt32 with the optional max_distance input of the *_distance functions above. */
+POLARS_PLUGIN_DECLARE(indel)
+POLARS_PLUGIN_DECLARE(indel_distance)
 
 /* Best match (not in the reference): input 0 = the query column (N rows), input 1 = the candidate column (any number of rows; the
  * length rule of the functions above does not apply).  Output: N rows of an Arrow struct {index: UInt32, score: Float64} named after

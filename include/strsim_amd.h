@@ -45,10 +45,15 @@ typedef enum strsim_measure {
     STRSIM_JACCARD       = 3, /* character-multiset Jaccard, strsim.rs:286-308 */
     STRSIM_SORENSEN_DICE = 4, /* character-multiset Sorensen-Dice, strsim.rs:322-345 */
     STRSIM_NUM_MEASURES  = 5, /* the reference's five; the value 5 itself is not a measure */
-    STRSIM_OSA           = 6  /* optimal string alignment (restricted Damerau-Levenshtein: no substring is edited twice), normalised
+    STRSIM_OSA           = 6, /* optimal string alignment (restricted Damerau-Levenshtein: no substring is edited twice), normalised
                                  like STRSIM_LEVENSHTEIN: 1.0 when a == b or both are empty, else 1.0 - d / max(|a|, |b|) over Unicode
                                  scalar values.  Pairwise entry points only (strsim_pairs_device, _small, strsim_pairs_host);
                                  not a measure of the reference */
+    STRSIM_INDEL         = 8  /* Indel (longest common subsequence) similarity, rapidfuzz's fuzz.ratio / 100: with l = LCS(a, b) and
+                                 d = |a| + |b| - 2 l (insertions and deletions only, a substitution costs 2), 1.0 when |a| + |b| == 0,
+                                 else 1.0 - d / (|a| + |b|) over Unicode scalar values (these two f64 operations, not 2 l / (|a| + |b|)).
+                                 Pairwise entry points and strsim_distance_*; not a measure of the reference.  8, not 7: ids 5 and 7
+                                 stay unassigned, callers were told (and tests hold) that every entry point refuses them */
 } strsim_measure_t;
 
 /* Entry points of strsim_measure_supported(). */
@@ -112,6 +117,10 @@ STRSIM_API void *strsim_ctx_stream(strsim_ctx_t *ctx);
  * its first kernel (a read-back of how many rows need the second kernel and how long their patterns are), so everything
  * enqueued on the context's stream before it has completed when it returns.  Its kernels read only the bytes the offsets
  * describe.  strsim_ctx_set_stream_ordered(ctx, 0) does not change an OSA call.
+ *
+ * STRSIM_INDEL: the same protocol and the same reports as STRSIM_OSA, with other tiers: rows where both strings are ASCII and at
+ * most 128 bytes are one pair per lane (strsim_ctx_last_wave_rows is 0 for a column of such rows), every other row one pair per
+ * wave (any length).  A literal that is not ASCII or longer than 128 bytes sends every row to the second kernel.
  *
  * Reads beyond the strings: the kernels copy the values of a block of rows in whole 16-byte chunks, from the
  * 16-byte-aligned address at or below the block's first byte (a_values + a_offsets[first row]) up to the chunk that
@@ -223,7 +232,9 @@ STRSIM_API int strsim_best_match_host(strsim_ctx_t *ctx, int measure,
 
 /*
  * Bounded edit distances as integers (found by dlsym, like strsim_measure_supported: the ABI version stays 1.7).  `measure` is
- * STRSIM_LEVENSHTEIN (0: insert, delete, substitute) or STRSIM_OSA (6: plus the restricted swap of two adjacent characters); any
+ * STRSIM_LEVENSHTEIN (0: insert, delete, substitute), STRSIM_OSA (6: plus the restricted swap of two adjacent characters) or
+ * STRSIM_INDEL (8: insert and delete only, d = |a| + |b| - 2 LCS(a, b); its similarity is 1.0 - d / (|a| + |b|), and the lane tier
+ * takes ASCII rows of up to 128 bytes; a pair whose lengths differ by more than max_distance is decided without the DP); any
  * other id is STRSIM_ERR_ARG (strsim_measure_supported does not describe these two entry points).  d is over Unicode scalar values.
  * out[i] = d when d <= max_distance, else max_distance + 1 (rapidfuzz's score_cutoff convention); STRSIM_DISTANCE_UNBOUNDED is
  * no cutoff and max_distance = 0 an equality test.  With no cutoff, 1.0 - d / max(|a|, |b|) (1.0 when both are empty) is bit for

@@ -1,4 +1,4 @@
-// plugin_distance.h -- the levenshtein_distance / osa_distance plugin functions: bounded integer edit distances as one Arrow
+// plugin_distance.h -- the levenshtein_distance / osa_distance / indel_distance plugin functions: bounded integer edit distances as one Arrow
 // UInt32 ("I") chunk.  Included by polars_plugin.cpp inside its anonymous namespace, after plugin_match.h.
 //
 // Inputs 0 and 1 are the two string series, with the shape rule, literal broadcast, null handling and error messages of the

@@ -460,8 +460,10 @@ POLARS_PLUGIN_DEFINE(jaro_winkler, STRSIM_JARO_WINKLER)
 POLARS_PLUGIN_DEFINE(jaccard, STRSIM_JACCARD)
 POLARS_PLUGIN_DEFINE(sorensen_dice, STRSIM_SORENSEN_DICE)
 POLARS_PLUGIN_DEFINE(osa, STRSIM_OSA)
+POLARS_PLUGIN_DEFINE(indel, STRSIM_INDEL)
 POLARS_PLUGIN_DEFINE_DISTANCE(levenshtein, STRSIM_LEVENSHTEIN)
 POLARS_PLUGIN_DEFINE_DISTANCE(osa, STRSIM_OSA)
+POLARS_PLUGIN_DEFINE_DISTANCE(indel, STRSIM_INDEL)
 POLARS_PLUGIN_DEFINE_NEAREST(levenshtein, STRSIM_LEVENSHTEIN)
 POLARS_PLUGIN_DEFINE_NEAREST(osa, STRSIM_OSA)
 POLARS_PLUGIN_DEFINE_MATCH(levenshtein, STRSIM_LEVENSHTEIN)

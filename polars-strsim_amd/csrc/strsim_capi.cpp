@@ -19,6 +19,7 @@
 #define STRSIM_OSA_NO_KERNELS // (constants and sizes only: the kernels are compiled in strsim_kernels.hip)
 #include "strsim_osa.h"
 #include "strsim_distance.h"
+#include "strsim_indel.h"
 #include "strsim_nearest.h"
 
 namespace strsim {
@@ -256,8 +257,8 @@ static int ctx_retire_slot(strsim_ctx *c, int s)
         set_error("fault injected at retirement %llu of this context (STRSIM_FAULT_RETIRE_AT)", (unsigned long long)c->retired);
         return STRSIM_ERR_INTERNAL;
     }
-    // (an OSA call has no lane_left: it says nothing about what the next call of the other measures leaves behind)
-    const uint32_t left = c->slot_measure[s] == STRSIM_OSA ? LANE_LEFT_UNKNOWN
+    // (an OSA or Indel call has no lane_left: it says nothing about what the next call of the other measures leaves behind)
+    const uint32_t left = (c->slot_measure[s] == STRSIM_OSA || c->slot_measure[s] == STRSIM_INDEL) ? LANE_LEFT_UNKNOWN
                                                            : *reinterpret_cast<const volatile uint32_t *>(&c->status_host[s].lane_left);
     if (left != LANE_LEFT_UNKNOWN) { // what the next call on this context is enqueued for
         c->expect_slow = left != 0u;
@@ -465,8 +466,9 @@ void strsim_split_offsets(uint64_t len, uint64_t n, uint64_t *out)
 // Optimal string alignment (strsim_osa.h): k_osa_lane over every row, a read-back of what it left for k_osa_wave (how many rows,
 // how long their patterns can be), then k_osa_wave sized for that.  Every row is complete in stream order; the call occupies a ring
 // slot like any other (its status block carries the ticket and the work-list count) and has nothing to do at retirement.
+// measure = STRSIM_INDEL runs the same flow with k_indel_lane / k_indel_wave (strsim_indel.h) on the same work list and scratch.
 static constexpr size_t OSA_SCRATCH_BUDGET = (size_t)1 << 30; // k_osa_wave runs fewer waves rather than use more scratch
-static int pairs_osa(strsim_ctx *c, int slot, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
+static int pairs_osa(strsim_ctx *c, int slot, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
                      const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t n)
 {
     int rc = ctx_reserve((void **)&c->osa_list, &c->osa_list_cap, n * sizeof(uint32_t));
@@ -480,8 +482,9 @@ static int pairs_osa(strsim_ctx *c, int slot, const uint32_t *a_off, const uint8
     la.out = out; la.n = n;
     la.status = c->status + slot; la.stream = c->stream;
     HIP_TRY(hipMemsetAsync(la.status, 0, sizeof(DevStatus), c->stream));
-    hipError_t e = launch_osa_lane(la, c->osa_list);
-    if (e != hipSuccess) return hip_fail(e, "kernel launch (k_osa_lane)");
+    const bool indel = measure == STRSIM_INDEL;
+    hipError_t e = indel ? launch_indel_lane(la, DIST_UNBOUNDED, nullptr, c->osa_list) : launch_osa_lane(la, c->osa_list);
+    if (e != hipSuccess) return hip_fail(e, indel ? "kernel launch (k_indel_lane)" : "kernel launch (k_osa_lane)");
     HIP_TRY(launch_publish_status(c->status + slot, c->status_host_dev + slot, c->slot_ticket[slot], c->stream));
     c->enqueued_ops += 3u;
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -492,21 +495,22 @@ static int pairs_osa(strsim_ctx *c, int slot, const uint32_t *a_off, const uint8
         uint32_t *scratch = nullptr;
         uint64_t slot_words = 0;
         if (max_pat > OSA_WAVE_LDS_CPS) { // (max_pat bounds the pattern in scalar values: it is a byte length)
-            slot_words = osa_wave_slot_words(max_pat);
+            slot_words = indel ? indel_wave_slot_words(max_pat) : osa_wave_slot_words(max_pat);
             const size_t per = (size_t)slot_words * sizeof(uint32_t);
             if ((size_t)grid * per > OSA_SCRATCH_BUDGET) grid = (int)std::max<size_t>(1, OSA_SCRATCH_BUDGET / per);
             rc = ctx_reserve((void **)&c->osa_scratch, &c->osa_scratch_cap, (size_t)grid * per);
             if (rc) return rc;
             scratch = c->osa_scratch;
         }
-        e = launch_osa_wave(la, c->osa_list, grid, scratch, slot_words);
-        if (e != hipSuccess) return hip_fail(e, "kernel launch (k_osa_wave)");
+        e = indel ? launch_indel_wave(la, DIST_UNBOUNDED, nullptr, c->osa_list, grid, scratch, slot_words)
+                  : launch_osa_wave(la, c->osa_list, grid, scratch, slot_words);
+        if (e != hipSuccess) return hip_fail(e, indel ? "kernel launch (k_indel_wave)" : "kernel launch (k_osa_wave)");
         c->enqueued_ops += 1u;
     }
     c->slot_timed[slot] = false;
     c->slot_deferred[slot] = false;
     c->slot_args[slot] = la;
-    c->slot_measure[slot] = STRSIM_OSA;
+    c->slot_measure[slot] = measure;
     for (int q = 0; q < STRSIM_NUM_MEASURES; ++q) c->slot_outs[slot][q] = nullptr;
     c->slot_pending[slot] = true;
     c->head = (slot + 1) % strsim_ctx::RING;
@@ -559,7 +563,7 @@ static int pairs_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_off
             return STRSIM_ERR_EARLIER_CALL;
         }
     }
-    if (measure == STRSIM_OSA) return pairs_osa(c, slot, a_off, a_val, a_rows, b_off, b_val, b_rows, outs[0], n);
+    if (measure == STRSIM_OSA || measure == STRSIM_INDEL) return pairs_osa(c, slot, measure, a_off, a_val, a_rows, b_off, b_val, b_rows, outs[0], n);
     const uint64_t nchunks = (n + 63) >> 6;
     // One launch (the lane kernel alone, the rest at retirement if it turns out to be needed) when the caller has opted in and the
     // context's last retired call left nothing behind its lane kernel.  Such a call owns a mask buffer until it is retired (there
@@ -1036,8 +1040,8 @@ static int distance_check(const char *who, strsim_ctx_t *c, int measure, const u
                           uint64_t a_rows, const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, const uint32_t *out,
                           uint64_t out_rows)
 {
-    if (measure != STRSIM_LEVENSHTEIN && measure != STRSIM_OSA) {
-        set_error("%s: measure %d has no distance (STRSIM_LEVENSHTEIN or STRSIM_OSA)", who, measure);
+    if (measure != STRSIM_LEVENSHTEIN && measure != STRSIM_OSA && measure != STRSIM_INDEL) {
+        set_error("%s: measure %d has no distance (STRSIM_LEVENSHTEIN, STRSIM_OSA or STRSIM_INDEL)", who, measure);
         return STRSIM_ERR_ARG;
     }
     if (a_rows != b_rows && a_rows != 1 && b_rows != 1) { // strsim.rs:48-52
@@ -1074,8 +1078,9 @@ static int distance_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_
     la.n = n;
     la.status = c->dist_status; la.stream = c->stream;
     HIP_TRY(hipMemsetAsync(la.status, 0, sizeof(DevStatus), c->stream));
-    hipError_t e = launch_dist_lane(measure, la, k, out, c->osa_list);
-    if (e != hipSuccess) return hip_fail(e, "kernel launch (k_dist_lane)");
+    const bool indel = measure == STRSIM_INDEL; // (k_indel_lane / k_indel_wave with the uint32 output, strsim_indel.h)
+    hipError_t e = indel ? launch_indel_lane(la, k, out, c->osa_list) : launch_dist_lane(measure, la, k, out, c->osa_list);
+    if (e != hipSuccess) return hip_fail(e, indel ? "kernel launch (k_indel_lane)" : "kernel launch (k_dist_lane)");
     HIP_TRY(hipMemcpyAsync(c->dist_status_host, c->dist_status, sizeof(DevStatus), hipMemcpyDeviceToHost, c->stream));
     c->enqueued_ops += 3u;
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1086,15 +1091,16 @@ static int distance_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_
     uint32_t *scratch = nullptr;
     uint64_t slot_words = 0;
     if (max_pat > OSA_WAVE_LDS_CPS) { // (a byte length: it bounds the pattern in scalar values)
-        slot_words = dist_wave_slot_words(max_pat);
+        slot_words = indel ? indel_wave_slot_words(max_pat) : dist_wave_slot_words(max_pat);
         const size_t per = (size_t)slot_words * sizeof(uint32_t);
         if ((size_t)grid * per > OSA_SCRATCH_BUDGET) grid = (int)std::max<size_t>(1, OSA_SCRATCH_BUDGET / per);
         rc = ctx_reserve((void **)&c->osa_scratch, &c->osa_scratch_cap, (size_t)grid * per);
         if (rc) return rc;
         scratch = c->osa_scratch;
     }
-    e = launch_dist_wave(measure, la, k, out, c->osa_list, grid, scratch, slot_words);
-    if (e != hipSuccess) return hip_fail(e, "kernel launch (k_dist_wave)");
+    e = indel ? launch_indel_wave(la, k, out, c->osa_list, grid, scratch, slot_words)
+              : launch_dist_wave(measure, la, k, out, c->osa_list, grid, scratch, slot_words);
+    if (e != hipSuccess) return hip_fail(e, indel ? "kernel launch (k_indel_wave)" : "kernel launch (k_dist_wave)");
     c->enqueued_ops += 1u;
     return STRSIM_OK;
 }

@@ -130,6 +130,11 @@ hipError_t launch_dist_lane(int measure, const LaunchArgs &a, uint32_t k, uint32
 hipError_t launch_dist_wave(int measure, const LaunchArgs &a, uint32_t k, uint32_t *out, const uint32_t *worklist, int grid,
                             uint32_t *scratch, uint64_t slot_words);
 
+// Indel similarity / distance (strsim_indel.h), measure id 8: the same two-kernel protocol.  out32 == nullptr: the f64 similarity
+// into a.out (k = DIST_UNBOUNDED); otherwise the uint32 distance clamped by k into out32 (a.out is not used).
+hipError_t launch_indel_lane(const LaunchArgs &a, uint32_t k, uint32_t *out32, uint32_t *worklist);
+hipError_t launch_indel_wave(const LaunchArgs &a, uint32_t k, uint32_t *out32, const uint32_t *worklist, int grid, uint32_t *scratch,
+                             uint64_t slot_words);
 
 // Nearest match by bounded edit distance (strsim_nearest_kernels.h), measure 0 (Levenshtein) or 6 (OSA).  The strings of both
 // sides are packed by launch_match_pack first; launch_nearest_order then puts them in length order on the device (histograms,

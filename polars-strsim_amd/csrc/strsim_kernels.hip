@@ -25,6 +25,8 @@
 //                     to 64 bytes, one pair per wave for the rest; both in stream order, no second pass.
 //   k_dist_lane / k_dist_wave  bounded integer edit distances (Levenshtein, OSA; strsim_distance.h): the same two tiers, uint32
 //                     outputs, a length prefilter and, in the wave tier, the block cutoff of Myers / Ukkonen.
+//   k_indel_lane / k_indel_wave  Indel (LCS) similarity and distance (measure 8, strsim_indel.h): one pair per lane for ASCII
+//                     strings of up to 128 bytes (1..4 mask words per wave), one pair per wave for the rest; in stream order.
 //   k_nearest_lane<TR, K>  nearest match by bounded edit distance (strsim_nearest_kernels.h): one query per lane in length
 //                     order against wave-uniform candidates, a candidate length window and a running bound per lane.
 //   k_huge_pairs<M>   strings beyond WAVE_CAP, scratch in global memory, launched from strsim_ctx_synchronize() only
@@ -47,6 +49,7 @@
 #include "strsim_lane_common.h"
 #include "strsim_osa.h"
 #include "strsim_distance.h"
+#include "strsim_indel.h"
 #include "strsim_nearest.h"
 
 namespace strsim {
@@ -551,6 +554,27 @@ hipError_t launch_dist_wave(int measure, const LaunchArgs &a, uint32_t k, uint32
     else
         hipLaunchKernelGGL(k_dist_wave<false>, dim3((unsigned)grid), dim3(64), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB,
                            a.rowsB, k, out, worklist, a.status, scratch, slot_words);
+    return hipGetLastError();
+}
+
+hipError_t launch_indel_lane(const LaunchArgs &a, uint32_t k, uint32_t *out32, uint32_t *worklist)
+{
+    const unsigned grid = (unsigned)((a.n + 255u) / 256u);
+    const int lit = a.rowsA == a.rowsB ? 0 : (a.rowsA == 1 ? 1 : 2);
+    if (lit == 1)
+        hipLaunchKernelGGL(k_indel_lane<1>, dim3(grid), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, k, a.out, out32, worklist, a.status);
+    else if (lit == 2)
+        hipLaunchKernelGGL(k_indel_lane<2>, dim3(grid), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, k, a.out, out32, worklist, a.status);
+    else
+        hipLaunchKernelGGL(k_indel_lane<0>, dim3(grid), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, k, a.out, out32, worklist, a.status);
+    return hipGetLastError();
+}
+
+hipError_t launch_indel_wave(const LaunchArgs &a, uint32_t k, uint32_t *out32, const uint32_t *worklist, int grid, uint32_t *scratch,
+                             uint64_t slot_words)
+{
+    hipLaunchKernelGGL(k_indel_wave, dim3((unsigned)grid), dim3(64), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB, a.rowsB, k,
+                       a.out, out32, worklist, a.status, scratch, slot_words);
     return hipGetLastError();
 }
 

@@ -89,6 +89,16 @@ def osa(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
     return _similarity("osa", expr, other)
 
 
+def indel(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
+    """Indel similarity: rapidfuzz `fuzz.ratio` / 100 (`Indel.normalized_similarity`).
+
+    With l the length of the longest common subsequence, the distance is len(a) + len(b) - 2 l: insertions and deletions only,
+    so a substitution costs 2 ("ab" / "ba" is 0.5).  The score is 1 - distance / (len(a) + len(b)) over characters, 1.0 when
+    both strings are empty.  Not a measure of the upstream polars-strsim.
+    """
+    return _similarity("indel", expr, other)
+
+
 def _distance(function_name: str, expr: IntoExpr, other: IntoExpr, max_distance: int | None) -> pl.Expr:
     args = [parse_into_expr(expr), other]
     if max_distance is not None:
@@ -116,12 +126,21 @@ def osa_distance(expr: IntoExpr, other: IntoExpr, max_distance: int | None = Non
     return _distance("osa_distance", expr, other, max_distance)
 
 
+def indel_distance(expr: IntoExpr, other: IntoExpr, max_distance: int | None = None) -> pl.Expr:
+    """Indel distance as UInt32: len(a) + len(b) - 2 LCS(a, b) over characters -- insertions and deletions only, a substitution
+    costs 2.  `indel` (rapidfuzz `fuzz.ratio` / 100) is 1 - indel_distance / (len(a) + len(b)).  max_distance as in
+    levenshtein_distance.  Not in the upstream polars-strsim."""
+    return _distance("indel_distance", expr, other, max_distance)
+
+
 __all__ = [
     "best_match",
     "nearest",
     "levenshtein_distance",
     "osa_distance",
     "osa",
+    "indel_distance",
+    "indel",
     "levenshtein",
     "jaro",
     "jaro_winkler",

@@ -8,7 +8,7 @@ validity mask), as in README.md:69-70.
 """
 import numpy as np
 
-from ._lib import DISTANCE_MEASURES, DISTANCE_UNBOUNDED, ENTRY_POINT_ID, EXTRA_MEASURES, MEASURES, MEASURE_ID, LIB_PATH, STATUS, ShapeMismatch, StrsimError, lib
+from ._lib import DISTANCE_MEASURES, DISTANCE_UNBOUNDED, ENTRY_POINT_ID, EXTRA_MEASURES, INDEL_MEASURES, MEASURES, MEASURE_ID, LIB_PATH, STATUS, ShapeMismatch, StrsimError, lib
 from .context import Codec, Context, device_count, pack_strings, split_offsets
 
 _default_ctx = None
@@ -74,6 +74,13 @@ def osa(a, b, ctx=None):
     return similarity("osa", a, b, ctx)
 
 
+def indel(a, b, ctx=None):
+    """Indel similarity: rapidfuzz's fuzz.ratio / 100 (Indel.normalized_similarity).  With l the length of the longest common
+    subsequence, d = len(a) + len(b) - 2 l (insertions and deletions only: a substitution costs 2) and the score is
+    1.0 - d / (len(a) + len(b)) over characters, 1.0 when both are empty."""
+    return similarity("indel", a, b, ctx)
+
+
 def measure_supported(measure, entry_point="pairwise"):
     """True if the library's `entry_point` ("pairwise", "best_match" or "codec") accepts `measure`; needs no device."""
     from ._lib import measure_id
@@ -81,11 +88,12 @@ def measure_supported(measure, entry_point="pairwise"):
 
 
 def distance(measure, a, b, max_distance=None, ctx=None):
-    """Integer edit distance ("levenshtein" or "osa", DISTANCE_MEASURES) over characters, for two columns / a column and a
+    """Integer edit distance ("levenshtein" or "osa", DISTANCE_MEASURES, or "indel", INDEL_MEASURES: insertions and deletions
+    only, len(a) + len(b) - 2 LCS) over characters, for two columns / a column and a
     literal -> numpy.ma.MaskedArray of uint32, masked where either input is null.  With max_distance=k a row is d when d <= k and
     k + 1 otherwise (rapidfuzz's score_cutoff convention); None is no cutoff."""
-    if measure not in DISTANCE_MEASURES:
-        raise ValueError(f"no distance for measure {measure!r} (one of {DISTANCE_MEASURES})")
+    if measure not in DISTANCE_MEASURES + INDEL_MEASURES:
+        raise ValueError(f"no distance for measure {measure!r} (one of {DISTANCE_MEASURES + INDEL_MEASURES})")
     ctx = ctx or default_context()
     A, va = _as_column(a)
     B, vb = _as_column(b)
@@ -110,10 +118,17 @@ def osa_distance(a, b, max_distance=None, ctx=None):
     return distance("osa", a, b, max_distance, ctx)
 
 
+def indel_distance(a, b, max_distance=None, ctx=None):
+    """Indel distance: len(a) + len(b) - 2 LCS(a, b) over characters (insert and delete, a substitution costs 2); see distance()."""
+    return distance("indel", a, b, max_distance, ctx)
+
+
 def best_match(measure, queries, candidates, k=1, min_score=None, ctx=None):
     """For every query, its k best candidates by `measure`: (index int64 [N, k], score f64 [N, k]).  Slots in descending order
     of the score, ties to the lower candidate index; a candidate below min_score is not reported.  Empty slots -- and every slot
     of a null query -- are (-1, NaN).  Null candidates are never matched; indices refer to the caller's candidate positions."""
+    if measure in INDEL_MEASURES:
+        raise ValueError(f"no best match by measure {measure!r} (one of {MEASURES})")
     ctx = ctx or default_context()
     Q, vq = _as_column(queries)
     cand = list(candidates)
@@ -158,5 +173,6 @@ def nearest(measure, queries, candidates, k=1, max_distance=None, ctx=None):
 
 
 __all__ = ["best_match", "nearest", "Codec", "Context", "device_count", "pack_strings", "split_offsets", "similarity", "levenshtein", "jaro",
-           "jaro_winkler", "jaccard", "sorensen_dice", "osa", "measure_supported", "distance", "levenshtein_distance", "osa_distance",
+           "jaro_winkler", "jaccard", "sorensen_dice", "osa", "indel", "measure_supported", "distance", "levenshtein_distance", "osa_distance",
+           "indel_distance", "INDEL_MEASURES",
            "DISTANCE_MEASURES", "DISTANCE_UNBOUNDED", "MEASURES", "EXTRA_MEASURES", "MEASURE_ID", "STATUS", "ShapeMismatch", "StrsimError"]

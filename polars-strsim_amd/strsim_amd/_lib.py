@@ -17,6 +17,10 @@ MEASURES = ("levenshtein", "jaro", "jaro_winkler", "jaccard", "sorensen_dice")  
 EXTRA_MEASURES = ("osa",)
 MEASURE_ID = {m: i for i, m in enumerate(MEASURES)}
 MEASURE_ID["osa"] = 6
+# Indel (LCS) similarity = STRSIM_INDEL = 8 (7 stays unassigned): pairwise entry points and the distance calls.  A tuple of its own:
+# EXTRA_MEASURES and DISTANCE_MEASURES keep what they listed (nearest() takes DISTANCE_MEASURES, and has no Indel form).
+INDEL_MEASURES = ("indel",)
+MEASURE_ID["indel"] = 8
 ENTRY_POINT_ID = {"pairwise": 0, "best_match": 1, "codec": 2}  # strsim_entry_point_t
 # The measures strsim_distance_device / _host accept (integer edit distances), with their ids; STRSIM_DISTANCE_UNBOUNDED = no cutoff.
 DISTANCE_MEASURES = ("levenshtein", "osa")
