@@ -2,8 +2,11 @@
 # Registers / LDS / scratch of the kernels in csrc/strsim_kernels.hip (device-only compile, then the code object's metadata).
 #   bash bench_support/kernel_resources.sh [name-filter-regex | group] [EXTRA flags]
 # groups: nearest -- the kernels of strsim_nearest_device (its own and the best-match kernels it reuses)
+#         partial -- the kernels of the partial ratio (strsim_partial.h), and below them the OSA / distance / Indel kernels whose
+#                    headers it includes (their figures must not move when strsim_partial.h changes)
 ROOT=$(cd "$(dirname "$0")/.." && pwd); OUT=${TMPDIR:-/tmp}/strsim_co; mkdir -p $OUT
 case "$1" in
+    partial) FILTER='k_partial_|k_indel_|k_osa_|k_dist_' ;;
     nearest) FILTER='k_nearest_|k_match_pack|k_match_clear|k_match_fold|k_match_merge' ;;
     *) FILTER=${1:-.} ;;
 esac

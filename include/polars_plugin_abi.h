@@ -112,6 +112,14 @@ POLARS_PLUGIN_DECLARE(osa_distance)
  * substitution costs 2), UInt32 with the optional max_distance input of the *_distance functions above. */
 POLARS_PLUGIN_DECLARE(indel)
 POLARS_PLUGIN_DECLARE(indel_distance)
+/* Not in the reference: the partial ratio (STRSIM_PARTIAL_RATIO of strsim_amd.h: the best Indel similarity of the shorter string
+ * against a window of the longer one, rapidfuzz's fuzz.partial_ratio / 100), Float64 named after input 0, through the same pipeline
+ * as the similarities above; and the same with its alignment (strsim_partial_alignment_host): one Arrow struct chunk {score: Float64,
+ * src_start, src_end, dest_start, dest_end: UInt32} named after input 0 -- src is input 0, dest input 1 (rapidfuzz's names), half-open
+ * spans in Unicode scalar values.  Shape rule, literal broadcast and nulls (null in, null out) as above; no kwargs.  The alignment
+ * call bypasses the small-call combiner. */
+POLARS_PLUGIN_DECLARE(partial_ratio)
+POLARS_PLUGIN_DECLARE(partial_ratio_alignment)
 
 /* Best match (not in the reference): input 0 = the query column (N rows), input 1 = the candidate column (any number of rows; the
  * length rule of the functions above does not apply).  Output: N rows of an Arrow struct {index: UInt32, score: Float64} named after

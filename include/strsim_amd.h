@@ -49,11 +49,19 @@ typedef enum strsim_measure {
                                  like STRSIM_LEVENSHTEIN: 1.0 when a == b or both are empty, else 1.0 - d / max(|a|, |b|) over Unicode
                                  scalar values.  Pairwise entry points only (strsim_pairs_device, _small, strsim_pairs_host);
                                  not a measure of the reference */
-    STRSIM_INDEL         = 8  /* Indel (longest common subsequence) similarity, rapidfuzz's fuzz.ratio / 100: with l = LCS(a, b) and
+    STRSIM_INDEL         = 8, /* Indel (longest common subsequence) similarity, rapidfuzz's fuzz.ratio / 100: with l = LCS(a, b) and
                                  d = |a| + |b| - 2 l (insertions and deletions only, a substitution costs 2), 1.0 when |a| + |b| == 0,
                                  else 1.0 - d / (|a| + |b|) over Unicode scalar values (these two f64 operations, not 2 l / (|a| + |b|)).
                                  Pairwise entry points and strsim_distance_*; not a measure of the reference.  8, not 7: ids 5 and 7
                                  stay unassigned, callers were told (and tests hold) that every entry point refuses them */
+    STRSIM_PARTIAL_RATIO = 10 /* partial ratio, rapidfuzz's fuzz.partial_ratio / 100: the best STRSIM_INDEL score of the shorter string
+                                 (the needle, m scalar values) against a window of the longer one (n values) -- its proper prefixes
+                                 of 1 .. m-1 values, every substring of m values, its proper suffixes of m-1 .. 1 values (n + m - 1
+                                 windows; for n > m the whole longer string is NOT one of them, so the result can be below
+                                 STRSIM_INDEL's).  Equal lengths: the larger of the two directions.  Both empty: 1.0; one empty: 0.0.
+                                 It is the maximum at every needle length (rapidfuzz's heuristic for needles of more than 64
+                                 characters is not followed).  Pairwise entry points and strsim_partial_alignment_*; 10, not 9: ids
+                                 5, 7 and 9 stay unassigned and refused */
 } strsim_measure_t;
 
 /* Entry points of strsim_measure_supported(). */
@@ -121,6 +129,11 @@ STRSIM_API void *strsim_ctx_stream(strsim_ctx_t *ctx);
  * STRSIM_INDEL: the same protocol and the same reports as STRSIM_OSA, with other tiers: rows where both strings are ASCII and at
  * most 128 bytes are one pair per lane (strsim_ctx_last_wave_rows is 0 for a column of such rows), every other row one pair per
  * wave (any length).  A literal that is not ASCII or longer than 128 bytes sends every row to the second kernel.
+ *
+ * STRSIM_PARTIAL_RATIO: the same protocol and the same reports as STRSIM_OSA.  Rows where both strings are ASCII and at most 32
+ * bytes are one pair per lane (strsim_ctx_last_wave_rows is 0 for a column of such rows), every other row one pair per wave (any
+ * UTF-8, any length; tables beyond 16 KB use a scratch buffer the context grows; needles of more than 64 scalar values cost
+ * O(n m ceil(m / 64)) word steps a pair).  Its kernels read only the bytes the offsets describe.
  *
  * Reads beyond the strings: the kernels copy the values of a block of rows in whole 16-byte chunks, from the
  * 16-byte-aligned address at or below the block's first byte (a_values + a_offsets[first row]) up to the chunk that
@@ -257,6 +270,31 @@ STRSIM_API int strsim_distance_host(strsim_ctx_t *ctx, int measure,
                                     const uint32_t *a_offsets, const uint8_t *a_values, uint64_t a_rows,
                                     const uint32_t *b_offsets, const uint8_t *b_values, uint64_t b_rows,
                                     uint32_t max_distance, uint32_t *out, uint64_t out_rows);
+
+/*
+ * Partial ratio with its alignment (found by dlsym, like the distance calls: the ABI version stays 1.7).  out_score[i] is bit for
+ * bit what strsim_pairs_device(STRSIM_PARTIAL_RATIO) returns for row i.  out_span is out_rows x 4 uint32, row-major: a_start, a_end,
+ * b_start, b_end -- half open, in Unicode scalar values (not bytes).  The needle (the shorter string; a when the lengths are equal,
+ * unless b as the needle scores strictly higher) spans (0, its length); the other string's span is the winning window.  Among
+ * windows with the same score the one with the smallest end wins, then the smallest start, whatever the order a kernel visits
+ * them in.  Both strings empty, or exactly one: all four are 0.
+ *
+ * Shape rule, literal broadcast and out_rows as strsim_pairs_device; zero rows is a no-op.  The arguments are checked first and
+ * the context last (a NULL ctx is STRSIM_ERR_ARG too): no argument error needs a device.  The tiers are those of
+ * STRSIM_PARTIAL_RATIO (ASCII rows of up to 32 bytes one pair per lane, every other row one pair per wave).  Every row is complete
+ * in stream order; the call waits once for the stream after its first kernel (to size the second), so everything enqueued before
+ * it has completed when it returns.  It is not a pending call of strsim_ctx_synchronize and adds nothing to
+ * strsim_ctx_last_long_rows / _last_late_rows.  Its kernels read only the bytes the offsets describe.  The host variant stages
+ * the columns (strsim_pairs_host's copy path) and is synchronous.
+ */
+STRSIM_API int strsim_partial_alignment_device(strsim_ctx_t *ctx,
+                                               const uint32_t *a_offsets, const uint8_t *a_values, uint64_t a_rows,
+                                               const uint32_t *b_offsets, const uint8_t *b_values, uint64_t b_rows,
+                                               double *out_score, uint32_t *out_span, uint64_t out_rows);
+STRSIM_API int strsim_partial_alignment_host(strsim_ctx_t *ctx,
+                                             const uint32_t *a_offsets, const uint8_t *a_values, uint64_t a_rows,
+                                             const uint32_t *b_offsets, const uint8_t *b_values, uint64_t b_rows,
+                                             double *out_score, uint32_t *out_span, uint64_t out_rows);
 
 /*
  * Nearest match by bounded edit distance (found by dlsym, like the distance calls: the ABI version stays 1.7, and

@@ -58,6 +58,7 @@ struct PluginError {
 #include "plugin_pipeline.h"
 #include "plugin_match.h"
 #include "plugin_distance.h"
+#include "plugin_partial.h"
 #include "plugin_nearest.h"
 
 void run(int measure, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret, bool engine_parallel)
@@ -461,6 +462,16 @@ POLARS_PLUGIN_DEFINE(jaccard, STRSIM_JACCARD)
 POLARS_PLUGIN_DEFINE(sorensen_dice, STRSIM_SORENSEN_DICE)
 POLARS_PLUGIN_DEFINE(osa, STRSIM_OSA)
 POLARS_PLUGIN_DEFINE(indel, STRSIM_INDEL)
+POLARS_PLUGIN_DEFINE(partial_ratio, STRSIM_PARTIAL_RATIO)
+void _polars_plugin_partial_ratio_alignment(SeriesExport *inputs, size_t n_inputs, const uint8_t *, size_t, SeriesExport *return_value,
+                                            CallerContext *)
+{
+    partial_alignment_entry(inputs, n_inputs, return_value);
+}
+void _polars_plugin_field_partial_ratio_alignment(ArrowSchema *input_fields, size_t n_fields, ArrowSchema *return_value)
+{
+    partial_alignment_field_entry(input_fields, n_fields, return_value);
+}
 POLARS_PLUGIN_DEFINE_DISTANCE(levenshtein, STRSIM_LEVENSHTEIN)
 POLARS_PLUGIN_DEFINE_DISTANCE(osa, STRSIM_OSA)
 POLARS_PLUGIN_DEFINE_DISTANCE(indel, STRSIM_INDEL)

@@ -20,6 +20,7 @@
 #include "strsim_osa.h"
 #include "strsim_distance.h"
 #include "strsim_indel.h"
+#include "strsim_partial.h"
 #include "strsim_nearest.h"
 
 namespace strsim {
@@ -258,7 +259,8 @@ static int ctx_retire_slot(strsim_ctx *c, int s)
         return STRSIM_ERR_INTERNAL;
     }
     // (an OSA or Indel call has no lane_left: it says nothing about what the next call of the other measures leaves behind)
-    const uint32_t left = (c->slot_measure[s] == STRSIM_OSA || c->slot_measure[s] == STRSIM_INDEL) ? LANE_LEFT_UNKNOWN
+    const uint32_t left = (c->slot_measure[s] == STRSIM_OSA || c->slot_measure[s] == STRSIM_INDEL || c->slot_measure[s] == STRSIM_PARTIAL_RATIO)
+                              ? LANE_LEFT_UNKNOWN
                                                            : *reinterpret_cast<const volatile uint32_t *>(&c->status_host[s].lane_left);
     if (left != LANE_LEFT_UNKNOWN) { // what the next call on this context is enqueued for
         c->expect_slow = left != 0u;
@@ -468,6 +470,31 @@ void strsim_split_offsets(uint64_t len, uint64_t n, uint64_t *out)
 // slot like any other (its status block carries the ticket and the work-list count) and has nothing to do at retirement.
 // measure = STRSIM_INDEL runs the same flow with k_indel_lane / k_indel_wave (strsim_indel.h) on the same work list and scratch.
 static constexpr size_t OSA_SCRATCH_BUDGET = (size_t)1 << 30; // k_osa_wave runs fewer waves rather than use more scratch
+
+// Partial ratio (strsim_partial.h): k_partial_lane over every row, then k_partial_wave over the `rows` rows of the work list;
+// max_pat / max_hay bound their needles and haystacks (bytes, hence scalar values).  span == nullptr: the score alone.
+static int partial_wave_pass(strsim_ctx *c, const LaunchArgs &la, uint32_t *span, uint32_t rows, uint32_t max_pat, uint32_t max_hay)
+{
+    int grid = c->num_cu * 16;
+    if ((uint64_t)grid > rows) grid = (int)rows;
+    uint32_t *scratch = nullptr;
+    // (partial_wave_words grows with both arguments: the larger of the two forms at the bounds covers every pair)
+    uint64_t slot_words = std::max(partial_wave_words(64u, max_hay), partial_wave_words(std::max(max_pat, 65u), max_hay));
+    if (slot_words > PARTIAL_WAVE_LDS_WORDS) {
+        slot_words = (slot_words + 1u) & ~(uint64_t)1; // (64-bit words inside a slot)
+        const size_t per = (size_t)slot_words * sizeof(uint32_t);
+        if ((size_t)grid * per > OSA_SCRATCH_BUDGET) grid = (int)std::max<size_t>(1, OSA_SCRATCH_BUDGET / per);
+        int rc = ctx_reserve((void **)&c->osa_scratch, &c->osa_scratch_cap, (size_t)grid * per);
+        if (rc) return rc;
+        scratch = c->osa_scratch;
+    } else {
+        slot_words = 0;
+    }
+    hipError_t e = launch_partial_wave(la, span, c->osa_list, grid, scratch, slot_words);
+    if (e != hipSuccess) return hip_fail(e, "kernel launch (k_partial_wave)");
+    c->enqueued_ops += 1u;
+    return STRSIM_OK;
+}
 static int pairs_osa(strsim_ctx *c, int slot, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
                      const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t n)
 {
@@ -482,14 +509,19 @@ static int pairs_osa(strsim_ctx *c, int slot, int measure, const uint32_t *a_off
     la.out = out; la.n = n;
     la.status = c->status + slot; la.stream = c->stream;
     HIP_TRY(hipMemsetAsync(la.status, 0, sizeof(DevStatus), c->stream));
-    const bool indel = measure == STRSIM_INDEL;
-    hipError_t e = indel ? launch_indel_lane(la, DIST_UNBOUNDED, nullptr, c->osa_list) : launch_osa_lane(la, c->osa_list);
-    if (e != hipSuccess) return hip_fail(e, indel ? "kernel launch (k_indel_lane)" : "kernel launch (k_osa_lane)");
+    const bool indel = measure == STRSIM_INDEL, partial = measure == STRSIM_PARTIAL_RATIO;
+    hipError_t e = partial ? launch_partial_lane(la, nullptr, c->osa_list)
+                 : indel ? launch_indel_lane(la, DIST_UNBOUNDED, nullptr, c->osa_list) : launch_osa_lane(la, c->osa_list);
+    if (e != hipSuccess)
+        return hip_fail(e, partial ? "kernel launch (k_partial_lane)" : indel ? "kernel launch (k_indel_lane)" : "kernel launch (k_osa_lane)");
     HIP_TRY(launch_publish_status(c->status + slot, c->status_host_dev + slot, c->slot_ticket[slot], c->stream));
     c->enqueued_ops += 3u;
     HIP_TRY(hipStreamSynchronize(c->stream));
     const uint32_t rows = c->status_host[slot].wave_rows, max_pat = c->status_host[slot].max_len;
-    if (rows != 0u) {
+    if (rows != 0u && partial) {
+        rc = partial_wave_pass(c, la, nullptr, rows, max_pat, c->status_host[slot].pad1[0]);
+        if (rc) return rc;
+    } else if (rows != 0u) {
         int grid = c->num_cu * 16;
         if ((uint64_t)grid > rows) grid = (int)rows;
         uint32_t *scratch = nullptr;
@@ -563,7 +595,7 @@ static int pairs_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_off
             return STRSIM_ERR_EARLIER_CALL;
         }
     }
-    if (measure == STRSIM_OSA || measure == STRSIM_INDEL) return pairs_osa(c, slot, measure, a_off, a_val, a_rows, b_off, b_val, b_rows, outs[0], n);
+    if (measure == STRSIM_OSA || measure == STRSIM_INDEL || measure == STRSIM_PARTIAL_RATIO) return pairs_osa(c, slot, measure, a_off, a_val, a_rows, b_off, b_val, b_rows, outs[0], n);
     const uint64_t nchunks = (n + 63) >> 6;
     // One launch (the lane kernel alone, the rest at retirement if it turns out to be needed) when the caller has opted in and the
     // context's last retired call left nothing behind its lane kernel.  Such a call owns a mask buffer until it is retired (there
@@ -1141,6 +1173,99 @@ int strsim_distance_host(strsim_ctx_t *c, int measure, const uint32_t *a_off, co
                               (uint32_t *)c->stage[4], n);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(out, c->stage[4], n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return STRSIM_OK;
+}
+
+} // extern "C"
+
+// ---- partial ratio with its alignment (strsim_partial.h) ----
+
+static int partial_check(const char *who, strsim_ctx_t *c, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
+                         const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, const double *out_score, const uint32_t *out_span,
+                         uint64_t out_rows)
+{
+    if (a_rows != b_rows && a_rows != 1 && b_rows != 1) { // strsim.rs:48-52
+        set_error("Inputs must have the same length, or one of them must be a Utf8 literal.");
+        return STRSIM_ERR_SHAPE;
+    }
+    const uint64_t n = (a_rows == 1) ? b_rows : a_rows;
+    if (out_rows != n) {
+        set_error("%s: out_rows=%llu but the inputs produce %llu rows", who, (unsigned long long)out_rows, (unsigned long long)n);
+        return STRSIM_ERR_ARG;
+    }
+    if (n > 0xFFFFFFFFull) {
+        set_error("%s: %llu rows in one call; split the column (at most 2^32 - 1 rows per call)", who, (unsigned long long)n);
+        return STRSIM_ERR_ARG;
+    }
+    if (n && (!a_off || !a_val || !b_off || !b_val || !out_score || !out_span)) { set_error("%s: NULL buffer", who); return STRSIM_ERR_ARG; }
+    if (!c) { set_error("%s: ctx is NULL", who); return STRSIM_ERR_ARG; }
+    return STRSIM_OK;
+}
+
+// k_partial_lane<ALIGN> over every row, a read-back of what it left, then k_partial_wave<ALIGN> (as distance_device_impl).
+static int partial_device_impl(strsim_ctx_t *c, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
+                               const uint8_t *b_val, uint64_t b_rows, double *out_score, uint32_t *out_span, uint64_t n)
+{
+    int rc = ctx_set_device(c);
+    if (rc) return rc;
+    rc = ctx_reserve((void **)&c->osa_list, &c->osa_list_cap, n * sizeof(uint32_t));
+    if (rc) return rc;
+    if (!c->dist_status) HIP_TRY(hipMalloc((void **)&c->dist_status, sizeof(DevStatus)));
+    if (!c->dist_status_host) HIP_TRY(hipHostMalloc((void **)&c->dist_status_host, sizeof(DevStatus), hipHostMallocDefault));
+    LaunchArgs la{};
+    la.offA = a_off; la.valA = a_val; la.rowsA = a_rows;
+    la.offB = b_off; la.valB = b_val; la.rowsB = b_rows;
+    la.out = out_score; la.n = n;
+    la.status = c->dist_status; la.stream = c->stream;
+    HIP_TRY(hipMemsetAsync(la.status, 0, sizeof(DevStatus), c->stream));
+    hipError_t e = launch_partial_lane(la, out_span, c->osa_list);
+    if (e != hipSuccess) return hip_fail(e, "kernel launch (k_partial_lane)");
+    HIP_TRY(hipMemcpyAsync(c->dist_status_host, c->dist_status, sizeof(DevStatus), hipMemcpyDeviceToHost, c->stream));
+    c->enqueued_ops += 3u;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const uint32_t rows = c->dist_status_host->wave_rows;
+    if (rows == 0u) return STRSIM_OK;
+    return partial_wave_pass(c, la, out_span, rows, c->dist_status_host->max_len, c->dist_status_host->pad1[0]);
+}
+
+extern "C" {
+
+int strsim_partial_alignment_device(strsim_ctx_t *c, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
+                                    const uint8_t *b_val, uint64_t b_rows, double *out_score, uint32_t *out_span, uint64_t out_rows)
+{
+    int rc = partial_check("strsim_partial_alignment_device", c, a_off, a_val, a_rows, b_off, b_val, b_rows, out_score, out_span, out_rows);
+    if (rc || out_rows == 0) return rc;
+    return partial_device_impl(c, a_off, a_val, a_rows, b_off, b_val, b_rows, out_score, out_span, out_rows);
+}
+
+int strsim_partial_alignment_host(strsim_ctx_t *c, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
+                                  const uint8_t *b_val, uint64_t b_rows, double *out_score, uint32_t *out_span, uint64_t out_rows)
+{
+    int rc = partial_check("strsim_partial_alignment_host", c, a_off, a_val, a_rows, b_off, b_val, b_rows, out_score, out_span, out_rows);
+    if (rc || out_rows == 0) return rc;
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    const uint64_t n = out_rows;
+    // (as strsim_pairs_host's copy path: the caller's offset base is kept and the values go up from byte 0)
+    const size_t span_at = (n * 8 + 255) & ~(size_t)255;
+    const size_t need[5] = {(a_rows + 1) * 4, (size_t)a_off[a_rows] + 1, (b_rows + 1) * 4, (size_t)b_off[b_rows] + 1, span_at + n * 16};
+    for (int i = 0; i < 5; ++i) {
+        rc = ctx_reserve(&c->stage[i], &c->stage_cap[i], need[i]);
+        if (rc) return rc;
+    }
+    hipStream_t st = c->stream;
+    HIP_TRY(hipMemcpyAsync(c->stage[0], a_off, (a_rows + 1) * 4, hipMemcpyHostToDevice, st));
+    if (a_off[a_rows]) HIP_TRY(hipMemcpyAsync(c->stage[1], a_val, a_off[a_rows], hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c->stage[2], b_off, (b_rows + 1) * 4, hipMemcpyHostToDevice, st));
+    if (b_off[b_rows]) HIP_TRY(hipMemcpyAsync(c->stage[3], b_val, b_off[b_rows], hipMemcpyHostToDevice, st));
+    double *const d_score = static_cast<double *>(c->stage[4]);
+    uint32_t *const d_span = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(c->stage[4]) + span_at);
+    rc = partial_device_impl(c, (const uint32_t *)c->stage[0], (const uint8_t *)c->stage[1], a_rows, (const uint32_t *)c->stage[2],
+                             (const uint8_t *)c->stage[3], b_rows, d_score, d_span, n);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out_score, d_score, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out_span, d_span, n * 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return STRSIM_OK;
 }

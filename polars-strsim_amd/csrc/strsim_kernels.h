@@ -136,6 +136,13 @@ hipError_t launch_indel_lane(const LaunchArgs &a, uint32_t k, uint32_t *out32, u
 hipError_t launch_indel_wave(const LaunchArgs &a, uint32_t k, uint32_t *out32, const uint32_t *worklist, int grid, uint32_t *scratch,
                              uint64_t slot_words);
 
+// Partial ratio (strsim_partial.h), measure id 10: the same two-kernel protocol.  The f64 score goes into a.out; span != nullptr
+// adds the alignment (four uint32 per row).  k_partial_lane also leaves a bound of the work list's haystacks (bytes) in
+// a.status->pad1[0]; slot_words (even) comes from partial_wave_words() of the two bounds.
+hipError_t launch_partial_lane(const LaunchArgs &a, uint32_t *span, uint32_t *worklist);
+hipError_t launch_partial_wave(const LaunchArgs &a, uint32_t *span, const uint32_t *worklist, int grid, uint32_t *scratch,
+                               uint64_t slot_words);
+
 // Nearest match by bounded edit distance (strsim_nearest_kernels.h), measure 0 (Levenshtein) or 6 (OSA).  The strings of both
 // sides are packed by launch_match_pack first; launch_nearest_order then puts them in length order on the device (histograms,
 // scan, scatter; the histograms must be zeroed), and launch_nearest_lane writes splits x nq x match_lane_k(k) partial lists in

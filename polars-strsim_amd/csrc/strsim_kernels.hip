@@ -27,6 +27,9 @@
 //                     outputs, a length prefilter and, in the wave tier, the block cutoff of Myers / Ukkonen.
 //   k_indel_lane / k_indel_wave  Indel (LCS) similarity and distance (measure 8, strsim_indel.h): one pair per lane for ASCII
 //                     strings of up to 128 bytes (1..4 mask words per wave), one pair per wave for the rest; in stream order.
+//   k_partial_lane / k_partial_wave  partial ratio and its alignment (measure 10, strsim_partial.h): the best window of the longer
+//                     string against the shorter one, match masks built once per pair; ASCII strings of up to 32 bytes per lane,
+//                     the rest one pair per wave; in stream order.
 //   k_nearest_lane<TR, K>  nearest match by bounded edit distance (strsim_nearest_kernels.h): one query per lane in length
 //                     order against wave-uniform candidates, a candidate length window and a running bound per lane.
 //   k_huge_pairs<M>   strings beyond WAVE_CAP, scratch in global memory, launched from strsim_ctx_synchronize() only
@@ -50,6 +53,7 @@
 #include "strsim_osa.h"
 #include "strsim_distance.h"
 #include "strsim_indel.h"
+#include "strsim_partial.h"
 #include "strsim_nearest.h"
 
 namespace strsim {
@@ -575,6 +579,37 @@ hipError_t launch_indel_wave(const LaunchArgs &a, uint32_t k, uint32_t *out32, c
 {
     hipLaunchKernelGGL(k_indel_wave, dim3((unsigned)grid), dim3(64), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB, a.rowsB, k,
                        a.out, out32, worklist, a.status, scratch, slot_words);
+    return hipGetLastError();
+}
+
+template <bool ALIGN>
+static void launch_partial_lane_al(const LaunchArgs &a, uint32_t *span, uint32_t *worklist)
+{
+    const unsigned grid = (unsigned)((a.n + 255u) / 256u);
+    const int lit = a.rowsA == a.rowsB ? 0 : (a.rowsA == 1 ? 1 : 2);
+    if (lit == 1)
+        hipLaunchKernelGGL((k_partial_lane<1, ALIGN>), dim3(grid), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, a.out, span, worklist, a.status);
+    else if (lit == 2)
+        hipLaunchKernelGGL((k_partial_lane<2, ALIGN>), dim3(grid), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, a.out, span, worklist, a.status);
+    else
+        hipLaunchKernelGGL((k_partial_lane<0, ALIGN>), dim3(grid), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, a.out, span, worklist, a.status);
+}
+
+hipError_t launch_partial_lane(const LaunchArgs &a, uint32_t *span, uint32_t *worklist)
+{
+    if (span) launch_partial_lane_al<true>(a, span, worklist);
+    else launch_partial_lane_al<false>(a, span, worklist);
+    return hipGetLastError();
+}
+
+hipError_t launch_partial_wave(const LaunchArgs &a, uint32_t *span, const uint32_t *worklist, int grid, uint32_t *scratch, uint64_t slot_words)
+{
+    if (span)
+        hipLaunchKernelGGL(k_partial_wave<true>, dim3((unsigned)grid), dim3(64), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB,
+                           a.rowsB, a.out, span, worklist, a.status, scratch, slot_words);
+    else
+        hipLaunchKernelGGL(k_partial_wave<false>, dim3((unsigned)grid), dim3(64), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB,
+                           a.rowsB, a.out, span, worklist, a.status, scratch, slot_words);
     return hipGetLastError();
 }
 

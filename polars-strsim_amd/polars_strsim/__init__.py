@@ -99,6 +99,33 @@ def indel(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
     return _similarity("indel", expr, other)
 
 
+def partial_ratio(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
+    """Partial ratio: rapidfuzz `fuzz.partial_ratio` / 100.
+
+    The best `indel` score of the shorter string (the needle, m characters) against a window of the longer one.  The windows are
+    the longer string's proper prefixes of 1 .. m-1 characters, every substring of m characters, and its proper suffixes: the
+    needle slid over it one step at a time, overhanging either end.  For equal lengths the larger of the two directions; 1.0 when
+    both strings are empty, 0.0 when exactly one is.  It can be lower than `indel` of the same pair: when the lengths differ the
+    whole longer string is not one of the windows.  It is the maximum at every needle length (rapidfuzz switches to a heuristic
+    for needles of more than 64 characters; this does not).  Not in the upstream polars-strsim.
+    """
+    return _similarity("partial_ratio", expr, other)
+
+
+def partial_ratio_alignment(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
+    """`partial_ratio` with the window that won (rapidfuzz `fuzz.partial_ratio` / 100 and `fuzz.partial_ratio_alignment`): a
+    struct {score: Float64, src_start, src_end, dest_start, dest_end: UInt32}; src is `expr`, dest is `other`, spans are half
+    open and counted in characters.  The needle (the shorter string) spans (0, its length), the other span is the winning window
+    out of the window set of `partial_ratio`; among windows with the same score the one with the smallest end wins, then the
+    smallest start.  Null in, null out.  Not in the upstream polars-strsim."""
+    return register_plugin_function(
+        plugin_path=_PLUGIN_DIR,
+        function_name="partial_ratio_alignment",
+        args=[parse_into_expr(expr), other],
+        is_elementwise=True,
+    )
+
+
 def _distance(function_name: str, expr: IntoExpr, other: IntoExpr, max_distance: int | None) -> pl.Expr:
     args = [parse_into_expr(expr), other]
     if max_distance is not None:
@@ -141,6 +168,8 @@ __all__ = [
     "osa",
     "indel_distance",
     "indel",
+    "partial_ratio",
+    "partial_ratio_alignment",
     "levenshtein",
     "jaro",
     "jaro_winkler",

@@ -8,7 +8,7 @@ validity mask), as in README.md:69-70.
 """
 import numpy as np
 
-from ._lib import DISTANCE_MEASURES, DISTANCE_UNBOUNDED, ENTRY_POINT_ID, EXTRA_MEASURES, INDEL_MEASURES, MEASURES, MEASURE_ID, LIB_PATH, STATUS, ShapeMismatch, StrsimError, lib
+from ._lib import DISTANCE_MEASURES, DISTANCE_UNBOUNDED, ENTRY_POINT_ID, EXTRA_MEASURES, INDEL_MEASURES, MEASURES, MEASURE_ID, PARTIAL_MEASURES, LIB_PATH, STATUS, ShapeMismatch, StrsimError, lib
 from .context import Codec, Context, device_count, pack_strings, split_offsets
 
 _default_ctx = None
@@ -81,6 +81,36 @@ def indel(a, b, ctx=None):
     return similarity("indel", a, b, ctx)
 
 
+def partial_ratio(a, b, ctx=None):
+    """Partial ratio: rapidfuzz's fuzz.partial_ratio / 100.  The best indel() score of the shorter string (the needle, m
+    characters) against a window of the longer one: its proper prefixes of 1 .. m-1 characters, every substring of m characters,
+    its proper suffixes (the needle slid over the longer string one step at a time, overhanging either end).  Equal lengths: the
+    larger of the two directions.  1.0 when both are empty, 0.0 when exactly one is.  It can be LOWER than indel(a, b): when the
+    lengths differ the whole longer string is not one of the windows.  It is the maximum at every needle length (rapidfuzz's
+    heuristic for needles of more than 64 characters is not followed)."""
+    return similarity("partial_ratio", a, b, ctx)
+
+
+def partial_ratio_alignment(a, b, ctx=None):
+    """partial_ratio() with the window that won: (score f64 [N], span masked uint32 [N, 4]).  span = a_start, a_end, b_start,
+    b_end, half open, in characters: the needle spans (0, its length), the other string's span is the winning window; among
+    windows with the same score the one with the smallest end wins, then the smallest start.  For equal lengths a is the needle
+    unless b as the needle scores strictly higher.  Both empty, or one empty: (0, 0, 0, 0).  Nulls: NaN and a masked row."""
+    ctx = ctx or default_context()
+    A, va = _as_column(a)
+    B, vb = _as_column(b)
+    ao, av = pack_strings(A)
+    bo, bv = pack_strings(B)
+    score, span = ctx.partial_alignment_host(ao, av, bo, bv)
+    n = score.size
+    mask = np.zeros(n, dtype=bool)
+    for v in (va, vb):
+        if v is not None:
+            mask |= ~(np.broadcast_to(v, (n,)) if v.size == 1 else v)
+    score[mask] = np.nan
+    return score, np.ma.MaskedArray(span, mask=np.repeat(mask[:, None], 4, axis=1))
+
+
 def measure_supported(measure, entry_point="pairwise"):
     """True if the library's `entry_point` ("pairwise", "best_match" or "codec") accepts `measure`; needs no device."""
     from ._lib import measure_id
@@ -127,7 +157,7 @@ def best_match(measure, queries, candidates, k=1, min_score=None, ctx=None):
     """For every query, its k best candidates by `measure`: (index int64 [N, k], score f64 [N, k]).  Slots in descending order
     of the score, ties to the lower candidate index; a candidate below min_score is not reported.  Empty slots -- and every slot
     of a null query -- are (-1, NaN).  Null candidates are never matched; indices refer to the caller's candidate positions."""
-    if measure in INDEL_MEASURES:
+    if measure in INDEL_MEASURES + PARTIAL_MEASURES:
         raise ValueError(f"no best match by measure {measure!r} (one of {MEASURES})")
     ctx = ctx or default_context()
     Q, vq = _as_column(queries)
@@ -174,5 +204,5 @@ def nearest(measure, queries, candidates, k=1, max_distance=None, ctx=None):
 
 __all__ = ["best_match", "nearest", "Codec", "Context", "device_count", "pack_strings", "split_offsets", "similarity", "levenshtein", "jaro",
            "jaro_winkler", "jaccard", "sorensen_dice", "osa", "indel", "measure_supported", "distance", "levenshtein_distance", "osa_distance",
-           "indel_distance", "INDEL_MEASURES",
+           "indel_distance", "INDEL_MEASURES", "partial_ratio", "partial_ratio_alignment", "PARTIAL_MEASURES",
            "DISTANCE_MEASURES", "DISTANCE_UNBOUNDED", "MEASURES", "EXTRA_MEASURES", "MEASURE_ID", "STATUS", "ShapeMismatch", "StrsimError"]

@@ -21,6 +21,10 @@ MEASURE_ID["osa"] = 6
 # EXTRA_MEASURES and DISTANCE_MEASURES keep what they listed (nearest() takes DISTANCE_MEASURES, and has no Indel form).
 INDEL_MEASURES = ("indel",)
 MEASURE_ID["indel"] = 8
+# Partial ratio = STRSIM_PARTIAL_RATIO = 10 (9 stays unassigned): pairwise entry points and strsim_partial_alignment_*.  A tuple of
+# its own again: it has no distance, no best match, no nearest match and no codec.
+PARTIAL_MEASURES = ("partial_ratio",)
+MEASURE_ID["partial_ratio"] = 10
 ENTRY_POINT_ID = {"pairwise": 0, "best_match": 1, "codec": 2}  # strsim_entry_point_t
 # The measures strsim_distance_device / _host accept (integer edit distances), with their ids; STRSIM_DISTANCE_UNBOUNDED = no cutoff.
 DISTANCE_MEASURES = ("levenshtein", "osa")
@@ -104,6 +108,10 @@ def lib():
         f = getattr(L, name)
         f.restype = i32
         f.argtypes = [vp, i32, vp, vp, u64, vp, vp, u64, C.c_uint32, vp, u64]
+    for name in ("strsim_partial_alignment_device", "strsim_partial_alignment_host"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, vp, u64]
     for name in ("strsim_nearest_device", "strsim_nearest_host"):
         f = getattr(L, name)
         f.restype = i32

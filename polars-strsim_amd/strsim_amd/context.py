@@ -189,6 +189,27 @@ class Context:
                                            out.data_ptr(), out.numel()))
         return out
 
+    def partial_alignment_device(self, a_offsets, a_values, b_offsets, b_values, score=None, span=None):
+        """Partial ratio with its alignment (strsim_partial_alignment_device) of device tensors laid out as for pairs_device ->
+        (score f64 [n], span int32 [n, 4] holding uint32 a_start, a_end, b_start, b_end in characters).  Complete in stream order."""
+        import torch
+        ra, rb = a_offsets.numel() - 1, b_offsets.numel() - 1
+        n = rb if ra == 1 else ra
+        for t in (a_offsets, b_offsets):
+            assert t.is_cuda and t.element_size() == 4 and t.is_contiguous()
+        for t in (a_values, b_values):
+            assert t.is_cuda and t.element_size() == 1 and t.is_contiguous()
+        rows = n if (ra == rb or ra == 1 or rb == 1) else 0
+        if score is None:
+            score = torch.empty(rows, dtype=torch.float64, device=a_offsets.device)
+        if span is None:
+            span = torch.empty((rows, 4), dtype=torch.int32, device=a_offsets.device)
+        assert span.is_cuda and span.element_size() == 4 and span.is_contiguous() and not span.is_floating_point()
+        check(lib().strsim_partial_alignment_device(self._h, a_offsets.data_ptr(), a_values.data_ptr(), ra,
+                                                    b_offsets.data_ptr(), b_values.data_ptr(), rb,
+                                                    score.data_ptr(), span.data_ptr(), score.numel()))
+        return score, span
+
     # ---- host-resident (numpy) ---------------------------------------------------------------------
     def pairs_host(self, measure, a_offsets, a_values, b_offsets, b_values):
         """Synchronous: numpy uint32 offsets + uint8 values in, numpy f64 out."""
@@ -228,6 +249,27 @@ class Context:
         check(lib().strsim_distance_host(self._h, measure_id(measure), ao.ctypes.data, av.ctypes.data, ra,
                                          bo.ctypes.data, bv.ctypes.data, rb, _max_distance(max_distance), out.ctypes.data, n))
         return out
+
+    def partial_alignment_host(self, a_offsets, a_values, b_offsets, b_values):
+        """Synchronous partial ratio with its alignment (strsim_partial_alignment_host): numpy uint32 offsets + uint8 values in ->
+        (score f64 [n], span uint32 [n, 4]: a_start, a_end, b_start, b_end, half open, in characters)."""
+        ao = np.ascontiguousarray(a_offsets, dtype=np.uint32)
+        bo = np.ascontiguousarray(b_offsets, dtype=np.uint32)
+        av = np.ascontiguousarray(a_values, dtype=np.uint8)
+        bv = np.ascontiguousarray(b_values, dtype=np.uint8)
+        if av.size == 0:
+            av = np.zeros(1, dtype=np.uint8)
+        if bv.size == 0:
+            bv = np.zeros(1, dtype=np.uint8)
+        ra, rb = ao.size - 1, bo.size - 1
+        n = rb if ra == 1 else ra
+        if ra != rb and ra != 1 and rb != 1:
+            n = 0
+        score = np.empty(n, dtype=np.float64)
+        span = np.empty((n, 4), dtype=np.uint32)
+        check(lib().strsim_partial_alignment_host(self._h, ao.ctypes.data, av.ctypes.data, ra, bo.ctypes.data, bv.ctypes.data, rb,
+                                                  score.ctypes.data, span.ctypes.data, n))
+        return score, span
 
     def best_match(self, measure, q_offsets, q_values, c_offsets, c_values, k=1, min_score=None):
         """Synchronous best match (strsim_best_match_host, ABI 1.7): numpy uint32 offsets + uint8 values of the queries and the
