@@ -56,6 +56,98 @@ struct PluginError {
 #include "plugin_arrow.h"
 #include "plugin_pack.h"
 #include "plugin_pipeline.h"
+
+// ---- pieces every plugin function is made of --------------------------------------------------------
+
+// A plugin call: the callee owns the inputs whatever happens, and no exception crosses the ABI -- a failure leaves `ret` empty
+// and its message in g_plugin_error.
+template <class Fn> void guarded(SeriesExport *inputs, size_t n_inputs, Fn fn)
+{
+    InputGuard guard{inputs, n_inputs};
+    try {
+        fn();
+    } catch (const PluginError &e) {
+        g_plugin_error = e.msg;
+    } catch (const std::bad_alloc &) {
+        g_plugin_error = "out of host memory";
+    } catch (const std::exception &e) {
+        g_plugin_error = std::string("unexpected failure: ") + e.what();
+    } catch (...) {
+        g_plugin_error = "unexpected failure";
+    }
+}
+
+// A planning-time field: fill(ret, name of input 0).  (No exception crosses the ABI: an unreleasable, empty schema is left behind.)
+template <class Fill> void field_named_after_input0(ArrowSchema *input_fields, size_t n_fields, ArrowSchema *ret, Fill fill)
+{
+    const char *name = (n_fields > 0 && input_fields && input_fields[0].name) ? input_fields[0].name : "";
+    try {
+        fill(ret, name);
+    } catch (...) {
+        memset(ret, 0, sizeof *ret);
+        g_plugin_error = "out of host memory";
+    }
+}
+
+void fill_named_schema(ArrowSchema *s, const char *format, const char *name)
+{
+    fill_f64_schema(s, name);
+    s->format = format;
+}
+
+// The two columns of an elementwise function: shape rule and literal broadcast exactly as strsim.rs:48-52,61-66.
+struct Elementwise {
+    Column col[2];
+    bool lit[2];
+    uint64_t n;
+    bool all_null; // a NULL literal: the reference unwrap()s and panics (strsim.rs:62,65,87,90); here every row is null
+    explicit Elementwise(SeriesExport *inputs)
+    {
+        describe(inputs[0], col[0]);
+        describe(inputs[1], col[1]);
+        const Column &a = col[0], &b = col[1];
+        if (a.rows != b.rows && a.rows != 1 && b.rows != 1)
+            fail("Inputs must have the same length, or one of them must be a Utf8 literal.");
+        lit[0] = a.rows == 1 && b.rows != 1;
+        lit[1] = b.rows == 1;
+        n = lit[0] ? b.rows : a.rows;
+        all_null = (lit[0] && !row_valid(a, 0)) || (lit[1] && !row_valid(b, 0));
+    }
+    bool any_null() const { return all_null || col[0].any_null || col[1].any_null; }
+};
+
+// Hands `data` (n values of Arrow format `format`; pinned: from pinned_pool()) and `validity` (or nullptr) to `ret` as one
+// chunk named `name`.  They are the caller's until this returns.
+void export_primitive(const char *format, const char *name, uint64_t n, void *data, uint8_t *validity, int64_t null_count, bool pinned,
+                      SeriesExport *ret)
+{
+    ArrowSchema *schema = static_cast<ArrowSchema *>(calloc(1, sizeof(ArrowSchema)));
+    ArrowArray *arr = static_cast<ArrowArray *>(calloc(1, sizeof(ArrowArray)));
+    ArrowArray **arrays = static_cast<ArrowArray **>(calloc(1, sizeof(ArrowArray *)));
+    std::unique_ptr<ArrayPriv> ap;
+    std::unique_ptr<SeriesPriv> sp;
+    try {
+        if (!schema || !arr || !arrays) throw std::bad_alloc();
+        ap.reset(new ArrayPriv{data, validity, {validity, data}, pinned});
+        sp.reset(new SeriesPriv{schema, arrays, 1});
+        fill_named_schema(schema, format, name); // (the last step that may throw)
+    } catch (...) {
+        free(schema); free(arr); free(arrays);
+        throw;
+    }
+    arr->length = (int64_t)n;
+    arr->null_count = null_count;
+    arr->n_buffers = 2;
+    arr->buffers = ap->bufs;
+    arr->release = release_f64_array; // (frees the data and validity buffers: nothing in it is specific to f64)
+    arr->private_data = ap.release();
+    arrays[0] = arr;
+    ret->field = schema;
+    ret->arrays = arrays;
+    ret->len = 1;
+    ret->release = release_series;
+    ret->private_data = sp.release();
+}
 #include "plugin_match.h"
 #include "plugin_distance.h"
 #include "plugin_partial.h"
@@ -66,15 +158,11 @@ void run(int measure, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret, 
     PhaseTimer tm;
     const auto t_begin = std::chrono::steady_clock::now();
     if (n_inputs != 2) fail("expected 2 input series, got " + std::to_string(n_inputs));
-    Column col[2];
-    describe(inputs[0], col[0]);
-    describe(inputs[1], col[1]);
-    const Column &a = col[0], &b = col[1];
-    // strsim.rs:48-52
-    if (a.rows != b.rows && a.rows != 1 && b.rows != 1)
-        fail("Inputs must have the same length, or one of them must be a Utf8 literal.");
-    const bool lit[2] = {a.rows == 1 && b.rows != 1, b.rows == 1};
-    const uint64_t n = lit[0] ? b.rows : a.rows;
+    const Elementwise e(inputs);
+    const Column(&col)[2] = e.col;
+    const bool(&lit)[2] = e.lit;
+    const uint64_t n = e.n;
+    const bool all_null = e.all_null;
 
     double *out = static_cast<double *>(pinned_pool().acquire(n * sizeof(double))); // large columns (see PinnedPool)
     const bool out_pinned = out != nullptr;
@@ -85,9 +173,6 @@ void run(int measure, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret, 
         double *&o; bool pinned; uint8_t *&v; bool armed = true;
         ~Cleanup() { if (armed) { if (pinned) pinned_pool().release(o); else free(o); free(v); } }
     } cleanup{out, out_pinned, validity};
-
-    // a NULL literal: the reference unwrap()s and panics (strsim.rs:62,65,87,90); here every row is null
-    const bool all_null = (lit[0] && !row_valid(a, 0)) || (lit[1] && !row_valid(b, 0));
 
     const PackGrant grant(engine_parallel, n); // (helper threads borrowed for an engine-parallel call go back when it returns)
     const unsigned T = grant.threads;
@@ -114,34 +199,12 @@ void run(int measure, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret, 
     }
 
     // output validity = AND of the input validities (broadcast for a literal; a null literal is the all_null case)
-    const bool need_validity = all_null || a.any_null || b.any_null;
-    if (need_validity && n != 0) {
+    if (e.any_null() && n != 0) {
         validity = static_cast<uint8_t *>(alloc64((n + 63) / 64 * 8));
         null_count = build_validity(col, lit, n, all_null, T, reinterpret_cast<uint64_t *>(validity), out);
     }
-
-    // one "g" chunk
-    ArrayPriv *ap = new ArrayPriv{out, validity, {validity, out}, out_pinned};
-    ArrowArray *arr = static_cast<ArrowArray *>(calloc(1, sizeof(ArrowArray)));
-    arr->length = (int64_t)n;
-    arr->null_count = null_count;
-    arr->offset = 0;
-    arr->n_buffers = 2;
-    arr->n_children = 0;
-    arr->buffers = ap->bufs;
-    arr->release = release_f64_array;
-    arr->private_data = ap;
+    export_primitive("g", col[0].name.c_str(), n, out, validity, null_count, out_pinned, ret); // one "g" chunk
     cleanup.armed = false;
-
-    ArrowSchema *schema = static_cast<ArrowSchema *>(calloc(1, sizeof(ArrowSchema)));
-    fill_f64_schema(schema, a.name.c_str());
-    SeriesPriv *sp = new SeriesPriv{schema, static_cast<ArrowArray **>(calloc(1, sizeof(ArrowArray *))), 1};
-    sp->arrays[0] = arr;
-    ret->field = schema;
-    ret->arrays = sp->arrays;
-    ret->len = 1;
-    ret->release = release_series;
-    ret->private_data = sp;
     if (tm.on) {
         double launch = 0, wait = 0, d2h = 0;
         for (const PipeTimes &p : ptimes) { launch += p.t_launch; wait += p.t_wait; d2h += p.t_d2h; }
@@ -155,25 +218,9 @@ void run(int measure, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret, 
     }
 }
 
-void plugin_entry(int measure, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret, const CallerContext *cc)
-{
-    InputGuard guard{inputs, n_inputs};
-    try {
-        run(measure, inputs, n_inputs, ret, cc && (cc->bitflags & 1u));
-    } catch (const PluginError &e) {
-        g_plugin_error = e.msg;
-    } catch (const std::bad_alloc &) {
-        g_plugin_error = "out of host memory";
-    } catch (const std::exception &e) {
-        g_plugin_error = std::string("unexpected failure: ") + e.what();
-    } catch (...) {
-        g_plugin_error = "unexpected failure";
-    }
-}
-
+// output_type=Float64 (mod.rs:8,13,18,23,28): a Float64 field carrying the first input's name
 void field_entry(ArrowSchema *input_fields, size_t n_fields, ArrowSchema *ret)
 {
-    // output_type=Float64 (mod.rs:8,13,18,23,28): a Float64 field carrying the first input's name
     const char *name = (n_fields > 0 && input_fields && input_fields[0].name) ? input_fields[0].name : "";
     fill_f64_schema(ret, name);
 }
@@ -190,49 +237,28 @@ void _polars_plugin_strsim_staging_stats(uint64_t out[8]) { if (out) staging_poo
 void _polars_plugin_strsim_staging_set_budget_mb(uint64_t megabytes) { staging_pool().set_budget(megabytes << 20); }
 void _polars_plugin_strsim_coalesce_stats(uint64_t out[4]) { if (out) combiner().stats(out); }
 
-#define POLARS_PLUGIN_DEFINE(name, id)                                                                          \
-    void _polars_plugin_##name(SeriesExport *inputs, size_t n_inputs, const uint8_t *, size_t,                  \
-                               SeriesExport *return_value, CallerContext *cc)                                   \
-    {                                                                                                           \
-        plugin_entry(id, inputs, n_inputs, return_value, cc);                                                   \
-    }                                                                                                           \
-    void _polars_plugin_field_##name(ArrowSchema *input_fields, size_t n_fields, ArrowSchema *return_value)     \
-    {                                                                                                           \
-        field_entry(input_fields, n_fields, return_value);                                                      \
+// One exported function and its planning-time field: `call` runs under guarded(), `field` fills return_value.
+#define POLARS_PLUGIN_EXPORT(name, call, field)                                                                  \
+    void _polars_plugin_##name(SeriesExport *inputs, size_t n_inputs, const uint8_t *, size_t,                   \
+                               SeriesExport *return_value, CallerContext *cc)                                    \
+    {                                                                                                            \
+        guarded(inputs, n_inputs, [&] { call; });                                                                \
+    }                                                                                                            \
+    void _polars_plugin_field_##name(ArrowSchema *input_fields, size_t n_fields, ArrowSchema *return_value)      \
+    {                                                                                                            \
+        field;                                                                                                   \
     }
-
-#define POLARS_PLUGIN_DEFINE_DISTANCE(name, id)                                                                 \
-    void _polars_plugin_##name##_distance(SeriesExport *inputs, size_t n_inputs, const uint8_t *, size_t,       \
-                                          SeriesExport *return_value, CallerContext *)                          \
-    {                                                                                                           \
-        distance_entry(id, inputs, n_inputs, return_value);                                                     \
-    }                                                                                                           \
-    void _polars_plugin_field_##name##_distance(ArrowSchema *input_fields, size_t n_fields, ArrowSchema *return_value) \
-    {                                                                                                           \
-        distance_field_entry(input_fields, n_fields, return_value);                                             \
-    }
-
-#define POLARS_PLUGIN_DEFINE_NEAREST(name, id)                                                                  \
-    void _polars_plugin_nearest_##name(SeriesExport *inputs, size_t n_inputs, const uint8_t *, size_t,          \
-                                       SeriesExport *return_value, CallerContext *)                             \
-    {                                                                                                           \
-        nearest_entry(id, inputs, n_inputs, return_value);                                                      \
-    }                                                                                                           \
-    void _polars_plugin_field_nearest_##name(ArrowSchema *input_fields, size_t n_fields, ArrowSchema *return_value) \
-    {                                                                                                           \
-        nearest_field_entry(input_fields, n_fields, return_value);                                              \
-    }
-
-#define POLARS_PLUGIN_DEFINE_MATCH(name, id)                                                                    \
-    void _polars_plugin_best_match_##name(SeriesExport *inputs, size_t n_inputs, const uint8_t *, size_t,       \
-                                          SeriesExport *return_value, CallerContext *)                          \
-    {                                                                                                           \
-        best_match_entry(id, inputs, n_inputs, return_value);                                                   \
-    }                                                                                                           \
-    void _polars_plugin_field_best_match_##name(ArrowSchema *input_fields, size_t n_fields, ArrowSchema *return_value) \
-    {                                                                                                           \
-        best_match_field_entry(input_fields, n_fields, return_value);                                           \
-    }
+#define STRUCT_FIELD(shape) \
+    field_named_after_input0(input_fields, n_fields, return_value, [](ArrowSchema *s, const char *n) { fill_struct_schema(s, n, shape); })
+#define POLARS_PLUGIN_DEFINE(name, id) \
+    POLARS_PLUGIN_EXPORT(name, run(id, inputs, n_inputs, return_value, cc && (cc->bitflags & 1u)), field_entry(input_fields, n_fields, return_value))
+#define POLARS_PLUGIN_DEFINE_DISTANCE(name, id)                                                \
+    POLARS_PLUGIN_EXPORT(name##_distance, run_distance(id, inputs, n_inputs, return_value), \
+                         field_named_after_input0(input_fields, n_fields, return_value, [](ArrowSchema *s, const char *n) { fill_named_schema(s, "I", n); }))
+#define POLARS_PLUGIN_DEFINE_NEAREST(name, id) \
+    POLARS_PLUGIN_EXPORT(nearest_##name, run_nearest(id, inputs, n_inputs, return_value), STRUCT_FIELD(NEAREST_STRUCT))
+#define POLARS_PLUGIN_DEFINE_MATCH(name, id) \
+    POLARS_PLUGIN_EXPORT(best_match_##name, run_best_match(id, inputs, n_inputs, return_value), STRUCT_FIELD(MATCH_STRUCT))
 
 #ifdef STRSIM_TEST_HOOKS
 // Test hooks (no GPU needed), compiled only into tests/cpu_harness/libplugin_testhooks.so (make testhooks) -- the product library
@@ -453,6 +479,46 @@ POLARS_PLUGIN_API int _strsim_test_combine(SeriesExport *two_series, int measure
     }
     return -1;
 }
+
+// (6) a struct result of `n` synthetic rows (every third row null) through export_struct, released the way a consumer may: whole
+// (move_child < 0), or with child `move_child` moved out first (Arrow C data interface: copied, its release cleared in the struct)
+// and released after the struct is gone.  sum_out: the moved child's first 4-byte values, read after the struct's release.
+POLARS_PLUGIN_API int _strsim_test_export_struct(uint64_t n, int move_child, uint64_t *sum_out)
+{
+    try {
+        const StructShape &shape = PARTIAL_STRUCT;
+        StructOwned own(n, shape);
+        int64_t nulls = 0;
+        memset(own.valid, 0, (n + 63) / 64 * 8);
+        for (uint64_t r = 0; r < n; ++r) {
+            if (r % 3 == 2) ++nulls; else static_cast<uint8_t *>(own.valid)[r >> 3] |= (uint8_t)(1u << (r & 7));
+            own.child<double>(0)[r] = (double)r;
+            for (int i = 1; i < shape.n; ++i) own.child<uint32_t>(i)[r] = (uint32_t)(r + (uint64_t)i);
+        }
+        SeriesExport ret{};
+        export_struct(own, n, nulls, "synthetic", shape, &ret);
+        ArrowArray arr = *ret.arrays[0]; // (the importer takes the arrays by bitwise copy, release_series frees the boxes)
+        ArrowArray moved{};
+        if (move_child >= 0) { moved = *arr.children[move_child]; arr.children[move_child]->release = nullptr; }
+        const bool ok = arr.length == (int64_t)n && arr.null_count == nulls && arr.n_children == shape.n;
+        arr.release(&arr);
+        ret.release(&ret);
+        uint64_t sum = 0;
+        if (move_child >= 0) {
+            for (uint64_t r = 0; r < n; ++r) sum += static_cast<const uint32_t *>(moved.buffers[1])[r];
+            if (nulls && !moved.buffers[0]) fail("the moved child lost its validity");
+            moved.release(&moved);
+        }
+        if (sum_out) *sum_out = sum;
+        if (!ok) fail("struct header");
+        return 0;
+    } catch (const PluginError &e) {
+        g_plugin_error = e.msg;
+    } catch (...) {
+        g_plugin_error = "unexpected failure";
+    }
+    return -1;
+}
 #endif // STRSIM_TEST_HOOKS
 
 POLARS_PLUGIN_DEFINE(levenshtein, STRSIM_LEVENSHTEIN)
@@ -463,15 +529,7 @@ POLARS_PLUGIN_DEFINE(sorensen_dice, STRSIM_SORENSEN_DICE)
 POLARS_PLUGIN_DEFINE(osa, STRSIM_OSA)
 POLARS_PLUGIN_DEFINE(indel, STRSIM_INDEL)
 POLARS_PLUGIN_DEFINE(partial_ratio, STRSIM_PARTIAL_RATIO)
-void _polars_plugin_partial_ratio_alignment(SeriesExport *inputs, size_t n_inputs, const uint8_t *, size_t, SeriesExport *return_value,
-                                            CallerContext *)
-{
-    partial_alignment_entry(inputs, n_inputs, return_value);
-}
-void _polars_plugin_field_partial_ratio_alignment(ArrowSchema *input_fields, size_t n_fields, ArrowSchema *return_value)
-{
-    partial_alignment_field_entry(input_fields, n_fields, return_value);
-}
+POLARS_PLUGIN_EXPORT(partial_ratio_alignment, run_partial_alignment(inputs, n_inputs, return_value), STRUCT_FIELD(PARTIAL_STRUCT))
 POLARS_PLUGIN_DEFINE_DISTANCE(levenshtein, STRSIM_LEVENSHTEIN)
 POLARS_PLUGIN_DEFINE_DISTANCE(osa, STRSIM_OSA)
 POLARS_PLUGIN_DEFINE_DISTANCE(indel, STRSIM_INDEL)

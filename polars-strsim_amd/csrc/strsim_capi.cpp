@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 
@@ -55,72 +56,96 @@ int hip_fail(hipError_t e, const char *what)
 
 using namespace strsim;
 
+// A grow-only device buffer: what a call needs is reserved before it is enqueued; a buffer that is too small is freed first and
+// allocated again with an eighth to spare.  Freed with the context.
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0; // bytes
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    int reserve(size_t bytes)
+    {
+        if (bytes <= cap) return STRSIM_OK;
+        if (p) { HIP_TRY(hipFree(p)); p = nullptr; cap = 0; }
+        const size_t want = bytes + bytes / 8 + 256;
+        HIP_TRY(hipMalloc(&p, want));
+        cap = want;
+        return STRSIM_OK;
+    }
+    template <class T> T *as() const { return static_cast<T *>(p); }
+};
+
+// The fields are grouped by the functions that own them; strsim_ctx_destroy releases them in this order (the DevBufs free
+// themselves when the context is deleted).
 struct strsim_ctx {
     int device = -1;
     hipStream_t stream = nullptr;
     bool own_stream = false;
     int num_cu = 0;
-    int stage_wg_per_cu = 5;  // resident workgroups of k_lane_stage per CU; STRSIM_STAGE_WG_PER_CU overrides (tuning knob)
-    int lev_waves_per_cu = 20; // five per SIMD (96 VGPRs, 7.6 KB of LDS = six 1 280-byte granules); STRSIM_LEV_WAVES_PER_CU overrides (tuning knob)
+
+    // ---- ring of pending calls and their status blocks (slot_begin / slot_commit, ctx_retire_slot, ctx_drain) ----
     // per-call deferred state: a ring of status words + event triples, so calls can be enqueued
     // back to back without a host sync; the ring is drained by strsim_ctx_synchronize()
     static constexpr int RING = 32;
-    // workspace (grow-only).  The "not finished yet" masks (+ backup + work list) of a call.  A call whose slow-row kernels may be
-    // launched late (a one-launch call, below) needs its mask intact while younger calls run: it OWNS one of the first RING
-    // buffers (the lowest free one; allocated on first use, so a caller that keeps k calls in flight touches k of them) until it is
-    // retired.  Calls that enqueue all their kernels up front share the last buffer (they use it in stream order).  Nothing is ever
-    // retired behind the caller's back to make room: a buffer is always free while a ring slot is.
-    static constexpr int MASKBUFS = RING + 1;
-    static constexpr int SHARED_MASKBUF = MASKBUFS - 1;
-    unsigned long long *slowmask[MASKBUFS] = {};
-    size_t slowmask_cap[MASKBUFS] = {}; // bytes
-    int maskbuf_owner[MASKBUFS];        // ring slot of the pending one-launch call that owns the buffer, or -1 (set in strsim_ctx_create)
-    DevStatus *status = nullptr;      // device, RING entries
-    uint32_t *sched = nullptr;        // device, RING x 4 words: work-distribution counters of k_lane_stage (zero between launches)
-    DevStatus *status_host = nullptr; // pinned, RING entries
-    DevStatus *status_host_dev = nullptr; // the same memory as the device addresses it
-    void *pin = nullptr;   // pinned staging of strsim_pairs_host's small calls (kernels work on it in place)
-    void *pin_dev = nullptr;
-    size_t pin_cap = 0;
-    hipEvent_t ev[RING][3] = {};
+    int head = 0;
     bool slot_pending[RING] = {};
     // A call whose lane kernel is EXPECTED to leave nothing behind (the last retired call did not: short ASCII columns) is
     // ONE kernel launch: k_lane_stage's last workgroup publishes lane_left and the ticket itself.  If it did leave rows, the
     // slow-row kernels are launched when the call is retired (strsim_ctx_synchronize / strsim_ctx_retire_oldest) -- like
     // the long-string pass -- and the next calls enqueue the whole chain up front again.
     bool slot_deferred[RING] = {};
-    bool expect_slow = false;
-    bool long_rows = false;        // ... and left more than 1/16 of its rows: frames of long strings (see k_lane_stage, TABLES)
-    bool stream_ordered = true;    // strsim_ctx_set_stream_ordered(ctx, 0) opts in to one-launch calls
-    uint64_t last_late_rows = 0;   // rows finished by a pass launched from synchronize / retire (deferred + long-string)
-    uint64_t carry_late_rows = 0, carry_long_rows = 0; // the same of calls the library had to retire itself (the ring of status
-                                   // slots wrapped): reported with the caller's next strsim_ctx_synchronize / _retire_oldest
-    hipEvent_t ev_late[2] = {};    // timing of a deferred slow pass
-    uint64_t enqueued_ops = 0;     // kernels + copies this context has put on its stream for pair calls (strsim_ctx_enqueued_ops)
-    uint32_t slot_ticket[RING] = {}; // what the device writes into status_host[slot].ticket when the call's status block is out
-    uint32_t ticket_seq = 0;
     bool slot_timed[RING] = {};
     LaunchArgs slot_args[RING] = {}; // what each pending call was launched with (for the long-string pass)
     int slot_measure[RING] = {};     // STRSIM_NUM_MEASURES = the fused all-measures call
     double *slot_outs[RING][5] = {};
-    uint32_t *lev_ws = nullptr;      // scratch of k_wave_pairs<LEVENSHTEIN>: staged texts + non-ASCII fallback arrays
-    size_t lev_ws_cap = 0;
-    uint32_t *huge_ws = nullptr;     // workspace of the long-string pass (grow-only)
-    size_t huge_ws_cap = 0;
-    uint32_t *scan_ws = nullptr;     // block sums of strsim_offsets_from_lengths (SCAN_WS_WORDS, allocated on first use)
-    int head = 0;
-    double *qtab = nullptr;          // QTAB_N x QTAB_N quotients a / b (strsim_lane_core.h), filled at creation
+    uint32_t slot_ticket[RING] = {}; // what the device writes into status_host[slot].ticket when the call's status block is out
+    uint32_t ticket_seq = 0;
+    DevStatus *status = nullptr;      // device, RING entries
+    uint32_t *sched = nullptr;        // device, RING x 4 words: work-distribution counters of k_lane_stage (zero between launches)
+    DevStatus *status_host = nullptr; // pinned, RING entries
+    DevStatus *status_host_dev = nullptr; // the same memory as the device addresses it
+    bool expect_slow = false;
+    bool long_rows = false;        // ... and left more than 1/16 of its rows: frames of long strings (see k_lane_stage, TABLES)
+    bool stream_ordered = true;    // strsim_ctx_set_stream_ordered(ctx, 0) opts in to one-launch calls
+    uint64_t enqueued_ops = 0;     // kernels + copies this context has put on its stream for pair calls (strsim_ctx_enqueued_ops)
     uint64_t last_wave_rows = 0;
-    uint64_t last_long_rows = 0; // over the slots retired by the last synchronize
-    // staging for strsim_pairs_host (grow-only device buffers)
-    void *stage[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t stage_cap[5] = {0, 0, 0, 0, 0};
-    // timing
+    uint64_t last_long_rows = 0;   // over the slots retired by the last synchronize
+    uint64_t last_late_rows = 0;   // rows finished by a pass launched from synchronize / retire (deferred + long-string)
+    uint64_t carry_late_rows = 0, carry_long_rows = 0; // the same of calls the library had to retire itself (the ring of status
+                                   // slots wrapped): reported with the caller's next strsim_ctx_synchronize / _retire_oldest
+
+    // ---- workspaces of the pairwise calls (pairs_device_impl, ctx_run_huge, strsim_pairs_host; all grow-only) ----
+    // The "not finished yet" masks (+ backup + work list) of a call.  A call whose slow-row kernels may be
+    // launched late (a one-launch call, above) needs its mask intact while younger calls run: it OWNS one of the first RING
+    // buffers (the lowest free one; allocated on first use, so a caller that keeps k calls in flight touches k of them) until it is
+    // retired.  Calls that enqueue all their kernels up front share the last buffer (they use it in stream order).  Nothing is ever
+    // retired behind the caller's back to make room: a buffer is always free while a ring slot is.
+    static constexpr int MASKBUFS = RING + 1;
+    static constexpr int SHARED_MASKBUF = MASKBUFS - 1;
+    DevBuf slowmask[MASKBUFS];
+    int maskbuf_owner[MASKBUFS];     // ring slot of the pending one-launch call that owns the buffer, or -1 (set in strsim_ctx_create)
+    DevBuf lev_ws;                   // scratch of k_wave_pairs<LEVENSHTEIN>: staged texts + non-ASCII fallback arrays
+    DevBuf huge_ws;                  // workspace of the long-string pass
+    double *qtab = nullptr;          // QTAB_N x QTAB_N quotients a / b (strsim_lane_core.h), filled at creation
+    uint32_t *scan_ws = nullptr;     // block sums of strsim_offsets_from_lengths (SCAN_WS_WORDS, allocated on first use)
+    DevBuf stage[5];                 // device copies of a *_host call's four input buffers and its outputs (ctx_stage)
+    void *pin = nullptr;   // pinned staging of strsim_pairs_host's small calls (kernels work on it in place)
+    void *pin_dev = nullptr;
+    size_t pin_cap = 0;
+
+    // ---- timing (strsim_ctx_timing_enable / _read) ----
     bool timing = false;
     double lane_ms = 0, wave_ms = 0;
     uint64_t lane_launches = 0, wave_launches = 0;
-    // environment knobs, read ONCE in strsim_ctx_create (not on the launch path: a small call is ~23 us, and a host that calls
-    // setenv concurrently must not race a getenv of ours per call)
+    hipEvent_t ev[RING][3] = {};
+    hipEvent_t ev_late[2] = {};    // timing of a deferred slow pass
+
+    // ---- environment knobs, read ONCE in strsim_ctx_create (not on the launch path: a small call is ~23 us, and a host that
+    // calls setenv concurrently must not race a getenv of ours per call) ----
+    int stage_wg_per_cu = 5;  // resident workgroups of k_lane_stage per CU; STRSIM_STAGE_WG_PER_CU overrides (tuning knob)
+    int lev_waves_per_cu = 20; // five per SIMD (96 VGPRs, 7.6 KB of LDS = six 1 280-byte granules); STRSIM_LEV_WAVES_PER_CU overrides (tuning knob)
     bool no_literal_path = false;      // STRSIM_NO_LITERAL_PATH (tuning / A-B knob)
     int wide_cap_per_cu = 192;         // STRSIM_WIDE_WG_PER_CU (tuning knob)
     int huge_waves_per_cu = 16;        // STRSIM_HUGE_WAVES_PER_CU (tuning knob); 8 KB of LDS per Levenshtein wave
@@ -129,33 +154,24 @@ struct strsim_ctx {
     // STRSIM_ERR_EARLIER_CALL and the "a slot is retired whatever fails" rule without breaking the device
     uint64_t fault_retire_at = 0;      // STRSIM_FAULT_RETIRE_AT (0 = never)
     uint64_t retired = 0;
-    // best match (strsim_best_match_device): packed strings + slow lists + partial lists, the fallback's score batches, and a
-    // pinned word pair for the two slow counts (all grow-only)
-    void *match_ws = nullptr;
-    size_t match_ws_cap = 0;
-    void *match_scratch = nullptr;
-    size_t match_scratch_cap = 0;
+
+    // ---- search calls (search_pack / search_fallback; strsim_best_match_device, strsim_nearest_device) ----
+    // packed strings + slow lists + partial lists (nearest: also the length order and the merged scores), the fallback's score
+    // (nearest: and distance) batches, and a pinned word pair for the two slow counts
+    DevBuf match_ws, match_scratch;
+    DevBuf nearest_ws, nearest_scratch;
     uint32_t *match_counts_host = nullptr;
-    // optimal string alignment (pairs_osa): the work list of k_osa_wave (one word per row) and its scratch for long patterns
-    uint32_t *osa_list = nullptr;
-    size_t osa_list_cap = 0;
-    uint32_t *osa_scratch = nullptr;
-    size_t osa_scratch_cap = 0;
-    // bounded distances (strsim_distance_device): the status block of k_dist_lane and its pinned read-back (the work list and
-    // the scratch are the OSA buffers above)
+
+    // ---- two-pass measures (two_pass: pairs_osa, distance_device_impl, partial_device_impl) ----
+    DevBuf osa_list;                 // the work list of the wave kernel (one word per row)
+    DevBuf osa_scratch;              // its scratch for patterns too long for LDS
+    // bounded distances and the alignment: the status block of the lane kernel and its pinned read-back (a pairwise call uses
+    // its ring slot's)
     DevStatus *dist_status = nullptr;
     DevStatus *dist_status_host = nullptr;
-    // nearest match (strsim_nearest_device): packed strings, their length order, partial lists and the merged scores, and the
-    // fallback's distance and score batches (grow-only; the slow counts come back through match_counts_host)
-    void *nearest_ws = nullptr;
-    size_t nearest_ws_cap = 0;
-    void *nearest_scratch = nullptr;
-    size_t nearest_scratch_cap = 0;
 };
 
 static int ctx_set_device(strsim_ctx *c) { HIP_TRY(hipSetDevice(c->device)); return STRSIM_OK; }
-
-static int ctx_reserve(void **p, size_t *cap, size_t bytes);
 
 // strsim_pairs_host computes calls up to this size in place on pinned host memory (see there).  Measured through ctypes
 // (bench_support/bench_small_host_calls.py), in place vs copies: 37 vs 70 us at 1..100 rows, 57 vs 95 us at 10 000,
@@ -171,18 +187,18 @@ static int ctx_run_huge(strsim_ctx *c, int slot, const DevStatus &st)
     size_t waves = st.huge_rows < max_waves ? st.huge_rows : max_waves;
     const size_t budget = (size_t)4 << 30; // keep the workspace under 4 GiB
     if (waves * per_wave > budget) waves = budget / per_wave ? budget / per_wave : 1;
-    int rc = ctx_reserve((void **)&c->huge_ws, &c->huge_ws_cap, waves * per_wave);
+    int rc = c->huge_ws.reserve(waves * per_wave);
     if (rc) return rc;
     LaunchArgs a = c->slot_args[slot];
     a.ev_lane0 = a.ev_lane1 = a.ev_wave1 = nullptr;
     if (c->slot_measure[slot] == STRSIM_NUM_MEASURES) {
         for (int m = 0; m < STRSIM_NUM_MEASURES; ++m) {
             a.out = c->slot_outs[slot][m];
-            hipError_t e = launch_huge(m, a, c->huge_ws, cap, (int)waves);
+            hipError_t e = launch_huge(m, a, c->huge_ws.as<uint32_t>(), cap, (int)waves);
             if (e != hipSuccess) return hip_fail(e, "long-string kernel launch");
         }
     } else {
-        hipError_t e = launch_huge(c->slot_measure[slot], a, c->huge_ws, cap, (int)waves);
+        hipError_t e = launch_huge(c->slot_measure[slot], a, c->huge_ws.as<uint32_t>(), cap, (int)waves);
         if (e != hipSuccess) return hip_fail(e, "long-string kernel launch");
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -240,13 +256,20 @@ static int ctx_run_deferred(strsim_ctx *c, int s)
     return STRSIM_OK;
 }
 
+static void release_maskbufs(strsim_ctx *c, int s)
+{
+    for (int b = 0; b < strsim_ctx::MASKBUFS; ++b) if (c->maskbuf_owner[b] == s) c->maskbuf_owner[b] = -1;
+}
+
+static bool two_pass_measure(int measure) { return measure == STRSIM_OSA || measure == STRSIM_INDEL || measure == STRSIM_PARTIAL_RATIO; }
+
 static int ctx_retire_slot(strsim_ctx *c, int s)
 {
     int rc = STRSIM_OK;
     c->slot_pending[s] = false;
     struct Release { // the slot's mask buffer is free again whichever way this function is left
         strsim_ctx *c; int s;
-        ~Release() { for (int b = 0; b < strsim_ctx::MASKBUFS; ++b) if (c->maskbuf_owner[b] == s) c->maskbuf_owner[b] = -1; }
+        ~Release() { release_maskbufs(c, s); }
     } release{c, s};
     if (!ctx_slot_published(c, s)) { // (cannot happen behind a stream synchronise; strsim_ctx_retire_oldest checks before it gets here)
         c->slot_timed[s] = c->slot_deferred[s] = false;
@@ -258,10 +281,9 @@ static int ctx_retire_slot(strsim_ctx *c, int s)
         set_error("fault injected at retirement %llu of this context (STRSIM_FAULT_RETIRE_AT)", (unsigned long long)c->retired);
         return STRSIM_ERR_INTERNAL;
     }
-    // (an OSA or Indel call has no lane_left: it says nothing about what the next call of the other measures leaves behind)
-    const uint32_t left = (c->slot_measure[s] == STRSIM_OSA || c->slot_measure[s] == STRSIM_INDEL || c->slot_measure[s] == STRSIM_PARTIAL_RATIO)
-                              ? LANE_LEFT_UNKNOWN
-                                                           : *reinterpret_cast<const volatile uint32_t *>(&c->status_host[s].lane_left);
+    // (a two-pass call has no lane_left: it says nothing about what the next call of the other measures leaves behind)
+    const uint32_t left = two_pass_measure(c->slot_measure[s]) ? LANE_LEFT_UNKNOWN
+                                                               : *reinterpret_cast<const volatile uint32_t *>(&c->status_host[s].lane_left);
     if (left != LANE_LEFT_UNKNOWN) { // what the next call on this context is enqueued for
         c->expect_slow = left != 0u;
         c->long_rows = (uint64_t)left * 16u > c->slot_args[s].n;
@@ -311,21 +333,10 @@ static int ctx_drain(strsim_ctx *c)
             rc = ctx_retire_slot(c, s);
         } else {
             c->slot_pending[s] = c->slot_timed[s] = c->slot_deferred[s] = false;
-            for (int b = 0; b < strsim_ctx::MASKBUFS; ++b) if (c->maskbuf_owner[b] == s) c->maskbuf_owner[b] = -1;
+            release_maskbufs(c, s);
         }
     }
     return rc;
-}
-
-static int ctx_reserve(void **p, size_t *cap, size_t bytes)
-{
-    using namespace strsim;
-    if (bytes <= *cap) return STRSIM_OK;
-    if (*p) { HIP_TRY(hipFree(*p)); *p = nullptr; *cap = 0; }
-    size_t want = bytes + bytes / 8 + 256;
-    HIP_TRY(hipMalloc(p, want));
-    *cap = want;
-    return STRSIM_OK;
 }
 
 extern "C" {
@@ -424,29 +435,20 @@ void strsim_ctx_destroy(strsim_ctx_t *c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    // in the order of the declaration (the grow-only buffers are freed by `delete`)
+    if (c->status) (void)hipFree(c->status);
+    if (c->sched) (void)hipFree(c->sched);
+    if (c->status_host) (void)hipHostFree(c->status_host);
+    if (c->qtab) (void)hipFree(c->qtab);
+    if (c->scan_ws) (void)hipFree(c->scan_ws);
+    if (c->pin) (void)hipHostFree(c->pin);
     for (int s = 0; s < strsim_ctx::RING; ++s)
         for (int i = 0; i < 3; ++i)
             if (c->ev[s][i]) (void)hipEventDestroy(c->ev[s][i]);
-    for (int i = 0; i < 5; ++i) if (c->stage[i]) (void)hipFree(c->stage[i]);
-    for (int i = 0; i < strsim_ctx::MASKBUFS; ++i) if (c->slowmask[i]) (void)hipFree(c->slowmask[i]);
     for (int i = 0; i < 2; ++i) if (c->ev_late[i]) (void)hipEventDestroy(c->ev_late[i]);
-    if (c->qtab) (void)hipFree(c->qtab);
-    if (c->sched) (void)hipFree(c->sched);
-    if (c->huge_ws) (void)hipFree(c->huge_ws);
-    if (c->scan_ws) (void)hipFree(c->scan_ws);
-    if (c->match_ws) (void)hipFree(c->match_ws);
-    if (c->match_scratch) (void)hipFree(c->match_scratch);
     if (c->match_counts_host) (void)hipHostFree(c->match_counts_host);
-    if (c->osa_list) (void)hipFree(c->osa_list);
-    if (c->osa_scratch) (void)hipFree(c->osa_scratch);
     if (c->dist_status) (void)hipFree(c->dist_status);
     if (c->dist_status_host) (void)hipHostFree(c->dist_status_host);
-    if (c->nearest_ws) (void)hipFree(c->nearest_ws);
-    if (c->nearest_scratch) (void)hipFree(c->nearest_scratch);
-    if (c->lev_ws) (void)hipFree(c->lev_ws);
-    if (c->status) (void)hipFree(c->status);
-    if (c->status_host) (void)hipHostFree(c->status_host);
-    if (c->pin) (void)hipHostFree(c->pin);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -465,87 +467,234 @@ void strsim_split_offsets(uint64_t len, uint64_t n, uint64_t *out)
     }
 }
 
-// Optimal string alignment (strsim_osa.h): k_osa_lane over every row, a read-back of what it left for k_osa_wave (how many rows,
-// how long their patterns can be), then k_osa_wave sized for that.  Every row is complete in stream order; the call occupies a ring
-// slot like any other (its status block carries the ticket and the work-list count) and has nothing to do at retirement.
-// measure = STRSIM_INDEL runs the same flow with k_indel_lane / k_indel_wave (strsim_indel.h) on the same work list and scratch.
-static constexpr size_t OSA_SCRATCH_BUDGET = (size_t)1 << 30; // k_osa_wave runs fewer waves rather than use more scratch
+} // extern "C"
 
-// Partial ratio (strsim_partial.h): k_partial_lane over every row, then k_partial_wave over the `rows` rows of the work list;
-// max_pat / max_hay bound their needles and haystacks (bytes, hence scalar values).  span == nullptr: the score alone.
-static int partial_wave_pass(strsim_ctx *c, const LaunchArgs &la, uint32_t *span, uint32_t rows, uint32_t max_pat, uint32_t max_hay)
+// ---- argument checks and staging shared by the entry points ----
+
+// Shape rule of parallel_apply, strsim.rs:48-52: the rows a call of two columns produces.
+static int shape_rows(uint64_t a_rows, uint64_t b_rows, uint64_t *n)
 {
-    int grid = c->num_cu * 16;
-    if ((uint64_t)grid > rows) grid = (int)rows;
-    uint32_t *scratch = nullptr;
-    // (partial_wave_words grows with both arguments: the larger of the two forms at the bounds covers every pair)
-    uint64_t slot_words = std::max(partial_wave_words(64u, max_hay), partial_wave_words(std::max(max_pat, 65u), max_hay));
-    if (slot_words > PARTIAL_WAVE_LDS_WORDS) {
-        slot_words = (slot_words + 1u) & ~(uint64_t)1; // (64-bit words inside a slot)
-        const size_t per = (size_t)slot_words * sizeof(uint32_t);
-        if ((size_t)grid * per > OSA_SCRATCH_BUDGET) grid = (int)std::max<size_t>(1, OSA_SCRATCH_BUDGET / per);
-        int rc = ctx_reserve((void **)&c->osa_scratch, &c->osa_scratch_cap, (size_t)grid * per);
-        if (rc) return rc;
-        scratch = c->osa_scratch;
-    } else {
-        slot_words = 0;
+    if (a_rows != b_rows && a_rows != 1 && b_rows != 1) {
+        set_error("Inputs must have the same length, or one of them must be a Utf8 literal.");
+        return STRSIM_ERR_SHAPE;
     }
-    hipError_t e = launch_partial_wave(la, span, c->osa_list, grid, scratch, slot_words);
-    if (e != hipSuccess) return hip_fail(e, "kernel launch (k_partial_wave)");
-    c->enqueued_ops += 1u;
+    *n = (a_rows == 1) ? b_rows : a_rows;
     return STRSIM_OK;
 }
-static int pairs_osa(strsim_ctx *c, int slot, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
-                     const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t n)
+
+// ... which must be what the caller's output holds, and fit the kernels: row and chunk indices are 32-bit inside them (as are
+// the offsets themselves).
+static int check_rows(const char *who, uint64_t a_rows, uint64_t b_rows, uint64_t out_rows, uint64_t *n)
 {
-    int rc = ctx_reserve((void **)&c->osa_list, &c->osa_list_cap, n * sizeof(uint32_t));
+    int rc = shape_rows(a_rows, b_rows, n);
     if (rc) return rc;
+    if (out_rows != *n) {
+        set_error("%s: out_rows=%llu but the inputs produce %llu rows", who, (unsigned long long)out_rows, (unsigned long long)*n);
+        return STRSIM_ERR_ARG;
+    }
+    if (*n > 0xFFFFFFFFull) {
+        set_error("%s: %llu rows in one call; split the column (at most 2^32 - 1 rows per call)", who, (unsigned long long)*n);
+        return STRSIM_ERR_ARG;
+    }
+    return STRSIM_OK;
+}
+
+// The checks of the distance and alignment entry points behind their measure test (buffers: every input and output pointer is set).
+static int elementwise_check(const char *who, strsim_ctx *c, uint64_t a_rows, uint64_t b_rows, uint64_t out_rows, bool buffers)
+{
+    uint64_t n;
+    int rc = check_rows(who, a_rows, b_rows, out_rows, &n);
+    if (rc) return rc;
+    if (n && !buffers) { set_error("%s: NULL buffer", who); return STRSIM_ERR_ARG; }
+    if (!c) { set_error("%s: ctx is NULL", who); return STRSIM_ERR_ARG; }
+    return STRSIM_OK;
+}
+
+// The checks of the two search families behind their measure test (best match: min_score may not be NaN; nearest passes 0).
+static int search_check(const char *who, strsim_ctx *c, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows, const uint32_t *c_off,
+                        const uint8_t *c_val, uint64_t c_rows, uint32_t k, uint32_t max_k, double min_score, const void *out_a, const void *out_b)
+{
+    if (k < 1u || k > max_k) { set_error("%s: k=%u is outside 1..%u", who, k, max_k); return STRSIM_ERR_ARG; }
+    if (min_score != min_score) { set_error("%s: min_score is NaN", who); return STRSIM_ERR_ARG; }
+    if (q_rows > 0xFFFFFFFFull) { set_error("%s: %llu queries (at most 2^32 - 1)", who, (unsigned long long)q_rows); return STRSIM_ERR_ARG; }
+    if (c_rows > 0xFFFFFFFEull) { set_error("%s: %llu candidates (at most 2^32 - 2)", who, (unsigned long long)c_rows); return STRSIM_ERR_ARG; }
+    if (q_rows && (!q_off || !q_val || !out_a || !out_b)) { set_error("%s: NULL query or output buffer", who); return STRSIM_ERR_ARG; }
+    if (c_rows && (!c_off || !c_val)) { set_error("%s: NULL candidate buffer", who); return STRSIM_ERR_ARG; }
+    if (!c) { set_error("%s: ctx is NULL", who); return STRSIM_ERR_ARG; }
+    return STRSIM_OK;
+}
+
+// The copy path of the *_host entry points: device copies of two host columns in stage[0..3] (uploads on the context's stream)
+// and out_bytes of stage[4] for the results.  The caller's offset base is kept and the values go up from byte 0 of the caller's
+// buffer, so every offset the kernels can form, 0 included, is inside the device copy.  The second column may have no rows.
+struct Staged {
+    const uint32_t *a_off; const uint8_t *a_val;
+    const uint32_t *b_off; const uint8_t *b_val;
+    uint8_t *out;
+};
+static int ctx_stage(strsim_ctx *c, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off, const uint8_t *b_val,
+                     uint64_t b_rows, size_t out_bytes, Staged *s)
+{
+    const size_t a_bytes = a_off[a_rows], b_bytes = b_rows ? b_off[b_rows] : 0;
+    const size_t need[5] = {(a_rows + 1) * 4, a_bytes + 1, (b_rows + 1) * 4, b_bytes + 1, out_bytes};
+    for (int i = 0; i < 5; ++i) {
+        int rc = c->stage[i].reserve(need[i]);
+        if (rc) return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(c->stage[0].p, a_off, need[0], hipMemcpyHostToDevice, c->stream));
+    if (a_bytes) HIP_TRY(hipMemcpyAsync(c->stage[1].p, a_val, a_bytes, hipMemcpyHostToDevice, c->stream));
+    if (b_rows) {
+        HIP_TRY(hipMemcpyAsync(c->stage[2].p, b_off, need[2], hipMemcpyHostToDevice, c->stream));
+        if (b_bytes) HIP_TRY(hipMemcpyAsync(c->stage[3].p, b_val, b_bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    *s = Staged{c->stage[0].as<uint32_t>(), c->stage[1].as<uint8_t>(), c->stage[2].as<uint32_t>(), c->stage[3].as<uint8_t>(), c->stage[4].as<uint8_t>()};
+    return STRSIM_OK;
+}
+
+static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// Take a ticket for the call in `slot` and clear the host copy of its status block.
+static void slot_begin(strsim_ctx *c, int slot)
+{
     if (++c->ticket_seq == 0u) c->ticket_seq = 1u;
     c->slot_ticket[slot] = c->ticket_seq;
     memset(&c->status_host[slot], 0, sizeof(DevStatus)); // (the slot is not pending: nothing on the device writes this block now)
+}
+
+// Record the call in its ring slot: it is pending from here on.  outs: the five outputs of a fused call, else nullptr.
+static void slot_commit(strsim_ctx *c, int slot, const LaunchArgs &la, int measure, bool timed, bool deferred, double *const *outs)
+{
+    c->slot_timed[slot] = timed;
+    c->slot_deferred[slot] = deferred;
+    c->slot_args[slot] = la;
+    c->slot_measure[slot] = measure;
+    for (int q = 0; q < STRSIM_NUM_MEASURES; ++q) c->slot_outs[slot][q] = outs ? outs[q] : nullptr;
+    c->slot_pending[slot] = true;
+    c->head = (slot + 1) % strsim_ctx::RING;
+}
+
+// The two ways a status block reaches the host: published into the ring slot's host-mapped block with the slot's ticket (pairwise
+// calls), or copied from dist_status (distance and alignment calls).
+static int publish_slot(strsim_ctx *c, int slot)
+{
+    HIP_TRY(launch_publish_status(c->status + slot, c->status_host_dev + slot, c->slot_ticket[slot], c->stream));
+    return STRSIM_OK;
+}
+static int dist_report(strsim_ctx *c)
+{
+    HIP_TRY(hipMemcpyAsync(c->dist_status_host, c->dist_status, sizeof(DevStatus), hipMemcpyDeviceToHost, c->stream));
+    return STRSIM_OK;
+}
+
+// ---- two-pass measures: optimal string alignment, Indel, partial ratio, and the bounded distances ----
+//
+// One-pair-per-lane kernel over every row, a read-back of what it left for the wave kernel (how many rows, how long their patterns
+// can be), then the wave kernel sized for that.  Every row is complete in stream order.
+
+static constexpr size_t OSA_SCRATCH_BUDGET = (size_t)1 << 30; // the wave kernel runs fewer waves rather than use more scratch
+
+// Which pair of kernels a call runs, and what they take beside the LaunchArgs.
+enum TwoPassKind { TP_OSA, TP_DIST, TP_INDEL, TP_PARTIAL };
+struct TwoPassCall {
+    TwoPassKind kind;
+    int measure;     // TP_DIST: STRSIM_LEVENSHTEIN or STRSIM_OSA
+    uint32_t k;      // TP_DIST, TP_INDEL: the cutoff (DIST_UNBOUNDED: none)
+    uint32_t *out32; // TP_DIST: the distances; TP_INDEL: the distances, or nullptr for the similarity in la.out
+    uint32_t *span;  // TP_PARTIAL: the alignment, or nullptr for the score alone
+};
+static const char *const TWO_PASS_LANE[] = {"kernel launch (k_osa_lane)", "kernel launch (k_dist_lane)", "kernel launch (k_indel_lane)",
+                                            "kernel launch (k_partial_lane)"};
+static const char *const TWO_PASS_WAVE[] = {"kernel launch (k_osa_wave)", "kernel launch (k_dist_wave)", "kernel launch (k_indel_wave)",
+                                            "kernel launch (k_partial_wave)"};
+
+static hipError_t two_pass_lane(const TwoPassCall &t, const LaunchArgs &la, uint32_t *list)
+{
+    switch (t.kind) {
+    case TP_OSA: return launch_osa_lane(la, list);
+    case TP_DIST: return launch_dist_lane(t.measure, la, t.k, t.out32, list);
+    case TP_INDEL: return launch_indel_lane(la, t.k, t.out32, list);
+    default: return launch_partial_lane(la, t.span, list);
+    }
+}
+
+static hipError_t two_pass_wave(const TwoPassCall &t, const LaunchArgs &la, const uint32_t *list, int grid, uint32_t *scratch, uint64_t words)
+{
+    switch (t.kind) {
+    case TP_OSA: return launch_osa_wave(la, list, grid, scratch, words);
+    case TP_DIST: return launch_dist_wave(t.measure, la, t.k, t.out32, list, grid, scratch, words);
+    case TP_INDEL: return launch_indel_wave(la, t.k, t.out32, list, grid, scratch, words);
+    default: return launch_partial_wave(la, t.span, list, grid, scratch, words);
+    }
+}
+
+// Words of global scratch one wave needs for the work list `st` describes; 0 when LDS holds its tables.
+static uint64_t two_pass_slot_words(TwoPassKind kind, const DevStatus &st)
+{
+    if (kind == TP_PARTIAL) { // max_len / pad1[0] bound the needles and haystacks (bytes, hence scalar values)
+        // (partial_wave_words grows with both arguments: the larger of the two forms at the bounds covers every pair)
+        const uint64_t w = std::max(partial_wave_words(64u, st.pad1[0]), partial_wave_words(std::max(st.max_len, 65u), st.pad1[0]));
+        return w > PARTIAL_WAVE_LDS_WORDS ? (w + 1u) & ~(uint64_t)1 : 0u; // (64-bit words inside a slot)
+    }
+    if (st.max_len <= OSA_WAVE_LDS_CPS) return 0u; // (max_len bounds the pattern in scalar values: it is a byte length)
+    return kind == TP_OSA ? osa_wave_slot_words(st.max_len) : kind == TP_DIST ? dist_wave_slot_words(st.max_len) : indel_wave_slot_words(st.max_len);
+}
+
+// The shared flow.  la.status is the device status block the lane kernel counts into.  slot >= 0: a pairwise call, whose status
+// is published into that ring slot; slot < 0: a distance or alignment call, whose status is copied.  c->osa_list holds la.n words.
+static int two_pass(strsim_ctx *c, const LaunchArgs &la, const TwoPassCall &t, int slot)
+{
+    uint32_t *const list = c->osa_list.as<uint32_t>();
+    HIP_TRY(hipMemsetAsync(la.status, 0, sizeof(DevStatus), c->stream));
+    hipError_t e = two_pass_lane(t, la, list);
+    if (e != hipSuccess) return hip_fail(e, TWO_PASS_LANE[t.kind]);
+    int rc = slot >= 0 ? publish_slot(c, slot) : dist_report(c);
+    if (rc) return rc;
+    c->enqueued_ops += 3u;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const DevStatus &st = slot >= 0 ? c->status_host[slot] : *c->dist_status_host;
+    const uint32_t rows = st.wave_rows;
+    if (rows == 0u) return STRSIM_OK;
+    int grid = c->num_cu * 16;
+    if ((uint64_t)grid > rows) grid = (int)rows;
+    uint32_t *scratch = nullptr;
+    const uint64_t words = two_pass_slot_words(t.kind, st);
+    if (words) {
+        const size_t per = (size_t)words * sizeof(uint32_t);
+        if ((size_t)grid * per > OSA_SCRATCH_BUDGET) grid = (int)std::max<size_t>(1, OSA_SCRATCH_BUDGET / per);
+        rc = c->osa_scratch.reserve((size_t)grid * per);
+        if (rc) return rc;
+        scratch = c->osa_scratch.as<uint32_t>();
+    }
+    e = two_pass_wave(t, la, list, grid, scratch, words);
+    if (e != hipSuccess) return hip_fail(e, TWO_PASS_WAVE[t.kind]);
+    c->enqueued_ops += 1u;
+    return STRSIM_OK;
+}
+
+static LaunchArgs two_pass_args(strsim_ctx *c, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
+                                const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t n, DevStatus *status)
+{
     LaunchArgs la{};
     la.offA = a_off; la.valA = a_val; la.rowsA = a_rows;
     la.offB = b_off; la.valB = b_val; la.rowsB = b_rows;
     la.out = out; la.n = n;
-    la.status = c->status + slot; la.stream = c->stream;
-    HIP_TRY(hipMemsetAsync(la.status, 0, sizeof(DevStatus), c->stream));
-    const bool indel = measure == STRSIM_INDEL, partial = measure == STRSIM_PARTIAL_RATIO;
-    hipError_t e = partial ? launch_partial_lane(la, nullptr, c->osa_list)
-                 : indel ? launch_indel_lane(la, DIST_UNBOUNDED, nullptr, c->osa_list) : launch_osa_lane(la, c->osa_list);
-    if (e != hipSuccess)
-        return hip_fail(e, partial ? "kernel launch (k_partial_lane)" : indel ? "kernel launch (k_indel_lane)" : "kernel launch (k_osa_lane)");
-    HIP_TRY(launch_publish_status(c->status + slot, c->status_host_dev + slot, c->slot_ticket[slot], c->stream));
-    c->enqueued_ops += 3u;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const uint32_t rows = c->status_host[slot].wave_rows, max_pat = c->status_host[slot].max_len;
-    if (rows != 0u && partial) {
-        rc = partial_wave_pass(c, la, nullptr, rows, max_pat, c->status_host[slot].pad1[0]);
-        if (rc) return rc;
-    } else if (rows != 0u) {
-        int grid = c->num_cu * 16;
-        if ((uint64_t)grid > rows) grid = (int)rows;
-        uint32_t *scratch = nullptr;
-        uint64_t slot_words = 0;
-        if (max_pat > OSA_WAVE_LDS_CPS) { // (max_pat bounds the pattern in scalar values: it is a byte length)
-            slot_words = indel ? indel_wave_slot_words(max_pat) : osa_wave_slot_words(max_pat);
-            const size_t per = (size_t)slot_words * sizeof(uint32_t);
-            if ((size_t)grid * per > OSA_SCRATCH_BUDGET) grid = (int)std::max<size_t>(1, OSA_SCRATCH_BUDGET / per);
-            rc = ctx_reserve((void **)&c->osa_scratch, &c->osa_scratch_cap, (size_t)grid * per);
-            if (rc) return rc;
-            scratch = c->osa_scratch;
-        }
-        e = indel ? launch_indel_wave(la, DIST_UNBOUNDED, nullptr, c->osa_list, grid, scratch, slot_words)
-                  : launch_osa_wave(la, c->osa_list, grid, scratch, slot_words);
-        if (e != hipSuccess) return hip_fail(e, indel ? "kernel launch (k_indel_wave)" : "kernel launch (k_osa_wave)");
-        c->enqueued_ops += 1u;
-    }
-    c->slot_timed[slot] = false;
-    c->slot_deferred[slot] = false;
-    c->slot_args[slot] = la;
-    c->slot_measure[slot] = measure;
-    for (int q = 0; q < STRSIM_NUM_MEASURES; ++q) c->slot_outs[slot][q] = nullptr;
-    c->slot_pending[slot] = true;
-    c->head = (slot + 1) % strsim_ctx::RING;
+    la.status = status; la.stream = c->stream;
+    return la;
+}
+
+// A pairwise call of a two-pass measure (OSA: strsim_osa.h, Indel: strsim_indel.h, partial ratio: strsim_partial.h).  It occupies
+// a ring slot like any other (its status block carries the ticket and the work-list count) and has nothing to do at retirement.
+static int pairs_osa(strsim_ctx *c, int slot, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
+                     const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t n)
+{
+    int rc = c->osa_list.reserve(n * sizeof(uint32_t));
+    if (rc) return rc;
+    slot_begin(c, slot);
+    const LaunchArgs la = two_pass_args(c, a_off, a_val, a_rows, b_off, b_val, b_rows, out, n, c->status + slot);
+    const TwoPassKind kind = measure == STRSIM_PARTIAL_RATIO ? TP_PARTIAL : measure == STRSIM_INDEL ? TP_INDEL : TP_OSA;
+    rc = two_pass(c, la, TwoPassCall{kind, measure, DIST_UNBOUNDED, nullptr, nullptr}, slot);
+    if (rc) return rc;
+    slot_commit(c, slot, la, measure, false, false, nullptr);
     return STRSIM_OK;
 }
 
@@ -559,26 +708,13 @@ static int pairs_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_off
         set_error("strsim_pairs_device: unknown measure %d", measure);
         return STRSIM_ERR_ARG;
     }
-    // shape rule of parallel_apply, strsim.rs:48-52
-    if (a_rows != b_rows && a_rows != 1 && b_rows != 1) {
-        set_error("Inputs must have the same length, or one of them must be a Utf8 literal.");
-        return STRSIM_ERR_SHAPE;
-    }
-    const uint64_t n = (a_rows == 1) ? b_rows : a_rows;
-    if (out_rows != n) {
-        set_error("strsim_pairs_device: out_rows=%llu but the inputs produce %llu rows", (unsigned long long)out_rows,
-                  (unsigned long long)n);
-        return STRSIM_ERR_ARG;
-    }
-    if (n == 0) return STRSIM_OK;
-    if (n > 0xFFFFFFFFull) { // row and chunk indices are 32-bit inside the kernels (as are the offsets themselves)
-        set_error("strsim_pairs_device: %llu rows in one call; split the column (at most 2^32 - 1 rows per call)", (unsigned long long)n);
-        return STRSIM_ERR_ARG;
-    }
+    uint64_t n;
+    int rc = check_rows("strsim_pairs_device", a_rows, b_rows, out_rows, &n);
+    if (rc || n == 0) return rc;
     if (!a_off || !b_off || !outs) { set_error("strsim_pairs_device: NULL buffer"); return STRSIM_ERR_ARG; }
     for (int q = 0; q < (all ? STRSIM_NUM_MEASURES : 1); ++q)
         if (!outs[q]) { set_error("strsim_pairs_device: NULL output buffer"); return STRSIM_ERR_ARG; }
-    int rc = ctx_set_device(c);
+    rc = ctx_set_device(c);
     if (rc) return rc;
     // the ring slot about to be reused must have been retired
     const int slot = c->head;
@@ -595,7 +731,7 @@ static int pairs_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_off
             return STRSIM_ERR_EARLIER_CALL;
         }
     }
-    if (measure == STRSIM_OSA || measure == STRSIM_INDEL || measure == STRSIM_PARTIAL_RATIO) return pairs_osa(c, slot, measure, a_off, a_val, a_rows, b_off, b_val, b_rows, outs[0], n);
+    if (two_pass_measure(measure)) return pairs_osa(c, slot, measure, a_off, a_val, a_rows, b_off, b_val, b_rows, outs[0], n);
     const uint64_t nchunks = (n + 63) >> 6;
     // One launch (the lane kernel alone, the rest at retirement if it turns out to be needed) when the caller has opted in and the
     // context's last retired call left nothing behind its lane kernel.  Such a call owns a mask buffer until it is retired (there
@@ -608,27 +744,22 @@ static int pairs_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_off
             if (c->maskbuf_owner[b] < 0) { mb = b; defer = true; break; }
     }
     // mask + backup (five-measure call) + the work list of k_lane_utf8 (one u32 per chunk)
-    {
-        void *p = c->slowmask[mb];
-        rc = ctx_reserve(&p, &c->slowmask_cap[mb], 2 * nchunks * sizeof(unsigned long long) + nchunks * sizeof(uint32_t));
-        c->slowmask[mb] = static_cast<unsigned long long *>(p);
-        if (rc) return rc;
-    }
+    rc = c->slowmask[mb].reserve(2 * nchunks * sizeof(unsigned long long) + nchunks * sizeof(uint32_t));
+    if (rc) return rc;
+    unsigned long long *const mask = c->slowmask[mb].as<unsigned long long>();
     // (the status block of the slot is cleared by the first kernel of the call)
-    if (++c->ticket_seq == 0u) c->ticket_seq = 1u;
-    c->slot_ticket[slot] = c->ticket_seq;
-    memset(&c->status_host[slot], 0, sizeof(DevStatus)); // (the slot is not pending: nothing on the device writes this block now)
+    slot_begin(c, slot);
     c->status_host[slot].lane_left = LANE_LEFT_UNKNOWN;
 
     LaunchArgs la;
     la.offA = a_off; la.valA = a_val; la.rowsA = a_rows;
     la.offB = b_off; la.valB = b_val; la.rowsB = b_rows;
     la.out = outs[0]; la.n = n;
-    la.slowmask = c->slowmask[mb]; la.status = c->status + slot; la.stream = c->stream;
+    la.slowmask = mask; la.status = c->status + slot; la.stream = c->stream;
     la.sched = c->sched + 4 * slot;
     la.publish_host = nullptr;
     la.publish_ticket = 0u;
-    la.worklist = reinterpret_cast<uint32_t *>(c->slowmask[mb] + 2 * nchunks);
+    la.worklist = reinterpret_cast<uint32_t *>(mask + 2 * nchunks);
     la.qtab = c->qtab;
     la.stage_grid = c->num_cu * c->stage_wg_per_cu;
     la.no_literal_path = c->no_literal_path;
@@ -639,9 +770,9 @@ static int pairs_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_off
     la.wave_grid_lev = c->num_cu * c->lev_waves_per_cu;
     {   // per-wave global scratch of k_wave_pairs (scalar-value arrays; Levenshtein: text arenas as well)
         const size_t waves = (size_t)std::max(la.wave_grid, la.wave_grid_lev);
-        rc = ctx_reserve((void **)&c->lev_ws, &c->lev_ws_cap, waves * LEV_WS_WORDS * sizeof(uint32_t));
+        rc = c->lev_ws.reserve(waves * LEV_WS_WORDS * sizeof(uint32_t));
         if (rc) return rc;
-        la.lev_ws = c->lev_ws;
+        la.lev_ws = c->lev_ws.as<uint32_t>();
     }
     la.ev_lane0 = la.ev_lane1 = la.ev_wave1 = nullptr;
     if (c->timing) {
@@ -679,14 +810,9 @@ static int pairs_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_off
         e0 = launch_slow_only(measure, la);
         if (e0 != hipSuccess) return hip_fail(e0, "kernel launch");
         c->enqueued_ops += 4u;
-        c->slot_timed[slot] = false;
-        c->slot_deferred[slot] = false;
-        c->slot_args[slot] = la;
-        c->slot_measure[slot] = measure;
-        for (int q = 0; q < STRSIM_NUM_MEASURES; ++q) c->slot_outs[slot][q] = nullptr;
-        HIP_TRY(launch_publish_status(c->status + slot, c->status_host_dev + slot, c->slot_ticket[slot], c->stream));
-        c->slot_pending[slot] = true;
-        c->head = (slot + 1) % strsim_ctx::RING;
+        rc = publish_slot(c, slot);
+        if (rc) return rc;
+        slot_commit(c, slot, la, measure, false, false, nullptr);
         return STRSIM_OK;
     }
     la.publish_host = c->status_host_dev + slot; // lane_left reaches the host either way: it sets expect_slow
@@ -695,22 +821,18 @@ static int pairs_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_off
         la.publish_ticket = c->slot_ticket[slot];
         e = all ? launch_lane_all_only(la, outs) : launch_lane_only(measure, la);
     } else {
-        e = all ? launch_pairs_all(la, outs, c->slowmask[mb] + nchunks) : launch_pairs(measure, la);
+        e = all ? launch_pairs_all(la, outs, mask + nchunks) : launch_pairs(measure, la);
     }
     if (e != hipSuccess) return hip_fail(e, "kernel launch");
     // lane kernel (+ k_publish_lit behind k_lane_lit) | + three slow-row kernels (x 5, + 5 mask copies) + status copy
     c->enqueued_ops += (uint64_t)lane_kernel_launches(measure, la) + (defer ? 0u : (all ? 21u : 4u));
-    c->slot_timed[slot] = c->timing;
-    c->slot_deferred[slot] = defer;
     if (defer) c->maskbuf_owner[mb] = slot;
-    c->slot_args[slot] = la;
-    c->slot_measure[slot] = measure;
-    for (int q = 0; q < STRSIM_NUM_MEASURES; ++q) c->slot_outs[slot][q] = all ? outs[q] : nullptr;
-    if (!defer) HIP_TRY(launch_publish_status(c->status + slot, c->status_host_dev + slot, c->slot_ticket[slot], c->stream));
-    c->slot_pending[slot] = true;
-    c->head = (slot + 1) % strsim_ctx::RING;
+    else if ((rc = publish_slot(c, slot)) != STRSIM_OK) return rc;
+    slot_commit(c, slot, la, measure, c->timing, defer, all ? outs : nullptr);
     return STRSIM_OK;
 }
+
+extern "C" {
 
 int strsim_pairs_device(strsim_ctx_t *c, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
                         const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t out_rows)
@@ -790,15 +912,13 @@ int strsim_pairs_host(strsim_ctx_t *c, int measure, const uint32_t *a_off, const
                       const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t out_rows)
 {
     if (!c) { set_error("strsim_pairs_host: ctx is NULL"); return STRSIM_ERR_ARG; }
-    if (a_rows != b_rows && a_rows != 1 && b_rows != 1) {
-        set_error("Inputs must have the same length, or one of them must be a Utf8 literal.");
-        return STRSIM_ERR_SHAPE;
-    }
-    const uint64_t n = (a_rows == 1) ? b_rows : a_rows;
+    uint64_t n;
+    int rc = shape_rows(a_rows, b_rows, &n);
+    if (rc) return rc;
     if (out_rows != n) { set_error("strsim_pairs_host: out_rows mismatch"); return STRSIM_ERR_ARG; }
     if (n == 0) return STRSIM_OK;
     if (!a_off || !b_off || !out) { set_error("strsim_pairs_host: NULL buffer"); return STRSIM_ERR_ARG; }
-    int rc = ctx_set_device(c);
+    rc = ctx_set_device(c);
     if (rc) return rc;
     const size_t abytes = (size_t)a_off[a_rows] - a_off[0], bbytes = (size_t)b_off[b_rows] - b_off[0];
     if (n <= c->host_direct_rows && abytes <= HOST_DIRECT_BYTES && bbytes <= HOST_DIRECT_BYTES) {
@@ -836,23 +956,14 @@ int strsim_pairs_host(strsim_ctx_t *c, int measure, const uint32_t *a_off, const
         memcpy(out, h + o_out, n * 8);
         return STRSIM_OK;
     }
-    // (the copy path keeps the caller's offset base and uploads the values from byte 0 of the caller's buffer, so every
-    //  offset the kernels can form, 0 included, is inside the device copy)
-    const size_t need[5] = {(a_rows + 1) * 4, (size_t)a_off[a_rows] + 1, (b_rows + 1) * 4, (size_t)b_off[b_rows] + 1, n * 8};
-    for (int i = 0; i < 5; ++i) {
-        rc = ctx_reserve(&c->stage[i], &c->stage_cap[i], need[i]);
-        if (rc) return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(c->stage[0], a_off, (a_rows + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    if (a_off[a_rows]) HIP_TRY(hipMemcpyAsync(c->stage[1], a_val, a_off[a_rows], hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->stage[2], b_off, (b_rows + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    if (b_off[b_rows]) HIP_TRY(hipMemcpyAsync(c->stage[3], b_val, b_off[b_rows], hipMemcpyHostToDevice, c->stream));
-    rc = strsim_pairs_device(c, measure, (const uint32_t *)c->stage[0], (const uint8_t *)c->stage[1], a_rows,
-                             (const uint32_t *)c->stage[2], (const uint8_t *)c->stage[3], b_rows, (double *)c->stage[4], n);
+    Staged s;
+    rc = ctx_stage(c, a_off, a_val, a_rows, b_off, b_val, b_rows, n * 8, &s);
+    if (rc) return rc;
+    rc = strsim_pairs_device(c, measure, s.a_off, s.a_val, a_rows, s.b_off, s.b_val, b_rows, (double *)s.out, n);
     if (rc) return rc;
     rc = strsim_ctx_synchronize(c); // also runs the long-string pass, which writes into the staged output
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, c->stage[4], n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out, s.out, n * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return STRSIM_OK;
 }
@@ -921,19 +1032,91 @@ static uint32_t match_splits(uint64_t nq, uint64_t nc, uint32_t kp, int num_cu)
 static constexpr uint64_t MATCH_FALLBACK_CALLS = 16;
 static constexpr uint64_t MATCH_FALLBACK_SCORES = (uint64_t)1 << 24;
 
+// The part of a search call's workspace that both families lay out alike: both sides packed by k_match_pack (32-byte words +
+// meta) and their slow lists; `tail` is the family's own, and starts with the two slow counts.
+struct SearchPack {
+    uint32_t *qw, *qm, *cw, *cm, *qs, *cs;
+    uint8_t *tail;
+    uint32_t q_slow, c_slow; // strings k_match_pack could not pack
+};
+
+// Reserve `ws` for the common part + tail_bytes, zero the first zero_bytes of the tail, pack both sides and read the two slow
+// counts back: they decide what runs (the only wait of a call without slow strings).
+static int search_pack(strsim_ctx *c, DevBuf &ws, size_t tail_bytes, size_t zero_bytes, const uint32_t *q_off, const uint8_t *q_val,
+                       uint32_t nq, const uint32_t *c_off, const uint8_t *c_val, uint32_t nc, SearchPack *p)
+{
+    const size_t o_qw = 0, o_qm = o_qw + up256((size_t)nq * 32), o_cw = o_qm + up256((size_t)nq * 4), o_cm = o_cw + up256((size_t)nc * 32),
+                 o_qs = o_cm + up256((size_t)nc * 4), o_cs = o_qs + up256((size_t)nq * 4), o_tail = o_cs + up256((size_t)nc * 4);
+    int rc = ws.reserve(o_tail + tail_bytes);
+    if (rc) return rc;
+    if (!c->match_counts_host) HIP_TRY(hipHostMalloc((void **)&c->match_counts_host, 64, hipHostMallocDefault));
+    uint8_t *const b = ws.as<uint8_t>();
+    p->qw = (uint32_t *)(b + o_qw); p->qm = (uint32_t *)(b + o_qm); p->cw = (uint32_t *)(b + o_cw); p->cm = (uint32_t *)(b + o_cm);
+    p->qs = (uint32_t *)(b + o_qs); p->cs = (uint32_t *)(b + o_cs); p->tail = b + o_tail;
+    uint32_t *const cnt = (uint32_t *)p->tail;
+    hipStream_t st = c->stream;
+    HIP_TRY(hipMemsetAsync(cnt, 0, zero_bytes, st));
+    HIP_TRY(launch_match_pack(q_off, q_val, nq, p->qw, p->qm, p->qs, cnt, st));
+    HIP_TRY(launch_match_pack(c_off, c_val, nc, p->cw, p->cm, p->cs, cnt + 1, st));
+    HIP_TRY(hipMemcpyAsync(c->match_counts_host, cnt, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    p->q_slow = c->match_counts_host[0];
+    p->c_slow = c->match_counts_host[1];
+    return STRSIM_OK;
+}
+
+// fallback: scores of up to MATCH_FALLBACK_CALLS literal calls per batch, at most MATCH_FALLBACK_SCORES doubles
+static uint64_t fallback_calls(uint32_t nq, uint32_t nc)
+{
+    const uint64_t calls = MATCH_FALLBACK_SCORES / std::max(nq, nc);
+    return std::min(std::max<uint64_t>(calls, 1), MATCH_FALLBACK_CALLS);
+}
+
+// Every pair with a slow side: that side as the literal of a pairwise call against the other column, `calls` of them per batch,
+// folded into the list (fs, fi).  score(lit_off, lit_val, col_off, col_val, rows, b) enqueues literal b of a batch;
+// finish(scores) leaves the batch's `scores` scores, row b at b * rows, in `batch` for the fold.
+template <class Score, class Finish>
+static int search_fallback(strsim_ctx *c, const char *who, const SearchPack &p, const uint32_t *q_off, const uint8_t *q_val, uint32_t nq,
+                           const uint32_t *c_off, const uint8_t *c_val, uint32_t nc, uint32_t k, uint32_t kp, double min_score,
+                           uint64_t calls, const double *batch, double *fs, uint32_t *fi, Score score, Finish finish)
+{
+    hipStream_t st = c->stream;
+    HIP_TRY(launch_match_clear(fs, fi, (uint64_t)nq * kp, st));
+    const uint32_t q_slow = p.q_slow, c_slow = p.c_slow;
+    const std::unique_ptr<uint32_t[]> host_list(new (std::nothrow) uint32_t[(size_t)q_slow + c_slow + 1]);
+    if (!host_list) { set_error("%s: out of host memory", who); return STRSIM_ERR_OOM; }
+    if (q_slow) HIP_TRY(hipMemcpyAsync(host_list.get(), p.qs, (size_t)q_slow * 4, hipMemcpyDeviceToHost, st));
+    if (c_slow) HIP_TRY(hipMemcpyAsync(host_list.get() + q_slow, p.cs, (size_t)c_slow * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (uint32_t b0 = 0; b0 < q_slow; b0 += (uint32_t)calls) { // a slow query against every candidate
+        const uint32_t nb = (uint32_t)(q_slow - b0 < calls ? q_slow - b0 : calls);
+        for (uint32_t b = 0; b < nb; ++b) {
+            int r = score(q_off + host_list[b0 + b], q_val, c_off, c_val, nc, b);
+            if (r) return r;
+        }
+        int r = finish((uint64_t)nb * nc);
+        if (r) return r;
+        HIP_TRY(launch_match_fold_cols(k, batch, p.qs + b0, nb, nc, min_score, fs, fi, st));
+    }
+    for (uint32_t b0 = 0; b0 < c_slow; b0 += (uint32_t)calls) { // a slow candidate against every query (the fast ones are kept)
+        const uint32_t nb = (uint32_t)(c_slow - b0 < calls ? c_slow - b0 : calls);
+        for (uint32_t b = 0; b < nb; ++b) {
+            int r = score(c_off + host_list[q_slow + b0 + b], c_val, q_off, q_val, nq, b);
+            if (r) return r;
+        }
+        int r = finish((uint64_t)nb * nq);
+        if (r) return r;
+        HIP_TRY(launch_match_fold_rows(k, batch, p.cs + b0, nb, p.qm, nq, min_score, fs, fi, st));
+    }
+    return STRSIM_OK;
+}
+
 static int best_match_check(const char *who, strsim_ctx_t *c, int measure, const uint32_t *q_off, const uint8_t *q_val,
                             uint64_t q_rows, const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, uint32_t k,
                             double min_score, const void *out_index, const void *out_score)
 {
     if (!measure_accepted(measure, STRSIM_ENTRY_BEST_MATCH)) { set_error("%s: unknown measure %d", who, measure); return STRSIM_ERR_ARG; }
-    if (k < 1u || k > STRSIM_BEST_MATCH_MAX_K) { set_error("%s: k=%u is outside 1..%u", who, k, STRSIM_BEST_MATCH_MAX_K); return STRSIM_ERR_ARG; }
-    if (min_score != min_score) { set_error("%s: min_score is NaN", who); return STRSIM_ERR_ARG; }
-    if (q_rows > 0xFFFFFFFFull) { set_error("%s: %llu queries (at most 2^32 - 1)", who, (unsigned long long)q_rows); return STRSIM_ERR_ARG; }
-    if (c_rows > 0xFFFFFFFEull) { set_error("%s: %llu candidates (at most 2^32 - 2)", who, (unsigned long long)c_rows); return STRSIM_ERR_ARG; }
-    if (q_rows && (!q_off || !q_val || !out_index || !out_score)) { set_error("%s: NULL query or output buffer", who); return STRSIM_ERR_ARG; }
-    if (c_rows && (!c_off || !c_val)) { set_error("%s: NULL candidate buffer", who); return STRSIM_ERR_ARG; }
-    if (!c) { set_error("%s: ctx is NULL", who); return STRSIM_ERR_ARG; }
-    return STRSIM_OK;
+    return search_check(who, c, q_off, q_val, q_rows, c_off, c_val, c_rows, k, STRSIM_BEST_MATCH_MAX_K, min_score, out_index, out_score);
 }
 
 extern "C" {
@@ -951,78 +1134,35 @@ int strsim_best_match_device(strsim_ctx_t *c, int measure, const uint32_t *q_off
     const uint32_t splits = nc ? match_splits(nq, nc, kp, c->num_cu) : 0u;
     const uint32_t per = splits ? (uint32_t)(((uint64_t)nc + splits - 1) / splits) : 0u;
     const uint32_t nsplit = splits ? (uint32_t)(((uint64_t)nc + per - 1) / per) : 0u;
-    // workspace: strings (32-byte words + meta), slow lists + counts, (nsplit + 1) lists of kp per query (the last: fallback)
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t nl = (size_t)nsplit + 1, lists = nl * nq * kp;
-    const size_t o_qw = 0, o_qm = o_qw + up((size_t)nq * 32), o_cw = o_qm + up((size_t)nq * 4), o_cm = o_cw + up((size_t)nc * 32),
-                 o_qs = o_cm + up((size_t)nc * 4), o_cs = o_qs + up((size_t)nq * 4), o_cnt = o_cs + up((size_t)nc * 4),
-                 o_ls = o_cnt + 256, o_li = o_ls + up(lists * 8), total = o_li + up(lists * 4);
-    rc = ctx_reserve(&c->match_ws, &c->match_ws_cap, total);
+    // the tail of the workspace: the slow counts, then (nsplit + 1) lists of kp per query (the last: fallback)
+    const size_t lists = ((size_t)nsplit + 1) * nq * kp;
+    const size_t o_ls = 256, o_li = o_ls + up256(lists * 8);
+    SearchPack p;
+    rc = search_pack(c, c->match_ws, o_li + up256(lists * 4), 8, q_off, q_val, nq, c_off, c_val, nc, &p);
     if (rc) return rc;
-    if (!c->match_counts_host) HIP_TRY(hipHostMalloc((void **)&c->match_counts_host, 64, hipHostMallocDefault));
-    uint8_t *const ws = static_cast<uint8_t *>(c->match_ws);
-    uint32_t *const qw = (uint32_t *)(ws + o_qw), *const qm = (uint32_t *)(ws + o_qm), *const cw = (uint32_t *)(ws + o_cw),
-                   *const cm = (uint32_t *)(ws + o_cm), *const qs = (uint32_t *)(ws + o_qs), *const cs = (uint32_t *)(ws + o_cs),
-                   *const cnt = (uint32_t *)(ws + o_cnt), *const lidx = (uint32_t *)(ws + o_li);
-    double *const lscore = (double *)(ws + o_ls);
+    double *const lscore = (double *)(p.tail + o_ls);
+    uint32_t *const lidx = (uint32_t *)(p.tail + o_li);
     hipStream_t st = c->stream;
-    HIP_TRY(hipMemsetAsync(cnt, 0, 8, st));
-    HIP_TRY(launch_match_pack(q_off, q_val, nq, qw, qm, qs, cnt, st));
-    HIP_TRY(launch_match_pack(c_off, c_val, nc, cw, cm, cs, cnt + 1, st));
-    // the sizes of the two slow classes decide what runs: one small read-back (the only wait of a call without slow strings)
-    HIP_TRY(hipMemcpyAsync(c->match_counts_host, cnt, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const uint32_t q_slow = c->match_counts_host[0], c_slow = c->match_counts_host[1];
     // fast x fast: lists 0 .. nsplit - 1
     uint32_t used = 0;
-    if (nsplit && q_slow < nq && c_slow < nc) {
-        MatchLaneArgs a{qw, qm, nq, cw, cm, nc, nsplit, per, k, c->qtab, min_score, lscore, lidx, st};
+    if (nsplit && p.q_slow < nq && p.c_slow < nc) {
+        MatchLaneArgs a{p.qw, p.qm, nq, p.cw, p.cm, nc, nsplit, per, k, c->qtab, min_score, lscore, lidx, st};
         HIP_TRY(launch_match_lane(measure, a));
         used = nsplit;
     }
     // every pair with a slow side: strsim_pairs_device with that side as the literal, batch by batch, folded into list `used`
-    if (nc && (q_slow || c_slow)) {
-        double *const fs = lscore + (size_t)used * nq * kp;
-        uint32_t *const fi = lidx + (size_t)used * nq * kp;
-        HIP_TRY(launch_match_clear(fs, fi, (uint64_t)nq * kp, st));
-        const uint64_t longest = nq > nc ? nq : nc;
-        uint64_t calls = MATCH_FALLBACK_SCORES / longest;
-        if (calls > MATCH_FALLBACK_CALLS) calls = MATCH_FALLBACK_CALLS;
-        if (calls < 1) calls = 1;
-        rc = ctx_reserve(&c->match_scratch, &c->match_scratch_cap, (size_t)(calls * longest * 8));
+    if (nc && (p.q_slow || p.c_slow)) {
+        const uint64_t calls = fallback_calls(nq, nc);
+        rc = c->match_scratch.reserve((size_t)(calls * std::max(nq, nc) * 8));
         if (rc) return rc;
-        double *const scratch = static_cast<double *>(c->match_scratch);
-        uint32_t *host_list = static_cast<uint32_t *>(malloc(((size_t)q_slow + c_slow + 1) * 4));
-        if (!host_list) { set_error("strsim_best_match_device: out of host memory"); return STRSIM_ERR_OOM; }
-        auto run = [&]() -> int {
-            if (q_slow) HIP_TRY(hipMemcpyAsync(host_list, qs, (size_t)q_slow * 4, hipMemcpyDeviceToHost, st));
-            if (c_slow) HIP_TRY(hipMemcpyAsync(host_list + q_slow, cs, (size_t)c_slow * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            for (uint32_t b0 = 0; b0 < q_slow; b0 += (uint32_t)calls) { // a slow query against every candidate
-                const uint32_t nb = (uint32_t)(q_slow - b0 < calls ? q_slow - b0 : calls);
-                for (uint32_t b = 0; b < nb; ++b) {
-                    int r = strsim_pairs_device(c, measure, q_off + host_list[b0 + b], q_val, 1, c_off, c_val, nc, scratch + (size_t)b * nc, nc);
-                    if (r) return r;
-                }
-                int r = strsim_ctx_synchronize(c);
-                if (r) return r;
-                HIP_TRY(launch_match_fold_cols(k, scratch, qs + b0, nb, nc, min_score, fs, fi, st));
-            }
-            for (uint32_t b0 = 0; b0 < c_slow; b0 += (uint32_t)calls) { // a slow candidate against every query (the fast ones are kept)
-                const uint32_t nb = (uint32_t)(c_slow - b0 < calls ? c_slow - b0 : calls);
-                for (uint32_t b = 0; b < nb; ++b) {
-                    const uint32_t j = host_list[q_slow + b0 + b];
-                    int r = strsim_pairs_device(c, measure, c_off + j, c_val, 1, q_off, q_val, nq, scratch + (size_t)b * nq, nq);
-                    if (r) return r;
-                }
-                int r = strsim_ctx_synchronize(c);
-                if (r) return r;
-                HIP_TRY(launch_match_fold_rows(k, scratch, cs + b0, nb, qm, nq, min_score, fs, fi, st));
-            }
-            return STRSIM_OK;
-        };
-        rc = run();
-        free(host_list);
+        double *const scratch = c->match_scratch.as<double>();
+        rc = search_fallback(
+            c, "strsim_best_match_device", p, q_off, q_val, nq, c_off, c_val, nc, k, kp, min_score, calls, scratch,
+            lscore + (size_t)used * nq * kp, lidx + (size_t)used * nq * kp,
+            [&](const uint32_t *lit_off, const uint8_t *lit_val, const uint32_t *off, const uint8_t *val, uint32_t rows, uint32_t b) {
+                return strsim_pairs_device(c, measure, lit_off, lit_val, 1, off, val, rows, scratch + (size_t)b * rows, rows);
+            },
+            [&](uint64_t) { return strsim_ctx_synchronize(c); });
         if (rc) return rc;
         ++used;
     }
@@ -1039,28 +1179,16 @@ int strsim_best_match_host(strsim_ctx_t *c, int measure, const uint32_t *q_off, 
     if (rc || q_rows == 0) return rc;
     rc = ctx_set_device(c);
     if (rc) return rc;
-    // (as strsim_pairs_host's copy path: the caller's offset base is kept and the values go up from byte 0)
     const size_t ob = q_rows * (size_t)k;
-    const size_t need[5] = {(q_rows + 1) * 4, (size_t)q_off[q_rows] + 1, (c_rows + 1) * 4, (c_rows ? (size_t)c_off[c_rows] : 0) + 1,
-                            ob * 12 + 256};
-    for (int i = 0; i < 5; ++i) {
-        rc = ctx_reserve(&c->stage[i], &c->stage_cap[i], need[i]);
-        if (rc) return rc;
-    }
-    hipStream_t st = c->stream;
-    HIP_TRY(hipMemcpyAsync(c->stage[0], q_off, (q_rows + 1) * 4, hipMemcpyHostToDevice, st));
-    if (q_off[q_rows]) HIP_TRY(hipMemcpyAsync(c->stage[1], q_val, q_off[q_rows], hipMemcpyHostToDevice, st));
-    if (c_rows) {
-        HIP_TRY(hipMemcpyAsync(c->stage[2], c_off, (c_rows + 1) * 4, hipMemcpyHostToDevice, st));
-        if (c_off[c_rows]) HIP_TRY(hipMemcpyAsync(c->stage[3], c_val, c_off[c_rows], hipMemcpyHostToDevice, st));
-    }
-    double *const d_score = static_cast<double *>(c->stage[4]);
-    uint32_t *const d_index = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(c->stage[4]) + ((ob * 8 + 255) & ~(size_t)255));
-    rc = strsim_best_match_device(c, measure, (const uint32_t *)c->stage[0], (const uint8_t *)c->stage[1], q_rows,
-                                  (const uint32_t *)c->stage[2], (const uint8_t *)c->stage[3], c_rows, k, min_score, d_index, d_score);
+    Staged s;
+    rc = ctx_stage(c, q_off, q_val, q_rows, c_off, c_val, c_rows, ob * 12 + 256, &s);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out_score, d_score, ob * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out_index, d_index, ob * 4, hipMemcpyDeviceToHost, st));
+    double *const d_score = reinterpret_cast<double *>(s.out);
+    uint32_t *const d_index = reinterpret_cast<uint32_t *>(s.out + up256(ob * 8));
+    rc = strsim_best_match_device(c, measure, s.a_off, s.a_val, q_rows, s.b_off, s.b_val, c_rows, k, min_score, d_index, d_score);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out_score, d_score, ob * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out_index, d_index, ob * 4, hipMemcpyDeviceToHost, c->stream));
     return strsim_ctx_synchronize(c);
 }
 
@@ -1076,65 +1204,29 @@ static int distance_check(const char *who, strsim_ctx_t *c, int measure, const u
         set_error("%s: measure %d has no distance (STRSIM_LEVENSHTEIN, STRSIM_OSA or STRSIM_INDEL)", who, measure);
         return STRSIM_ERR_ARG;
     }
-    if (a_rows != b_rows && a_rows != 1 && b_rows != 1) { // strsim.rs:48-52
-        set_error("Inputs must have the same length, or one of them must be a Utf8 literal.");
-        return STRSIM_ERR_SHAPE;
-    }
-    const uint64_t n = (a_rows == 1) ? b_rows : a_rows;
-    if (out_rows != n) {
-        set_error("%s: out_rows=%llu but the inputs produce %llu rows", who, (unsigned long long)out_rows, (unsigned long long)n);
-        return STRSIM_ERR_ARG;
-    }
-    if (n > 0xFFFFFFFFull) {
-        set_error("%s: %llu rows in one call; split the column (at most 2^32 - 1 rows per call)", who, (unsigned long long)n);
-        return STRSIM_ERR_ARG;
-    }
-    if (n && (!a_off || !a_val || !b_off || !b_val || !out)) { set_error("%s: NULL buffer", who); return STRSIM_ERR_ARG; }
-    if (!c) { set_error("%s: ctx is NULL", who); return STRSIM_ERR_ARG; }
-    return STRSIM_OK;
+    return elementwise_check(who, c, a_rows, b_rows, out_rows, a_off && a_val && b_off && b_val && out);
 }
 
-// k_dist_lane over every row, a read-back of what it left for k_dist_wave, then k_dist_wave sized for that (as pairs_osa).
-static int distance_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
-                                const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, uint32_t k, uint32_t *out, uint64_t n)
+// The status block of a distance or alignment call and its pinned read-back, and the work list for n rows.
+static int dist_prepare(strsim_ctx *c, uint64_t n)
 {
     int rc = ctx_set_device(c);
     if (rc) return rc;
-    rc = ctx_reserve((void **)&c->osa_list, &c->osa_list_cap, n * sizeof(uint32_t));
+    rc = c->osa_list.reserve(n * sizeof(uint32_t));
     if (rc) return rc;
     if (!c->dist_status) HIP_TRY(hipMalloc((void **)&c->dist_status, sizeof(DevStatus)));
     if (!c->dist_status_host) HIP_TRY(hipHostMalloc((void **)&c->dist_status_host, sizeof(DevStatus), hipHostMallocDefault));
-    LaunchArgs la{};
-    la.offA = a_off; la.valA = a_val; la.rowsA = a_rows;
-    la.offB = b_off; la.valB = b_val; la.rowsB = b_rows;
-    la.n = n;
-    la.status = c->dist_status; la.stream = c->stream;
-    HIP_TRY(hipMemsetAsync(la.status, 0, sizeof(DevStatus), c->stream));
-    const bool indel = measure == STRSIM_INDEL; // (k_indel_lane / k_indel_wave with the uint32 output, strsim_indel.h)
-    hipError_t e = indel ? launch_indel_lane(la, k, out, c->osa_list) : launch_dist_lane(measure, la, k, out, c->osa_list);
-    if (e != hipSuccess) return hip_fail(e, indel ? "kernel launch (k_indel_lane)" : "kernel launch (k_dist_lane)");
-    HIP_TRY(hipMemcpyAsync(c->dist_status_host, c->dist_status, sizeof(DevStatus), hipMemcpyDeviceToHost, c->stream));
-    c->enqueued_ops += 3u;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const uint32_t rows = c->dist_status_host->wave_rows, max_pat = c->dist_status_host->max_len;
-    if (rows == 0u) return STRSIM_OK;
-    int grid = c->num_cu * 16;
-    if ((uint64_t)grid > rows) grid = (int)rows;
-    uint32_t *scratch = nullptr;
-    uint64_t slot_words = 0;
-    if (max_pat > OSA_WAVE_LDS_CPS) { // (a byte length: it bounds the pattern in scalar values)
-        slot_words = indel ? indel_wave_slot_words(max_pat) : dist_wave_slot_words(max_pat);
-        const size_t per = (size_t)slot_words * sizeof(uint32_t);
-        if ((size_t)grid * per > OSA_SCRATCH_BUDGET) grid = (int)std::max<size_t>(1, OSA_SCRATCH_BUDGET / per);
-        rc = ctx_reserve((void **)&c->osa_scratch, &c->osa_scratch_cap, (size_t)grid * per);
-        if (rc) return rc;
-        scratch = c->osa_scratch;
-    }
-    e = indel ? launch_indel_wave(la, k, out, c->osa_list, grid, scratch, slot_words)
-              : launch_dist_wave(measure, la, k, out, c->osa_list, grid, scratch, slot_words);
-    if (e != hipSuccess) return hip_fail(e, indel ? "kernel launch (k_indel_wave)" : "kernel launch (k_dist_wave)");
-    c->enqueued_ops += 1u;
     return STRSIM_OK;
+}
+
+// k_dist_lane, then k_dist_wave (Indel: k_indel_lane / k_indel_wave with the uint32 output, strsim_indel.h).
+static int distance_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
+                                const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, uint32_t k, uint32_t *out, uint64_t n)
+{
+    int rc = dist_prepare(c, n);
+    if (rc) return rc;
+    const LaunchArgs la = two_pass_args(c, a_off, a_val, a_rows, b_off, b_val, b_rows, nullptr, n, c->dist_status);
+    return two_pass(c, la, TwoPassCall{measure == STRSIM_INDEL ? TP_INDEL : TP_DIST, measure, k, out, nullptr}, -1);
 }
 
 extern "C" {
@@ -1157,23 +1249,13 @@ int strsim_distance_host(strsim_ctx_t *c, int measure, const uint32_t *a_off, co
     rc = ctx_set_device(c);
     if (rc) return rc;
     const uint64_t n = out_rows;
-    // (as strsim_pairs_host's copy path: the caller's offset base is kept and the values go up from byte 0)
-    const size_t need[5] = {(a_rows + 1) * 4, (size_t)a_off[a_rows] + 1, (b_rows + 1) * 4, (size_t)b_off[b_rows] + 1, n * 4};
-    for (int i = 0; i < 5; ++i) {
-        rc = ctx_reserve(&c->stage[i], &c->stage_cap[i], need[i]);
-        if (rc) return rc;
-    }
-    hipStream_t st = c->stream;
-    HIP_TRY(hipMemcpyAsync(c->stage[0], a_off, (a_rows + 1) * 4, hipMemcpyHostToDevice, st));
-    if (a_off[a_rows]) HIP_TRY(hipMemcpyAsync(c->stage[1], a_val, a_off[a_rows], hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(c->stage[2], b_off, (b_rows + 1) * 4, hipMemcpyHostToDevice, st));
-    if (b_off[b_rows]) HIP_TRY(hipMemcpyAsync(c->stage[3], b_val, b_off[b_rows], hipMemcpyHostToDevice, st));
-    rc = distance_device_impl(c, measure, (const uint32_t *)c->stage[0], (const uint8_t *)c->stage[1], a_rows,
-                              (const uint32_t *)c->stage[2], (const uint8_t *)c->stage[3], b_rows, max_distance,
-                              (uint32_t *)c->stage[4], n);
+    Staged s;
+    rc = ctx_stage(c, a_off, a_val, a_rows, b_off, b_val, b_rows, n * 4, &s);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, c->stage[4], n * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    rc = distance_device_impl(c, measure, s.a_off, s.a_val, a_rows, s.b_off, s.b_val, b_rows, max_distance, (uint32_t *)s.out, n);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, s.out, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return STRSIM_OK;
 }
 
@@ -1181,52 +1263,14 @@ int strsim_distance_host(strsim_ctx_t *c, int measure, const uint32_t *a_off, co
 
 // ---- partial ratio with its alignment (strsim_partial.h) ----
 
-static int partial_check(const char *who, strsim_ctx_t *c, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
-                         const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, const double *out_score, const uint32_t *out_span,
-                         uint64_t out_rows)
-{
-    if (a_rows != b_rows && a_rows != 1 && b_rows != 1) { // strsim.rs:48-52
-        set_error("Inputs must have the same length, or one of them must be a Utf8 literal.");
-        return STRSIM_ERR_SHAPE;
-    }
-    const uint64_t n = (a_rows == 1) ? b_rows : a_rows;
-    if (out_rows != n) {
-        set_error("%s: out_rows=%llu but the inputs produce %llu rows", who, (unsigned long long)out_rows, (unsigned long long)n);
-        return STRSIM_ERR_ARG;
-    }
-    if (n > 0xFFFFFFFFull) {
-        set_error("%s: %llu rows in one call; split the column (at most 2^32 - 1 rows per call)", who, (unsigned long long)n);
-        return STRSIM_ERR_ARG;
-    }
-    if (n && (!a_off || !a_val || !b_off || !b_val || !out_score || !out_span)) { set_error("%s: NULL buffer", who); return STRSIM_ERR_ARG; }
-    if (!c) { set_error("%s: ctx is NULL", who); return STRSIM_ERR_ARG; }
-    return STRSIM_OK;
-}
-
-// k_partial_lane<ALIGN> over every row, a read-back of what it left, then k_partial_wave<ALIGN> (as distance_device_impl).
+// k_partial_lane<ALIGN>, then k_partial_wave<ALIGN>.
 static int partial_device_impl(strsim_ctx_t *c, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
                                const uint8_t *b_val, uint64_t b_rows, double *out_score, uint32_t *out_span, uint64_t n)
 {
-    int rc = ctx_set_device(c);
+    int rc = dist_prepare(c, n);
     if (rc) return rc;
-    rc = ctx_reserve((void **)&c->osa_list, &c->osa_list_cap, n * sizeof(uint32_t));
-    if (rc) return rc;
-    if (!c->dist_status) HIP_TRY(hipMalloc((void **)&c->dist_status, sizeof(DevStatus)));
-    if (!c->dist_status_host) HIP_TRY(hipHostMalloc((void **)&c->dist_status_host, sizeof(DevStatus), hipHostMallocDefault));
-    LaunchArgs la{};
-    la.offA = a_off; la.valA = a_val; la.rowsA = a_rows;
-    la.offB = b_off; la.valB = b_val; la.rowsB = b_rows;
-    la.out = out_score; la.n = n;
-    la.status = c->dist_status; la.stream = c->stream;
-    HIP_TRY(hipMemsetAsync(la.status, 0, sizeof(DevStatus), c->stream));
-    hipError_t e = launch_partial_lane(la, out_span, c->osa_list);
-    if (e != hipSuccess) return hip_fail(e, "kernel launch (k_partial_lane)");
-    HIP_TRY(hipMemcpyAsync(c->dist_status_host, c->dist_status, sizeof(DevStatus), hipMemcpyDeviceToHost, c->stream));
-    c->enqueued_ops += 3u;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const uint32_t rows = c->dist_status_host->wave_rows;
-    if (rows == 0u) return STRSIM_OK;
-    return partial_wave_pass(c, la, out_span, rows, c->dist_status_host->max_len, c->dist_status_host->pad1[0]);
+    const LaunchArgs la = two_pass_args(c, a_off, a_val, a_rows, b_off, b_val, b_rows, out_score, n, c->dist_status);
+    return two_pass(c, la, TwoPassCall{TP_PARTIAL, STRSIM_PARTIAL_RATIO, 0u, nullptr, out_span}, -1);
 }
 
 extern "C" {
@@ -1234,7 +1278,7 @@ extern "C" {
 int strsim_partial_alignment_device(strsim_ctx_t *c, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
                                     const uint8_t *b_val, uint64_t b_rows, double *out_score, uint32_t *out_span, uint64_t out_rows)
 {
-    int rc = partial_check("strsim_partial_alignment_device", c, a_off, a_val, a_rows, b_off, b_val, b_rows, out_score, out_span, out_rows);
+    int rc = elementwise_check("strsim_partial_alignment_device", c, a_rows, b_rows, out_rows, a_off && a_val && b_off && b_val && out_score && out_span);
     if (rc || out_rows == 0) return rc;
     return partial_device_impl(c, a_off, a_val, a_rows, b_off, b_val, b_rows, out_score, out_span, out_rows);
 }
@@ -1242,31 +1286,22 @@ int strsim_partial_alignment_device(strsim_ctx_t *c, const uint32_t *a_off, cons
 int strsim_partial_alignment_host(strsim_ctx_t *c, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
                                   const uint8_t *b_val, uint64_t b_rows, double *out_score, uint32_t *out_span, uint64_t out_rows)
 {
-    int rc = partial_check("strsim_partial_alignment_host", c, a_off, a_val, a_rows, b_off, b_val, b_rows, out_score, out_span, out_rows);
+    int rc = elementwise_check("strsim_partial_alignment_host", c, a_rows, b_rows, out_rows, a_off && a_val && b_off && b_val && out_score && out_span);
     if (rc || out_rows == 0) return rc;
     rc = ctx_set_device(c);
     if (rc) return rc;
     const uint64_t n = out_rows;
-    // (as strsim_pairs_host's copy path: the caller's offset base is kept and the values go up from byte 0)
-    const size_t span_at = (n * 8 + 255) & ~(size_t)255;
-    const size_t need[5] = {(a_rows + 1) * 4, (size_t)a_off[a_rows] + 1, (b_rows + 1) * 4, (size_t)b_off[b_rows] + 1, span_at + n * 16};
-    for (int i = 0; i < 5; ++i) {
-        rc = ctx_reserve(&c->stage[i], &c->stage_cap[i], need[i]);
-        if (rc) return rc;
-    }
-    hipStream_t st = c->stream;
-    HIP_TRY(hipMemcpyAsync(c->stage[0], a_off, (a_rows + 1) * 4, hipMemcpyHostToDevice, st));
-    if (a_off[a_rows]) HIP_TRY(hipMemcpyAsync(c->stage[1], a_val, a_off[a_rows], hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(c->stage[2], b_off, (b_rows + 1) * 4, hipMemcpyHostToDevice, st));
-    if (b_off[b_rows]) HIP_TRY(hipMemcpyAsync(c->stage[3], b_val, b_off[b_rows], hipMemcpyHostToDevice, st));
-    double *const d_score = static_cast<double *>(c->stage[4]);
-    uint32_t *const d_span = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(c->stage[4]) + span_at);
-    rc = partial_device_impl(c, (const uint32_t *)c->stage[0], (const uint8_t *)c->stage[1], a_rows, (const uint32_t *)c->stage[2],
-                             (const uint8_t *)c->stage[3], b_rows, d_score, d_span, n);
+    const size_t span_at = up256(n * 8);
+    Staged s;
+    rc = ctx_stage(c, a_off, a_val, a_rows, b_off, b_val, b_rows, span_at + n * 16, &s);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out_score, d_score, n * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out_span, d_span, n * 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    double *const d_score = reinterpret_cast<double *>(s.out);
+    uint32_t *const d_span = reinterpret_cast<uint32_t *>(s.out + span_at);
+    rc = partial_device_impl(c, s.a_off, s.a_val, a_rows, s.b_off, s.b_val, b_rows, d_score, d_span, n);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out_score, d_score, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out_span, d_span, n * 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return STRSIM_OK;
 }
 
@@ -1282,13 +1317,7 @@ static int nearest_check(const char *who, strsim_ctx_t *c, int measure, const ui
         set_error("%s: measure %d has no distance (STRSIM_LEVENSHTEIN or STRSIM_OSA)", who, measure);
         return STRSIM_ERR_ARG;
     }
-    if (k < 1u || k > STRSIM_NEAREST_MAX_K) { set_error("%s: k=%u is outside 1..%u", who, k, STRSIM_NEAREST_MAX_K); return STRSIM_ERR_ARG; }
-    if (q_rows > 0xFFFFFFFFull) { set_error("%s: %llu queries (at most 2^32 - 1)", who, (unsigned long long)q_rows); return STRSIM_ERR_ARG; }
-    if (c_rows > 0xFFFFFFFEull) { set_error("%s: %llu candidates (at most 2^32 - 2)", who, (unsigned long long)c_rows); return STRSIM_ERR_ARG; }
-    if (q_rows && (!q_off || !q_val || !out_index || !out_distance)) { set_error("%s: NULL query or output buffer", who); return STRSIM_ERR_ARG; }
-    if (c_rows && (!c_off || !c_val)) { set_error("%s: NULL candidate buffer", who); return STRSIM_ERR_ARG; }
-    if (!c) { set_error("%s: ctx is NULL", who); return STRSIM_ERR_ARG; }
-    return STRSIM_OK;
+    return search_check(who, c, q_off, q_val, q_rows, c_off, c_val, c_rows, k, STRSIM_NEAREST_MAX_K, 0.0, out_index, out_distance);
 }
 
 extern "C" {
@@ -1303,91 +1332,46 @@ int strsim_nearest_device(strsim_ctx_t *c, int measure, const uint32_t *q_off, c
     if (rc) return rc;
     const uint32_t nq = (uint32_t)q_rows, nc = (uint32_t)c_rows, kp = (uint32_t)match_lane_k(k);
     const uint32_t splits = nc ? match_splits(nq, nc, kp, c->num_cu) : 0u;
-    // workspace: both sides packed (32-byte words + meta) and their slow lists, the small block (slow counts, histograms, bucket
-    // starts, cursors), the query permutation, the candidates in length order, (splits + 1) lists of kp per query (the last: the
-    // fallback) and the merged scores
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t nl = (size_t)splits + 1, lists = nl * nq * kp, ob = (size_t)nq * k;
-    const size_t o_qw = 0, o_qm = o_qw + up((size_t)nq * 32), o_cw = o_qm + up((size_t)nq * 4), o_cm = o_cw + up((size_t)nc * 32),
-                 o_qs = o_cm + up((size_t)nc * 4), o_cs = o_qs + up((size_t)nq * 4), o_small = o_cs + up((size_t)nc * 4),
-                 o_qp = o_small + 1024, o_sw = o_qp + up((size_t)nq * 4), o_sm = o_sw + up((size_t)nc * 32),
-                 o_si = o_sm + up((size_t)nc * 4), o_ls = o_si + up((size_t)nc * 4), o_li = o_ls + up(lists * 8),
-                 o_ms = o_li + up(lists * 4), total = o_ms + up(ob * 8);
-    rc = ctx_reserve(&c->nearest_ws, &c->nearest_ws_cap, total);
+    // the tail of the workspace: the small block (slow counts, histograms, bucket starts, cursors), the query permutation, the
+    // candidates in length order, (splits + 1) lists of kp per query (the last: the fallback) and the merged scores
+    const size_t lists = ((size_t)splits + 1) * nq * kp, ob = (size_t)nq * k;
+    const size_t o_qp = 1024, o_sw = o_qp + up256((size_t)nq * 4), o_sm = o_sw + up256((size_t)nc * 32), o_si = o_sm + up256((size_t)nc * 4),
+                 o_ls = o_si + up256((size_t)nc * 4), o_li = o_ls + up256(lists * 8), o_ms = o_li + up256(lists * 4);
+    SearchPack p;
+    // (of the small block, the counts and histograms are zeroed)
+    rc = search_pack(c, c->nearest_ws, o_ms + up256(ob * 8), 4 * 88, q_off, q_val, nq, c_off, c_val, nc, &p);
     if (rc) return rc;
-    if (!c->match_counts_host) HIP_TRY(hipHostMalloc((void **)&c->match_counts_host, 64, hipHostMallocDefault));
-    uint8_t *const ws = static_cast<uint8_t *>(c->nearest_ws);
-    uint32_t *const qw = (uint32_t *)(ws + o_qw), *const qm = (uint32_t *)(ws + o_qm), *const cw = (uint32_t *)(ws + o_cw),
-                   *const cm = (uint32_t *)(ws + o_cm), *const qs = (uint32_t *)(ws + o_qs), *const cs = (uint32_t *)(ws + o_cs),
-                   *const small = (uint32_t *)(ws + o_small), *const lidx = (uint32_t *)(ws + o_li);
-    double *const lscore = (double *)(ws + o_ls), *const mscore = (double *)(ws + o_ms);
-    // the small block: slow counts [0, 2), histograms, bucket starts, cursors (the counts and histograms are zeroed)
-    uint32_t *const cnt = small, *const qhist = small + 8, *const chist = qhist + 40, *const qstart = chist + 40,
-                   *const cstart = qstart + 40, *const qcur = cstart + 40, *const ccur = qcur + 40;
+    uint32_t *const small = (uint32_t *)p.tail, *const lidx = (uint32_t *)(p.tail + o_li);
+    double *const lscore = (double *)(p.tail + o_ls), *const mscore = (double *)(p.tail + o_ms);
     hipStream_t st = c->stream;
-    HIP_TRY(hipMemsetAsync(small, 0, 4 * 88, st));
-    HIP_TRY(launch_match_pack(q_off, q_val, nq, qw, qm, qs, cnt, st));
-    HIP_TRY(launch_match_pack(c_off, c_val, nc, cw, cm, cs, cnt + 1, st));
-    // the sizes of the two slow classes decide what runs: one small read-back (the only wait of a call without slow strings)
-    HIP_TRY(hipMemcpyAsync(c->match_counts_host, cnt, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const uint32_t q_slow = c->match_counts_host[0], c_slow = c->match_counts_host[1];
     // fast x fast: length order on the device, then lists 0 .. splits - 1
     uint32_t used = 0;
-    if (splits && q_slow < nq && c_slow < nc) {
-        uint32_t *const qperm = (uint32_t *)(ws + o_qp), *const sw = (uint32_t *)(ws + o_sw), *const sm = (uint32_t *)(ws + o_sm),
-                       *const si = (uint32_t *)(ws + o_si);
-        NearestOrderArgs oa{qm, nq, cw, cm, nc, qhist, chist, qstart, cstart, qcur, ccur, qperm, sw, sm, si, st};
+    if (splits && p.q_slow < nq && p.c_slow < nc) {
+        uint32_t *const qhist = small + 8, *const chist = qhist + 40, *const qstart = chist + 40, *const cstart = qstart + 40,
+                       *const qcur = cstart + 40, *const ccur = qcur + 40;
+        uint32_t *const qperm = (uint32_t *)(p.tail + o_qp), *const sw = (uint32_t *)(p.tail + o_sw), *const sm = (uint32_t *)(p.tail + o_sm),
+                       *const si = (uint32_t *)(p.tail + o_si);
+        NearestOrderArgs oa{p.qm, nq, p.cw, p.cm, nc, qhist, chist, qstart, cstart, qcur, ccur, qperm, sw, sm, si, st};
         HIP_TRY(launch_nearest_order(oa));
-        NearestLaneArgs a{qw, qm, qperm, qstart, nq, sw, sm, si, cstart, splits, k, max_distance, lscore, lidx, st};
+        NearestLaneArgs a{p.qw, p.qm, qperm, qstart, nq, sw, sm, si, cstart, splits, k, max_distance, lscore, lidx, st};
         HIP_TRY(launch_nearest_lane(measure, a));
         used = splits;
     }
     // every pair with a slow side: strsim_distance_device with that side as the literal (its length prefilter and block cutoff
     // apply), batch by batch, folded into list `used` as the scores -(double)d
-    if (nc && (q_slow || c_slow)) {
-        double *const fs = lscore + (size_t)used * nq * kp;
-        uint32_t *const fi = lidx + (size_t)used * nq * kp;
-        const double min_score = -(double)max_distance; // (a cut pair comes back as max_distance + 1)
-        HIP_TRY(launch_match_clear(fs, fi, (uint64_t)nq * kp, st));
-        const uint64_t longest = nq > nc ? nq : nc;
-        uint64_t calls = MATCH_FALLBACK_SCORES / longest;
-        if (calls > MATCH_FALLBACK_CALLS) calls = MATCH_FALLBACK_CALLS;
-        if (calls < 1) calls = 1;
-        rc = ctx_reserve(&c->nearest_scratch, &c->nearest_scratch_cap, (size_t)(calls * longest * 12));
+    if (nc && (p.q_slow || p.c_slow)) {
+        const uint64_t calls = fallback_calls(nq, nc), longest = std::max(nq, nc);
+        rc = c->nearest_scratch.reserve((size_t)(calls * longest * 12));
         if (rc) return rc;
-        double *const scores = static_cast<double *>(c->nearest_scratch);
+        double *const scores = c->nearest_scratch.as<double>();
         uint32_t *const dist = reinterpret_cast<uint32_t *>(scores + calls * longest);
-        uint32_t *host_list = static_cast<uint32_t *>(malloc(((size_t)q_slow + c_slow + 1) * 4));
-        if (!host_list) { set_error("strsim_nearest_device: out of host memory"); return STRSIM_ERR_OOM; }
-        auto run = [&]() -> int {
-            if (q_slow) HIP_TRY(hipMemcpyAsync(host_list, qs, (size_t)q_slow * 4, hipMemcpyDeviceToHost, st));
-            if (c_slow) HIP_TRY(hipMemcpyAsync(host_list + q_slow, cs, (size_t)c_slow * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            for (uint32_t b0 = 0; b0 < q_slow; b0 += (uint32_t)calls) { // a slow query against every candidate
-                const uint32_t nb = (uint32_t)(q_slow - b0 < calls ? q_slow - b0 : calls);
-                for (uint32_t b = 0; b < nb; ++b) {
-                    int r = strsim_distance_device(c, measure, q_off + host_list[b0 + b], q_val, 1, c_off, c_val, nc, max_distance,
-                                                   dist + (size_t)b * nc, nc);
-                    if (r) return r;
-                }
-                HIP_TRY(launch_nearest_scores(dist, (uint64_t)nb * nc, scores, st));
-                HIP_TRY(launch_match_fold_cols(k, scores, qs + b0, nb, nc, min_score, fs, fi, st));
-            }
-            for (uint32_t b0 = 0; b0 < c_slow; b0 += (uint32_t)calls) { // a slow candidate against every query (the fast ones are kept)
-                const uint32_t nb = (uint32_t)(c_slow - b0 < calls ? c_slow - b0 : calls);
-                for (uint32_t b = 0; b < nb; ++b) {
-                    const uint32_t j = host_list[q_slow + b0 + b];
-                    int r = strsim_distance_device(c, measure, c_off + j, c_val, 1, q_off, q_val, nq, max_distance, dist + (size_t)b * nq, nq);
-                    if (r) return r;
-                }
-                HIP_TRY(launch_nearest_scores(dist, (uint64_t)nb * nq, scores, st));
-                HIP_TRY(launch_match_fold_rows(k, scores, cs + b0, nb, qm, nq, min_score, fs, fi, st));
-            }
-            return STRSIM_OK;
-        };
-        rc = run();
-        free(host_list);
+        rc = search_fallback(
+            c, "strsim_nearest_device", p, q_off, q_val, nq, c_off, c_val, nc, k, kp, -(double)max_distance /* a cut pair comes back as max_distance + 1 */,
+            calls, scores, lscore + (size_t)used * nq * kp, lidx + (size_t)used * nq * kp,
+            [&](const uint32_t *lit_off, const uint8_t *lit_val, const uint32_t *off, const uint8_t *val, uint32_t rows, uint32_t b) {
+                return strsim_distance_device(c, measure, lit_off, lit_val, 1, off, val, rows, max_distance, dist + (size_t)b * rows, rows);
+            },
+            [&](uint64_t count) -> int { HIP_TRY(launch_nearest_scores(dist, count, scores, st)); return STRSIM_OK; });
         if (rc) return rc;
         ++used;
     }
@@ -1404,29 +1388,17 @@ int strsim_nearest_host(strsim_ctx_t *c, int measure, const uint32_t *q_off, con
     if (rc || q_rows == 0) return rc;
     rc = ctx_set_device(c);
     if (rc) return rc;
-    // (as strsim_best_match_host: the caller's offset base is kept and the values go up from byte 0)
     const size_t ob = q_rows * (size_t)k;
-    const size_t need[5] = {(q_rows + 1) * 4, (size_t)q_off[q_rows] + 1, (c_rows + 1) * 4, (c_rows ? (size_t)c_off[c_rows] : 0) + 1,
-                            ob * 8 + 256};
-    for (int i = 0; i < 5; ++i) {
-        rc = ctx_reserve(&c->stage[i], &c->stage_cap[i], need[i]);
-        if (rc) return rc;
-    }
-    hipStream_t st = c->stream;
-    HIP_TRY(hipMemcpyAsync(c->stage[0], q_off, (q_rows + 1) * 4, hipMemcpyHostToDevice, st));
-    if (q_off[q_rows]) HIP_TRY(hipMemcpyAsync(c->stage[1], q_val, q_off[q_rows], hipMemcpyHostToDevice, st));
-    if (c_rows) {
-        HIP_TRY(hipMemcpyAsync(c->stage[2], c_off, (c_rows + 1) * 4, hipMemcpyHostToDevice, st));
-        if (c_off[c_rows]) HIP_TRY(hipMemcpyAsync(c->stage[3], c_val, c_off[c_rows], hipMemcpyHostToDevice, st));
-    }
-    uint32_t *const d_index = static_cast<uint32_t *>(c->stage[4]);
-    uint32_t *const d_dist = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(c->stage[4]) + ((ob * 4 + 255) & ~(size_t)255));
-    rc = strsim_nearest_device(c, measure, (const uint32_t *)c->stage[0], (const uint8_t *)c->stage[1], q_rows,
-                               (const uint32_t *)c->stage[2], (const uint8_t *)c->stage[3], c_rows, k, max_distance, d_index, d_dist);
+    Staged s;
+    rc = ctx_stage(c, q_off, q_val, q_rows, c_off, c_val, c_rows, ob * 8 + 256, &s);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out_index, d_index, ob * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out_distance, d_dist, ob * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    uint32_t *const d_index = reinterpret_cast<uint32_t *>(s.out);
+    uint32_t *const d_dist = reinterpret_cast<uint32_t *>(s.out + up256(ob * 4));
+    rc = strsim_nearest_device(c, measure, s.a_off, s.a_val, q_rows, s.b_off, s.b_val, c_rows, k, max_distance, d_index, d_dist);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out_index, d_index, ob * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out_distance, d_dist, ob * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return STRSIM_OK;
 }
 

@@ -385,20 +385,34 @@ hipError_t launch_match_pack(const uint32_t *off, const uint8_t *val, uint32_t r
     return hipGetLastError();
 }
 
-template <int M, int K>
-static void launch_match_lane_t(const MatchLaneArgs &a)
+// f(std::integral_constant<int, K>) at the K = 1, 4 or 16 a call with k slots runs at
+template <class F>
+static void with_lane_k(uint32_t k, F f)
 {
-    hipLaunchKernelGGL((k_match_lane<M, K>), dim3(match_grid(a.nq), a.splits), dim3(MATCH_BLOCK), 0, a.stream, a.qwords, a.qmeta, a.nq,
-                       a.cwords, a.cmeta, a.nc, a.per, a.qtab, a.min_score, a.pscore, a.pidx);
+    const int K = match_lane_k(k);
+    if (K == 1) f(std::integral_constant<int, 1>{});
+    else if (K == 4) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 16>{});
 }
+
+// f(std::integral_constant<int, LIT>): which side of the call is a literal (0: neither, 1: A, 2: B)
+template <class F>
+static void with_literal(const LaunchArgs &a, F f)
+{
+    const int lit = a.rowsA == a.rowsB ? 0 : (a.rowsA == 1 ? 1 : 2);
+    if (lit == 1) f(std::integral_constant<int, 1>{});
+    else if (lit == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 0>{});
+}
+static dim3 lane_grid(const LaunchArgs &a) { return dim3((unsigned)((a.n + 255u) / 256u)); }
 
 template <int M>
 static void launch_match_lane_m(const MatchLaneArgs &a)
 {
-    const int K = match_lane_k(a.k);
-    if (K == 1) launch_match_lane_t<M, 1>(a);
-    else if (K == 4) launch_match_lane_t<M, 4>(a);
-    else launch_match_lane_t<M, 16>(a);
+    with_lane_k(a.k, [&](auto K) {
+        hipLaunchKernelGGL((k_match_lane<M, decltype(K)::value>), dim3(match_grid(a.nq), a.splits), dim3(MATCH_BLOCK), 0, a.stream, a.qwords,
+                           a.qmeta, a.nq, a.cwords, a.cmeta, a.nc, a.per, a.qtab, a.min_score, a.pscore, a.pidx);
+    });
 }
 
 hipError_t launch_match_lane(int measure, const MatchLaneArgs &a)
@@ -424,10 +438,9 @@ hipError_t launch_match_fold_cols(uint32_t k, const double *scores, const uint32
                                   double *fscore, uint32_t *fidx, hipStream_t stream)
 {
     if (nb == 0u) return hipSuccess;
-    const int K = match_lane_k(k);
-    if (K == 1) hipLaunchKernelGGL(k_match_fold_cols<1>, dim3(nb), dim3(MATCH_BLOCK), 0, stream, scores, qlist, nc, min_score, fscore, fidx);
-    else if (K == 4) hipLaunchKernelGGL(k_match_fold_cols<4>, dim3(nb), dim3(MATCH_BLOCK), 0, stream, scores, qlist, nc, min_score, fscore, fidx);
-    else hipLaunchKernelGGL(k_match_fold_cols<16>, dim3(nb), dim3(MATCH_BLOCK), 0, stream, scores, qlist, nc, min_score, fscore, fidx);
+    with_lane_k(k, [&](auto K) {
+        hipLaunchKernelGGL(k_match_fold_cols<decltype(K)::value>, dim3(nb), dim3(MATCH_BLOCK), 0, stream, scores, qlist, nc, min_score, fscore, fidx);
+    });
     return hipGetLastError();
 }
 
@@ -435,11 +448,10 @@ hipError_t launch_match_fold_rows(uint32_t k, const double *scores, const uint32
                                   double min_score, double *fscore, uint32_t *fidx, hipStream_t stream)
 {
     if (nb == 0u || nq == 0u) return hipSuccess;
-    const int K = match_lane_k(k);
-    const dim3 g(match_grid(nq)), b(MATCH_BLOCK);
-    if (K == 1) hipLaunchKernelGGL(k_match_fold_rows<1>, g, b, 0, stream, scores, clist, nb, qmeta, nq, min_score, fscore, fidx);
-    else if (K == 4) hipLaunchKernelGGL(k_match_fold_rows<4>, g, b, 0, stream, scores, clist, nb, qmeta, nq, min_score, fscore, fidx);
-    else hipLaunchKernelGGL(k_match_fold_rows<16>, g, b, 0, stream, scores, clist, nb, qmeta, nq, min_score, fscore, fidx);
+    with_lane_k(k, [&](auto K) {
+        hipLaunchKernelGGL(k_match_fold_rows<decltype(K)::value>, dim3(match_grid(nq)), dim3(MATCH_BLOCK), 0, stream, scores, clist, nb, qmeta, nq,
+                           min_score, fscore, fidx);
+    });
     return hipGetLastError();
 }
 
@@ -447,11 +459,10 @@ hipError_t launch_match_merge(uint32_t k, const double *pscore, const uint32_t *
                               double *out_score, hipStream_t stream)
 {
     if (nq == 0u) return hipSuccess;
-    const int K = match_lane_k(k);
-    const dim3 g(match_grid(nq)), b(MATCH_BLOCK);
-    if (K == 1) hipLaunchKernelGGL(k_match_merge<1>, g, b, 0, stream, pscore, pidx, nl, nq, k, out_index, out_score);
-    else if (K == 4) hipLaunchKernelGGL(k_match_merge<4>, g, b, 0, stream, pscore, pidx, nl, nq, k, out_index, out_score);
-    else hipLaunchKernelGGL(k_match_merge<16>, g, b, 0, stream, pscore, pidx, nl, nq, k, out_index, out_score);
+    with_lane_k(k, [&](auto K) {
+        hipLaunchKernelGGL(k_match_merge<decltype(K)::value>, dim3(match_grid(nq)), dim3(MATCH_BLOCK), 0, stream, pscore, pidx, nl, nq, k,
+                           out_index, out_score);
+    });
     return hipGetLastError();
 }
 
@@ -472,20 +483,13 @@ hipError_t launch_nearest_order(const NearestOrderArgs &a)
     return hipGetLastError();
 }
 
-template <bool TR, int K>
-static void launch_nearest_lane_t(const NearestLaneArgs &a)
-{
-    hipLaunchKernelGGL((k_nearest_lane<TR, K>), dim3(match_grid(a.nq), a.splits), dim3(MATCH_BLOCK), 0, a.stream, a.qwords, a.qmeta,
-                       a.qperm, a.qstart, a.nq, a.swords, a.smeta, a.sidx, a.cstart, a.max_distance, a.pscore, a.pidx);
-}
-
 template <bool TR>
 static void launch_nearest_lane_tr(const NearestLaneArgs &a)
 {
-    const int K = match_lane_k(a.k);
-    if (K == 1) launch_nearest_lane_t<TR, 1>(a);
-    else if (K == 4) launch_nearest_lane_t<TR, 4>(a);
-    else launch_nearest_lane_t<TR, 16>(a);
+    with_lane_k(a.k, [&](auto K) {
+        hipLaunchKernelGGL((k_nearest_lane<TR, decltype(K)::value>), dim3(match_grid(a.nq), a.splits), dim3(MATCH_BLOCK), 0, a.stream, a.qwords,
+                           a.qmeta, a.qperm, a.qstart, a.nq, a.swords, a.smeta, a.sidx, a.cstart, a.max_distance, a.pscore, a.pidx);
+    });
 }
 
 hipError_t launch_nearest_lane(int measure, const NearestLaneArgs &a)
@@ -511,14 +515,10 @@ hipError_t launch_nearest_finish(const double *score, const uint32_t *index, uin
 
 hipError_t launch_osa_lane(const LaunchArgs &a, uint32_t *worklist)
 {
-    const unsigned grid = (unsigned)((a.n + 255u) / 256u);
-    const int lit = a.rowsA == a.rowsB ? 0 : (a.rowsA == 1 ? 1 : 2);
-    if (lit == 1)
-        hipLaunchKernelGGL(k_osa_lane<1>, dim3(grid), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, a.out, worklist, a.status);
-    else if (lit == 2)
-        hipLaunchKernelGGL(k_osa_lane<2>, dim3(grid), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, a.out, worklist, a.status);
-    else
-        hipLaunchKernelGGL(k_osa_lane<0>, dim3(grid), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, a.out, worklist, a.status);
+    with_literal(a, [&](auto LIT) {
+        hipLaunchKernelGGL(k_osa_lane<decltype(LIT)::value>, lane_grid(a), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, a.out,
+                           worklist, a.status);
+    });
     return hipGetLastError();
 }
 
@@ -532,14 +532,10 @@ hipError_t launch_osa_wave(const LaunchArgs &a, const uint32_t *worklist, int gr
 template <bool TR>
 static void launch_dist_lane_tr(const LaunchArgs &a, uint32_t k, uint32_t *out, uint32_t *worklist)
 {
-    const unsigned grid = (unsigned)((a.n + 255u) / 256u);
-    const int lit = a.rowsA == a.rowsB ? 0 : (a.rowsA == 1 ? 1 : 2);
-    if (lit == 1)
-        hipLaunchKernelGGL((k_dist_lane<TR, 1>), dim3(grid), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, k, out, worklist, a.status);
-    else if (lit == 2)
-        hipLaunchKernelGGL((k_dist_lane<TR, 2>), dim3(grid), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, k, out, worklist, a.status);
-    else
-        hipLaunchKernelGGL((k_dist_lane<TR, 0>), dim3(grid), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, k, out, worklist, a.status);
+    with_literal(a, [&](auto LIT) {
+        hipLaunchKernelGGL((k_dist_lane<TR, decltype(LIT)::value>), lane_grid(a), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, k,
+                           out, worklist, a.status);
+    });
 }
 
 hipError_t launch_dist_lane(int measure, const LaunchArgs &a, uint32_t k, uint32_t *out, uint32_t *worklist)
@@ -563,14 +559,10 @@ hipError_t launch_dist_wave(int measure, const LaunchArgs &a, uint32_t k, uint32
 
 hipError_t launch_indel_lane(const LaunchArgs &a, uint32_t k, uint32_t *out32, uint32_t *worklist)
 {
-    const unsigned grid = (unsigned)((a.n + 255u) / 256u);
-    const int lit = a.rowsA == a.rowsB ? 0 : (a.rowsA == 1 ? 1 : 2);
-    if (lit == 1)
-        hipLaunchKernelGGL(k_indel_lane<1>, dim3(grid), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, k, a.out, out32, worklist, a.status);
-    else if (lit == 2)
-        hipLaunchKernelGGL(k_indel_lane<2>, dim3(grid), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, k, a.out, out32, worklist, a.status);
-    else
-        hipLaunchKernelGGL(k_indel_lane<0>, dim3(grid), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, k, a.out, out32, worklist, a.status);
+    with_literal(a, [&](auto LIT) {
+        hipLaunchKernelGGL(k_indel_lane<decltype(LIT)::value>, lane_grid(a), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, k, a.out,
+                           out32, worklist, a.status);
+    });
     return hipGetLastError();
 }
 
@@ -585,14 +577,10 @@ hipError_t launch_indel_wave(const LaunchArgs &a, uint32_t k, uint32_t *out32, c
 template <bool ALIGN>
 static void launch_partial_lane_al(const LaunchArgs &a, uint32_t *span, uint32_t *worklist)
 {
-    const unsigned grid = (unsigned)((a.n + 255u) / 256u);
-    const int lit = a.rowsA == a.rowsB ? 0 : (a.rowsA == 1 ? 1 : 2);
-    if (lit == 1)
-        hipLaunchKernelGGL((k_partial_lane<1, ALIGN>), dim3(grid), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, a.out, span, worklist, a.status);
-    else if (lit == 2)
-        hipLaunchKernelGGL((k_partial_lane<2, ALIGN>), dim3(grid), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, a.out, span, worklist, a.status);
-    else
-        hipLaunchKernelGGL((k_partial_lane<0, ALIGN>), dim3(grid), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, a.out, span, worklist, a.status);
+    with_literal(a, [&](auto LIT) {
+        hipLaunchKernelGGL((k_partial_lane<decltype(LIT)::value, ALIGN>), lane_grid(a), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n,
+                           a.out, span, worklist, a.status);
+    });
 }
 
 hipError_t launch_partial_lane(const LaunchArgs &a, uint32_t *span, uint32_t *worklist)

@@ -39,11 +39,33 @@ def similarity(measure, a, b, ctx=None):
     ao, av = pack_strings(A)
     bo, bv = pack_strings(B)
     out = ctx.pairs_host(measure, ao, av, bo, bv)
-    n = out.size
-    for v in (va, vb):
+    out[_null_mask(out.size, va, vb)] = np.nan
+    return out
+
+
+def _null_mask(n, *validities):
+    """Boolean array, True where a row of any input is null.  A validity of None has no nulls; one of a single row is a literal's."""
+    mask = np.zeros(n, dtype=bool)
+    for v in validities:
         if v is not None:
-            out = out.copy()
-            out[~(np.broadcast_to(v, (n,)) if v.size == 1 else v)] = np.nan
+            mask |= ~(np.broadcast_to(v, (n,)) if v.size == 1 else v)
+    return mask
+
+
+def _pack_candidates(candidates):
+    """The non-null candidates packed -> (offsets, values, pos: each packed candidate's position in `candidates`)."""
+    cand = list(candidates)
+    pos = np.flatnonzero(np.array([c is not None for c in cand], dtype=bool))
+    return (*pack_strings([cand[j] for j in pos]), pos)
+
+
+def _remap_candidates(idx, pos, query_valid):
+    """Indices into the packed candidates -> int64 positions in the caller's list, -1 in empty slots and for null queries."""
+    empty = idx == 0xFFFFFFFF
+    out = np.full(idx.shape, -1, dtype=np.int64)
+    out[~empty] = pos[idx[~empty].astype(np.int64)]
+    if query_valid is not None:
+        out[~query_valid] = -1
     return out
 
 
@@ -102,11 +124,7 @@ def partial_ratio_alignment(a, b, ctx=None):
     ao, av = pack_strings(A)
     bo, bv = pack_strings(B)
     score, span = ctx.partial_alignment_host(ao, av, bo, bv)
-    n = score.size
-    mask = np.zeros(n, dtype=bool)
-    for v in (va, vb):
-        if v is not None:
-            mask |= ~(np.broadcast_to(v, (n,)) if v.size == 1 else v)
+    mask = _null_mask(score.size, va, vb)
     score[mask] = np.nan
     return score, np.ma.MaskedArray(span, mask=np.repeat(mask[:, None], 4, axis=1))
 
@@ -130,12 +148,7 @@ def distance(measure, a, b, max_distance=None, ctx=None):
     ao, av = pack_strings(A)
     bo, bv = pack_strings(B)
     out = ctx.distance_host(measure, ao, av, bo, bv, max_distance)
-    n = out.size
-    mask = np.zeros(n, dtype=bool)
-    for v in (va, vb):
-        if v is not None:
-            mask |= ~(np.broadcast_to(v, (n,)) if v.size == 1 else v)
-    return np.ma.MaskedArray(out, mask=mask)
+    return np.ma.MaskedArray(out, mask=_null_mask(out.size, va, vb))
 
 
 def levenshtein_distance(a, b, max_distance=None, ctx=None):
@@ -161,17 +174,11 @@ def best_match(measure, queries, candidates, k=1, min_score=None, ctx=None):
         raise ValueError(f"no best match by measure {measure!r} (one of {MEASURES})")
     ctx = ctx or default_context()
     Q, vq = _as_column(queries)
-    cand = list(candidates)
-    keep = np.array([c is not None for c in cand], dtype=bool)
-    pos = np.flatnonzero(keep)
     qo, qv = pack_strings(Q)
-    co, cv = pack_strings([cand[j] for j in pos])
+    co, cv, pos = _pack_candidates(candidates)
     idx, score = ctx.best_match(measure, qo, qv, co, cv, k, min_score)
-    empty = idx == 0xFFFFFFFF
-    out = np.full(idx.shape, -1, dtype=np.int64)
-    out[~empty] = pos[idx[~empty].astype(np.int64)]
+    out = _remap_candidates(idx, pos, vq)
     if vq is not None:
-        out[~vq] = -1
         score[~vq] = np.nan
     return out, score
 
@@ -186,20 +193,11 @@ def nearest(measure, queries, candidates, k=1, max_distance=None, ctx=None):
         raise ValueError(f"no distance for measure {measure!r} (one of {DISTANCE_MEASURES})")
     ctx = ctx or default_context()
     Q, vq = _as_column(queries)
-    cand = list(candidates)
-    keep = np.array([c is not None for c in cand], dtype=bool)
-    pos = np.flatnonzero(keep)
     qo, qv = pack_strings(Q)
-    co, cv = pack_strings([cand[j] for j in pos])
+    co, cv, pos = _pack_candidates(candidates)
     idx, dist = ctx.nearest(measure, qo, qv, co, cv, k, max_distance)
-    empty = idx == 0xFFFFFFFF
-    out = np.full(idx.shape, -1, dtype=np.int64)
-    out[~empty] = pos[idx[~empty].astype(np.int64)]
-    d = np.where(empty, -1, dist.astype(np.int64))
-    if vq is not None:
-        out[~vq] = -1
-        d[~vq] = -1
-    return out, d
+    out = _remap_candidates(idx, pos, vq)
+    return out, np.where(out < 0, -1, dist.astype(np.int64))
 
 
 __all__ = ["best_match", "nearest", "Codec", "Context", "device_count", "pack_strings", "split_offsets", "similarity", "levenshtein", "jaro",

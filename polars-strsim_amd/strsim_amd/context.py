@@ -112,10 +112,8 @@ class Context:
         import torch
         ra, rb = a_offsets.numel() - 1, b_offsets.numel() - 1
         n = rb if ra == 1 else ra
-        for t in (a_offsets, b_offsets):
-            assert t.is_cuda and t.element_size() == 4 and t.is_contiguous()
-        for t in (a_values, b_values):
-            assert t.is_cuda and t.element_size() == 1 and t.is_contiguous()
+        _check_device_column(a_offsets, a_values)
+        _check_device_column(b_offsets, b_values)
         if out is None:
             out = torch.empty(n if (ra == rb or ra == 1 or rb == 1) else 0, dtype=torch.float64, device=a_offsets.device)
         check(lib().strsim_pairs_device(self._h, measure_id(measure),
@@ -176,10 +174,8 @@ class Context:
         import torch
         ra, rb = a_offsets.numel() - 1, b_offsets.numel() - 1
         n = rb if ra == 1 else ra
-        for t in (a_offsets, b_offsets):
-            assert t.is_cuda and t.element_size() == 4 and t.is_contiguous()
-        for t in (a_values, b_values):
-            assert t.is_cuda and t.element_size() == 1 and t.is_contiguous()
+        _check_device_column(a_offsets, a_values)
+        _check_device_column(b_offsets, b_values)
         if out is None:
             out = torch.empty(n if (ra == rb or ra == 1 or rb == 1) else 0, dtype=torch.int32, device=a_offsets.device)
         assert out.is_cuda and out.device == a_offsets.device and out.element_size() == 4 and out.is_contiguous() \
@@ -195,10 +191,8 @@ class Context:
         import torch
         ra, rb = a_offsets.numel() - 1, b_offsets.numel() - 1
         n = rb if ra == 1 else ra
-        for t in (a_offsets, b_offsets):
-            assert t.is_cuda and t.element_size() == 4 and t.is_contiguous()
-        for t in (a_values, b_values):
-            assert t.is_cuda and t.element_size() == 1 and t.is_contiguous()
+        _check_device_column(a_offsets, a_values)
+        _check_device_column(b_offsets, b_values)
         rows = n if (ra == rb or ra == 1 or rb == 1) else 0
         if score is None:
             score = torch.empty(rows, dtype=torch.float64, device=a_offsets.device)
@@ -213,38 +207,19 @@ class Context:
     # ---- host-resident (numpy) ---------------------------------------------------------------------
     def pairs_host(self, measure, a_offsets, a_values, b_offsets, b_values):
         """Synchronous: numpy uint32 offsets + uint8 values in, numpy f64 out."""
-        ao = np.ascontiguousarray(a_offsets, dtype=np.uint32)
-        bo = np.ascontiguousarray(b_offsets, dtype=np.uint32)
-        av = np.ascontiguousarray(a_values, dtype=np.uint8)
-        bv = np.ascontiguousarray(b_values, dtype=np.uint8)
-        if av.size == 0:
-            av = np.zeros(1, dtype=np.uint8)
-        if bv.size == 0:
-            bv = np.zeros(1, dtype=np.uint8)
-        ra, rb = ao.size - 1, bo.size - 1
-        n = rb if ra == 1 else ra
-        if ra != rb and ra != 1 and rb != 1:
-            n = 0
+        ao, av, ra = _host_column(a_offsets, a_values)
+        bo, bv, rb = _host_column(b_offsets, b_values)
+        n = _rows_out(ra, rb)
         out = np.empty(n, dtype=np.float64)
         check(lib().strsim_pairs_host(self._h, measure_id(measure), ao.ctypes.data, av.ctypes.data, ra,
                                       bo.ctypes.data, bv.ctypes.data, rb, out.ctypes.data, n))
         return out
 
-
     def distance_host(self, measure, a_offsets, a_values, b_offsets, b_values, max_distance=None):
         """Synchronous bounded edit distances (strsim_distance_host): numpy uint32 offsets + uint8 values in, numpy uint32 out."""
-        ao = np.ascontiguousarray(a_offsets, dtype=np.uint32)
-        bo = np.ascontiguousarray(b_offsets, dtype=np.uint32)
-        av = np.ascontiguousarray(a_values, dtype=np.uint8)
-        bv = np.ascontiguousarray(b_values, dtype=np.uint8)
-        if av.size == 0:
-            av = np.zeros(1, dtype=np.uint8)
-        if bv.size == 0:
-            bv = np.zeros(1, dtype=np.uint8)
-        ra, rb = ao.size - 1, bo.size - 1
-        n = rb if ra == 1 else ra
-        if ra != rb and ra != 1 and rb != 1:
-            n = 0
+        ao, av, ra = _host_column(a_offsets, a_values)
+        bo, bv, rb = _host_column(b_offsets, b_values)
+        n = _rows_out(ra, rb)
         out = np.empty(n, dtype=np.uint32)
         check(lib().strsim_distance_host(self._h, measure_id(measure), ao.ctypes.data, av.ctypes.data, ra,
                                          bo.ctypes.data, bv.ctypes.data, rb, _max_distance(max_distance), out.ctypes.data, n))
@@ -253,18 +228,9 @@ class Context:
     def partial_alignment_host(self, a_offsets, a_values, b_offsets, b_values):
         """Synchronous partial ratio with its alignment (strsim_partial_alignment_host): numpy uint32 offsets + uint8 values in ->
         (score f64 [n], span uint32 [n, 4]: a_start, a_end, b_start, b_end, half open, in characters)."""
-        ao = np.ascontiguousarray(a_offsets, dtype=np.uint32)
-        bo = np.ascontiguousarray(b_offsets, dtype=np.uint32)
-        av = np.ascontiguousarray(a_values, dtype=np.uint8)
-        bv = np.ascontiguousarray(b_values, dtype=np.uint8)
-        if av.size == 0:
-            av = np.zeros(1, dtype=np.uint8)
-        if bv.size == 0:
-            bv = np.zeros(1, dtype=np.uint8)
-        ra, rb = ao.size - 1, bo.size - 1
-        n = rb if ra == 1 else ra
-        if ra != rb and ra != 1 and rb != 1:
-            n = 0
+        ao, av, ra = _host_column(a_offsets, a_values)
+        bo, bv, rb = _host_column(b_offsets, b_values)
+        n = _rows_out(ra, rb)
         score = np.empty(n, dtype=np.float64)
         span = np.empty((n, 4), dtype=np.uint32)
         check(lib().strsim_partial_alignment_host(self._h, ao.ctypes.data, av.ctypes.data, ra, bo.ctypes.data, bv.ctypes.data, rb,
@@ -275,15 +241,8 @@ class Context:
         """Synchronous best match (strsim_best_match_host, ABI 1.7): numpy uint32 offsets + uint8 values of the queries and the
         candidates -> (index uint32 [rows, k], score f64 [rows, k]), each query's k best candidates by descending score, ties to the
         lower index; empty slots are (0xFFFFFFFF, NaN).  min_score=None reports every candidate."""
-        qo = np.ascontiguousarray(q_offsets, dtype=np.uint32)
-        co = np.ascontiguousarray(c_offsets, dtype=np.uint32)
-        qv = np.ascontiguousarray(q_values, dtype=np.uint8)
-        cv = np.ascontiguousarray(c_values, dtype=np.uint8)
-        if qv.size == 0:
-            qv = np.zeros(1, dtype=np.uint8)
-        if cv.size == 0:
-            cv = np.zeros(1, dtype=np.uint8)
-        nq, nc = qo.size - 1, co.size - 1
+        qo, qv, nq = _host_column(q_offsets, q_values)
+        co, cv, nc = _host_column(c_offsets, c_values)
         index = np.empty((nq, int(k)), dtype=np.uint32)
         score = np.empty((nq, int(k)), dtype=np.float64)
         ms = -np.inf if min_score is None else float(min_score)
@@ -296,15 +255,8 @@ class Context:
         (index uint32 [rows, k], distance uint32 [rows, k]), each query's k nearest candidates by edit distance ("levenshtein" or
         "osa"), ascending, ties to the lower index; only d <= max_distance is reported (None: no cutoff).  Empty slots are
         (0xFFFFFFFF, 0xFFFFFFFF)."""
-        qo = np.ascontiguousarray(q_offsets, dtype=np.uint32)
-        co = np.ascontiguousarray(c_offsets, dtype=np.uint32)
-        qv = np.ascontiguousarray(q_values, dtype=np.uint8)
-        cv = np.ascontiguousarray(c_values, dtype=np.uint8)
-        if qv.size == 0:
-            qv = np.zeros(1, dtype=np.uint8)
-        if cv.size == 0:
-            cv = np.zeros(1, dtype=np.uint8)
-        nq, nc = qo.size - 1, co.size - 1
+        qo, qv, nq = _host_column(q_offsets, q_values)
+        co, cv, nc = _host_column(c_offsets, c_values)
         index = np.empty((nq, int(k)), dtype=np.uint32)
         dist = np.empty((nq, int(k)), dtype=np.uint32)
         check(lib().strsim_nearest_host(self._h, measure_id(measure), qo.ctypes.data, qv.ctypes.data, nq,
@@ -417,6 +369,27 @@ class Codec:
         ctx = ctx or self.ctx
         check(lib().strsim_codec_patch(ctx._h, out.data_ptr(), int(row_base), exc_rows.data_ptr(), exc_vals.data_ptr(),
                                        int(count)))
+
+
+def _host_column(offsets, values):
+    """-> (contiguous uint32 offsets, contiguous uint8 values with one padding byte when empty, rows)"""
+    off = np.ascontiguousarray(offsets, dtype=np.uint32)
+    val = np.ascontiguousarray(values, dtype=np.uint8)
+    if val.size == 0:
+        val = np.zeros(1, dtype=np.uint8)
+    return off, val, off.size - 1
+
+
+def _rows_out(ra, rb):
+    """Rows an elementwise call produces; 0 for a shape the library is going to refuse (it reports the error)."""
+    if ra != rb and ra != 1 and rb != 1:
+        return 0
+    return rb if ra == 1 else ra
+
+
+def _check_device_column(offsets, values):
+    assert offsets.is_cuda and offsets.element_size() == 4 and offsets.is_contiguous()
+    assert values.is_cuda and values.element_size() == 1 and values.is_contiguous()
 
 
 def _max_distance(k):

@@ -33,6 +33,7 @@ int _strsim_test_pack_views(SeriesExport *series, uint64_t r0, uint64_t r1, uint
                             uint8_t *long_out, uint64_t long_cap, uint64_t *span_out, uint64_t *bytes_out);
 int _strsim_test_staging_lease(uint64_t budget_bytes, uint64_t need, uint64_t grow, unsigned hold_us, uint64_t *stats8);
 int _strsim_test_combine(SeriesExport *two_series, int measure, double *out, uint64_t *rows_out);
+int _strsim_test_export_struct(uint64_t n, int move_child, uint64_t *sum_out);
 }
 
 namespace {
@@ -335,6 +336,18 @@ void one_round(unsigned seed)
             CHECK(out[r] == want, "combined call, row %llu: %f / %f", (unsigned long long)r, out[r], want);
         }
         CHECK(two[0].release == nullptr && two[1].release == nullptr, "the inputs were not released");
+    }
+    // ---- (3d) the struct result (export_struct): released whole, and with one child moved out first and released after the struct
+    {
+        const uint64_t n = rng() % 200;
+        const int child = (int)(rng() % 5) + 1; // (a UInt32 child: row r holds r + child)
+        uint64_t sum = 0;
+        int rc = _strsim_test_export_struct(n, -1, nullptr);
+        CHECK(rc == 0, "struct export rc %d (%s)", rc, _polars_plugin_get_last_error_message());
+        rc = _strsim_test_export_struct(n, child == 5 ? 4 : child, &sum);
+        CHECK(rc == 0, "struct export with a moved child rc %d (%s)", rc, _polars_plugin_get_last_error_message());
+        const uint64_t c = (uint64_t)(child == 5 ? 4 : child);
+        CHECK(sum == n * (n - 1) / 2 + n * c, "the moved child's values after the struct's release: %llu", (unsigned long long)sum);
     }
     // ---- (4) the helper-thread budget of engine-parallel calls, borrowed and returned by several caller threads at once: what is
     //      lent out at any moment never exceeds half the CPUs (the grant of every call in flight, other threads' included)

@@ -5,7 +5,8 @@
 #   2. csrc/polars_plugin.cpp (test-hooks build: packers, validity builder, thread pool, input ownership) under ASan + UBSan and
 #      under TSan, driven by tests/cpu_harness/plugin_sanitize_driver.cpp: several caller threads, each call fanning out over the
 #      packing pool
-#   3. the Python-driven packer tests (tests/test_plugin_packing_cpu.py) and the ABI ownership test against the ASan build
+#   3. the Python-driven packer tests (tests/test_plugin_packing_cpu.py) and the result-export test
+#      (tests/test_plugin_results_cpu.py) against the ASan build
 # Logs: <out-dir>/sanitize_*.txt (default profiles/; committed as profiles/r6_sanitize_*.txt).  Exit code 0 = every run clean.
 set -u
 ROOT=$(cd "$(dirname "$0")/.." && pwd); cd "$ROOT"
@@ -41,5 +42,10 @@ done
 ( export STRSIM_TESTHOOKS_LIB=$B/libhooks_asan_ubsan.so LD_PRELOAD=$RT/libclang_rt.asan-x86_64.so ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1
   python -m pytest tests/test_plugin_packing_cpu.py -x -q ) > "$OUT/sanitize_plugin_pytest_asan_ubsan.txt" 2>&1 || FAIL=1
 tail -2 "$OUT/sanitize_plugin_pytest_asan_ubsan.txt"
+# ... and the result export of every plugin family (tests/test_plugin_results_cpu.py): the binding loads the ASan build in place of
+# the product library (it holds the whole plugin layer and forwards the kernel ABI)
+( export STRSIM_AMD_LIB=$B/libhooks_asan_ubsan.so LD_PRELOAD=$RT/libclang_rt.asan-x86_64.so ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1
+  python -m pytest tests/test_plugin_results_cpu.py -x -q ) > "$OUT/sanitize_plugin_results_asan_ubsan.txt" 2>&1 || FAIL=1
+tail -2 "$OUT/sanitize_plugin_results_asan_ubsan.txt"
 [ $FAIL = 0 ] && echo "sanitizers: all clean" || echo "sanitizers: FAILURES (see $OUT/sanitize_*.txt)"
 exit $FAIL
