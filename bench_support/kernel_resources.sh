@@ -4,8 +4,11 @@
 # groups: nearest -- the kernels of strsim_nearest_device (its own and the best-match kernels it reuses)
 #         partial -- the kernels of the partial ratio (strsim_partial.h), and below them the OSA / distance / Indel kernels whose
 #                    headers it includes (their figures must not move when strsim_partial.h changes)
+#         token   -- the kernels of the token ratios (strsim_token.h), and below them the OSA / distance / Indel / partial kernels
+#                    whose headers it includes (their figures must not move when strsim_token.h changes)
 ROOT=$(cd "$(dirname "$0")/.." && pwd); OUT=${TMPDIR:-/tmp}/strsim_co; mkdir -p $OUT
 case "$1" in
+    token) FILTER='k_token_|k_partial_|k_indel_|k_osa_|k_dist_' ;;
     partial) FILTER='k_partial_|k_indel_|k_osa_|k_dist_' ;;
     nearest) FILTER='k_nearest_|k_match_pack|k_match_clear|k_match_fold|k_match_merge' ;;
     *) FILTER=${1:-.} ;;

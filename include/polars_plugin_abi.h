@@ -120,6 +120,11 @@ POLARS_PLUGIN_DECLARE(indel_distance)
  * call bypasses the small-call combiner. */
 POLARS_PLUGIN_DECLARE(partial_ratio)
 POLARS_PLUGIN_DECLARE(partial_ratio_alignment)
+/* Not in the reference: token_sort_ratio and token_set_ratio (STRSIM_TOKEN_SORT_RATIO, STRSIM_TOKEN_SET_RATIO of strsim_amd.h:
+ * rapidfuzz's fuzz.token_sort_ratio / 100 and fuzz.token_set_ratio / 100, tokens split at Python's str.isspace set), Float64 named
+ * after input 0, through the same pipeline as the similarities above.  Shape rule, literal broadcast and nulls as above; no kwargs. */
+POLARS_PLUGIN_DECLARE(token_sort_ratio)
+POLARS_PLUGIN_DECLARE(token_set_ratio)
 
 /* Best match (not in the reference): input 0 = the query column (N rows), input 1 = the candidate column (any number of rows; the
  * length rule of the functions above does not apply).  Output: N rows of an Arrow struct {index: UInt32, score: Float64} named after

@@ -54,7 +54,7 @@ typedef enum strsim_measure {
                                  else 1.0 - d / (|a| + |b|) over Unicode scalar values (these two f64 operations, not 2 l / (|a| + |b|)).
                                  Pairwise entry points and strsim_distance_*; not a measure of the reference.  8, not 7: ids 5 and 7
                                  stay unassigned, callers were told (and tests hold) that every entry point refuses them */
-    STRSIM_PARTIAL_RATIO = 10 /* partial ratio, rapidfuzz's fuzz.partial_ratio / 100: the best STRSIM_INDEL score of the shorter string
+    STRSIM_PARTIAL_RATIO = 10,/* partial ratio, rapidfuzz's fuzz.partial_ratio / 100: the best STRSIM_INDEL score of the shorter string
                                  (the needle, m scalar values) against a window of the longer one (n values) -- its proper prefixes
                                  of 1 .. m-1 values, every substring of m values, its proper suffixes of m-1 .. 1 values (n + m - 1
                                  windows; for n > m the whole longer string is NOT one of them, so the result can be below
@@ -62,6 +62,19 @@ typedef enum strsim_measure {
                                  It is the maximum at every needle length (rapidfuzz's heuristic for needles of more than 64
                                  characters is not followed).  Pairwise entry points and strsim_partial_alignment_*; 10, not 9: ids
                                  5, 7 and 9 stay unassigned and refused */
+    STRSIM_TOKEN_SORT_RATIO = 14, /* rapidfuzz's fuzz.token_sort_ratio / 100: STRSIM_INDEL of join(sorted(tokens(a))) and
+                                 join(sorted(tokens(b))), bit for bit.  Whitespace is Python's str.isspace set (29 code points: U+0009-000D,
+                                 001C-001F, 0020, 0085, 00A0, 1680, 2000-200A, 2028, 2029, 202F, 205F, 3000); tokens are the maximal runs
+                                 of other scalar values (a NUL is a token character); token order is lexicographic by scalar value, a
+                                 proper prefix first (= bytewise order of the UTF-8); join puts one U+0020 between tokens; duplicates
+                                 are kept.  Two tokenless strings: 1.0; exactly one: 0.0.  Pairwise entry points only */
+    STRSIM_TOKEN_SET_RATIO = 16   /* rapidfuzz's fuzz.token_set_ratio / 100 over the SETS A, B of tokens (tokenised as above): 0.0 when A
+                                 or B is empty; 1.0 when A & B is not empty and A - B or B - A is; else, with sect, ab, ba the joined
+                                 sorted A & B, A - B, B - A of sl, la, lb scalar values, sep = (sl > 0), sab = sl + sep + la,
+                                 sba = sl + sep + lb, d = indel_distance(ab, ba) and E(d, s) = 1.0 when s == 0 else 1.0 - d / s:
+                                 r0 = E(d, sab + sba) when sl == 0, else max(r0, E(sep + la, sl + sab), E(sep + lb, sl + sba)) -- the
+                                 maximum of STRSIM_INDEL over the pairs of sect, sect + " " + ab, sect + " " + ba.  Pairwise entry
+                                 points only.  14 and 16: ids 5, 7, 9, 11 and 12 stay unassigned and refused */
 } strsim_measure_t;
 
 /* Entry points of strsim_measure_supported(). */
@@ -134,6 +147,17 @@ STRSIM_API void *strsim_ctx_stream(strsim_ctx_t *ctx);
  * bytes are one pair per lane (strsim_ctx_last_wave_rows is 0 for a column of such rows), every other row one pair per wave (any
  * UTF-8, any length; tables beyond 16 KB use a scratch buffer the context grows; needles of more than 64 scalar values cost
  * O(n m ceil(m / 64)) word steps a pair).  Its kernels read only the bytes the offsets describe.
+ *
+ * STRSIM_TOKEN_SORT_RATIO, STRSIM_TOKEN_SET_RATIO: the columns are first rewritten on the device into scratch the context grows with
+ * the call -- the sort form normalises each column (a literal stays one row), the set form writes the two difference columns at
+ * full length (about one copy of each input column's bytes, 4 bytes of offsets and 4 of work list a row and side; the set form 20
+ * more a row) -- and STRSIM_INDEL's two kernels then run over them; every row is complete in stream order.  Such a call waits
+ * for the stream twice: once at its start for the columns' byte sizes and longest rows (they size the scratch; a failed
+ * reservation is STRSIM_ERR_OOM), once as STRSIM_OSA does.  Rows whose strings are ASCII with at most 64 bytes and 16 tokens are
+ * rewritten one string per lane, every other row one string per wave (any UTF-8, any length, any token count);
+ * strsim_ctx_last_token_wave_rows() counts the latter.  A token_sort_ratio call reports strsim_ctx_last_wave_rows as STRSIM_INDEL
+ * does; a token_set_ratio call is not a pending call of strsim_ctx_synchronize and leaves that counter alone.  The kernels read
+ * only the bytes the offsets describe.
  *
  * Reads beyond the strings: the kernels copy the values of a block of rows in whole 16-byte chunks, from the
  * 16-byte-aligned address at or below the block's first byte (a_values + a_offsets[first row]) up to the chunk that
@@ -295,6 +319,25 @@ STRSIM_API int strsim_partial_alignment_host(strsim_ctx_t *ctx,
                                              const uint32_t *a_offsets, const uint8_t *a_values, uint64_t a_rows,
                                              const uint32_t *b_offsets, const uint8_t *b_values, uint64_t b_rows,
                                              double *out_score, uint32_t *out_span, uint64_t out_rows);
+
+/*
+ * The token_sort transform itself (found by dlsym: the ABI version stays 1.7): row i of the output column is
+ * join(sorted(tokens(row i))) as STRSIM_TOKEN_SORT_RATIO defines it, so that
+ * strsim_pairs_device(STRSIM_INDEL) over two transformed columns is strsim_pairs_device(STRSIM_TOKEN_SORT_RATIO) over the
+ * originals, bit for bit -- normalise once, compare many times; strsim_best_match_* and strsim_nearest_* over transformed columns
+ * search without regard to token order.  out_offsets holds rows + 1 words and starts at 0; out_values holds out_capacity bytes.
+ * A normalised string is never longer than its input, so the column's byte size (offsets[rows] - offsets[0]) always suffices;
+ * a smaller capacity is STRSIM_ERR_ARG (the device variant learns the size from the device: it waits once for the stream at its
+ * start, and makes no other wait).  The output is complete in stream order.  Zero rows: out_offsets[0] = 0.  The arguments are
+ * checked first and the context last.  The host variant stages the column and is synchronous.
+ * strsim_ctx_last_token_wave_rows: the rows the last token call of the context (these two, or a pairwise call of measure 14 or 16)
+ * rewrote one string per wave, both columns added up; valid once the stream has completed that call.
+ */
+STRSIM_API int strsim_token_sort_device(strsim_ctx_t *ctx, const uint32_t *offsets, const uint8_t *values, uint64_t rows,
+                                        uint32_t *out_offsets, uint8_t *out_values, uint64_t out_capacity);
+STRSIM_API int strsim_token_sort_host(strsim_ctx_t *ctx, const uint32_t *offsets, const uint8_t *values, uint64_t rows,
+                                      uint32_t *out_offsets, uint8_t *out_values, uint64_t out_capacity);
+STRSIM_API uint64_t strsim_ctx_last_token_wave_rows(strsim_ctx_t *ctx);
 
 /*
  * Nearest match by bounded edit distance (found by dlsym, like the distance calls: the ABI version stays 1.7, and

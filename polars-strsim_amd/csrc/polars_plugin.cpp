@@ -529,6 +529,8 @@ POLARS_PLUGIN_DEFINE(sorensen_dice, STRSIM_SORENSEN_DICE)
 POLARS_PLUGIN_DEFINE(osa, STRSIM_OSA)
 POLARS_PLUGIN_DEFINE(indel, STRSIM_INDEL)
 POLARS_PLUGIN_DEFINE(partial_ratio, STRSIM_PARTIAL_RATIO)
+POLARS_PLUGIN_DEFINE(token_sort_ratio, STRSIM_TOKEN_SORT_RATIO)
+POLARS_PLUGIN_DEFINE(token_set_ratio, STRSIM_TOKEN_SET_RATIO)
 POLARS_PLUGIN_EXPORT(partial_ratio_alignment, run_partial_alignment(inputs, n_inputs, return_value), STRUCT_FIELD(PARTIAL_STRUCT))
 POLARS_PLUGIN_DEFINE_DISTANCE(levenshtein, STRSIM_LEVENSHTEIN)
 POLARS_PLUGIN_DEFINE_DISTANCE(osa, STRSIM_OSA)

@@ -22,6 +22,7 @@
 #include "strsim_distance.h"
 #include "strsim_indel.h"
 #include "strsim_partial.h"
+#include "strsim_token.h"
 #include "strsim_nearest.h"
 
 namespace strsim {
@@ -169,6 +170,15 @@ struct strsim_ctx {
     // its ring slot's)
     DevStatus *dist_status = nullptr;
     DevStatus *dist_status_host = nullptr;
+
+    // ---- token transforms (token_bounds, token_sort_column, token_set_columns; strsim_token.h) ----
+    DevBuf tok_off[2], tok_val[2];   // the normalised columns (sort form: of a and b; set form: ab and ba)
+    DevBuf tok_list[2];              // work lists of the wave kernels (one word per row)
+    DevBuf tok_desc;                 // their token descriptors beyond LDS
+    DevBuf tok_sums;                 // block sums of the offset scan
+    DevBuf tok_rec;                  // set form: one record a row, then the uint32 distances
+    TokenStatus *tok_status = nullptr;      // device
+    TokenStatus *tok_status_host = nullptr; // pinned: bounds before the transform, the work-list counts behind it
 };
 
 static int ctx_set_device(strsim_ctx *c) { HIP_TRY(hipSetDevice(c->device)); return STRSIM_OK; }
@@ -449,6 +459,8 @@ void strsim_ctx_destroy(strsim_ctx_t *c)
     if (c->match_counts_host) (void)hipHostFree(c->match_counts_host);
     if (c->dist_status) (void)hipFree(c->dist_status);
     if (c->dist_status_host) (void)hipHostFree(c->dist_status_host);
+    if (c->tok_status) (void)hipFree(c->tok_status);
+    if (c->tok_status_host) (void)hipHostFree(c->tok_status_host);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -698,6 +710,162 @@ static int pairs_osa(strsim_ctx *c, int slot, int measure, const uint32_t *a_off
     return STRSIM_OK;
 }
 
+// ---- token transforms (strsim_token.h): token_sort_ratio, token_set_ratio, strsim_token_sort_* ----
+//
+// A call first reads the bounds of its columns (k_token_bounds: longest row, first and last offset) and waits for them: they size
+// the scratch columns (a normalised string is never longer than its input) and the descriptor slots of the wave kernels.  That is
+// the one host wait a token call makes beyond two_pass's; everything behind it is enqueued without another.  The work-list counts
+// are copied to the pinned block behind the transform: strsim_ctx_last_token_wave_rows reads them once the stream has got there.
+
+static constexpr size_t TOKEN_PAD = 64; // bytes behind a scratch value column
+static int dist_prepare(strsim_ctx *c, uint64_t n);
+
+static int token_prepare(strsim_ctx *c)
+{
+    int rc = ctx_set_device(c);
+    if (rc) return rc;
+    if (!c->tok_status) HIP_TRY(hipMalloc((void **)&c->tok_status, sizeof(TokenStatus)));
+    if (!c->tok_status_host) HIP_TRY(hipHostMalloc((void **)&c->tok_status_host, sizeof(TokenStatus), hipHostMallocDefault));
+    return STRSIM_OK;
+}
+
+// The bounds of one or two columns into c->tok_status_host (b_off == nullptr: one column); waits for the stream.
+static int token_bounds(strsim_ctx *c, const uint32_t *a_off, uint64_t a_rows, const uint32_t *b_off, uint64_t b_rows)
+{
+    HIP_TRY(hipMemsetAsync(c->tok_status, 0, sizeof(TokenStatus), c->stream));
+    HIP_TRY(launch_token_bounds(a_off, a_rows, c->tok_status, 0, c->stream));
+    if (b_off) HIP_TRY(launch_token_bounds(b_off, b_rows, c->tok_status, 1, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->tok_status_host, c->tok_status, sizeof(TokenStatus), hipMemcpyDeviceToHost, c->stream));
+    c->enqueued_ops += b_off ? 4u : 3u;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return STRSIM_OK;
+}
+
+// The grid of a wave kernel and its descriptor scratch for rows that hold up to max_tokens tokens.
+static int token_wave_scratch(strsim_ctx *c, uint64_t max_tokens, int *grid, uint32_t **scratch, uint64_t *slot_words)
+{
+    *grid = c->num_cu * 8;
+    *scratch = nullptr;
+    *slot_words = 0;
+    if (max_tokens <= TOKEN_WAVE_LDS_TOKENS) return STRSIM_OK;
+    *slot_words = 2u * max_tokens + 2u;
+    const size_t per = (size_t)*slot_words * sizeof(uint32_t);
+    if ((size_t)*grid * per > OSA_SCRATCH_BUDGET) *grid = (int)std::max<size_t>(1, OSA_SCRATCH_BUDGET / per);
+    int rc = c->tok_desc.reserve((size_t)*grid * per);
+    if (rc) return rc;
+    *scratch = c->tok_desc.as<uint32_t>();
+    return STRSIM_OK;
+}
+
+static int token_copy_counts(strsim_ctx *c)
+{
+    HIP_TRY(hipMemcpyAsync(c->tok_status_host->wave_rows, c->tok_status->wave_rows, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    c->enqueued_ops += 1u;
+    return STRSIM_OK;
+}
+
+// The sort form of one column into (out_off, out_val): out_off holds rows + 1 words, out_val the column's byte size.  max_len: the
+// column's longest row (token_bounds).  side: which work list and counter (zeroed by token_bounds) the column uses.
+static int token_sort_column(strsim_ctx *c, int side, const uint32_t *off, const uint8_t *val, uint64_t rows, uint32_t max_len,
+                             uint32_t *out_off, uint8_t *out_val)
+{
+    int rc = c->tok_list[side].reserve(rows * sizeof(uint32_t));
+    if (rc) return rc;
+    rc = c->tok_sums.reserve(((rows + 4095u) / 4096u) * sizeof(uint32_t));
+    if (rc) return rc;
+    int grid;
+    uint32_t *scratch;
+    uint64_t slot_words;
+    rc = token_wave_scratch(c, token_max_tokens(max_len), &grid, &scratch, &slot_words);
+    if (rc) return rc;
+    uint32_t *const list = c->tok_list[side].as<uint32_t>(), *const count = &c->tok_status->wave_rows[side];
+    hipError_t e = launch_token_sort(false, off, val, rows, out_off, out_val, list, count, grid, scratch, slot_words, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "kernel launch (k_token_sort_lane / _wave, measuring)");
+    e = launch_token_scan(out_off, rows, c->tok_sums.as<uint32_t>(), c->stream);
+    if (e != hipSuccess) return hip_fail(e, "kernel launch (k_token_scan)");
+    e = launch_token_sort(true, off, val, rows, out_off, out_val, list, count, grid, scratch, slot_words, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "kernel launch (k_token_sort_lane / _wave, writing)");
+    c->enqueued_ops += 7u;
+    return STRSIM_OK;
+}
+
+// A pairwise call of a token measure.  Sort form: both columns normalised into scratch (a literal stays one row), then the Indel
+// flow into the caller's out, in this call's ring slot.  Set form: ab and ba into scratch at full length, the Indel flow with the
+// unbounded integer distance, then the epilogue; it takes no ring slot (nothing is left to do at retirement).
+static int pairs_token(strsim_ctx *c, int slot, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
+                       const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t n)
+{
+    int rc = token_prepare(c);
+    if (rc) return rc;
+    rc = token_bounds(c, a_off, a_rows, b_off, b_rows);
+    if (rc) return rc;
+    const TokenStatus st = *c->tok_status_host;
+    const uint64_t bytes[2] = {(uint64_t)st.end[0] - st.begin[0], (uint64_t)st.end[1] - st.begin[1]};
+    const uint64_t rows[2] = {a_rows, b_rows};
+    if (measure == STRSIM_TOKEN_SORT_RATIO) {
+        const uint32_t *const in_off[2] = {a_off, b_off};
+        const uint8_t *const in_val[2] = {a_val, b_val};
+        for (int s = 0; s < 2; ++s) {
+            rc = c->tok_off[s].reserve((rows[s] + 1) * sizeof(uint32_t));
+            if (rc == STRSIM_OK) rc = c->tok_val[s].reserve(bytes[s] + TOKEN_PAD);
+            if (rc == STRSIM_OK)
+                rc = token_sort_column(c, s, in_off[s], in_val[s], rows[s], st.max_len[s], c->tok_off[s].as<uint32_t>(), c->tok_val[s].as<uint8_t>());
+            if (rc) return rc;
+        }
+        rc = token_copy_counts(c);
+        if (rc) return rc;
+        return pairs_osa(c, slot, STRSIM_INDEL, c->tok_off[0].as<uint32_t>(), c->tok_val[0].as<uint8_t>(), a_rows, c->tok_off[1].as<uint32_t>(),
+                         c->tok_val[1].as<uint8_t>(), b_rows, out, n);
+    }
+    // set form: a difference is never longer than its string; a literal's is materialised for every row
+    const uint64_t cap[2] = {a_rows == 1 ? n * bytes[0] : bytes[0], b_rows == 1 ? n * bytes[1] : bytes[1]};
+    if (cap[0] > 0xFFFFFFFFull || cap[1] > 0xFFFFFFFFull) {
+        set_error("strsim_pairs_device: token_set_ratio with a literal of %llu bytes against %llu rows exceeds 32-bit offsets; split the column",
+                  (unsigned long long)(a_rows == 1 ? bytes[0] : bytes[1]), (unsigned long long)n);
+        return STRSIM_ERR_ARG;
+    }
+    for (int s = 0; s < 2; ++s) {
+        rc = c->tok_off[s].reserve((n + 1) * sizeof(uint32_t));
+        if (rc == STRSIM_OK) rc = c->tok_val[s].reserve(cap[s] + TOKEN_PAD);
+        if (rc) return rc;
+    }
+    const size_t d32_at = up256(n * sizeof(TokenSetRec));
+    rc = c->tok_rec.reserve(d32_at + n * sizeof(uint32_t));
+    if (rc == STRSIM_OK) rc = c->tok_list[0].reserve(n * sizeof(uint32_t));
+    if (rc == STRSIM_OK) rc = c->tok_sums.reserve(((n + 4095u) / 4096u) * sizeof(uint32_t));
+    if (rc) return rc;
+    int grid;
+    uint32_t *scratch;
+    uint64_t slot_words;
+    rc = token_wave_scratch(c, token_max_tokens(st.max_len[0]) + token_max_tokens(st.max_len[1]), &grid, &scratch, &slot_words);
+    if (rc) return rc;
+    uint32_t *const off_ab = c->tok_off[0].as<uint32_t>(), *const off_ba = c->tok_off[1].as<uint32_t>();
+    uint8_t *const val_ab = c->tok_val[0].as<uint8_t>(), *const val_ba = c->tok_val[1].as<uint8_t>();
+    TokenSetRec *const rec = c->tok_rec.as<TokenSetRec>();
+    uint32_t *const d32 = reinterpret_cast<uint32_t *>(c->tok_rec.as<uint8_t>() + d32_at);
+    uint32_t *const list = c->tok_list[0].as<uint32_t>(), *const count = &c->tok_status->wave_rows[0];
+    LaunchArgs in = two_pass_args(c, a_off, a_val, a_rows, b_off, b_val, b_rows, nullptr, n, nullptr);
+    hipError_t e = launch_token_set(false, in, off_ab, val_ab, off_ba, val_ba, rec, list, count, grid, scratch, slot_words);
+    if (e != hipSuccess) return hip_fail(e, "kernel launch (k_token_set_lane / _wave, measuring)");
+    e = launch_token_scan(off_ab, n, c->tok_sums.as<uint32_t>(), c->stream);
+    if (e == hipSuccess) e = launch_token_scan(off_ba, n, c->tok_sums.as<uint32_t>(), c->stream);
+    if (e != hipSuccess) return hip_fail(e, "kernel launch (k_token_scan)");
+    e = launch_token_set(true, in, off_ab, val_ab, off_ba, val_ba, rec, list, count, grid, scratch, slot_words);
+    if (e != hipSuccess) return hip_fail(e, "kernel launch (k_token_set_lane / _wave, writing)");
+    c->enqueued_ops += 10u;
+    rc = token_copy_counts(c);
+    if (rc) return rc;
+    rc = dist_prepare(c, n);
+    if (rc) return rc;
+    const LaunchArgs la = two_pass_args(c, off_ab, val_ab, n, off_ba, val_ba, n, nullptr, n, c->dist_status);
+    rc = two_pass(c, la, TwoPassCall{TP_INDEL, STRSIM_INDEL, DIST_UNBOUNDED, d32, nullptr}, -1);
+    if (rc) return rc;
+    e = launch_token_set_epilogue(rec, d32, out, n, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "kernel launch (k_token_set_epilogue)");
+    c->enqueued_ops += 1u;
+    return STRSIM_OK;
+}
+
 static int pairs_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
                              const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, double *const *outs,
                              uint64_t out_rows, bool eager = false)
@@ -732,6 +900,8 @@ static int pairs_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_off
         }
     }
     if (two_pass_measure(measure)) return pairs_osa(c, slot, measure, a_off, a_val, a_rows, b_off, b_val, b_rows, outs[0], n);
+    if (measure == STRSIM_TOKEN_SORT_RATIO || measure == STRSIM_TOKEN_SET_RATIO)
+        return pairs_token(c, slot, measure, a_off, a_val, a_rows, b_off, b_val, b_rows, outs[0], n);
     const uint64_t nchunks = (n + 63) >> 6;
     // One launch (the lane kernel alone, the rest at retirement if it turns out to be needed) when the caller has opted in and the
     // context's last retired call left nothing behind its lane kernel.  Such a call owns a mask buffer until it is retired (there
@@ -1303,6 +1473,86 @@ int strsim_partial_alignment_host(strsim_ctx_t *c, const uint32_t *a_off, const 
     HIP_TRY(hipMemcpyAsync(out_span, d_span, n * 16, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return STRSIM_OK;
+}
+
+} // extern "C"
+
+// ---- the token_sort transform itself (strsim_token.h) ----
+
+static int token_sort_check(const char *who, strsim_ctx_t *c, const uint32_t *off, const uint8_t *val, uint64_t rows, const uint32_t *out_off,
+                            const uint8_t *out_val)
+{
+    if (rows > 0xFFFFFFFFull) {
+        set_error("%s: %llu rows in one call; split the column (at most 2^32 - 1 rows per call)", who, (unsigned long long)rows);
+        return STRSIM_ERR_ARG;
+    }
+    if (!off || !out_off || (rows && (!val || !out_val))) { set_error("%s: NULL buffer", who); return STRSIM_ERR_ARG; }
+    if (!c) { set_error("%s: ctx is NULL", who); return STRSIM_ERR_ARG; }
+    return STRSIM_OK;
+}
+
+extern "C" {
+
+int strsim_token_sort_device(strsim_ctx_t *c, const uint32_t *off, const uint8_t *val, uint64_t rows, uint32_t *out_off, uint8_t *out_val,
+                             uint64_t out_capacity)
+{
+    int rc = token_sort_check("strsim_token_sort_device", c, off, val, rows, out_off, out_val);
+    if (rc) return rc;
+    rc = token_prepare(c);
+    if (rc) return rc;
+    if (rows == 0) {
+        HIP_TRY(hipMemsetAsync(out_off, 0, sizeof(uint32_t), c->stream));
+        return STRSIM_OK;
+    }
+    rc = token_bounds(c, off, rows, nullptr, 0);
+    if (rc) return rc;
+    const TokenStatus st = *c->tok_status_host;
+    const uint64_t bytes = (uint64_t)st.end[0] - st.begin[0];
+    if (out_capacity < bytes) {
+        set_error("strsim_token_sort_device: out_capacity=%llu but the column holds %llu bytes (its byte size always suffices)",
+                  (unsigned long long)out_capacity, (unsigned long long)bytes);
+        return STRSIM_ERR_ARG;
+    }
+    rc = token_sort_column(c, 0, off, val, rows, st.max_len[0], out_off, out_val);
+    if (rc) return rc;
+    return token_copy_counts(c);
+}
+
+int strsim_token_sort_host(strsim_ctx_t *c, const uint32_t *off, const uint8_t *val, uint64_t rows, uint32_t *out_off, uint8_t *out_val,
+                           uint64_t out_capacity)
+{
+    int rc = token_sort_check("strsim_token_sort_host", c, off, val, rows, out_off, out_val);
+    if (rc) return rc;
+    const uint64_t bytes = (uint64_t)off[rows] - off[0];
+    if (out_capacity < bytes) {
+        set_error("strsim_token_sort_host: out_capacity=%llu but the column holds %llu bytes (its byte size always suffices)",
+                  (unsigned long long)out_capacity, (unsigned long long)bytes);
+        return STRSIM_ERR_ARG;
+    }
+    if (rows == 0) { out_off[0] = 0u; return STRSIM_OK; }
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    // stage[0..1]: the column; stage[2]: the new offsets; stage[3]: the new values
+    Staged s;
+    rc = ctx_stage(c, off, val, rows, nullptr, nullptr, 0, 0, &s);
+    if (rc == STRSIM_OK) rc = c->stage[2].reserve((rows + 1) * sizeof(uint32_t));
+    if (rc == STRSIM_OK) rc = c->stage[3].reserve(bytes + TOKEN_PAD);
+    if (rc) return rc;
+    uint32_t *const d_off = c->stage[2].as<uint32_t>();
+    uint8_t *const d_val = c->stage[3].as<uint8_t>();
+    rc = strsim_token_sort_device(c, s.a_off, s.a_val, rows, d_off, d_val, bytes);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out_off, d_off, (rows + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (out_off[rows]) HIP_TRY(hipMemcpy(out_val, d_val, out_off[rows], hipMemcpyDeviceToHost));
+    return STRSIM_OK;
+}
+
+uint64_t strsim_ctx_last_token_wave_rows(strsim_ctx_t *c)
+{
+    if (!c || !c->tok_status_host) return 0;
+    const volatile uint32_t *w = c->tok_status_host->wave_rows;
+    return (uint64_t)w[0] + w[1];
 }
 
 } // extern "C"

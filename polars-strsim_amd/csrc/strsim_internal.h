@@ -17,7 +17,8 @@ inline bool measure_accepted(int measure, int entry_point)
 {
     const bool reference_five = measure >= 0 && measure < STRSIM_NUM_MEASURES;
     switch (entry_point) {
-    case STRSIM_ENTRY_PAIRWISE: return reference_five || measure == STRSIM_OSA || measure == STRSIM_INDEL || measure == STRSIM_PARTIAL_RATIO;
+    case STRSIM_ENTRY_PAIRWISE: return reference_five || measure == STRSIM_OSA || measure == STRSIM_INDEL || measure == STRSIM_PARTIAL_RATIO ||
+                                       measure == STRSIM_TOKEN_SORT_RATIO || measure == STRSIM_TOKEN_SET_RATIO;
     case STRSIM_ENTRY_BEST_MATCH: return reference_five;
     case STRSIM_ENTRY_CODEC: return reference_five;
     default: return false;

@@ -143,6 +143,24 @@ hipError_t launch_partial_lane(const LaunchArgs &a, uint32_t *span, uint32_t *wo
 hipError_t launch_partial_wave(const LaunchArgs &a, uint32_t *span, const uint32_t *worklist, int grid, uint32_t *scratch,
                                uint64_t slot_words);
 
+// Token transforms (strsim_token.h), measure ids 14 and 16.  launch_token_bounds leaves a column's longest row and its first and
+// last offset in st (side 0 or 1; max_len zeroed first).  A form is a measuring pass (write = false: the bytes of row i into
+// out_off[i + 1], out_off[0] = 0, the rows the lane kernel cannot take onto `list`, counted in *count, zeroed first), then
+// launch_token_scan over out_off (sums: ceil(rows / 4096) words), then the writing pass (write = true) with the same list.  Each
+// pass is the lane kernel over every row and the wave kernel over the list on `grid` waves with slot_words words of `scratch` each
+// (rows that can hold more than TOKEN_WAVE_LDS_TOKENS tokens; nullptr when there are none).
+struct TokenStatus;
+struct TokenSetRec;
+hipError_t launch_token_bounds(const uint32_t *off, uint64_t rows, TokenStatus *st, int side, hipStream_t stream);
+hipError_t launch_token_sort(bool write, const uint32_t *off, const uint8_t *val, uint64_t rows, uint32_t *out_off, uint8_t *out_val,
+                             uint32_t *list, uint32_t *count, int grid, uint32_t *scratch, uint64_t slot_words, hipStream_t stream);
+// the set form of a.n pairs (a.rowsA / a.rowsB == 1: a literal): ab into (off_ab, val_ab), ba into (off_ba, val_ba), one record a row
+hipError_t launch_token_set(bool write, const LaunchArgs &a, uint32_t *off_ab, uint8_t *val_ab, uint32_t *off_ba, uint8_t *val_ba,
+                            TokenSetRec *rec, uint32_t *list, uint32_t *count, int grid, uint32_t *scratch, uint64_t slot_words);
+hipError_t launch_token_scan(uint32_t *out_off, uint64_t rows, uint32_t *sums, hipStream_t stream);
+// out[i] = the rule of token_set_ratio over rec[i] and d32[i] = indel_distance(ab, ba)
+hipError_t launch_token_set_epilogue(const TokenSetRec *rec, const uint32_t *d32, double *out, uint64_t n, hipStream_t stream);
+
 // Nearest match by bounded edit distance (strsim_nearest_kernels.h), measure 0 (Levenshtein) or 6 (OSA).  The strings of both
 // sides are packed by launch_match_pack first; launch_nearest_order then puts them in length order on the device (histograms,
 // scan, scatter; the histograms must be zeroed), and launch_nearest_lane writes splits x nq x match_lane_k(k) partial lists in

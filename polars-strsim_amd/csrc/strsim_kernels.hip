@@ -30,6 +30,9 @@
 //   k_partial_lane / k_partial_wave  partial ratio and its alignment (measure 10, strsim_partial.h): the best window of the longer
 //                     string against the shorter one, match masks built once per pair; ASCII strings of up to 32 bytes per lane,
 //                     the rest one pair per wave; in stream order.
+//   k_token_sort_* / k_token_set_*  token_sort_ratio and token_set_ratio (measures 14 and 16, strsim_token.h): tokenise, sort and
+//                     join (or merge as sets) every string into scratch columns that k_indel_lane / k_indel_wave then align;
+//                     ASCII strings of up to 64 bytes and 16 tokens per lane, the rest one string per wave.
 //   k_nearest_lane<TR, K>  nearest match by bounded edit distance (strsim_nearest_kernels.h): one query per lane in length
 //                     order against wave-uniform candidates, a candidate length window and a running bound per lane.
 //   k_huge_pairs<M>   strings beyond WAVE_CAP, scratch in global memory, launched from strsim_ctx_synchronize() only
@@ -54,6 +57,7 @@
 #include "strsim_distance.h"
 #include "strsim_indel.h"
 #include "strsim_partial.h"
+#include "strsim_token.h"
 #include "strsim_nearest.h"
 
 namespace strsim {
@@ -598,6 +602,60 @@ hipError_t launch_partial_wave(const LaunchArgs &a, uint32_t *span, const uint32
     else
         hipLaunchKernelGGL(k_partial_wave<false>, dim3((unsigned)grid), dim3(64), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB,
                            a.rowsB, a.out, span, worklist, a.status, scratch, slot_words);
+    return hipGetLastError();
+}
+
+hipError_t launch_token_bounds(const uint32_t *off, uint64_t rows, TokenStatus *st, int side, hipStream_t stream)
+{
+    const uint64_t blocks = (rows + 255u) / 256u;
+    hipLaunchKernelGGL(k_token_bounds, dim3((unsigned)(blocks < 4096u ? blocks : 4096u)), dim3(256), 0, stream, off, rows, st, side);
+    return hipGetLastError();
+}
+
+hipError_t launch_token_sort(bool write, const uint32_t *off, const uint8_t *val, uint64_t rows, uint32_t *out_off, uint8_t *out_val,
+                             uint32_t *list, uint32_t *count, int grid, uint32_t *scratch, uint64_t slot_words, hipStream_t stream)
+{
+    const dim3 lane_grid((unsigned)((rows + 255u) / 256u));
+    if (write) {
+        hipLaunchKernelGGL(k_token_sort_lane<true>, lane_grid, dim3(256), 0, stream, off, val, rows, out_off, out_val, list, count);
+        hipLaunchKernelGGL(k_token_sort_wave<true>, dim3((unsigned)grid), dim3(64), 0, stream, off, val, out_off, out_val, list, count, scratch, slot_words);
+    } else {
+        hipLaunchKernelGGL(k_token_sort_lane<false>, lane_grid, dim3(256), 0, stream, off, val, rows, out_off, out_val, list, count);
+        hipLaunchKernelGGL(k_token_sort_wave<false>, dim3((unsigned)grid), dim3(64), 0, stream, off, val, out_off, out_val, list, count, scratch, slot_words);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_token_set(bool write, const LaunchArgs &a, uint32_t *off_ab, uint8_t *val_ab, uint32_t *off_ba, uint8_t *val_ba,
+                            TokenSetRec *rec, uint32_t *list, uint32_t *count, int grid, uint32_t *scratch, uint64_t slot_words)
+{
+    const dim3 lane_grid((unsigned)((a.n + 255u) / 256u));
+    if (write) {
+        hipLaunchKernelGGL(k_token_set_lane<true>, lane_grid, dim3(256), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB, a.rowsB, a.n,
+                           off_ab, val_ab, off_ba, val_ba, rec, list, count);
+        hipLaunchKernelGGL(k_token_set_wave<true>, dim3((unsigned)grid), dim3(64), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB, a.rowsB,
+                           off_ab, val_ab, off_ba, val_ba, rec, list, count, scratch, slot_words);
+    } else {
+        hipLaunchKernelGGL(k_token_set_lane<false>, lane_grid, dim3(256), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB, a.rowsB, a.n,
+                           off_ab, val_ab, off_ba, val_ba, rec, list, count);
+        hipLaunchKernelGGL(k_token_set_wave<false>, dim3((unsigned)grid), dim3(64), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB, a.rowsB,
+                           off_ab, val_ab, off_ba, val_ba, rec, list, count, scratch, slot_words);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_token_scan(uint32_t *out_off, uint64_t rows, uint32_t *sums, hipStream_t stream)
+{
+    const unsigned nb = (unsigned)((rows + TOKEN_SCAN_BLOCK - 1u) / TOKEN_SCAN_BLOCK);
+    hipLaunchKernelGGL(k_token_scan_sums, dim3(nb), dim3(256), 0, stream, out_off + 1, rows, sums);
+    hipLaunchKernelGGL(k_token_scan_top, dim3(1), dim3(256), 0, stream, sums, nb);
+    hipLaunchKernelGGL(k_token_scan_apply, dim3(nb), dim3(256), 0, stream, out_off + 1, rows, sums);
+    return hipGetLastError();
+}
+
+hipError_t launch_token_set_epilogue(const TokenSetRec *rec, const uint32_t *d32, double *out, uint64_t n, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_token_set_epilogue, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, stream, rec, d32, out, n);
     return hipGetLastError();
 }
 

@@ -126,6 +126,25 @@ def partial_ratio_alignment(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
     )
 
 
+def token_sort_ratio(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
+    """rapidfuzz `fuzz.token_sort_ratio` / 100: `indel` of the two strings with their tokens sorted.
+
+    Tokens are split at whitespace -- exactly Python's `str.isspace` set, 29 code points, as `str.split()` does -- sorted by code
+    point (a proper prefix first) and joined with one space; duplicates are kept.  `"smith john"` and `"john  smith"` score 1.0.
+    Two strings without tokens give 1.0, exactly one gives 0.0.  No lower-casing or other pre-processing.
+    Not in the upstream polars-strsim.
+    """
+    return _similarity("token_sort_ratio", expr, other)
+
+
+def token_set_ratio(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
+    """rapidfuzz `fuzz.token_set_ratio` / 100 over the sets of tokens (split at Python's `str.isspace` set, as
+    `token_sort_ratio`): 0.0 when either string has no token; 1.0 when the sets share a token and one contains the other; else
+    the best `indel` among the pairs of sect, sect + " " + ab and sect + " " + ba (the joined sorted intersection and the two
+    differences).  Not in the upstream polars-strsim."""
+    return _similarity("token_set_ratio", expr, other)
+
+
 def _distance(function_name: str, expr: IntoExpr, other: IntoExpr, max_distance: int | None) -> pl.Expr:
     args = [parse_into_expr(expr), other]
     if max_distance is not None:
@@ -170,6 +189,8 @@ __all__ = [
     "indel",
     "partial_ratio",
     "partial_ratio_alignment",
+    "token_sort_ratio",
+    "token_set_ratio",
     "levenshtein",
     "jaro",
     "jaro_winkler",

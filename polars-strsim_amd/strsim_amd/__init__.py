@@ -8,7 +8,7 @@ validity mask), as in README.md:69-70.
 """
 import numpy as np
 
-from ._lib import DISTANCE_MEASURES, DISTANCE_UNBOUNDED, ENTRY_POINT_ID, EXTRA_MEASURES, INDEL_MEASURES, MEASURES, MEASURE_ID, PARTIAL_MEASURES, LIB_PATH, STATUS, ShapeMismatch, StrsimError, lib
+from ._lib import DISTANCE_MEASURES, DISTANCE_UNBOUNDED, ENTRY_POINT_ID, EXTRA_MEASURES, INDEL_MEASURES, MEASURES, MEASURE_ID, PARTIAL_MEASURES, TOKEN_MEASURES, LIB_PATH, STATUS, ShapeMismatch, StrsimError, lib
 from .context import Codec, Context, device_count, pack_strings, split_offsets
 
 _default_ctx = None
@@ -129,6 +129,35 @@ def partial_ratio_alignment(a, b, ctx=None):
     return score, np.ma.MaskedArray(span, mask=np.repeat(mask[:, None], 4, axis=1))
 
 
+def token_sort_ratio(a, b, ctx=None):
+    """rapidfuzz's fuzz.token_sort_ratio / 100: indel() of the two strings with their tokens sorted, bit for bit.  Tokens are split
+    at whitespace -- exactly Python's str.isspace set, 29 code points -- as str.split() does, sorted as Python sorts str (by code
+    point, a proper prefix first) and joined with one space; duplicates are kept.  Two strings without tokens give 1.0, exactly
+    one gives 0.0.  No lower-casing and no other pre-processing."""
+    return similarity("token_sort_ratio", a, b, ctx)
+
+
+def token_set_ratio(a, b, ctx=None):
+    """rapidfuzz's fuzz.token_set_ratio / 100 over the SETS of tokens (split as for token_sort_ratio): 0.0 when either string has
+    no token, 1.0 when the sets share a token and one contains the other, else the best indel() among the pairs of
+    sect, sect + " " + ab and sect + " " + ba -- the joined sorted intersection and the two differences."""
+    return similarity("token_set_ratio", a, b, ctx)
+
+
+def token_sort(col, ctx=None):
+    """The normalisation of token_sort_ratio on its own: a list of str or None -> a list of str or None, each string
+    " ".join(sorted(s.split())) computed on the GPU.  indel(token_sort(a), token_sort(b)) is token_sort_ratio(a, b); best_match
+    and nearest over normalised columns search without regard to token order."""
+    ctx = ctx or default_context()
+    X, valid = _as_column(col)
+    off, val = ctx.token_sort_host(*pack_strings(X))
+    raw = val.tobytes()
+    out = [raw[int(off[i]):int(off[i + 1])].decode("utf-8") for i in range(len(X))]
+    if valid is not None:
+        out = [s if ok else None for s, ok in zip(out, valid)]
+    return out
+
+
 def measure_supported(measure, entry_point="pairwise"):
     """True if the library's `entry_point` ("pairwise", "best_match" or "codec") accepts `measure`; needs no device."""
     from ._lib import measure_id
@@ -170,7 +199,7 @@ def best_match(measure, queries, candidates, k=1, min_score=None, ctx=None):
     """For every query, its k best candidates by `measure`: (index int64 [N, k], score f64 [N, k]).  Slots in descending order
     of the score, ties to the lower candidate index; a candidate below min_score is not reported.  Empty slots -- and every slot
     of a null query -- are (-1, NaN).  Null candidates are never matched; indices refer to the caller's candidate positions."""
-    if measure in INDEL_MEASURES + PARTIAL_MEASURES:
+    if measure in INDEL_MEASURES + PARTIAL_MEASURES + TOKEN_MEASURES:
         raise ValueError(f"no best match by measure {measure!r} (one of {MEASURES})")
     ctx = ctx or default_context()
     Q, vq = _as_column(queries)
@@ -203,4 +232,5 @@ def nearest(measure, queries, candidates, k=1, max_distance=None, ctx=None):
 __all__ = ["best_match", "nearest", "Codec", "Context", "device_count", "pack_strings", "split_offsets", "similarity", "levenshtein", "jaro",
            "jaro_winkler", "jaccard", "sorensen_dice", "osa", "indel", "measure_supported", "distance", "levenshtein_distance", "osa_distance",
            "indel_distance", "INDEL_MEASURES", "partial_ratio", "partial_ratio_alignment", "PARTIAL_MEASURES",
+           "token_sort_ratio", "token_set_ratio", "token_sort", "TOKEN_MEASURES",
            "DISTANCE_MEASURES", "DISTANCE_UNBOUNDED", "MEASURES", "EXTRA_MEASURES", "MEASURE_ID", "STATUS", "ShapeMismatch", "StrsimError"]

@@ -25,6 +25,11 @@ MEASURE_ID["indel"] = 8
 # its own again: it has no distance, no best match, no nearest match and no codec.
 PARTIAL_MEASURES = ("partial_ratio",)
 MEASURE_ID["partial_ratio"] = 10
+# token_sort_ratio = STRSIM_TOKEN_SORT_RATIO = 14, token_set_ratio = STRSIM_TOKEN_SET_RATIO = 16 (11 .. 13 and 15 stay unassigned):
+# pairwise entry points only, plus strsim_token_sort_* for the transform itself.  No distance, best match, nearest match or codec.
+TOKEN_MEASURES = ("token_sort_ratio", "token_set_ratio")
+MEASURE_ID["token_sort_ratio"] = 14
+MEASURE_ID["token_set_ratio"] = 16
 ENTRY_POINT_ID = {"pairwise": 0, "best_match": 1, "codec": 2}  # strsim_entry_point_t
 # The measures strsim_distance_device / _host accept (integer edit distances), with their ids; STRSIM_DISTANCE_UNBOUNDED = no cutoff.
 DISTANCE_MEASURES = ("levenshtein", "osa")
@@ -112,6 +117,12 @@ def lib():
         f = getattr(L, name)
         f.restype = i32
         f.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, vp, u64]
+    for name in ("strsim_token_sort_device", "strsim_token_sort_host"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, vp, vp, u64, vp, vp, u64]
+    L.strsim_ctx_last_token_wave_rows.restype = u64
+    L.strsim_ctx_last_token_wave_rows.argtypes = [vp]
     for name in ("strsim_nearest_device", "strsim_nearest_host"):
         f = getattr(L, name)
         f.restype = i32

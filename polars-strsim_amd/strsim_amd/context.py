@@ -79,6 +79,13 @@ class Context:
         return int(lib().strsim_ctx_last_wave_rows(self._h))
 
     @property
+    def last_token_wave_rows(self):
+        """Rows the last token call (token_sort_*, or a pairwise call of token_sort_ratio / token_set_ratio) rewrote one string per
+        wave, both columns added up; 0 when every row took the one-string-per-lane tier.  Valid once the stream has completed
+        that call (synchronize())."""
+        return int(lib().strsim_ctx_last_token_wave_rows(self._h))
+
+    @property
     def last_late_rows(self):
         """Rows finished by a pass that the last synchronize() / retire_oldest() launched (slow rows of a one-launch call,
         long strings): written AFTER whatever was enqueued on the stream behind the call."""
@@ -204,7 +211,34 @@ class Context:
                                                     score.data_ptr(), span.data_ptr(), score.numel()))
         return score, span
 
+    def token_sort_device(self, offsets, values, out_offsets=None, out_values=None):
+        """The token_sort transform (strsim_token_sort_device) of a device column laid out as for pairs_device -> (offsets int32
+        [rows + 1], values uint8): row i becomes join(sorted(tokens(row i))).  out_values must hold the input's bytes (the
+        default: as many as `values`).  Complete in stream order; the call waits once for the stream at its start."""
+        import torch
+        rows = offsets.numel() - 1
+        _check_device_column(offsets, values)
+        if out_offsets is None:
+            out_offsets = torch.empty(rows + 1, dtype=torch.int32, device=offsets.device)
+        if out_values is None:
+            out_values = torch.empty(max(values.numel(), 1), dtype=torch.uint8, device=offsets.device)
+        _check_device_column(out_offsets, out_values)
+        assert out_offsets.numel() == rows + 1
+        check(lib().strsim_token_sort_device(self._h, offsets.data_ptr(), values.data_ptr(), rows, out_offsets.data_ptr(),
+                                             out_values.data_ptr(), out_values.numel()))
+        return out_offsets, out_values
+
     # ---- host-resident (numpy) ---------------------------------------------------------------------
+    def token_sort_host(self, offsets, values):
+        """Synchronous token_sort transform (strsim_token_sort_host): numpy uint32 offsets + uint8 values in -> (uint32 offsets
+        from 0, uint8 values of offsets[-1] bytes)."""
+        off, val, rows = _host_column(offsets, values)
+        out_off = np.empty(rows + 1, dtype=np.uint32)
+        cap = int(off[rows]) - int(off[0])
+        out_val = np.empty(max(cap, 1), dtype=np.uint8)
+        check(lib().strsim_token_sort_host(self._h, off.ctypes.data, val.ctypes.data, rows, out_off.ctypes.data, out_val.ctypes.data, cap))
+        return out_off, out_val[:int(out_off[rows])]
+
     def pairs_host(self, measure, a_offsets, a_values, b_offsets, b_values):
         """Synchronous: numpy uint32 offsets + uint8 values in, numpy f64 out."""
         ao, av, ra = _host_column(a_offsets, a_values)
