@@ -145,6 +145,16 @@ POLARS_PLUGIN_DECLARE(best_match_sorensen_dice)
 POLARS_PLUGIN_DECLARE(nearest_levenshtein)
 POLARS_PLUGIN_DECLARE(nearest_osa)
 
+/* Extract: the best candidate by ratio or token_sort_ratio with a score cutoff (not in the reference; rapidfuzz's
+ * process.extractOne with fuzz.ratio / 100 or fuzz.token_sort_ratio / 100): inputs 0 and 1 as best match (queries, candidates of
+ * any length), an optional input 2 is score_cutoff, one Float64 value (a null or absent input: no cutoff; NaN, more than one row or
+ * another dtype is an error that names score_cutoff).  Output: N rows of an Arrow struct {index: UInt32, score: Float64} named after
+ * input 0 -- the candidate with the highest score >= score_cutoff (ties to the lower index; the index is its row in input 1), as
+ * strsim_extract_host with k = 1.  Null where the query is null or no non-null candidate reaches score_cutoff; null candidates are
+ * never matched. */
+POLARS_PLUGIN_DECLARE(extract_ratio)
+POLARS_PLUGIN_DECLARE(extract_token_sort_ratio)
+
 /* ---- diagnostics of this implementation (not part of the polars-ffi contract; the engine never calls them) ----
  * The plugin's staging -- pinned host memory and its device mirrors, per pipeline set -- is leased per call from one process-wide
  * pool under POLARS_STRSIM_STAGING_BUDGET_MB (csrc/plugin_pack.h: StagingPool; reference counterpart: the per-call scratch of

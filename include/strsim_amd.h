@@ -374,6 +374,45 @@ STRSIM_API int strsim_nearest_host(strsim_ctx_t *ctx, int measure,
                                    const uint32_t *c_offsets, const uint8_t *c_values, uint64_t c_rows,
                                    uint32_t k, uint32_t max_distance, uint32_t *out_index, uint32_t *out_distance);
 
+/*
+ * Extract: top-k search by ratio or token_sort_ratio with a score cutoff -- rapidfuzz's process.extract / extractOne with
+ * fuzz.ratio / 100 or fuzz.token_sort_ratio / 100 as the scorer (found by dlsym, like the distance and nearest calls: the ABI
+ * version stays 1.7, and strsim_measure_supported does not describe these two entry points).  `scorer` is STRSIM_INDEL (8) or
+ * STRSIM_TOKEN_SORT_RATIO (14); any other id is STRSIM_ERR_ARG.  score(i, j) is bit for bit what
+ * strsim_pairs_device(scorer, queries[i], candidates[j]) returns; for scorer 14 that is indel(token_sort(q), token_sort(c)).
+ * Row-major outputs of q_rows x k (uint32 index, f64 score): query i gets the (up to) k candidates j with the highest
+ * score(i, j) >= score_cutoff, in descending order of score, ties to the lower candidate index -- one total order, so the result
+ * does not depend on the order in which candidates are visited.  Slots left empty hold index 0xFFFFFFFF and a NaN score, as best
+ * match's.  score_cutoff = -INFINITY or 0.0 reports everything, a cutoff above 1.0 nothing; NaN is STRSIM_ERR_ARG.
+ *
+ * 1 <= k <= STRSIM_EXTRACT_MAX_K, q_rows <= 2^32 - 1, c_rows <= 2^32 - 2; c_rows == 0 is allowed (every slot empty) and
+ * q_rows == 0 is a no-op.  A NULL buffer of a non-empty side or output, a bad scorer or k: STRSIM_ERR_ARG.  The arguments are
+ * checked first, the context last (a NULL ctx is STRSIM_ERR_ARG too): no argument error needs a device.  Nulls are not seen here:
+ * a caller drops null candidates and maps the indices back.
+ *
+ * Device-resident: the same column layout as strsim_pairs_device.  Strings of at most 32 ASCII bytes are searched one query per
+ * lane, in length order, visiting only candidate lengths whose best possible score 1 - ||q| - |c|| / (|q| + |c|) can still reach
+ * the cutoff or enter a full list; every pair with a longer or non-ASCII side goes through strsim_pairs_device(STRSIM_INDEL)
+ * (that string as the literal) and reads what it documents.  Scorer 14 first normalises both columns on the device with the
+ * token_sort transform into scratch of the context (no string goes to the host) and then searches those; it updates
+ * strsim_ctx_last_token_wave_rows like any token call.
+ * Waits for the stream: scorer 14 waits once for the bounds of its columns; every call waits once for a read-back of how many
+ * strings fall outside the one-query-per-lane class.  Without such strings it then returns with the search enqueued: results are
+ * complete after strsim_ctx_synchronize(), or in stream order.  With them it runs those pairs through strsim_pairs_device batch
+ * by batch, each of which waits for the stream.
+ */
+#define STRSIM_EXTRACT_MAX_K 16u
+STRSIM_API int strsim_extract_device(strsim_ctx_t *ctx, int scorer,
+                                     const uint32_t *q_offsets, const uint8_t *q_values, uint64_t q_rows,
+                                     const uint32_t *c_offsets, const uint8_t *c_values, uint64_t c_rows,
+                                     uint32_t k, double score_cutoff, uint32_t *out_index, double *out_score);
+
+/* The same with HOST-RESIDENT buffers (the column layout of strsim_pairs_host); synchronous. */
+STRSIM_API int strsim_extract_host(strsim_ctx_t *ctx, int scorer,
+                                   const uint32_t *q_offsets, const uint8_t *q_values, uint64_t q_rows,
+                                   const uint32_t *c_offsets, const uint8_t *c_values, uint64_t c_rows,
+                                   uint32_t k, double score_cutoff, uint32_t *out_index, double *out_score);
+
 /* Row partition used to shard a column over `n` GPUs/ranks: the reference's split_offsets
  * (strsim.rs:21-39).  Writes n (offset,len) pairs into out_offset_len[2*n]. */
 STRSIM_API void strsim_split_offsets(uint64_t len, uint64_t n, uint64_t *out_offset_len);

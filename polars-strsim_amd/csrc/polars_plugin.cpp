@@ -152,6 +152,7 @@ void export_primitive(const char *format, const char *name, uint64_t n, void *da
 #include "plugin_distance.h"
 #include "plugin_partial.h"
 #include "plugin_nearest.h"
+#include "plugin_extract.h"
 
 void run(int measure, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret, bool engine_parallel)
 {
@@ -257,6 +258,8 @@ void _polars_plugin_strsim_coalesce_stats(uint64_t out[4]) { if (out) combiner()
                          field_named_after_input0(input_fields, n_fields, return_value, [](ArrowSchema *s, const char *n) { fill_named_schema(s, "I", n); }))
 #define POLARS_PLUGIN_DEFINE_NEAREST(name, id) \
     POLARS_PLUGIN_EXPORT(nearest_##name, run_nearest(id, inputs, n_inputs, return_value), STRUCT_FIELD(NEAREST_STRUCT))
+#define POLARS_PLUGIN_DEFINE_EXTRACT(name, id) \
+    POLARS_PLUGIN_EXPORT(extract_##name, run_extract(id, inputs, n_inputs, return_value), STRUCT_FIELD(MATCH_STRUCT))
 #define POLARS_PLUGIN_DEFINE_MATCH(name, id) \
     POLARS_PLUGIN_EXPORT(best_match_##name, run_best_match(id, inputs, n_inputs, return_value), STRUCT_FIELD(MATCH_STRUCT))
 
@@ -537,6 +540,8 @@ POLARS_PLUGIN_DEFINE_DISTANCE(osa, STRSIM_OSA)
 POLARS_PLUGIN_DEFINE_DISTANCE(indel, STRSIM_INDEL)
 POLARS_PLUGIN_DEFINE_NEAREST(levenshtein, STRSIM_LEVENSHTEIN)
 POLARS_PLUGIN_DEFINE_NEAREST(osa, STRSIM_OSA)
+POLARS_PLUGIN_DEFINE_EXTRACT(ratio, STRSIM_INDEL)
+POLARS_PLUGIN_DEFINE_EXTRACT(token_sort_ratio, STRSIM_TOKEN_SORT_RATIO)
 POLARS_PLUGIN_DEFINE_MATCH(levenshtein, STRSIM_LEVENSHTEIN)
 POLARS_PLUGIN_DEFINE_MATCH(jaro, STRSIM_JARO)
 POLARS_PLUGIN_DEFINE_MATCH(jaro_winkler, STRSIM_JARO_WINKLER)

@@ -24,6 +24,7 @@
 #include "strsim_partial.h"
 #include "strsim_token.h"
 #include "strsim_nearest.h"
+#include "strsim_extract.h"
 
 namespace strsim {
 
@@ -162,6 +163,12 @@ struct strsim_ctx {
     DevBuf match_ws, match_scratch;
     DevBuf nearest_ws, nearest_scratch;
     uint32_t *match_counts_host = nullptr;
+    // strsim_extract_device: its workspace and fallback batches, the device copy of the rank table (extract_table) and, for
+    // STRSIM_TOKEN_SORT_RATIO, the normalised columns -- buffers of its own, so that the pairwise calls of the fallback (which
+    // may use any scratch of the pairwise flows) can neither reuse nor grow over them
+    DevBuf extract_ws, extract_scratch, extract_tab;
+    bool extract_tab_ready = false;
+    DevBuf extract_off[2], extract_val[2];
 
     // ---- two-pass measures (two_pass: pairs_osa, distance_device_impl, partial_device_impl) ----
     DevBuf osa_list;                 // the work list of the wave kernel (one word per row)
@@ -522,7 +529,8 @@ static int elementwise_check(const char *who, strsim_ctx *c, uint64_t a_rows, ui
     return STRSIM_OK;
 }
 
-// The checks of the two search families behind their measure test (best match: min_score may not be NaN; nearest passes 0).
+// The checks of the search families behind their measure test (best match: min_score may not be NaN; nearest passes 0; extract
+// tests its score_cutoff itself).
 static int search_check(const char *who, strsim_ctx *c, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows, const uint32_t *c_off,
                         const uint8_t *c_val, uint64_t c_rows, uint32_t k, uint32_t max_k, double min_score, const void *out_a, const void *out_b)
 {
@@ -1650,6 +1658,151 @@ int strsim_nearest_host(strsim_ctx_t *c, int measure, const uint32_t *q_off, con
     HIP_TRY(hipMemcpyAsync(out_distance, d_dist, ob * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return STRSIM_OK;
+}
+
+} // extern "C"
+
+// ---- extract: top-k by Indel similarity with a score cutoff (strsim_extract.h, strsim_extract_kernels.h) ----
+
+static int extract_check(const char *who, strsim_ctx_t *c, int scorer, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows,
+                         const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, uint32_t k, double score_cutoff,
+                         const void *out_index, const void *out_score)
+{
+    if (scorer != STRSIM_INDEL && scorer != STRSIM_TOKEN_SORT_RATIO) {
+        set_error("%s: scorer %d is not a scorer of extract (STRSIM_INDEL = 8 or STRSIM_TOKEN_SORT_RATIO = 14)", who, scorer);
+        return STRSIM_ERR_ARG;
+    }
+    if (score_cutoff != score_cutoff) { set_error("%s: score_cutoff is NaN", who); return STRSIM_ERR_ARG; }
+    return search_check(who, c, q_off, q_val, q_rows, c_off, c_val, c_rows, k, STRSIM_EXTRACT_MAX_K, score_cutoff, out_index, out_score);
+}
+
+// The rank table of strsim_extract.h, built once per process.
+static const ExtractTable &extract_table()
+{
+    static const ExtractTable *const t = [] {
+        ExtractTable *n = new ExtractTable;
+        extract_build_table(*n);
+        return n;
+    }();
+    return *t;
+}
+
+// The search over two columns of Indel scores (for STRSIM_TOKEN_SORT_RATIO: the normalised ones).
+static int extract_search(strsim_ctx *c, const uint32_t *q_off, const uint8_t *q_val, uint32_t nq, const uint32_t *c_off, const uint8_t *c_val,
+                          uint32_t nc, uint32_t k, double score_cutoff, uint32_t *out_index, double *out_score)
+{
+    const ExtractTable &tab = extract_table();
+    hipStream_t st = c->stream;
+    if (!c->extract_tab_ready) {
+        int rc = c->extract_tab.reserve(sizeof(ExtractTable));
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(c->extract_tab.p, &tab, sizeof(ExtractTable), hipMemcpyHostToDevice, st));
+        c->extract_tab_ready = true;
+    }
+    const uint32_t rlimit = extract_rank_limit(tab, score_cutoff); // 0: the cutoff is above 1.0 and nothing is reported
+    const uint32_t kp = (uint32_t)match_lane_k(k);
+    const uint32_t splits = nc ? match_splits(nq, nc, kp, c->num_cu) : 0u;
+    // the tail of the workspace: the small block (slow counts, histograms, bucket starts, cursors), the query permutation, the
+    // candidates in length order and (splits + 1) lists of kp per query (the last: the fallback)
+    const size_t lists = ((size_t)splits + 1) * nq * kp;
+    const size_t o_qp = 1024, o_sw = o_qp + up256((size_t)nq * 4), o_sm = o_sw + up256((size_t)nc * 32), o_si = o_sm + up256((size_t)nc * 4),
+                 o_ls = o_si + up256((size_t)nc * 4), o_li = o_ls + up256(lists * 8);
+    SearchPack p;
+    // (of the small block, the counts and histograms are zeroed)
+    int rc = search_pack(c, c->extract_ws, o_li + up256(lists * 4), 4 * 88, q_off, q_val, nq, c_off, c_val, nc, &p);
+    if (rc) return rc;
+    uint32_t *const small = (uint32_t *)p.tail, *const lidx = (uint32_t *)(p.tail + o_li);
+    double *const lscore = (double *)(p.tail + o_ls);
+    // fast x fast: length order on the device, then lists 0 .. splits - 1
+    uint32_t used = 0;
+    if (splits && rlimit && p.q_slow < nq && p.c_slow < nc) {
+        uint32_t *const qhist = small + 8, *const chist = qhist + 40, *const qstart = chist + 40, *const cstart = qstart + 40,
+                       *const qcur = cstart + 40, *const ccur = qcur + 40;
+        uint32_t *const qperm = (uint32_t *)(p.tail + o_qp), *const sw = (uint32_t *)(p.tail + o_sw), *const sm = (uint32_t *)(p.tail + o_sm),
+                       *const si = (uint32_t *)(p.tail + o_si);
+        NearestOrderArgs oa{p.qm, nq, p.cw, p.cm, nc, qhist, chist, qstart, cstart, qcur, ccur, qperm, sw, sm, si, st};
+        HIP_TRY(launch_nearest_order(oa));
+        ExtractLaneArgs a{p.qw, p.qm, qperm, qstart, nq, sw, sm, si, cstart, splits, k, c->extract_tab.as<ExtractTable>(), rlimit, lscore, lidx, st};
+        HIP_TRY(launch_extract_lane(a));
+        used = splits;
+    }
+    // every pair with a slow side: strsim_pairs_device(STRSIM_INDEL) with that side as the literal, batch by batch, folded into
+    // list `used` with score_cutoff as the least score
+    if (nc && rlimit && (p.q_slow || p.c_slow)) {
+        const uint64_t calls = fallback_calls(nq, nc);
+        rc = c->extract_scratch.reserve((size_t)(calls * std::max(nq, nc) * 8));
+        if (rc) return rc;
+        double *const scratch = c->extract_scratch.as<double>();
+        rc = search_fallback(
+            c, "strsim_extract_device", p, q_off, q_val, nq, c_off, c_val, nc, k, kp, score_cutoff, calls, scratch,
+            lscore + (size_t)used * nq * kp, lidx + (size_t)used * nq * kp,
+            [&](const uint32_t *lit_off, const uint8_t *lit_val, const uint32_t *off, const uint8_t *val, uint32_t rows, uint32_t b) {
+                return strsim_pairs_device(c, STRSIM_INDEL, lit_off, lit_val, 1, off, val, rows, scratch + (size_t)b * rows, rows);
+            },
+            [&](uint64_t) { return strsim_ctx_synchronize(c); });
+        if (rc) return rc;
+        ++used;
+    }
+    HIP_TRY(launch_match_merge(k, lscore, lidx, used, nq, out_index, out_score, st));
+    return STRSIM_OK;
+}
+
+extern "C" {
+
+int strsim_extract_device(strsim_ctx_t *c, int scorer, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows,
+                          const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, uint32_t k, double score_cutoff,
+                          uint32_t *out_index, double *out_score)
+{
+    int rc = extract_check("strsim_extract_device", c, scorer, q_off, q_val, q_rows, c_off, c_val, c_rows, k, score_cutoff, out_index, out_score);
+    if (rc || q_rows == 0) return rc;
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    const uint32_t nq = (uint32_t)q_rows, nc = (uint32_t)c_rows;
+    if (scorer == STRSIM_TOKEN_SORT_RATIO) {
+        // both sides through the token_sort transform into the context's own columns, on the device; one wait (the bounds)
+        rc = token_prepare(c);
+        if (rc) return rc;
+        rc = token_bounds(c, q_off, q_rows, nc ? c_off : nullptr, c_rows);
+        if (rc) return rc;
+        const TokenStatus ts = *c->tok_status_host;
+        const uint32_t *const in_off[2] = {q_off, c_off};
+        const uint8_t *const in_val[2] = {q_val, c_val};
+        const uint64_t rows[2] = {q_rows, c_rows};
+        for (int s = 0; s < 2 && rows[s]; ++s) {
+            rc = c->extract_off[s].reserve((rows[s] + 1) * sizeof(uint32_t));
+            if (rc == STRSIM_OK) rc = c->extract_val[s].reserve((uint64_t)ts.end[s] - ts.begin[s] + TOKEN_PAD);
+            if (rc == STRSIM_OK)
+                rc = token_sort_column(c, s, in_off[s], in_val[s], rows[s], ts.max_len[s], c->extract_off[s].as<uint32_t>(),
+                                       c->extract_val[s].as<uint8_t>());
+            if (rc) return rc;
+        }
+        rc = token_copy_counts(c);
+        if (rc) return rc;
+        q_off = c->extract_off[0].as<uint32_t>(); q_val = c->extract_val[0].as<uint8_t>();
+        if (nc) { c_off = c->extract_off[1].as<uint32_t>(); c_val = c->extract_val[1].as<uint8_t>(); }
+    }
+    return extract_search(c, q_off, q_val, nq, c_off, c_val, nc, k, score_cutoff, out_index, out_score);
+}
+
+int strsim_extract_host(strsim_ctx_t *c, int scorer, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows,
+                        const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, uint32_t k, double score_cutoff,
+                        uint32_t *out_index, double *out_score)
+{
+    int rc = extract_check("strsim_extract_host", c, scorer, q_off, q_val, q_rows, c_off, c_val, c_rows, k, score_cutoff, out_index, out_score);
+    if (rc || q_rows == 0) return rc;
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    const size_t ob = q_rows * (size_t)k;
+    Staged s;
+    rc = ctx_stage(c, q_off, q_val, q_rows, c_off, c_val, c_rows, ob * 12 + 256, &s);
+    if (rc) return rc;
+    double *const d_score = reinterpret_cast<double *>(s.out);
+    uint32_t *const d_index = reinterpret_cast<uint32_t *>(s.out + up256(ob * 8));
+    rc = strsim_extract_device(c, scorer, s.a_off, s.a_val, q_rows, s.b_off, s.b_val, c_rows, k, score_cutoff, d_index, d_score);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out_score, d_score, ob * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out_index, d_index, ob * 4, hipMemcpyDeviceToHost, c->stream));
+    return strsim_ctx_synchronize(c);
 }
 
 } // extern "C"

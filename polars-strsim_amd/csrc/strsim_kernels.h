@@ -189,5 +189,19 @@ hipError_t launch_nearest_lane(int measure, const NearestLaneArgs &a);
 hipError_t launch_nearest_scores(const uint32_t *dist, uint64_t n, double *score, hipStream_t stream);
 hipError_t launch_nearest_finish(const double *score, const uint32_t *index, uint64_t n, uint32_t *dist, hipStream_t stream);
 
+// Top-k search by Indel similarity (strsim_extract_kernels.h).  Both sides packed by launch_match_pack and put in length order by
+// launch_nearest_order; launch_extract_lane writes splits x nq x match_lane_k(k) partial lists in the encoding of k_match_merge.
+// tab: the device copy of the rank table (strsim_extract.h); rlimit >= 1: the number of ranks the cutoff admits.
+struct ExtractTable;
+struct ExtractLaneArgs {
+    const uint32_t *qwords, *qmeta, *qperm, *qstart; uint32_t nq;
+    const uint32_t *swords, *smeta, *sidx, *cstart;
+    uint32_t splits, k;
+    const ExtractTable *tab; uint32_t rlimit;
+    double *pscore; uint32_t *pidx;
+    hipStream_t stream;
+};
+hipError_t launch_extract_lane(const ExtractLaneArgs &a);
+
 } // namespace strsim
 

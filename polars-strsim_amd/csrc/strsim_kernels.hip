@@ -35,6 +35,8 @@
 //                     ASCII strings of up to 64 bytes and 16 tokens per lane, the rest one string per wave.
 //   k_nearest_lane<TR, K>  nearest match by bounded edit distance (strsim_nearest_kernels.h): one query per lane in length
 //                     order against wave-uniform candidates, a candidate length window and a running bound per lane.
+//   k_extract_lane<K>  top-k search by Indel similarity with a score cutoff (strsim_extract_kernels.h): the shape of
+//                     k_nearest_lane, scores ordered through a rank table in LDS, a length window and a running bound per lane.
 //   k_huge_pairs<M>   strings beyond WAVE_CAP, scratch in global memory, launched from strsim_ctx_synchronize() only
 //                     when such rows were counted; Levenshtein: the block step in stripes of 64 blocks, any length.
 //
@@ -59,6 +61,7 @@
 #include "strsim_partial.h"
 #include "strsim_token.h"
 #include "strsim_nearest.h"
+#include "strsim_extract.h"
 
 namespace strsim {
 
@@ -75,6 +78,7 @@ struct OutPtrs {
 #include "strsim_lane_lit.h"
 #include "strsim_match.h"
 #include "strsim_nearest_kernels.h"
+#include "strsim_extract_kernels.h"
 
 #include "strsim_kernel_wide.h"
 #include "strsim_kernel_utf8.h"
@@ -514,6 +518,18 @@ hipError_t launch_nearest_finish(const double *score, const uint32_t *index, uin
 {
     if (n == 0u) return hipSuccess;
     hipLaunchKernelGGL(k_nearest_finish, dim3(match_grid(n)), dim3(MATCH_BLOCK), 0, stream, score, index, n, dist);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// extract (strsim_extract_kernels.h)
+// ------------------------------------------------------------------------------------------------
+hipError_t launch_extract_lane(const ExtractLaneArgs &a)
+{
+    with_lane_k(a.k, [&](auto K) {
+        hipLaunchKernelGGL(k_extract_lane<decltype(K)::value>, dim3(match_grid(a.nq), a.splits), dim3(MATCH_BLOCK), 0, a.stream, a.qwords, a.qmeta,
+                           a.qperm, a.qstart, a.nq, a.swords, a.smeta, a.sidx, a.cstart, a.tab, a.rlimit, a.pscore, a.pidx);
+    });
     return hipGetLastError();
 }
 

@@ -196,6 +196,7 @@ __all__ = [
     "jaro_winkler",
     "jaccard",
     "sorensen_dice",
+    "extract",
 ]
 
 
@@ -231,6 +232,28 @@ def nearest(expr: IntoExpr, candidates: IntoExpr, measure: str = "levenshtein", 
     return register_plugin_function(
         plugin_path=_PLUGIN_DIR,
         function_name="nearest_" + measure,
+        args=args,
+        is_elementwise=False,
+    )
+
+
+_EXTRACT_SCORERS = ("ratio", "token_sort_ratio")
+
+
+def extract(expr: IntoExpr, candidates: IntoExpr, scorer: str = "ratio", score_cutoff: float | None = None) -> pl.Expr:
+    """The best candidate of every row of `expr` among all rows of `candidates` (any length) by `scorer` ("ratio" or
+    "token_sort_ratio"): a struct {index: UInt32, score: Float64}, null where the row is null or no candidate scores at least
+    score_cutoff (None: no cutoff); ties go to the lower candidate index.  rapidfuzz's process.extractOne with fuzz.ratio or
+    fuzz.token_sort_ratio as the scorer; the score is theirs / 100, in [0, 1], and so is score_cutoff.  Not in the upstream
+    polars-strsim."""
+    if scorer not in _EXTRACT_SCORERS:
+        raise ValueError(f"unknown scorer {scorer!r}; expected one of {_EXTRACT_SCORERS}")
+    args = [parse_into_expr(expr, dtype=pl.Utf8), parse_into_expr(candidates, dtype=pl.Utf8)]
+    if score_cutoff is not None:
+        args.append(pl.lit(score_cutoff, dtype=pl.Float64))
+    return register_plugin_function(
+        plugin_path=_PLUGIN_DIR,
+        function_name="extract_" + scorer,
         args=args,
         is_elementwise=False,
     )

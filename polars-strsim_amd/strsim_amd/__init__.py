@@ -229,8 +229,33 @@ def nearest(measure, queries, candidates, k=1, max_distance=None, ctx=None):
     return out, np.where(out < 0, -1, dist.astype(np.int64))
 
 
+EXTRACT_SCORERS = ("ratio", "token_sort_ratio")
+_EXTRACT_SCORER_MEASURE = {"ratio": "indel", "indel": "indel", "token_sort_ratio": "token_sort_ratio"}
+
+
+def extract(scorer, queries, candidates, k=1, score_cutoff=None, ctx=None):
+    """For every query, its k best candidates by `scorer` ("ratio" -- "indel" is an alias -- or "token_sort_ratio",
+    EXTRACT_SCORERS): (index int64 [N, k], score f64 [N, k]).  The score is indel(q, c) or token_sort_ratio(q, c), in [0, 1], bit
+    for bit the pairwise call's.  Slots in descending order of the score, ties to the lower candidate index; a candidate below
+    score_cutoff is not reported (None: no cutoff).  Empty slots -- and every slot of a null query -- are (-1, NaN).  Null
+    candidates are never matched; indices refer to the caller's candidate positions.
+    rapidfuzz: process.extract(q, candidates, scorer=fuzz.ratio, score_cutoff=100 * score_cutoff, limit=k), scores / 100."""
+    if scorer not in _EXTRACT_SCORER_MEASURE:
+        raise ValueError(f"no extract by scorer {scorer!r} (one of {EXTRACT_SCORERS})")
+    ctx = ctx or default_context()
+    Q, vq = _as_column(queries)
+    qo, qv = pack_strings(Q)
+    co, cv, pos = _pack_candidates(candidates)
+    idx, score = ctx.extract(_EXTRACT_SCORER_MEASURE[scorer], qo, qv, co, cv, k, score_cutoff)
+    out = _remap_candidates(idx, pos, vq)
+    if vq is not None:
+        score[~vq] = np.nan
+    return out, score
+
+
 __all__ = ["best_match", "nearest", "Codec", "Context", "device_count", "pack_strings", "split_offsets", "similarity", "levenshtein", "jaro",
            "jaro_winkler", "jaccard", "sorensen_dice", "osa", "indel", "measure_supported", "distance", "levenshtein_distance", "osa_distance",
            "indel_distance", "INDEL_MEASURES", "partial_ratio", "partial_ratio_alignment", "PARTIAL_MEASURES",
            "token_sort_ratio", "token_set_ratio", "token_sort", "TOKEN_MEASURES",
-           "DISTANCE_MEASURES", "DISTANCE_UNBOUNDED", "MEASURES", "EXTRA_MEASURES", "MEASURE_ID", "STATUS", "ShapeMismatch", "StrsimError"]
+           "DISTANCE_MEASURES", "DISTANCE_UNBOUNDED", "MEASURES", "EXTRA_MEASURES", "MEASURE_ID", "STATUS", "ShapeMismatch", "StrsimError",
+           "extract", "EXTRACT_SCORERS"]

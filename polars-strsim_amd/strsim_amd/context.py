@@ -298,6 +298,29 @@ class Context:
                                         index.ctypes.data, dist.ctypes.data))
         return index, dist
 
+    def extract(self, scorer, q_offsets, q_values, c_offsets, c_values, k=1, score_cutoff=None):
+        """Top-k search by "indel" (rapidfuzz's ratio / 100) or "token_sort_ratio" (strsim_extract_host for numpy columns,
+        strsim_extract_device for torch tensors on this context's device): uint32 offsets + uint8 values of the queries and the
+        candidates -> (index uint32 [rows, k], score f64 [rows, k]), each query's k best candidates by descending score, ties to
+        the lower index; only scores >= score_cutoff are reported (None: no cutoff).  Empty slots are (0xFFFFFFFF, NaN).  Device
+        inputs give device outputs, complete in stream order."""
+        cut = -np.inf if score_cutoff is None else float(score_cutoff)
+        if not isinstance(q_offsets, np.ndarray) and hasattr(q_offsets, "data_ptr"):
+            import torch
+            nq, nc = q_offsets.numel() - 1, max(c_offsets.numel() - 1, 0)
+            index = torch.empty((nq, int(k)), dtype=torch.int32, device=q_offsets.device)
+            score = torch.empty((nq, int(k)), dtype=torch.float64, device=q_offsets.device)
+            check(lib().strsim_extract_device(self._h, measure_id(scorer), q_offsets.data_ptr(), q_values.data_ptr(), nq,
+                                              c_offsets.data_ptr(), c_values.data_ptr(), nc, int(k), cut, index.data_ptr(), score.data_ptr()))
+            return index, score
+        qo, qv, nq = _host_column(q_offsets, q_values)
+        co, cv, nc = _host_column(c_offsets, c_values)
+        index = np.empty((nq, int(k)), dtype=np.uint32)
+        score = np.empty((nq, int(k)), dtype=np.float64)
+        check(lib().strsim_extract_host(self._h, measure_id(scorer), qo.ctypes.data, qv.ctypes.data, nq,
+                                        co.ctypes.data, cv.ctypes.data, nc, int(k), cut, index.ctypes.data, score.ctypes.data))
+        return index, score
+
 
 class Codec:
     """Lossless 16-bit transport codec for one measure's result column (include/strsim_amd.h: strsim_codec_*)."""
