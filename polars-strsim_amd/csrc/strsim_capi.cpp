@@ -1213,6 +1213,8 @@ static constexpr uint64_t MATCH_FALLBACK_SCORES = (uint64_t)1 << 24;
 // The part of a search call's workspace that both families lay out alike: both sides packed by k_match_pack (32-byte words +
 // meta) and their slow lists; `tail` is the family's own, and starts with the two slow counts.
 struct SearchPack {
+    const uint32_t *q_off; const uint8_t *q_val; uint32_t nq; // the call's columns
+    const uint32_t *c_off; const uint8_t *c_val; uint32_t nc;
     uint32_t *qw, *qm, *cw, *cm, *qs, *cs;
     uint8_t *tail;
     uint32_t q_slow, c_slow; // strings k_match_pack could not pack
@@ -1229,6 +1231,7 @@ static int search_pack(strsim_ctx *c, DevBuf &ws, size_t tail_bytes, size_t zero
     if (rc) return rc;
     if (!c->match_counts_host) HIP_TRY(hipHostMalloc((void **)&c->match_counts_host, 64, hipHostMallocDefault));
     uint8_t *const b = ws.as<uint8_t>();
+    p->q_off = q_off; p->q_val = q_val; p->nq = nq; p->c_off = c_off; p->c_val = c_val; p->nc = nc;
     p->qw = (uint32_t *)(b + o_qw); p->qm = (uint32_t *)(b + o_qm); p->cw = (uint32_t *)(b + o_cw); p->cm = (uint32_t *)(b + o_cm);
     p->qs = (uint32_t *)(b + o_qs); p->cs = (uint32_t *)(b + o_cs); p->tail = b + o_tail;
     uint32_t *const cnt = (uint32_t *)p->tail;
@@ -1243,7 +1246,6 @@ static int search_pack(strsim_ctx *c, DevBuf &ws, size_t tail_bytes, size_t zero
     return STRSIM_OK;
 }
 
-// fallback: scores of up to MATCH_FALLBACK_CALLS literal calls per batch, at most MATCH_FALLBACK_SCORES doubles
 static uint64_t fallback_calls(uint32_t nq, uint32_t nc)
 {
     const uint64_t calls = MATCH_FALLBACK_SCORES / std::max(nq, nc);
@@ -1254,11 +1256,11 @@ static uint64_t fallback_calls(uint32_t nq, uint32_t nc)
 // folded into the list (fs, fi).  score(lit_off, lit_val, col_off, col_val, rows, b) enqueues literal b of a batch;
 // finish(scores) leaves the batch's `scores` scores, row b at b * rows, in `batch` for the fold.
 template <class Score, class Finish>
-static int search_fallback(strsim_ctx *c, const char *who, const SearchPack &p, const uint32_t *q_off, const uint8_t *q_val, uint32_t nq,
-                           const uint32_t *c_off, const uint8_t *c_val, uint32_t nc, uint32_t k, uint32_t kp, double min_score,
-                           uint64_t calls, const double *batch, double *fs, uint32_t *fi, Score score, Finish finish)
+static int search_fallback(strsim_ctx *c, const char *who, const SearchPack &p, uint32_t k, uint32_t kp, double min_score, uint64_t calls,
+                           const double *batch, double *fs, uint32_t *fi, Score score, Finish finish)
 {
     hipStream_t st = c->stream;
+    const uint32_t nq = p.nq, nc = p.nc;
     HIP_TRY(launch_match_clear(fs, fi, (uint64_t)nq * kp, st));
     const uint32_t q_slow = p.q_slow, c_slow = p.c_slow;
     const std::unique_ptr<uint32_t[]> host_list(new (std::nothrow) uint32_t[(size_t)q_slow + c_slow + 1]);
@@ -1269,7 +1271,7 @@ static int search_fallback(strsim_ctx *c, const char *who, const SearchPack &p, 
     for (uint32_t b0 = 0; b0 < q_slow; b0 += (uint32_t)calls) { // a slow query against every candidate
         const uint32_t nb = (uint32_t)(q_slow - b0 < calls ? q_slow - b0 : calls);
         for (uint32_t b = 0; b < nb; ++b) {
-            int r = score(q_off + host_list[b0 + b], q_val, c_off, c_val, nc, b);
+            int r = score(p.q_off + host_list[b0 + b], p.q_val, p.c_off, p.c_val, nc, b);
             if (r) return r;
         }
         int r = finish((uint64_t)nb * nc);
@@ -1279,7 +1281,7 @@ static int search_fallback(strsim_ctx *c, const char *who, const SearchPack &p, 
     for (uint32_t b0 = 0; b0 < c_slow; b0 += (uint32_t)calls) { // a slow candidate against every query (the fast ones are kept)
         const uint32_t nb = (uint32_t)(c_slow - b0 < calls ? c_slow - b0 : calls);
         for (uint32_t b = 0; b < nb; ++b) {
-            int r = score(c_off + host_list[q_slow + b0 + b], c_val, q_off, q_val, nq, b);
+            int r = score(p.c_off + host_list[q_slow + b0 + b], p.c_val, p.q_off, p.q_val, nq, b);
             if (r) return r;
         }
         int r = finish((uint64_t)nb * nq);
@@ -1287,6 +1289,89 @@ static int search_fallback(strsim_ctx *c, const char *who, const SearchPack &p, 
         HIP_TRY(launch_match_fold_rows(k, batch, p.cs + b0, nb, p.qm, nq, min_score, fs, fi, st));
     }
     return STRSIM_OK;
+}
+
+// The end of every search call: when `fallback` and a side has slow strings, every pair with a slow side goes through
+// search_fallback, its batches in `scratch` (pair_bytes per pair, the f64 scores first), into list `used`; then the lists are
+// merged.  score / finish read their batch pointers from `scratch` when they run: it is reserved only here.
+template <class Score, class Finish>
+static int search_fallback_merge(strsim_ctx *c, const char *who, const SearchPack &p, uint32_t k, double min_score, bool fallback,
+                                 DevBuf &scratch, size_t pair_bytes, uint32_t used, double *lscore, uint32_t *lidx, uint32_t *out_index,
+                                 double *out_score, Score score, Finish finish)
+{
+    const uint32_t kp = (uint32_t)match_lane_k(k);
+    if (fallback && p.nc && (p.q_slow || p.c_slow)) {
+        const uint64_t calls = fallback_calls(p.nq, p.nc);
+        int rc = scratch.reserve((size_t)(calls * std::max(p.nq, p.nc) * pair_bytes));
+        if (rc) return rc;
+        const size_t o = (size_t)used * p.nq * kp;
+        rc = search_fallback(c, who, p, k, kp, min_score, calls, scratch.as<double>(), lscore + o, lidx + o, score, finish);
+        if (rc) return rc;
+        ++used;
+    }
+    HIP_TRY(launch_match_merge(k, lscore, lidx, used, p.nq, out_index, out_score, c->stream));
+    return STRSIM_OK;
+}
+
+// A length-ordered search (nearest, extract) up to its lane launch.  The tail of its workspace: the small block (slow counts,
+// histograms, bucket starts, cursors), the query permutation, the candidates in length order, (splits + 1) lists of kp per query
+// (the last: the fallback) and extra_bytes of the family's own.
+struct OrderedSearch {
+    SearchPack p;
+    SweepLaneArgs lane; // what the family's lane launch takes; lane.pscore / lane.pidx are the lists
+    uint8_t *extra;
+    bool fast;          // the length order is in place and the lane kernel has work: lists 0 .. splits - 1 are its
+};
+// `sweep`: the family admits a sweep at all (extract under a cutoff above 1.0 does not).
+static int ordered_search_pack(strsim_ctx *c, DevBuf &ws, size_t extra_bytes, bool sweep, const uint32_t *q_off, const uint8_t *q_val,
+                               uint32_t nq, const uint32_t *c_off, const uint8_t *c_val, uint32_t nc, uint32_t k, OrderedSearch *o)
+{
+    const uint32_t kp = (uint32_t)match_lane_k(k);
+    const uint32_t splits = nc ? match_splits(nq, nc, kp, c->num_cu) : 0u;
+    const size_t lists = ((size_t)splits + 1) * nq * kp;
+    const size_t o_qp = 1024, o_sw = o_qp + up256((size_t)nq * 4), o_sm = o_sw + up256((size_t)nc * 32), o_si = o_sm + up256((size_t)nc * 4),
+                 o_ls = o_si + up256((size_t)nc * 4), o_li = o_ls + up256(lists * 8), o_ex = o_li + up256(lists * 4);
+    SearchPack &p = o->p;
+    // (of the small block, the counts and histograms are zeroed)
+    int rc = search_pack(c, ws, o_ex + extra_bytes, 4 * 88, q_off, q_val, nq, c_off, c_val, nc, &p);
+    if (rc) return rc;
+    uint32_t *const small = (uint32_t *)p.tail;
+    uint32_t *const qhist = small + 8, *const chist = qhist + 40, *const qstart = chist + 40, *const cstart = qstart + 40,
+                   *const qcur = cstart + 40, *const ccur = qcur + 40;
+    uint32_t *const qperm = (uint32_t *)(p.tail + o_qp), *const sw = (uint32_t *)(p.tail + o_sw), *const sm = (uint32_t *)(p.tail + o_sm),
+                   *const si = (uint32_t *)(p.tail + o_si);
+    o->lane = SweepLaneArgs{p.qw, p.qm, qperm, qstart, nq, sw, sm, si, cstart, splits, k, (double *)(p.tail + o_ls), (uint32_t *)(p.tail + o_li),
+                            c->stream};
+    o->extra = p.tail + o_ex;
+    // fast x fast: length order on the device
+    o->fast = sweep && splits && p.q_slow < nq && p.c_slow < nc;
+    if (o->fast) {
+        NearestOrderArgs oa{p.qm, nq, p.cw, p.cm, nc, qhist, chist, qstart, cstart, qcur, ccur, qperm, sw, sm, si, c->stream};
+        HIP_TRY(launch_nearest_order(oa));
+    }
+    return STRSIM_OK;
+}
+
+// The *_host entry point of a search family behind its check (`checked`: what the check returned): both columns staged, the
+// device entry point on the staged columns with outputs a then b in stage[4], the two copies back and the family's wait.
+template <class A, class B, class Device, class Wait>
+static int search_host(strsim_ctx *c, int checked, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows, const uint32_t *c_off,
+                       const uint8_t *c_val, uint64_t c_rows, uint32_t k, A *out_a, B *out_b, Device device, Wait wait)
+{
+    if (checked || q_rows == 0) return checked;
+    int rc = ctx_set_device(c);
+    if (rc) return rc;
+    const size_t ob = q_rows * (size_t)k;
+    Staged s;
+    rc = ctx_stage(c, q_off, q_val, q_rows, c_off, c_val, c_rows, ob * (sizeof(A) + sizeof(B)) + 256, &s);
+    if (rc) return rc;
+    A *const d_a = reinterpret_cast<A *>(s.out);
+    B *const d_b = reinterpret_cast<B *>(s.out + up256(ob * sizeof(A)));
+    rc = device(s, d_a, d_b);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out_a, d_a, ob * sizeof(A), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out_b, d_b, ob * sizeof(B), hipMemcpyDeviceToHost, c->stream));
+    return wait();
 }
 
 static int best_match_check(const char *who, strsim_ctx_t *c, int measure, const uint32_t *q_off, const uint8_t *q_val,
@@ -1329,45 +1414,25 @@ int strsim_best_match_device(strsim_ctx_t *c, int measure, const uint32_t *q_off
         used = nsplit;
     }
     // every pair with a slow side: strsim_pairs_device with that side as the literal, batch by batch, folded into list `used`
-    if (nc && (p.q_slow || p.c_slow)) {
-        const uint64_t calls = fallback_calls(nq, nc);
-        rc = c->match_scratch.reserve((size_t)(calls * std::max(nq, nc) * 8));
-        if (rc) return rc;
-        double *const scratch = c->match_scratch.as<double>();
-        rc = search_fallback(
-            c, "strsim_best_match_device", p, q_off, q_val, nq, c_off, c_val, nc, k, kp, min_score, calls, scratch,
-            lscore + (size_t)used * nq * kp, lidx + (size_t)used * nq * kp,
-            [&](const uint32_t *lit_off, const uint8_t *lit_val, const uint32_t *off, const uint8_t *val, uint32_t rows, uint32_t b) {
-                return strsim_pairs_device(c, measure, lit_off, lit_val, 1, off, val, rows, scratch + (size_t)b * rows, rows);
-            },
-            [&](uint64_t) { return strsim_ctx_synchronize(c); });
-        if (rc) return rc;
-        ++used;
-    }
-    HIP_TRY(launch_match_merge(k, lscore, lidx, used, nq, out_index, out_score, st));
-    return STRSIM_OK;
+    return search_fallback_merge(
+        c, "strsim_best_match_device", p, k, min_score, true, c->match_scratch, 8, used, lscore, lidx, out_index, out_score,
+        [&](const uint32_t *lit_off, const uint8_t *lit_val, const uint32_t *off, const uint8_t *val, uint32_t rows, uint32_t b) {
+            return strsim_pairs_device(c, measure, lit_off, lit_val, 1, off, val, rows, c->match_scratch.as<double>() + (size_t)b * rows, rows);
+        },
+        [&](uint64_t) { return strsim_ctx_synchronize(c); });
 }
 
 int strsim_best_match_host(strsim_ctx_t *c, int measure, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows,
                            const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, uint32_t k, double min_score,
                            uint32_t *out_index, double *out_score)
 {
-    int rc = best_match_check("strsim_best_match_host", c, measure, q_off, q_val, q_rows, c_off, c_val, c_rows, k, min_score,
-                              out_index, out_score);
-    if (rc || q_rows == 0) return rc;
-    rc = ctx_set_device(c);
-    if (rc) return rc;
-    const size_t ob = q_rows * (size_t)k;
-    Staged s;
-    rc = ctx_stage(c, q_off, q_val, q_rows, c_off, c_val, c_rows, ob * 12 + 256, &s);
-    if (rc) return rc;
-    double *const d_score = reinterpret_cast<double *>(s.out);
-    uint32_t *const d_index = reinterpret_cast<uint32_t *>(s.out + up256(ob * 8));
-    rc = strsim_best_match_device(c, measure, s.a_off, s.a_val, q_rows, s.b_off, s.b_val, c_rows, k, min_score, d_index, d_score);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out_score, d_score, ob * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(out_index, d_index, ob * 4, hipMemcpyDeviceToHost, c->stream));
-    return strsim_ctx_synchronize(c);
+    return search_host(
+        c, best_match_check("strsim_best_match_host", c, measure, q_off, q_val, q_rows, c_off, c_val, c_rows, k, min_score, out_index, out_score),
+        q_off, q_val, q_rows, c_off, c_val, c_rows, k, out_score, out_index,
+        [&](const Staged &s, double *d_score, uint32_t *d_index) {
+            return strsim_best_match_device(c, measure, s.a_off, s.a_val, q_rows, s.b_off, s.b_val, c_rows, k, min_score, d_index, d_score);
+        },
+        [&] { return strsim_ctx_synchronize(c); });
 }
 
 } // extern "C"
@@ -1588,52 +1653,26 @@ int strsim_nearest_device(strsim_ctx_t *c, int measure, const uint32_t *q_off, c
     if (rc || q_rows == 0) return rc;
     rc = ctx_set_device(c);
     if (rc) return rc;
-    const uint32_t nq = (uint32_t)q_rows, nc = (uint32_t)c_rows, kp = (uint32_t)match_lane_k(k);
-    const uint32_t splits = nc ? match_splits(nq, nc, kp, c->num_cu) : 0u;
-    // the tail of the workspace: the small block (slow counts, histograms, bucket starts, cursors), the query permutation, the
-    // candidates in length order, (splits + 1) lists of kp per query (the last: the fallback) and the merged scores
-    const size_t lists = ((size_t)splits + 1) * nq * kp, ob = (size_t)nq * k;
-    const size_t o_qp = 1024, o_sw = o_qp + up256((size_t)nq * 4), o_sm = o_sw + up256((size_t)nc * 32), o_si = o_sm + up256((size_t)nc * 4),
-                 o_ls = o_si + up256((size_t)nc * 4), o_li = o_ls + up256(lists * 8), o_ms = o_li + up256(lists * 4);
-    SearchPack p;
-    // (of the small block, the counts and histograms are zeroed)
-    rc = search_pack(c, c->nearest_ws, o_ms + up256(ob * 8), 4 * 88, q_off, q_val, nq, c_off, c_val, nc, &p);
+    const uint32_t nq = (uint32_t)q_rows, nc = (uint32_t)c_rows;
+    const size_t ob = (size_t)nq * k;
+    OrderedSearch o; // (extra: the merged scores)
+    rc = ordered_search_pack(c, c->nearest_ws, up256(ob * 8), true, q_off, q_val, nq, c_off, c_val, nc, k, &o);
     if (rc) return rc;
-    uint32_t *const small = (uint32_t *)p.tail, *const lidx = (uint32_t *)(p.tail + o_li);
-    double *const lscore = (double *)(p.tail + o_ls), *const mscore = (double *)(p.tail + o_ms);
-    hipStream_t st = c->stream;
-    // fast x fast: length order on the device, then lists 0 .. splits - 1
-    uint32_t used = 0;
-    if (splits && p.q_slow < nq && p.c_slow < nc) {
-        uint32_t *const qhist = small + 8, *const chist = qhist + 40, *const qstart = chist + 40, *const cstart = qstart + 40,
-                       *const qcur = cstart + 40, *const ccur = qcur + 40;
-        uint32_t *const qperm = (uint32_t *)(p.tail + o_qp), *const sw = (uint32_t *)(p.tail + o_sw), *const sm = (uint32_t *)(p.tail + o_sm),
-                       *const si = (uint32_t *)(p.tail + o_si);
-        NearestOrderArgs oa{p.qm, nq, p.cw, p.cm, nc, qhist, chist, qstart, cstart, qcur, ccur, qperm, sw, sm, si, st};
-        HIP_TRY(launch_nearest_order(oa));
-        NearestLaneArgs a{p.qw, p.qm, qperm, qstart, nq, sw, sm, si, cstart, splits, k, max_distance, lscore, lidx, st};
-        HIP_TRY(launch_nearest_lane(measure, a));
-        used = splits;
-    }
+    if (o.fast) HIP_TRY(launch_nearest_lane(measure, NearestLaneArgs{o.lane, max_distance}));
     // every pair with a slow side: strsim_distance_device with that side as the literal (its length prefilter and block cutoff
-    // apply), batch by batch, folded into list `used` as the scores -(double)d
-    if (nc && (p.q_slow || p.c_slow)) {
-        const uint64_t calls = fallback_calls(nq, nc), longest = std::max(nq, nc);
-        rc = c->nearest_scratch.reserve((size_t)(calls * longest * 12));
-        if (rc) return rc;
-        double *const scores = c->nearest_scratch.as<double>();
-        uint32_t *const dist = reinterpret_cast<uint32_t *>(scores + calls * longest);
-        rc = search_fallback(
-            c, "strsim_nearest_device", p, q_off, q_val, nq, c_off, c_val, nc, k, kp, -(double)max_distance /* a cut pair comes back as max_distance + 1 */,
-            calls, scores, lscore + (size_t)used * nq * kp, lidx + (size_t)used * nq * kp,
-            [&](const uint32_t *lit_off, const uint8_t *lit_val, const uint32_t *off, const uint8_t *val, uint32_t rows, uint32_t b) {
-                return strsim_distance_device(c, measure, lit_off, lit_val, 1, off, val, rows, max_distance, dist + (size_t)b * rows, rows);
-            },
-            [&](uint64_t count) -> int { HIP_TRY(launch_nearest_scores(dist, count, scores, st)); return STRSIM_OK; });
-        if (rc) return rc;
-        ++used;
-    }
-    HIP_TRY(launch_match_merge(k, lscore, lidx, used, nq, out_index, mscore, st));
+    // apply), batch by batch, folded into list `used` as the scores -(double)d; a batch's distances lie behind its scores
+    hipStream_t st = c->stream;
+    double *const mscore = (double *)o.extra;
+    const uint64_t pairs = fallback_calls(nq, nc) * std::max(nq, nc);
+    auto dist = [&] { return reinterpret_cast<uint32_t *>(c->nearest_scratch.as<double>() + pairs); };
+    rc = search_fallback_merge(
+        c, "strsim_nearest_device", o.p, k, -(double)max_distance /* a cut pair comes back as max_distance + 1 */, true, c->nearest_scratch, 12,
+        o.fast ? o.lane.splits : 0u, o.lane.pscore, o.lane.pidx, out_index, mscore,
+        [&](const uint32_t *lit_off, const uint8_t *lit_val, const uint32_t *off, const uint8_t *val, uint32_t rows, uint32_t b) {
+            return strsim_distance_device(c, measure, lit_off, lit_val, 1, off, val, rows, max_distance, dist() + (size_t)b * rows, rows);
+        },
+        [&](uint64_t count) -> int { HIP_TRY(launch_nearest_scores(dist(), count, c->nearest_scratch.as<double>(), st)); return STRSIM_OK; });
+    if (rc) return rc;
     HIP_TRY(launch_nearest_finish(mscore, out_index, ob, out_distance, st));
     return STRSIM_OK;
 }
@@ -1642,22 +1681,13 @@ int strsim_nearest_host(strsim_ctx_t *c, int measure, const uint32_t *q_off, con
                         const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, uint32_t k, uint32_t max_distance,
                         uint32_t *out_index, uint32_t *out_distance)
 {
-    int rc = nearest_check("strsim_nearest_host", c, measure, q_off, q_val, q_rows, c_off, c_val, c_rows, k, out_index, out_distance);
-    if (rc || q_rows == 0) return rc;
-    rc = ctx_set_device(c);
-    if (rc) return rc;
-    const size_t ob = q_rows * (size_t)k;
-    Staged s;
-    rc = ctx_stage(c, q_off, q_val, q_rows, c_off, c_val, c_rows, ob * 8 + 256, &s);
-    if (rc) return rc;
-    uint32_t *const d_index = reinterpret_cast<uint32_t *>(s.out);
-    uint32_t *const d_dist = reinterpret_cast<uint32_t *>(s.out + up256(ob * 4));
-    rc = strsim_nearest_device(c, measure, s.a_off, s.a_val, q_rows, s.b_off, s.b_val, c_rows, k, max_distance, d_index, d_dist);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out_index, d_index, ob * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(out_distance, d_dist, ob * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return STRSIM_OK;
+    return search_host(
+        c, nearest_check("strsim_nearest_host", c, measure, q_off, q_val, q_rows, c_off, c_val, c_rows, k, out_index, out_distance), q_off, q_val,
+        q_rows, c_off, c_val, c_rows, k, out_index, out_distance,
+        [&](const Staged &s, uint32_t *d_index, uint32_t *d_dist) {
+            return strsim_nearest_device(c, measure, s.a_off, s.a_val, q_rows, s.b_off, s.b_val, c_rows, k, max_distance, d_index, d_dist);
+        },
+        [&]() -> int { HIP_TRY(hipStreamSynchronize(c->stream)); return STRSIM_OK; });
 }
 
 } // extern "C"
@@ -1700,51 +1730,19 @@ static int extract_search(strsim_ctx *c, const uint32_t *q_off, const uint8_t *q
         c->extract_tab_ready = true;
     }
     const uint32_t rlimit = extract_rank_limit(tab, score_cutoff); // 0: the cutoff is above 1.0 and nothing is reported
-    const uint32_t kp = (uint32_t)match_lane_k(k);
-    const uint32_t splits = nc ? match_splits(nq, nc, kp, c->num_cu) : 0u;
-    // the tail of the workspace: the small block (slow counts, histograms, bucket starts, cursors), the query permutation, the
-    // candidates in length order and (splits + 1) lists of kp per query (the last: the fallback)
-    const size_t lists = ((size_t)splits + 1) * nq * kp;
-    const size_t o_qp = 1024, o_sw = o_qp + up256((size_t)nq * 4), o_sm = o_sw + up256((size_t)nc * 32), o_si = o_sm + up256((size_t)nc * 4),
-                 o_ls = o_si + up256((size_t)nc * 4), o_li = o_ls + up256(lists * 8);
-    SearchPack p;
-    // (of the small block, the counts and histograms are zeroed)
-    int rc = search_pack(c, c->extract_ws, o_li + up256(lists * 4), 4 * 88, q_off, q_val, nq, c_off, c_val, nc, &p);
+    OrderedSearch o;
+    int rc = ordered_search_pack(c, c->extract_ws, 0, rlimit != 0u, q_off, q_val, nq, c_off, c_val, nc, k, &o);
     if (rc) return rc;
-    uint32_t *const small = (uint32_t *)p.tail, *const lidx = (uint32_t *)(p.tail + o_li);
-    double *const lscore = (double *)(p.tail + o_ls);
-    // fast x fast: length order on the device, then lists 0 .. splits - 1
-    uint32_t used = 0;
-    if (splits && rlimit && p.q_slow < nq && p.c_slow < nc) {
-        uint32_t *const qhist = small + 8, *const chist = qhist + 40, *const qstart = chist + 40, *const cstart = qstart + 40,
-                       *const qcur = cstart + 40, *const ccur = qcur + 40;
-        uint32_t *const qperm = (uint32_t *)(p.tail + o_qp), *const sw = (uint32_t *)(p.tail + o_sw), *const sm = (uint32_t *)(p.tail + o_sm),
-                       *const si = (uint32_t *)(p.tail + o_si);
-        NearestOrderArgs oa{p.qm, nq, p.cw, p.cm, nc, qhist, chist, qstart, cstart, qcur, ccur, qperm, sw, sm, si, st};
-        HIP_TRY(launch_nearest_order(oa));
-        ExtractLaneArgs a{p.qw, p.qm, qperm, qstart, nq, sw, sm, si, cstart, splits, k, c->extract_tab.as<ExtractTable>(), rlimit, lscore, lidx, st};
-        HIP_TRY(launch_extract_lane(a));
-        used = splits;
-    }
+    if (o.fast) HIP_TRY(launch_extract_lane(ExtractLaneArgs{o.lane, c->extract_tab.as<ExtractTable>(), rlimit}));
     // every pair with a slow side: strsim_pairs_device(STRSIM_INDEL) with that side as the literal, batch by batch, folded into
     // list `used` with score_cutoff as the least score
-    if (nc && rlimit && (p.q_slow || p.c_slow)) {
-        const uint64_t calls = fallback_calls(nq, nc);
-        rc = c->extract_scratch.reserve((size_t)(calls * std::max(nq, nc) * 8));
-        if (rc) return rc;
-        double *const scratch = c->extract_scratch.as<double>();
-        rc = search_fallback(
-            c, "strsim_extract_device", p, q_off, q_val, nq, c_off, c_val, nc, k, kp, score_cutoff, calls, scratch,
-            lscore + (size_t)used * nq * kp, lidx + (size_t)used * nq * kp,
-            [&](const uint32_t *lit_off, const uint8_t *lit_val, const uint32_t *off, const uint8_t *val, uint32_t rows, uint32_t b) {
-                return strsim_pairs_device(c, STRSIM_INDEL, lit_off, lit_val, 1, off, val, rows, scratch + (size_t)b * rows, rows);
-            },
-            [&](uint64_t) { return strsim_ctx_synchronize(c); });
-        if (rc) return rc;
-        ++used;
-    }
-    HIP_TRY(launch_match_merge(k, lscore, lidx, used, nq, out_index, out_score, st));
-    return STRSIM_OK;
+    return search_fallback_merge(
+        c, "strsim_extract_device", o.p, k, score_cutoff, rlimit != 0u, c->extract_scratch, 8, o.fast ? o.lane.splits : 0u, o.lane.pscore,
+        o.lane.pidx, out_index, out_score,
+        [&](const uint32_t *lit_off, const uint8_t *lit_val, const uint32_t *off, const uint8_t *val, uint32_t rows, uint32_t b) {
+            return strsim_pairs_device(c, STRSIM_INDEL, lit_off, lit_val, 1, off, val, rows, c->extract_scratch.as<double>() + (size_t)b * rows, rows);
+        },
+        [&](uint64_t) { return strsim_ctx_synchronize(c); });
 }
 
 extern "C" {
@@ -1788,21 +1786,13 @@ int strsim_extract_host(strsim_ctx_t *c, int scorer, const uint32_t *q_off, cons
                         const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, uint32_t k, double score_cutoff,
                         uint32_t *out_index, double *out_score)
 {
-    int rc = extract_check("strsim_extract_host", c, scorer, q_off, q_val, q_rows, c_off, c_val, c_rows, k, score_cutoff, out_index, out_score);
-    if (rc || q_rows == 0) return rc;
-    rc = ctx_set_device(c);
-    if (rc) return rc;
-    const size_t ob = q_rows * (size_t)k;
-    Staged s;
-    rc = ctx_stage(c, q_off, q_val, q_rows, c_off, c_val, c_rows, ob * 12 + 256, &s);
-    if (rc) return rc;
-    double *const d_score = reinterpret_cast<double *>(s.out);
-    uint32_t *const d_index = reinterpret_cast<uint32_t *>(s.out + up256(ob * 8));
-    rc = strsim_extract_device(c, scorer, s.a_off, s.a_val, q_rows, s.b_off, s.b_val, c_rows, k, score_cutoff, d_index, d_score);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out_score, d_score, ob * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(out_index, d_index, ob * 4, hipMemcpyDeviceToHost, c->stream));
-    return strsim_ctx_synchronize(c);
+    return search_host(
+        c, extract_check("strsim_extract_host", c, scorer, q_off, q_val, q_rows, c_off, c_val, c_rows, k, score_cutoff, out_index, out_score), q_off,
+        q_val, q_rows, c_off, c_val, c_rows, k, out_score, out_index,
+        [&](const Staged &s, double *d_score, uint32_t *d_index) {
+            return strsim_extract_device(c, scorer, s.a_off, s.a_val, q_rows, s.b_off, s.b_val, c_rows, k, score_cutoff, d_index, d_score);
+        },
+        [&] { return strsim_ctx_synchronize(c); });
 }
 
 } // extern "C"

@@ -4,7 +4,9 @@
 //
 // This header holds what the host shares with the kernel (tests/cpu_harness/extract_harness.cpp compiles it with g++): the rank
 // table that orders scores without a division per pair, the window / skip / stop rules of a wave's sweep and the Indel core on
-// wave-uniform text.  The kernel is in strsim_extract_kernels.h.
+// wave-uniform text, and ExtractRules, which hands them to the one sweep loop that nearest match runs too (search_sweep_lane of
+// strsim_nearest_kernels.h on the device, tests/cpu_harness/sweep_host.h on the host).  The kernel is in
+// strsim_extract_kernels.h.
 //
 // Ranking.  In the lane class both strings have at most 32 bytes, so a pair is (d, s) with s = |q| + |c| <= 64 and d <= s.  Two
 // distinct rationals d / s with s <= 64 differ by at least 1 / (64 * 63), far more than an ulp, so the correctly rounded f64
@@ -134,5 +136,30 @@ STRSIM_HD uint32_t extract_indel_uniform_text(const uint32_t (&wt)[8], uint32_t 
     const uint32_t l = popc32(~V & low_ones(lp));
     return lp + lt - 2u * l;
 }
+
+// The rule set of the extract sweep over a rank table (`rank`: the kernel's LDS copy) under rlimit >= 1.  The value a lane
+// keeps per candidate length is the rank of ub(lq, lc) and the table row of the pair's length sum, so a pair costs one read;
+// the sweep stops after a step none of whose lengths any live lane needed.
+struct ExtractRules {
+    static constexpr bool STOP_BY_BOUND = false;
+    struct Len { uint32_t ubr; const uint16_t *row; };
+    const uint16_t *rank, *rep;
+    uint32_t rlimit;
+    STRSIM_HD void window(uint32_t lmin, uint32_t lmax, uint32_t &lo, uint32_t &hi) const { extract_window(rank, lmin, lmax, rlimit, lo, hi); }
+    STRSIM_HD Len at(uint32_t lq, uint32_t lc) const { return Len{extract_ub(rank, lq, lc), rank + (lq + lc) * EXTRACT_TAB_W}; }
+    STRSIM_HD bool needs(uint32_t, const Len &len, uint64_t kth) const { return extract_needs(len.ubr, extract_bound(kth, rlimit)); }
+    template <int NP>
+    STRSIM_HD uint32_t distance(const uint32_t (&wt)[8], uint32_t lc, const uint32_t (&P)[NP], uint32_t lq) const
+    {
+        return extract_indel_uniform_text<NP>(wt, lc, P, lq);
+    }
+    STRSIM_HD uint64_t key(uint32_t d, const Len &len, uint32_t j, bool &ok) const
+    {
+        const uint32_t r = len.row[d]; // d <= lq + lc: inside the row
+        ok = r < rlimit;
+        return extract_key(r, j);
+    }
+    STRSIM_HD double score(uint64_t key) const { return extract_rank_score(rep, (uint32_t)(key >> 32)); }
+};
 
 } // namespace strsim

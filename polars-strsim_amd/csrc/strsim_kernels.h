@@ -164,7 +164,7 @@ hipError_t launch_token_set_epilogue(const TokenSetRec *rec, const uint32_t *d32
 // Nearest match by bounded edit distance (strsim_nearest_kernels.h), measure 0 (Levenshtein) or 6 (OSA).  The strings of both
 // sides are packed by launch_match_pack first; launch_nearest_order then puts them in length order on the device (histograms,
 // scan, scatter; the histograms must be zeroed), and launch_nearest_lane writes splits x nq x match_lane_k(k) partial lists in
-// the encoding of k_match_merge (score -(double)d).
+// the encoding of k_match_merge (score -(double)d).  SweepLaneArgs is what the two length-ordered lane kernels take alike.
 struct NearestOrderArgs {
     const uint32_t *qmeta; uint32_t nq;                // queries (k_match_pack)
     const uint32_t *cwords, *cmeta; uint32_t nc;       // candidates
@@ -176,12 +176,16 @@ struct NearestOrderArgs {
     hipStream_t stream;
 };
 hipError_t launch_nearest_order(const NearestOrderArgs &a);
-struct NearestLaneArgs {
+struct SweepLaneArgs {
     const uint32_t *qwords, *qmeta, *qperm, *qstart; uint32_t nq;
     const uint32_t *swords, *smeta, *sidx, *cstart;
-    uint32_t splits, k, max_distance;
+    uint32_t splits, k;
     double *pscore; uint32_t *pidx;
     hipStream_t stream;
+};
+struct NearestLaneArgs {
+    SweepLaneArgs s;
+    uint32_t max_distance;
 };
 hipError_t launch_nearest_lane(int measure, const NearestLaneArgs &a);
 // fallback distances -> scores -(double)d for launch_match_fold_cols / _rows; the merged scores -> distances (0xFFFFFFFF where the
@@ -194,12 +198,8 @@ hipError_t launch_nearest_finish(const double *score, const uint32_t *index, uin
 // tab: the device copy of the rank table (strsim_extract.h); rlimit >= 1: the number of ranks the cutoff admits.
 struct ExtractTable;
 struct ExtractLaneArgs {
-    const uint32_t *qwords, *qmeta, *qperm, *qstart; uint32_t nq;
-    const uint32_t *swords, *smeta, *sidx, *cstart;
-    uint32_t splits, k;
+    SweepLaneArgs s;
     const ExtractTable *tab; uint32_t rlimit;
-    double *pscore; uint32_t *pidx;
-    hipStream_t stream;
 };
 hipError_t launch_extract_lane(const ExtractLaneArgs &a);
 

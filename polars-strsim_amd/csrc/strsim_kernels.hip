@@ -33,10 +33,11 @@
 //   k_token_sort_* / k_token_set_*  token_sort_ratio and token_set_ratio (measures 14 and 16, strsim_token.h): tokenise, sort and
 //                     join (or merge as sets) every string into scratch columns that k_indel_lane / k_indel_wave then align;
 //                     ASCII strings of up to 64 bytes and 16 tokens per lane, the rest one string per wave.
-//   k_nearest_lane<TR, K>  nearest match by bounded edit distance (strsim_nearest_kernels.h): one query per lane in length
-//                     order against wave-uniform candidates, a candidate length window and a running bound per lane.
-//   k_extract_lane<K>  top-k search by Indel similarity with a score cutoff (strsim_extract_kernels.h): the shape of
-//                     k_nearest_lane, scores ordered through a rank table in LDS, a length window and a running bound per lane.
+//   k_nearest_lane<TR, K> / k_extract_lane<K>  the two length-ordered searches, one sweep (search_sweep_lane,
+//                     strsim_nearest_kernels.h) under two rule sets: one query per lane in length order against wave-uniform
+//                     candidates, a candidate length window and a running bound per lane.  Nearest match by bounded edit
+//                     distance (NearestRules, strsim_nearest.h); top-k by Indel similarity with a score cutoff, scores ordered
+//                     through a rank table in LDS (ExtractRules, strsim_extract.h; strsim_extract_kernels.h).
 //   k_huge_pairs<M>   strings beyond WAVE_CAP, scratch in global memory, launched from strsim_ctx_synchronize() only
 //                     when such rows were counted; Levenshtein: the block step in stripes of 64 blocks, any length.
 //
@@ -494,9 +495,10 @@ hipError_t launch_nearest_order(const NearestOrderArgs &a)
 template <bool TR>
 static void launch_nearest_lane_tr(const NearestLaneArgs &a)
 {
-    with_lane_k(a.k, [&](auto K) {
-        hipLaunchKernelGGL((k_nearest_lane<TR, decltype(K)::value>), dim3(match_grid(a.nq), a.splits), dim3(MATCH_BLOCK), 0, a.stream, a.qwords,
-                           a.qmeta, a.qperm, a.qstart, a.nq, a.swords, a.smeta, a.sidx, a.cstart, a.max_distance, a.pscore, a.pidx);
+    const SweepLaneArgs &s = a.s;
+    with_lane_k(s.k, [&](auto K) {
+        hipLaunchKernelGGL((k_nearest_lane<TR, decltype(K)::value>), dim3(match_grid(s.nq), s.splits), dim3(MATCH_BLOCK), 0, s.stream, s.qwords,
+                           s.qmeta, s.qperm, s.qstart, s.nq, s.swords, s.smeta, s.sidx, s.cstart, a.max_distance, s.pscore, s.pidx);
     });
 }
 
@@ -526,9 +528,10 @@ hipError_t launch_nearest_finish(const double *score, const uint32_t *index, uin
 // ------------------------------------------------------------------------------------------------
 hipError_t launch_extract_lane(const ExtractLaneArgs &a)
 {
-    with_lane_k(a.k, [&](auto K) {
-        hipLaunchKernelGGL(k_extract_lane<decltype(K)::value>, dim3(match_grid(a.nq), a.splits), dim3(MATCH_BLOCK), 0, a.stream, a.qwords, a.qmeta,
-                           a.qperm, a.qstart, a.nq, a.swords, a.smeta, a.sidx, a.cstart, a.tab, a.rlimit, a.pscore, a.pidx);
+    const SweepLaneArgs &s = a.s;
+    with_lane_k(s.k, [&](auto K) {
+        hipLaunchKernelGGL(k_extract_lane<decltype(K)::value>, dim3(match_grid(s.nq), s.splits), dim3(MATCH_BLOCK), 0, s.stream, s.qwords, s.qmeta,
+                           s.qperm, s.qstart, s.nq, s.swords, s.smeta, s.sidx, s.cstart, a.tab, a.rlimit, s.pscore, s.pidx);
     });
     return hipGetLastError();
 }

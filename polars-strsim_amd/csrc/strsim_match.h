@@ -4,7 +4,8 @@
 //   k_match_pack        one thread per string: its bytes into eight registers' worth of words (zeros behind the string), its
 //                       length and which of bits 5 / 6 its bytes take, or "slow" (longer than 32 bytes, non-ASCII) -- then the
 //                       string's index goes to the slow list of its side.
-//   k_match_lane<M, K>  ONE QUERY PER LANE, both strings <= 32 ASCII bytes.  The query's bit-planes are built once and stay in
+//   k_match_lane<M, K>  ONE QUERY PER LANE, both strings <= 32 ASCII bytes.  The query's bit-planes are built once
+//                       (match_lane_query, which the length-ordered sweep of strsim_nearest_kernels.h shares) and stay in
 //                       registers for the whole sweep; the candidate is wave-uniform text, as the literal of k_lane_lit: its
 //                       words, length and class come in through scalar loads and its per-column bit fills are scalar.  Each lane
 //                       keeps its running top-K in VGPRs.  blockIdx.y splits the candidates; every split writes a partial
@@ -85,6 +86,32 @@ __device__ __forceinline__ bool match_five_planes(uint32_t cls)
     return (cls & 3u) != 3u && (cls & 12u) != 12u;
 }
 
+// The query of a lane as every sweep holds it (k_match_lane, search_sweep_lane): the bit-planes of query i's eight words (of
+// zeros unless `live`), the first five of them again, the first word, and which values bits 5 / 6 take over the wave's live
+// queries (uniform; qm is the query's meta).
+struct LaneQuery {
+    uint32_t P[7], P5[5], w0, wcls;
+};
+__device__ __forceinline__ LaneQuery match_lane_query(const uint32_t *__restrict__ qwords, uint32_t i, bool live, uint32_t qm)
+{
+    uint32_t wp[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    if (live) {
+        const uint4 *const src = reinterpret_cast<const uint4 *>(qwords + (size_t)i * 8u);
+        const uint4 a = src[0], b = src[1];
+        wp[0] = a.x; wp[1] = a.y; wp[2] = a.z; wp[3] = a.w; wp[4] = b.x; wp[5] = b.y; wp[6] = b.z; wp[7] = b.w;
+    }
+    LaneQuery q;
+    build_planes<7>(wp, q.P);
+#pragma unroll
+    for (int b = 0; b < 5; ++b) q.P5[b] = q.P[b];
+    q.w0 = wp[0];
+    q.wcls = 0u;
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+        if (__ballot(live && ((qm >> (8 + b)) & 1u))) q.wcls |= 1u << b;
+    return q;
+}
+
 template <int MEASURE, int NP>
 __device__ __forceinline__ double match_score(const double *q, const uint32_t (&wt)[8], uint32_t lt, const uint32_t (&P)[NP],
                                               uint32_t wp0, uint32_t lp)
@@ -138,20 +165,7 @@ __global__ __launch_bounds__(MATCH_BLOCK) void k_match_lane(const uint32_t *__re
     const uint32_t qm = have ? qmeta[i] : MATCH_SLOW;
     const bool mine = (qm & MATCH_SLOW) == 0u;
     const uint32_t lp = qm & 63u;
-    uint32_t wp[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-    if (mine) {
-        const uint4 *const src = reinterpret_cast<const uint4 *>(qwords + (size_t)i * 8u);
-        const uint4 a = src[0], b = src[1];
-        wp[0] = a.x; wp[1] = a.y; wp[2] = a.z; wp[3] = a.w; wp[4] = b.x; wp[5] = b.y; wp[6] = b.z; wp[7] = b.w;
-    }
-    uint32_t P[7];
-    build_planes<7>(wp, P);
-    const uint32_t P5[5] = {P[0], P[1], P[2], P[3], P[4]};
-    // which values bits 5 / 6 take over the wave's queries (uniform)
-    uint32_t wcls = 0u;
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-        if (__ballot(mine && ((qm >> (8 + b)) & 1u))) wcls |= 1u << b;
+    const LaneQuery q = match_lane_query(qwords, i, mine, qm);
 
     double ts[K];
     uint32_t ti[K];
@@ -169,8 +183,8 @@ __global__ __launch_bounds__(MATCH_BLOCK) void k_match_lane(const uint32_t *__re
             for (int q = 0; q < 8; ++q) wt[q] = cwords[(size_t)j * 8u + q];
             const uint32_t lt = cm & 63u;
             double v;
-            if (match_five_planes(wcls | ((cm >> 8) & 15u))) v = match_score<MEASURE, 5>(s_q, wt, lt, P5, wp[0], lp);
-            else v = match_score<MEASURE, 7>(s_q, wt, lt, P, wp[0], lp);
+            if (match_five_planes(q.wcls | ((cm >> 8) & 15u))) v = match_score<MEASURE, 5>(s_q, wt, lt, q.P5, q.w0, lp);
+            else v = match_score<MEASURE, 7>(s_q, wt, lt, q.P, q.w0, lp);
             if (mine && v >= min_score && match_better(v, j, ts[K - 1], ti[K - 1])) match_insert<K>(ts, ti, v, j);
         }
     }

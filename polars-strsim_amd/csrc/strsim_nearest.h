@@ -2,7 +2,9 @@
 // query, the k candidates with the smallest d <= max_distance, d the Levenshtein (measure 0) or OSA (measure 6) distance.
 //
 // This header holds what the host shares with the kernels (tests/cpu_harness/nearest_harness.cpp compiles it with g++): the
-// order of a list, the window / skip / stop rules of a wave's sweep and the two distance cores on wave-uniform text.  The kernels are in
+// order of a list, the window / skip / stop rules of a wave's sweep and the two distance cores on wave-uniform text, and
+// NearestRules, which hands them to the one sweep loop (search_sweep_lane of strsim_nearest_kernels.h on the device,
+// tests/cpu_harness/sweep_host.h on the host; strsim_extract.h has the other rule set).  The kernels are in
 // strsim_nearest_kernels.h.
 //
 // The sweep of one wave (64 queries of the lane class, taken in length order, so they span one or two lengths lmin..lmax):
@@ -124,5 +126,25 @@ STRSIM_HD uint32_t nearest_osa_uniform_text(const uint32_t (&wt)[8], uint32_t lt
     const uint32_t rows = low_ones(lp);
     return lt + popc32(VP & rows) - popc32(VN & rows);
 }
+
+// The rule set of the nearest-match sweep (TR: OSA instead of Levenshtein).  The value a lane keeps per candidate length is
+// the length itself; the sweep stops before step g once g exceeds the largest bound of the wave's live lanes.
+template <bool TR>
+struct NearestRules {
+    static constexpr bool STOP_BY_BOUND = true;
+    uint32_t kmax;
+    STRSIM_HD void window(uint32_t lmin, uint32_t lmax, uint32_t &lo, uint32_t &hi) const { nearest_window(lmin, lmax, kmax, lo, hi); }
+    STRSIM_HD uint32_t at(uint32_t, uint32_t lc) const { return lc; }
+    STRSIM_HD uint32_t bound(uint64_t kth) const { return nearest_bound(kth, kmax); }
+    STRSIM_HD bool needs(uint32_t lq, uint32_t lc, uint64_t kth) const { return nearest_needs(lq, lc, bound(kth)); }
+    STRSIM_HD bool done(uint32_t next, uint32_t max_bound) const { return nearest_done(next, max_bound); }
+    template <int NP>
+    STRSIM_HD uint32_t distance(const uint32_t (&wt)[8], uint32_t lc, const uint32_t (&P)[NP], uint32_t lq) const
+    {
+        return TR ? nearest_osa_uniform_text<NP>(wt, lc, P, lq) : nearest_lev_uniform_text<NP>(wt, lc, P, lq);
+    }
+    STRSIM_HD uint64_t key(uint32_t d, uint32_t, uint32_t j, bool &ok) const { ok = d <= kmax; return nearest_key(d, j); }
+    STRSIM_HD double score(uint64_t key) const { return -(double)(uint32_t)(key >> 32); } // (match_better's order: ascending d)
+};
 
 } // namespace strsim

@@ -9,10 +9,12 @@
 //                       strings take their places in it by an LDS atomic, so the order inside a bucket varies from run to run).
 //                       Queries: the permutation (the slow ones at the end).  Candidates: words, meta and original index,
 //                       copied into length order so that a sweep reads them contiguously.
-//   k_nearest_lane<TR, K>  ONE QUERY PER LANE in length order, the query's bit-planes in registers, the candidate wave-uniform
-//                       text read through scalar loads, the running top-K of (d, j) in VGPRs as 64-bit keys.  The wave sweeps
-//                       the candidate lengths of its window nearest-first with the skip and stop rules of strsim_nearest.h.
+//   search_sweep_lane<Rules, K>  the body of the two length-ordered lane kernels (k_nearest_lane here, k_extract_lane in
+//                       strsim_extract_kernels.h): ONE QUERY PER LANE in length order, the query's bit-planes in registers, the
+//                       candidate wave-uniform text read through scalar loads, the running top-K in VGPRs as 64-bit keys.  The
+//                       wave sweeps the candidate lengths of its window nearest-first with the skip and stop rules of its Rules.
 //                       blockIdx.y takes its slice of every length bucket; the partial lists go to the query's original row.
+//   k_nearest_lane<TR, K>  that sweep under NearestRules<TR> (strsim_nearest.h): keys (d, j).
 //   k_nearest_scores    fallback distances (uint32) -> the scores the fold kernels take.
 //   k_nearest_finish    the merged scores -> distances, 0xFFFFFFFF in an empty slot.
 #pragma once
@@ -86,23 +88,22 @@ __device__ __forceinline__ uint32_t nearest_wave_min(uint32_t v)
 
 __device__ __forceinline__ uint32_t nearest_wave_max(uint32_t v) { return wave_uniform(osa_wave_max(v)); }
 
-// d of the lane's query (planes P, length lq) against the uniform candidate text wt of length lt
-template <bool TR, int NP>
-__device__ __forceinline__ uint32_t nearest_distance(const uint32_t (&wt)[8], uint32_t lt, const uint32_t (&P)[NP], uint32_t lq)
-{
-    return TR ? nearest_osa_uniform_text<NP>(wt, lt, P, lq) : nearest_lev_uniform_text<NP>(wt, lt, P, lq);
-}
-
+// The sweep of the length-ordered searches, written once: k_nearest_lane runs it with NearestRules (strsim_nearest.h) and
+// k_extract_lane (strsim_extract_kernels.h) with ExtractRules (strsim_extract.h) -- one sweep, two rule sets.  Rules supplies the
+// window, the value a lane keeps per candidate length (at), the skip test (needs), the distance core, the key of a pair and the
+// f64 score of a kept key; the stop rule is chosen at compile time by Rules::STOP_BY_BOUND.  What is here is the loop and its wave
+// operations (the ballots and the wave minimum / maximum); tests/cpu_harness/sweep_host.h is the same loop on the host.
+//
 // Grid: (ceil(nq / MATCH_BLOCK), splits).  Position p of the query permutation (qstart[NEAREST_SLOW_BUCKET] fast queries in
 // length order, the slow ones behind them) writes the partial list of split blockIdx.y for its query i: pscore / pidx[(y * nq +
 // i) * K ..], empty for a slow query.  Split y takes [c0 + n * y / splits, c0 + n * (y + 1) / splits) of every length bucket
 // [c0, c0 + n) of the length-ordered candidates (sw / sm / sidx, bucket starts in cstart).
-template <bool TR, int K>
-__global__ __launch_bounds__(MATCH_BLOCK) void k_nearest_lane(const uint32_t *__restrict__ qwords, const uint32_t *__restrict__ qmeta,
-                                                              const uint32_t *__restrict__ qperm, const uint32_t *__restrict__ qstart,
-                                                              uint32_t nq, const uint32_t *__restrict__ sw, const uint32_t *__restrict__ sm,
-                                                              const uint32_t *__restrict__ sidx, const uint32_t *__restrict__ cstart,
-                                                              uint32_t kmax, double *__restrict__ pscore, uint32_t *__restrict__ pidx)
+template <class Rules, int K>
+__device__ __forceinline__ void search_sweep_lane(const Rules &R, const uint32_t *__restrict__ qwords, const uint32_t *__restrict__ qmeta,
+                                                  const uint32_t *__restrict__ qperm, const uint32_t *__restrict__ qstart, uint32_t nq,
+                                                  const uint32_t *__restrict__ sw, const uint32_t *__restrict__ sm,
+                                                  const uint32_t *__restrict__ sidx, const uint32_t *__restrict__ cstart,
+                                                  double *__restrict__ pscore, uint32_t *__restrict__ pidx)
 {
     const uint32_t p = blockIdx.x * MATCH_BLOCK + threadIdx.x;
     const uint32_t split = blockIdx.y, splits = gridDim.y;
@@ -111,20 +112,7 @@ __global__ __launch_bounds__(MATCH_BLOCK) void k_nearest_lane(const uint32_t *__
     const bool live = have && p < qstart[NEAREST_SLOW_BUCKET];
     const uint32_t qm = live ? qmeta[i] : 0u;
     const uint32_t lq = qm & 63u;
-    uint32_t wp[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-    if (live) {
-        const uint4 *const src = reinterpret_cast<const uint4 *>(qwords + (size_t)i * 8u);
-        const uint4 a = src[0], b = src[1];
-        wp[0] = a.x; wp[1] = a.y; wp[2] = a.z; wp[3] = a.w; wp[4] = b.x; wp[5] = b.y; wp[6] = b.z; wp[7] = b.w;
-    }
-    uint32_t P[7];
-    build_planes<7>(wp, P);
-    const uint32_t P5[5] = {P[0], P[1], P[2], P[3], P[4]};
-    // which values bits 5 / 6 take over the wave's queries (uniform)
-    uint32_t wcls = 0u;
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-        if (__ballot(live && ((qm >> (8 + b)) & 1u))) wcls |= 1u << b;
+    const LaneQuery q = match_lane_query(qwords, i, live, qm);
 
     uint64_t keys[K];
 #pragma unroll
@@ -133,29 +121,37 @@ __global__ __launch_bounds__(MATCH_BLOCK) void k_nearest_lane(const uint32_t *__
     if (__ballot(live) != 0ull) {
         const uint32_t lmin = nearest_wave_min(live ? lq : 0xFFFFFFFFu), lmax = nearest_wave_max(live ? lq : 0u);
         uint32_t lo, hi;
-        nearest_window(lmin, lmax, kmax, lo, hi);
+        R.window(lmin, lmax, lo, hi);
         const uint32_t steps = nearest_steps(lmin, lmax, lo, hi);
         for (uint32_t g = 0; g < steps; ++g) {
-            if (g && nearest_done(g, nearest_wave_max(live ? nearest_bound(keys[K - 1], kmax) : 0u))) break;
+            if constexpr (Rules::STOP_BY_BOUND)
+                if (g && R.done(g, nearest_wave_max(live ? R.bound(keys[K - 1]) : 0u))) break;
             uint32_t first, last, stride;
             if (!nearest_step_range(lmin, lmax, lo, hi, g, first, last, stride)) continue;
+            [[maybe_unused]] bool needed = false; // (uniform) some live lane needs a length of this step
             for (uint32_t lc = first; lc <= last; lc += stride) {
+                const auto len = R.at(lq, lc);
+                if constexpr (!Rules::STOP_BY_BOUND)
+                    if (__ballot(live && R.needs(lq, len, keys[K - 1])) != 0ull) needed = true;
                 // this split's slice of the bucket of length lc, while some lane still needs that length
                 const uint32_t c0 = cstart[lc], n = cstart[lc + 1u] - c0;
                 const uint32_t x1 = c0 + (uint32_t)((uint64_t)n * (split + 1u) / splits);
                 for (uint32_t x = c0 + (uint32_t)((uint64_t)n * split / splits); x < x1; ++x) { // (uniform: scalar loads)
-                    if (__ballot(live && nearest_needs(lq, lc, nearest_bound(keys[K - 1], kmax))) == 0ull) break;
+                    if (__ballot(live && R.needs(lq, len, keys[K - 1])) == 0ull) break;
                     const uint32_t cm = sm[x], j = sidx[x];
                     uint32_t wt[8];
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) wt[q] = sw[(size_t)x * 8u + q];
+                    for (int w = 0; w < 8; ++w) wt[w] = sw[(size_t)x * 8u + w];
                     uint32_t d;
-                    if (match_five_planes(wcls | ((cm >> 8) & 15u))) d = nearest_distance<TR, 5>(wt, lc, P5, lq);
-                    else d = nearest_distance<TR, 7>(wt, lc, P, lq);
-                    const uint64_t key = nearest_key(d, j);
-                    if (live && d <= kmax && key < keys[K - 1]) nearest_insert<K>(keys, key);
+                    if (match_five_planes(q.wcls | ((cm >> 8) & 15u))) d = R.template distance<5>(wt, lc, q.P5, lq);
+                    else d = R.template distance<7>(wt, lc, q.P, lq);
+                    bool ok;
+                    const uint64_t key = R.key(d, len, j, ok);
+                    if (live && ok && key < keys[K - 1]) nearest_insert<K>(keys, key);
                 }
             }
+            if constexpr (!Rules::STOP_BY_BOUND)
+                if (!needed) break;
         }
     }
     if (!have) return;
@@ -163,9 +159,21 @@ __global__ __launch_bounds__(MATCH_BLOCK) void k_nearest_lane(const uint32_t *__
 #pragma unroll
     for (int s = 0; s < K; ++s) {
         const bool e = keys[s] == NEAREST_EMPTY;
-        pscore[o + s] = e ? -__builtin_inf() : -(double)(uint32_t)(keys[s] >> 32);
+        const double v = R.score(e ? 0ull : keys[s]); // (an empty key has no score)
+        pscore[o + s] = e ? -__builtin_inf() : v;
         pidx[o + s] = e ? MATCH_NONE : (uint32_t)keys[s];
     }
+}
+
+// search_sweep_lane under NearestRules<TR>: the partial lists carry the score -(double)d.
+template <bool TR, int K>
+__global__ __launch_bounds__(MATCH_BLOCK) void k_nearest_lane(const uint32_t *__restrict__ qwords, const uint32_t *__restrict__ qmeta,
+                                                              const uint32_t *__restrict__ qperm, const uint32_t *__restrict__ qstart,
+                                                              uint32_t nq, const uint32_t *__restrict__ sw, const uint32_t *__restrict__ sm,
+                                                              const uint32_t *__restrict__ sidx, const uint32_t *__restrict__ cstart,
+                                                              uint32_t kmax, double *__restrict__ pscore, uint32_t *__restrict__ pidx)
+{
+    search_sweep_lane<NearestRules<TR>, K>(NearestRules<TR>{kmax}, qwords, qmeta, qperm, qstart, nq, sw, sm, sidx, cstart, pscore, pidx);
 }
 
 __global__ __launch_bounds__(MATCH_BLOCK) void k_nearest_scores(const uint32_t *__restrict__ dist, uint64_t n, double *__restrict__ score)

@@ -2,26 +2,14 @@
 //   extract_core   what one lane of k_extract_lane computes for a query (the pattern, <= 32 ASCII bytes) against a candidate (the
 //                  uniform text, <= 32 bytes): the planes of build_planes and the Indel core, on NP = 5 or 7 planes.
 //   extract_tab_*  the rank table the library builds, its scores and the cutoff -> rank-limit conversion.
-//   extract_wave   the sweep of one wave of k_extract_lane (one split) over given distances: the same window, nearest-first
-//                  order, skip and stop rules and the same list insertion, with the ballots written as loops over the lanes.
-#include <stdint.h>
-#include <string.h>
-
-#include <algorithm>
+//   extract_wave   the sweep of one wave of k_extract_lane (one split) over given distances: sweep_host.h's loop under the
+//                  kernel's own ExtractRules.
 #include <limits>
-#include <numeric>
-#include <vector>
 
 #include "strsim_extract.h"
+#include "sweep_host.h"
 
 using namespace strsim;
-
-static void window32(const char *s, uint32_t len, uint32_t (&w)[8])
-{
-    uint8_t b[32] = {};
-    memcpy(b, s, len);
-    for (int d = 0; d < 8; ++d) w[d] = (uint32_t)b[4 * d] | ((uint32_t)b[4 * d + 1] << 8) | ((uint32_t)b[4 * d + 2] << 16) | ((uint32_t)b[4 * d + 3] << 24);
-}
 
 extern "C" uint32_t extract_core(const char *q, uint32_t lq, const char *c, uint32_t lc, int np)
 {
@@ -58,52 +46,15 @@ template <int K>
 static uint64_t wave(const uint32_t *qlen, uint32_t nq, const uint32_t *clen, uint32_t nc, const uint32_t *dist, double cutoff,
                      uint32_t *out_idx, double *out_score)
 {
-    const uint16_t *const rank = table().rank;
-    const uint32_t rlimit = extract_rank_limit(table(), cutoff);
-    std::vector<std::vector<uint64_t>> keys(nq, std::vector<uint64_t>(K, NEAREST_EMPTY));
-    // the candidates in length order (any order inside a length: the lists must not depend on it -- here, descending index)
-    std::vector<uint32_t> order(nc);
-    std::iota(order.begin(), order.end(), 0u);
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return clen[a] != clen[b] ? clen[a] < clen[b] : a > b; });
-    uint64_t visited = 0;
-    auto kth = [&](uint32_t i) { return keys[i][K - 1]; };
-    if (rlimit) { // (the library launches no sweep when nothing is admissible)
-        uint32_t lmin = 0xFFFFFFFFu, lmax = 0u;
-        for (uint32_t i = 0; i < nq; ++i) { lmin = std::min(lmin, qlen[i]); lmax = std::max(lmax, qlen[i]); }
-        uint32_t lo, hi;
-        extract_window(rank, lmin, lmax, rlimit, lo, hi);
-        const uint32_t steps = nearest_steps(lmin, lmax, lo, hi);
-        for (uint32_t g = 0; g < steps; ++g) {
-            uint32_t first, last, stride;
-            if (!nearest_step_range(lmin, lmax, lo, hi, g, first, last, stride)) continue;
-            bool needed = false;
-            for (uint32_t lc = first; lc <= last; lc += stride) {
-                auto any_needs = [&] {
-                    bool any = false;
-                    for (uint32_t i = 0; i < nq; ++i) any |= extract_needs(extract_ub(rank, qlen[i], lc), extract_bound(kth(i), rlimit));
-                    return any;
-                };
-                if (any_needs()) needed = true;
-                for (uint32_t x = 0; x < nc; ++x) {
-                    const uint32_t j = order[x];
-                    if (clen[j] != lc) continue;
-                    if (!any_needs()) break;
-                    ++visited;
-                    for (uint32_t i = 0; i < nq; ++i) {
-                        const uint32_t r = extract_rank(rank, dist[(size_t)i * nc + j], qlen[i] + lc);
-                        uint64_t (&k)[K] = *reinterpret_cast<uint64_t(*)[K]>(keys[i].data());
-                        if (r < rlimit && extract_key(r, j) < k[K - 1]) nearest_insert<K>(k, extract_key(r, j));
-                    }
-                }
-            }
-            if (!needed) break;
-        }
-    }
+    const ExtractRules R{table().rank, table().rep, extract_rank_limit(table(), cutoff)};
+    std::vector<SweepKeys<K>> keys = sweep_empty<K>(nq);
+    // (the library launches no sweep when nothing is admissible)
+    const uint64_t visited = R.rlimit ? sweep_wave<ExtractRules, K>(R, qlen, nq, clen, nc, dist, keys) : 0;
     for (uint32_t i = 0; i < nq; ++i)
         for (int s = 0; s < K; ++s) {
-            const bool e = keys[i][s] == NEAREST_EMPTY;
-            out_idx[(size_t)i * K + s] = e ? 0xFFFFFFFFu : (uint32_t)keys[i][s];
-            out_score[(size_t)i * K + s] = e ? std::numeric_limits<double>::quiet_NaN() : extract_rank_score(table().rep, (uint32_t)(keys[i][s] >> 32));
+            const bool e = keys[i].k[s] == NEAREST_EMPTY;
+            out_idx[(size_t)i * K + s] = e ? 0xFFFFFFFFu : (uint32_t)keys[i].k[s];
+            out_score[(size_t)i * K + s] = e ? std::numeric_limits<double>::quiet_NaN() : R.score(keys[i].k[s]);
         }
     return visited;
 }

@@ -1,25 +1,11 @@
 // Host build of the shared nearest-match code of strsim_nearest.h, for tests/test_nearest_cpu.py: g++ compiles the same header.
 //   nearest_core  what one lane of k_nearest_lane computes for a query (the pattern, <= 32 ASCII bytes) against a candidate (the
 //                 uniform text, <= 32 bytes): the planes of build_planes and the Levenshtein or OSA core, on NP = 5 or 7 planes.
-//   nearest_wave  the sweep of one wave of k_nearest_lane (one split) over given distances: the same window, nearest-first
-//                 order, skip and stop rules and the same list insertion, with the ballots written as loops over the lanes.
-#include <stdint.h>
-#include <string.h>
-
-#include <algorithm>
-#include <numeric>
-#include <vector>
-
-#include "strsim_nearest.h"
+//   nearest_wave  the sweep of one wave of k_nearest_lane (one split) over given distances: sweep_host.h's loop under the
+//                 kernel's own NearestRules.
+#include "sweep_host.h"
 
 using namespace strsim;
-
-static void window32(const char *s, uint32_t len, uint32_t (&w)[8])
-{
-    uint8_t b[32] = {};
-    memcpy(b, s, len);
-    for (int d = 0; d < 8; ++d) w[d] = (uint32_t)b[4 * d] | ((uint32_t)b[4 * d + 1] << 8) | ((uint32_t)b[4 * d + 2] << 16) | ((uint32_t)b[4 * d + 3] << 24);
-}
 
 extern "C" uint32_t nearest_core(const char *q, uint32_t lq, const char *c, uint32_t lc, int np, int tr)
 {
@@ -40,46 +26,12 @@ template <int K>
 static uint64_t wave(const uint32_t *qlen, uint32_t nq, const uint32_t *clen, uint32_t nc, const uint32_t *dist, uint32_t kmax,
                      uint32_t *out_idx, uint32_t *out_d)
 {
-    std::vector<std::vector<uint64_t>> keys(nq, std::vector<uint64_t>(K, NEAREST_EMPTY));
-    // the candidates in length order (any order inside a length: the lists must not depend on it -- here, descending index)
-    std::vector<uint32_t> order(nc);
-    std::iota(order.begin(), order.end(), 0u);
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return clen[a] != clen[b] ? clen[a] < clen[b] : a > b; });
-    uint64_t visited = 0;
-    uint32_t lmin = 0xFFFFFFFFu, lmax = 0u;
-    for (uint32_t i = 0; i < nq; ++i) { lmin = std::min(lmin, qlen[i]); lmax = std::max(lmax, qlen[i]); }
-    uint32_t lo, hi;
-    nearest_window(lmin, lmax, kmax, lo, hi);
-    const uint32_t steps = nearest_steps(lmin, lmax, lo, hi);
-    auto kth = [&](uint32_t i) { uint64_t (&k)[K] = *reinterpret_cast<uint64_t(*)[K]>(keys[i].data()); return k[K - 1]; };
-    for (uint32_t g = 0; g < steps; ++g) {
-        if (g) {
-            uint32_t maxb = 0;
-            for (uint32_t i = 0; i < nq; ++i) maxb = std::max(maxb, nearest_bound(kth(i), kmax));
-            if (nearest_done(g, maxb)) break;
-        }
-        uint32_t first, last, stride;
-        if (!nearest_step_range(lmin, lmax, lo, hi, g, first, last, stride)) continue;
-        for (uint32_t lc = first; lc <= last; lc += stride) {
-            for (uint32_t x = 0; x < nc; ++x) {
-                const uint32_t j = order[x];
-                if (clen[j] != lc) continue;
-                bool any = false;
-                for (uint32_t i = 0; i < nq; ++i) any |= nearest_needs(qlen[i], lc, nearest_bound(kth(i), kmax));
-                if (!any) break;
-                ++visited;
-                for (uint32_t i = 0; i < nq; ++i) {
-                    const uint32_t d = dist[(size_t)i * nc + j];
-                    uint64_t (&k)[K] = *reinterpret_cast<uint64_t(*)[K]>(keys[i].data());
-                    if (d <= kmax && nearest_key(d, j) < k[K - 1]) nearest_insert<K>(k, nearest_key(d, j));
-                }
-            }
-        }
-    }
+    std::vector<SweepKeys<K>> keys = sweep_empty<K>(nq);
+    const uint64_t visited = sweep_wave<NearestRules<false>, K>(NearestRules<false>{kmax}, qlen, nq, clen, nc, dist, keys); // (no rule depends on TR)
     for (uint32_t i = 0; i < nq; ++i)
         for (int s = 0; s < K; ++s) {
-            out_idx[(size_t)i * K + s] = (uint32_t)keys[i][s];
-            out_d[(size_t)i * K + s] = (uint32_t)(keys[i][s] >> 32);
+            out_idx[(size_t)i * K + s] = (uint32_t)keys[i].k[s];
+            out_d[(size_t)i * K + s] = (uint32_t)(keys[i].k[s] >> 32);
         }
     return visited;
 }
