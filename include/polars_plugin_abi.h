@@ -125,6 +125,15 @@ POLARS_PLUGIN_DECLARE(partial_ratio_alignment)
  * after input 0, through the same pipeline as the similarities above.  Shape rule, literal broadcast and nulls as above; no kwargs. */
 POLARS_PLUGIN_DECLARE(token_sort_ratio)
 POLARS_PLUGIN_DECLARE(token_set_ratio)
+/* Not in the reference: token_ratio, partial_token_sort_ratio, partial_token_set_ratio, partial_token_ratio and wratio
+ * (STRSIM_TOKEN_RATIO .. STRSIM_WRATIO of strsim_amd.h: rapidfuzz's fuzz.token_ratio, fuzz.partial_token_sort_ratio,
+ * fuzz.partial_token_set_ratio, fuzz.partial_token_ratio and fuzz.WRatio, each / 100, without a processor), Float64 named after
+ * input 0, through the same pipeline as the similarities above.  Shape rule, literal broadcast and nulls as above; no kwargs. */
+POLARS_PLUGIN_DECLARE(token_ratio)
+POLARS_PLUGIN_DECLARE(partial_token_sort_ratio)
+POLARS_PLUGIN_DECLARE(partial_token_set_ratio)
+POLARS_PLUGIN_DECLARE(partial_token_ratio)
+POLARS_PLUGIN_DECLARE(wratio)
 
 /* Best match (not in the reference): input 0 = the query column (N rows), input 1 = the candidate column (any number of rows; the
  * length rule of the functions above does not apply).  Output: N rows of an Arrow struct {index: UInt32, score: Float64} named after

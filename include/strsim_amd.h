@@ -68,13 +68,25 @@ typedef enum strsim_measure {
                                  of other scalar values (a NUL is a token character); token order is lexicographic by scalar value, a
                                  proper prefix first (= bytewise order of the UTF-8); join puts one U+0020 between tokens; duplicates
                                  are kept.  Two tokenless strings: 1.0; exactly one: 0.0.  Pairwise entry points only */
-    STRSIM_TOKEN_SET_RATIO = 16   /* rapidfuzz's fuzz.token_set_ratio / 100 over the SETS A, B of tokens (tokenised as above): 0.0 when A
+    STRSIM_TOKEN_SET_RATIO = 16,  /* rapidfuzz's fuzz.token_set_ratio / 100 over the SETS A, B of tokens (tokenised as above): 0.0 when A
                                  or B is empty; 1.0 when A & B is not empty and A - B or B - A is; else, with sect, ab, ba the joined
                                  sorted A & B, A - B, B - A of sl, la, lb scalar values, sep = (sl > 0), sab = sl + sep + la,
                                  sba = sl + sep + lb, d = indel_distance(ab, ba) and E(d, s) = 1.0 when s == 0 else 1.0 - d / s:
                                  r0 = E(d, sab + sba) when sl == 0, else max(r0, E(sep + la, sl + sab), E(sep + lb, sl + sba)) -- the
                                  maximum of STRSIM_INDEL over the pairs of sect, sect + " " + ab, sect + " " + ba.  Pairwise entry
                                  points only.  14 and 16: ids 5, 7, 9, 11 and 12 stay unassigned and refused */
+    /* Compositions of the measures above (rapidfuzz's fuzz.* / 100, no processor), pairwise entry points only; the odd ids up to
+       25 stay unassigned and refused.  Tokens, sorting, join, A, B, ab, ba as for ids 14 and 16. */
+    STRSIM_TOKEN_RATIO = 18,      /* max(STRSIM_TOKEN_SORT_RATIO, STRSIM_TOKEN_SET_RATIO) */
+    STRSIM_PARTIAL_TOKEN_SORT_RATIO = 20, /* STRSIM_PARTIAL_RATIO of join(sorted(tokens(a))) and join(sorted(tokens(b))) */
+    STRSIM_PARTIAL_TOKEN_SET_RATIO = 22,  /* 0.0 when A or B is empty; 1.0 when A & B is not empty; else STRSIM_PARTIAL_RATIO of ab, ba */
+    STRSIM_PARTIAL_TOKEN_RATIO = 24,      /* max(STRSIM_PARTIAL_TOKEN_SORT_RATIO, STRSIM_PARTIAL_TOKEN_SET_RATIO) */
+    STRSIM_WRATIO = 26            /* rapidfuzz's fuzz.WRatio / 100.  With la, lb the scalar values of the RAW strings, lo = min, hi = max,
+                                 r = STRSIM_INDEL(a, b): 0.0 when lo == 0; when 2 hi < 3 lo: max(r, STRSIM_TOKEN_RATIO * 0.95); else, with
+                                 ps = 0.9 when hi <= 8 lo and 0.6 otherwise: max(r, STRSIM_PARTIAL_RATIO(a, b) * ps,
+                                 (STRSIM_PARTIAL_TOKEN_RATIO * 0.95) * ps) -- f64 products in exactly this association.  The rows
+                                 are classified on the device and each family runs over its own rows only
+                                 (strsim_ctx_last_wratio_rows) */
 } strsim_measure_t;
 
 /* Entry points of strsim_measure_supported(). */
@@ -338,6 +350,21 @@ STRSIM_API int strsim_token_sort_device(strsim_ctx_t *ctx, const uint32_t *offse
 STRSIM_API int strsim_token_sort_host(strsim_ctx_t *ctx, const uint32_t *offsets, const uint8_t *values, uint64_t rows,
                                       uint32_t *out_offsets, uint8_t *out_values, uint64_t out_capacity);
 STRSIM_API uint64_t strsim_ctx_last_token_wave_rows(strsim_ctx_t *ctx);
+
+/*
+ * STRSIM_TOKEN_RATIO .. STRSIM_WRATIO (ids 18 .. 26; strsim_measure_supported(id, STRSIM_ENTRY_PAIRWISE) detects them, the ABI
+ * version stays 1.7).  Ids 18 .. 24 run the token transforms and the Indel / partial-ratio kernels over the whole frame.
+ * STRSIM_WRATIO computes STRSIM_INDEL over every row into `out`, classifies the rows on the device and gathers the near rows and
+ * the far rows into two sub-frames in context scratch (a literal side stays a literal); STRSIM_TOKEN_RATIO runs over the near
+ * sub-frame, STRSIM_PARTIAL_RATIO and STRSIM_PARTIAL_TOKEN_RATIO over the far one, and a last kernel writes the rule's result.  A
+ * sub-frame without rows launches nothing.  Scratch beyond the token calls': 5 bytes a row of classes and positions, 8 of lists, one
+ * copy of each gathered column and 8 bytes a sub-score; a failed reservation is STRSIM_ERR_OOM.  None of
+ * these calls is a pending call of strsim_ctx_synchronize; every row is complete in stream order.
+ *
+ * strsim_ctx_last_wratio_rows: how the last completed STRSIM_WRATIO call of the context routed its rows (found by dlsym).  Rows in
+ * neither count had an empty string.  STRSIM_ERR_ARG when ctx is NULL (both counts are set to 0 when given).
+ */
+STRSIM_API int strsim_ctx_last_wratio_rows(strsim_ctx_t *ctx, uint64_t *near_rows, uint64_t *far_rows);
 
 /*
  * Nearest match by bounded edit distance (found by dlsym, like the distance calls: the ABI version stays 1.7, and

@@ -460,7 +460,7 @@ class Combiner {
   private:
     std::mutex m_;
     std::condition_variable cv_;
-    ComboBatch *open_[STRSIM_TOKEN_SET_RATIO + 1] = {}; // indexed by measure id (the ids of strsim_amd.h, 5, 7, 9, 11 .. 13 and 15 unused)
+    ComboBatch *open_[STRSIM_WRATIO + 1] = {}; // indexed by measure id (the ids of strsim_amd.h, 5, 7, 9, 11 .. 13 and the odd ids above unused)
     std::vector<ComboBatch *> free_;
     std::atomic<bool> launch_in_flight_{false};
     uint64_t batches_ = 0, combined_ = 0, max_members_ = 0;

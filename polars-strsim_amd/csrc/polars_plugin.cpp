@@ -534,6 +534,11 @@ POLARS_PLUGIN_DEFINE(indel, STRSIM_INDEL)
 POLARS_PLUGIN_DEFINE(partial_ratio, STRSIM_PARTIAL_RATIO)
 POLARS_PLUGIN_DEFINE(token_sort_ratio, STRSIM_TOKEN_SORT_RATIO)
 POLARS_PLUGIN_DEFINE(token_set_ratio, STRSIM_TOKEN_SET_RATIO)
+POLARS_PLUGIN_DEFINE(token_ratio, STRSIM_TOKEN_RATIO)
+POLARS_PLUGIN_DEFINE(partial_token_sort_ratio, STRSIM_PARTIAL_TOKEN_SORT_RATIO)
+POLARS_PLUGIN_DEFINE(partial_token_set_ratio, STRSIM_PARTIAL_TOKEN_SET_RATIO)
+POLARS_PLUGIN_DEFINE(partial_token_ratio, STRSIM_PARTIAL_TOKEN_RATIO)
+POLARS_PLUGIN_DEFINE(wratio, STRSIM_WRATIO)
 POLARS_PLUGIN_EXPORT(partial_ratio_alignment, run_partial_alignment(inputs, n_inputs, return_value), STRUCT_FIELD(PARTIAL_STRUCT))
 POLARS_PLUGIN_DEFINE_DISTANCE(levenshtein, STRSIM_LEVENSHTEIN)
 POLARS_PLUGIN_DEFINE_DISTANCE(osa, STRSIM_OSA)

@@ -23,6 +23,7 @@
 #include "strsim_indel.h"
 #include "strsim_partial.h"
 #include "strsim_token.h"
+#include "strsim_wratio.h"
 #include "strsim_nearest.h"
 #include "strsim_extract.h"
 
@@ -186,6 +187,16 @@ struct strsim_ctx {
     DevBuf tok_rec;                  // set form: one record a row, then the uint32 distances
     TokenStatus *tok_status = nullptr;      // device
     TokenStatus *tok_status_host = nullptr; // pinned: bounds before the transform, the work-list counts behind it
+
+    // ---- token_ratio, the partial token ratios and WRatio (pairs_weighted; strsim_wratio.h) ----
+    // buffers of their own: the flows a call composes (two_pass, the token transforms) use every buffer above freely
+    DevBuf wr_score;                 // sub-scores: one f64 a row (ids 18, 24); WRatio: near | far x 2 | one more of the longer list
+    DevBuf wr_cls, wr_pos;           // WRatio: a row's class (a byte) and its position on its list
+    DevBuf wr_list[2];               // the near and the far list (one word per row)
+    DevBuf wr_off[2], wr_val[2];     // the gathered sub-frame (near first, then far, in stream order)
+    WratioStatus *wr_status = nullptr;      // device
+    WratioStatus *wr_status_host = nullptr; // pinned: the list counts, read behind the wait of token_bounds
+    uint64_t last_wratio_rows[2] = {};      // strsim_ctx_last_wratio_rows
 };
 
 static int ctx_set_device(strsim_ctx *c) { HIP_TRY(hipSetDevice(c->device)); return STRSIM_OK; }
@@ -468,6 +479,8 @@ void strsim_ctx_destroy(strsim_ctx_t *c)
     if (c->dist_status_host) (void)hipHostFree(c->dist_status_host);
     if (c->tok_status) (void)hipFree(c->tok_status);
     if (c->tok_status_host) (void)hipHostFree(c->tok_status_host);
+    if (c->wr_status) (void)hipFree(c->wr_status);
+    if (c->wr_status_host) (void)hipHostFree(c->wr_status_host);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -797,41 +810,53 @@ static int token_sort_column(strsim_ctx *c, int side, const uint32_t *off, const
     return STRSIM_OK;
 }
 
-// A pairwise call of a token measure.  Sort form: both columns normalised into scratch (a literal stays one row), then the Indel
-// flow into the caller's out, in this call's ring slot.  Set form: ab and ba into scratch at full length, the Indel flow with the
-// unbounded integer distance, then the epilogue; it takes no ring slot (nothing is left to do at retirement).
-static int pairs_token(strsim_ctx *c, int slot, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
-                       const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t n)
+// The two columns of a pairwise call, and what sizes their scratch: upper bounds of each column's bytes and longest row (token_bounds
+// of the columns themselves, or of the columns a sub-frame was gathered from).
+struct PairCols {
+    const uint32_t *a_off; const uint8_t *a_val; uint64_t a_rows;
+    const uint32_t *b_off; const uint8_t *b_val; uint64_t b_rows;
+    uint64_t n;
+};
+struct ColBounds {
+    uint64_t bytes[2];
+    uint32_t max_len[2];
+};
+
+static ColBounds token_col_bounds(const strsim_ctx *c)
 {
-    int rc = token_prepare(c);
-    if (rc) return rc;
-    rc = token_bounds(c, a_off, a_rows, b_off, b_rows);
-    if (rc) return rc;
     const TokenStatus st = *c->tok_status_host;
-    const uint64_t bytes[2] = {(uint64_t)st.end[0] - st.begin[0], (uint64_t)st.end[1] - st.begin[1]};
-    const uint64_t rows[2] = {a_rows, b_rows};
-    if (measure == STRSIM_TOKEN_SORT_RATIO) {
-        const uint32_t *const in_off[2] = {a_off, b_off};
-        const uint8_t *const in_val[2] = {a_val, b_val};
-        for (int s = 0; s < 2; ++s) {
-            rc = c->tok_off[s].reserve((rows[s] + 1) * sizeof(uint32_t));
-            if (rc == STRSIM_OK) rc = c->tok_val[s].reserve(bytes[s] + TOKEN_PAD);
-            if (rc == STRSIM_OK)
-                rc = token_sort_column(c, s, in_off[s], in_val[s], rows[s], st.max_len[s], c->tok_off[s].as<uint32_t>(), c->tok_val[s].as<uint8_t>());
-            if (rc) return rc;
-        }
-        rc = token_copy_counts(c);
+    return ColBounds{{(uint64_t)st.end[0] - st.begin[0], (uint64_t)st.end[1] - st.begin[1]}, {st.max_len[0], st.max_len[1]}};
+}
+
+// The sort form of both columns into c->tok_off / c->tok_val (a literal stays one row); the work-list counters are zero on entry.
+static int token_sort_columns(strsim_ctx *c, const PairCols &p, const ColBounds &bd)
+{
+    const uint64_t rows[2] = {p.a_rows, p.b_rows};
+    const uint32_t *const in_off[2] = {p.a_off, p.b_off};
+    const uint8_t *const in_val[2] = {p.a_val, p.b_val};
+    for (int s = 0; s < 2; ++s) {
+        int rc = c->tok_off[s].reserve((rows[s] + 1) * sizeof(uint32_t));
+        if (rc == STRSIM_OK) rc = c->tok_val[s].reserve(bd.bytes[s] + TOKEN_PAD);
+        if (rc == STRSIM_OK)
+            rc = token_sort_column(c, s, in_off[s], in_val[s], rows[s], bd.max_len[s], c->tok_off[s].as<uint32_t>(), c->tok_val[s].as<uint8_t>());
         if (rc) return rc;
-        return pairs_osa(c, slot, STRSIM_INDEL, c->tok_off[0].as<uint32_t>(), c->tok_val[0].as<uint8_t>(), a_rows, c->tok_off[1].as<uint32_t>(),
-                         c->tok_val[1].as<uint8_t>(), b_rows, out, n);
     }
-    // set form: a difference is never longer than its string; a literal's is materialised for every row
-    const uint64_t cap[2] = {a_rows == 1 ? n * bytes[0] : bytes[0], b_rows == 1 ? n * bytes[1] : bytes[1]};
+    return token_copy_counts(c);
+}
+
+// The set form of p.n pairs: ab and ba into c->tok_off / c->tok_val at full length, the records into *rec, and room for the uint32
+// distances behind them (*d32).  The work-list counters are zero on entry.
+static int token_set_columns(strsim_ctx *c, const PairCols &p, const ColBounds &bd, TokenSetRec **rec_out, uint32_t **d32_out)
+{
+    const uint64_t n = p.n;
+    // a difference is never longer than its string; a literal's is materialised for every row
+    const uint64_t cap[2] = {p.a_rows == 1 ? n * bd.bytes[0] : bd.bytes[0], p.b_rows == 1 ? n * bd.bytes[1] : bd.bytes[1]};
     if (cap[0] > 0xFFFFFFFFull || cap[1] > 0xFFFFFFFFull) {
         set_error("strsim_pairs_device: token_set_ratio with a literal of %llu bytes against %llu rows exceeds 32-bit offsets; split the column",
-                  (unsigned long long)(a_rows == 1 ? bytes[0] : bytes[1]), (unsigned long long)n);
+                  (unsigned long long)(p.a_rows == 1 ? bd.bytes[0] : bd.bytes[1]), (unsigned long long)n);
         return STRSIM_ERR_ARG;
     }
+    int rc = STRSIM_OK;
     for (int s = 0; s < 2; ++s) {
         rc = c->tok_off[s].reserve((n + 1) * sizeof(uint32_t));
         if (rc == STRSIM_OK) rc = c->tok_val[s].reserve(cap[s] + TOKEN_PAD);
@@ -845,14 +870,13 @@ static int pairs_token(strsim_ctx *c, int slot, int measure, const uint32_t *a_o
     int grid;
     uint32_t *scratch;
     uint64_t slot_words;
-    rc = token_wave_scratch(c, token_max_tokens(st.max_len[0]) + token_max_tokens(st.max_len[1]), &grid, &scratch, &slot_words);
+    rc = token_wave_scratch(c, token_max_tokens(bd.max_len[0]) + token_max_tokens(bd.max_len[1]), &grid, &scratch, &slot_words);
     if (rc) return rc;
     uint32_t *const off_ab = c->tok_off[0].as<uint32_t>(), *const off_ba = c->tok_off[1].as<uint32_t>();
     uint8_t *const val_ab = c->tok_val[0].as<uint8_t>(), *const val_ba = c->tok_val[1].as<uint8_t>();
     TokenSetRec *const rec = c->tok_rec.as<TokenSetRec>();
-    uint32_t *const d32 = reinterpret_cast<uint32_t *>(c->tok_rec.as<uint8_t>() + d32_at);
     uint32_t *const list = c->tok_list[0].as<uint32_t>(), *const count = &c->tok_status->wave_rows[0];
-    LaunchArgs in = two_pass_args(c, a_off, a_val, a_rows, b_off, b_val, b_rows, nullptr, n, nullptr);
+    LaunchArgs in = two_pass_args(c, p.a_off, p.a_val, p.a_rows, p.b_off, p.b_val, p.b_rows, nullptr, n, nullptr);
     hipError_t e = launch_token_set(false, in, off_ab, val_ab, off_ba, val_ba, rec, list, count, grid, scratch, slot_words);
     if (e != hipSuccess) return hip_fail(e, "kernel launch (k_token_set_lane / _wave, measuring)");
     e = launch_token_scan(off_ab, n, c->tok_sums.as<uint32_t>(), c->stream);
@@ -861,17 +885,208 @@ static int pairs_token(strsim_ctx *c, int slot, int measure, const uint32_t *a_o
     e = launch_token_set(true, in, off_ab, val_ab, off_ba, val_ba, rec, list, count, grid, scratch, slot_words);
     if (e != hipSuccess) return hip_fail(e, "kernel launch (k_token_set_lane / _wave, writing)");
     c->enqueued_ops += 10u;
-    rc = token_copy_counts(c);
+    *rec_out = rec;
+    *d32_out = reinterpret_cast<uint32_t *>(c->tok_rec.as<uint8_t>() + d32_at);
+    return token_copy_counts(c);
+}
+
+// token_set_ratio of p.n pairs into out: the set columns, the Indel flow with the unbounded integer distance, the epilogue.
+static int token_set_scores(strsim_ctx *c, const PairCols &p, const ColBounds &bd, double *out)
+{
+    TokenSetRec *rec;
+    uint32_t *d32;
+    int rc = token_set_columns(c, p, bd, &rec, &d32);
     if (rc) return rc;
-    rc = dist_prepare(c, n);
+    rc = dist_prepare(c, p.n);
     if (rc) return rc;
-    const LaunchArgs la = two_pass_args(c, off_ab, val_ab, n, off_ba, val_ba, n, nullptr, n, c->dist_status);
+    const LaunchArgs la = two_pass_args(c, c->tok_off[0].as<uint32_t>(), c->tok_val[0].as<uint8_t>(), p.n, c->tok_off[1].as<uint32_t>(),
+                                        c->tok_val[1].as<uint8_t>(), p.n, nullptr, p.n, c->dist_status);
     rc = two_pass(c, la, TwoPassCall{TP_INDEL, STRSIM_INDEL, DIST_UNBOUNDED, d32, nullptr}, -1);
     if (rc) return rc;
-    e = launch_token_set_epilogue(rec, d32, out, n, c->stream);
+    const hipError_t e = launch_token_set_epilogue(rec, d32, out, p.n, c->stream);
     if (e != hipSuccess) return hip_fail(e, "kernel launch (k_token_set_epilogue)");
     c->enqueued_ops += 1u;
     return STRSIM_OK;
+}
+
+// A pairwise call of a token measure.  Sort form: both columns normalised into scratch (a literal stays one row), then the Indel
+// flow into the caller's out, in this call's ring slot.  Set form: ab and ba into scratch at full length, the Indel flow with the
+// unbounded integer distance, then the epilogue; it takes no ring slot (nothing is left to do at retirement).
+static int pairs_token(strsim_ctx *c, int slot, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
+                       const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t n)
+{
+    int rc = token_prepare(c);
+    if (rc) return rc;
+    rc = token_bounds(c, a_off, a_rows, b_off, b_rows);
+    if (rc) return rc;
+    const ColBounds bd = token_col_bounds(c);
+    const PairCols p{a_off, a_val, a_rows, b_off, b_val, b_rows, n};
+    if (measure == STRSIM_TOKEN_SET_RATIO) return token_set_scores(c, p, bd, out);
+    rc = token_sort_columns(c, p, bd);
+    if (rc) return rc;
+    return pairs_osa(c, slot, STRSIM_INDEL, c->tok_off[0].as<uint32_t>(), c->tok_val[0].as<uint8_t>(), a_rows, c->tok_off[1].as<uint32_t>(),
+                     c->tok_val[1].as<uint8_t>(), b_rows, out, n);
+}
+
+// ---- token_ratio, the partial token ratios and WRatio (strsim_wratio.h) ----
+//
+// Compositions of the flows above.  None takes a ring slot: every two_pass below reports through dist_status, and nothing is left
+// to do at retirement.  A composition reads the bounds of its raw columns once (token_bounds, one wait); the sub-frames of WRatio are
+// sized by the bounds of the columns they were gathered from.
+
+// The work-list counters of the token transforms, which token_bounds zeroes for the first transform of a call only.
+static int token_zero_counts(strsim_ctx *c)
+{
+    HIP_TRY(hipMemsetAsync(c->tok_status->wave_rows, 0, 2 * sizeof(uint32_t), c->stream));
+    c->enqueued_ops += 1u;
+    return STRSIM_OK;
+}
+
+// Indel similarity (TP_INDEL) or partial ratio (TP_PARTIAL) of p.n pairs into out.
+static int two_pass_scores(strsim_ctx *c, const PairCols &p, TwoPassKind kind, double *out)
+{
+    int rc = dist_prepare(c, p.n);
+    if (rc) return rc;
+    const LaunchArgs la = two_pass_args(c, p.a_off, p.a_val, p.a_rows, p.b_off, p.b_val, p.b_rows, out, p.n, c->dist_status);
+    if (kind == TP_PARTIAL) return two_pass(c, la, TwoPassCall{TP_PARTIAL, STRSIM_PARTIAL_RATIO, 0u, nullptr, nullptr}, -1);
+    return two_pass(c, la, TwoPassCall{TP_INDEL, STRSIM_INDEL, DIST_UNBOUNDED, nullptr, nullptr}, -1);
+}
+
+// token_sort_ratio (TP_INDEL) or partial_token_sort_ratio (TP_PARTIAL) into out
+static int token_sort_scores(strsim_ctx *c, const PairCols &p, const ColBounds &bd, TwoPassKind kind, double *out)
+{
+    int rc = token_zero_counts(c);
+    if (rc == STRSIM_OK) rc = token_sort_columns(c, p, bd);
+    if (rc) return rc;
+    const PairCols t{c->tok_off[0].as<uint32_t>(), c->tok_val[0].as<uint8_t>(), p.a_rows, c->tok_off[1].as<uint32_t>(), c->tok_val[1].as<uint8_t>(),
+                     p.b_rows, p.n};
+    return two_pass_scores(c, t, kind, out);
+}
+
+// partial_token_set_ratio into out: the set columns, partial ratio of ab and ba into out, the rule over the records in place
+static int partial_token_set_scores(strsim_ctx *c, const PairCols &p, const ColBounds &bd, double *out)
+{
+    TokenSetRec *rec;
+    uint32_t *d32;
+    int rc = token_zero_counts(c);
+    if (rc == STRSIM_OK) rc = token_set_columns(c, p, bd, &rec, &d32);
+    if (rc) return rc;
+    const PairCols t{c->tok_off[0].as<uint32_t>(), c->tok_val[0].as<uint8_t>(), p.n, c->tok_off[1].as<uint32_t>(), c->tok_val[1].as<uint8_t>(), p.n,
+                     p.n};
+    rc = two_pass_scores(c, t, TP_PARTIAL, out);
+    if (rc) return rc;
+    const hipError_t e = launch_partial_token_set_epilogue(rec, out, out, p.n, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "kernel launch (k_partial_token_set_epilogue)");
+    c->enqueued_ops += 1u;
+    return STRSIM_OK;
+}
+
+// token_ratio (partial = false) or partial_token_ratio (partial = true) into out; tmp: p.n more f64
+static int token_max_scores(strsim_ctx *c, const PairCols &p, const ColBounds &bd, bool partial, double *out, double *tmp)
+{
+    int rc = token_sort_scores(c, p, bd, partial ? TP_PARTIAL : TP_INDEL, out);
+    if (rc) return rc;
+    if (partial) rc = partial_token_set_scores(c, p, bd, tmp);
+    else {
+        rc = token_zero_counts(c);
+        if (rc == STRSIM_OK) rc = token_set_scores(c, p, bd, tmp);
+    }
+    if (rc) return rc;
+    const hipError_t e = launch_max_f64(out, tmp, out, p.n, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "kernel launch (k_max_f64)");
+    c->enqueued_ops += 1u;
+    return STRSIM_OK;
+}
+
+static int wratio_prepare(strsim_ctx *c)
+{
+    if (!c->wr_status) HIP_TRY(hipMalloc((void **)&c->wr_status, sizeof(WratioStatus)));
+    if (!c->wr_status_host) HIP_TRY(hipHostMalloc((void **)&c->wr_status_host, sizeof(WratioStatus), hipHostMallocDefault));
+    return STRSIM_OK;
+}
+
+// WRatio of p.n pairs into out: Indel over every row, the classes and the two lists, then each family over the gather of its rows.
+static int pairs_wratio(strsim_ctx *c, const PairCols &p, double *out)
+{
+    const uint64_t n = p.n;
+    int rc = wratio_prepare(c);
+    if (rc == STRSIM_OK) rc = c->wr_cls.reserve(n);
+    if (rc == STRSIM_OK) rc = c->wr_pos.reserve(n * sizeof(uint32_t));
+    for (int f = 0; f < 2 && rc == STRSIM_OK; ++f) rc = c->wr_list[f].reserve(n * sizeof(uint32_t));
+    if (rc) return rc;
+    rc = two_pass_scores(c, p, TP_INDEL, out);
+    if (rc) return rc;
+    uint8_t *const cls = c->wr_cls.as<uint8_t>();
+    uint32_t *const pos = c->wr_pos.as<uint32_t>();
+    uint32_t *const list[2] = {c->wr_list[0].as<uint32_t>(), c->wr_list[1].as<uint32_t>()};
+    const LaunchArgs la = two_pass_args(c, p.a_off, p.a_val, p.a_rows, p.b_off, p.b_val, p.b_rows, out, n, nullptr);
+    HIP_TRY(hipMemsetAsync(c->wr_status, 0, sizeof(WratioStatus), c->stream));
+    hipError_t e = launch_wratio_classify(la, cls, pos, list[0], list[1], c->wr_status);
+    if (e != hipSuccess) return hip_fail(e, "kernel launch (k_wratio_classify)");
+    HIP_TRY(hipMemcpyAsync(c->wr_status_host, c->wr_status, sizeof(WratioStatus), hipMemcpyDeviceToHost, c->stream));
+    c->enqueued_ops += 3u;
+    rc = token_bounds(c, p.a_off, p.a_rows, p.b_off, p.b_rows); // (the list counts ride on this wait)
+    if (rc) return rc;
+    const ColBounds bd = token_col_bounds(c);
+    const uint64_t m[2] = {c->wr_status_host->rows[0], c->wr_status_host->rows[1]};
+    const uint64_t longer = std::max(m[0], m[1]);
+    // sub-scores: token_ratio of the near rows | partial_ratio, partial_token_ratio of the far rows | one column of the longer list
+    rc = c->wr_score.reserve((m[0] + 2u * m[1] + longer) * sizeof(double));
+    if (rc == STRSIM_OK) rc = c->tok_sums.reserve(((longer + 4095u) / 4096u) * sizeof(uint32_t));
+    const uint64_t rows[2] = {p.a_rows, p.b_rows};
+    for (int s = 0; s < 2 && rc == STRSIM_OK; ++s) {
+        if (rows[s] == 1) continue; // a literal is not gathered
+        rc = c->wr_off[s].reserve((longer + 1) * sizeof(uint32_t));
+        if (rc == STRSIM_OK) rc = c->wr_val[s].reserve(bd.bytes[s] + TOKEN_PAD);
+    }
+    if (rc) return rc;
+    double *const s_near = c->wr_score.as<double>(), *const s_far0 = s_near + m[0], *const s_far1 = s_far0 + m[1], *const tmp = s_far1 + m[1];
+    const uint32_t *const in_off[2] = {p.a_off, p.b_off};
+    const uint8_t *const in_val[2] = {p.a_val, p.b_val};
+    for (int f = 0; f < 2; ++f) {
+        if (m[f] == 0) continue; // a family without rows launches nothing
+        PairCols sub{p.a_off, p.a_val, p.a_rows, p.b_off, p.b_val, p.b_rows, m[f]};
+        for (int s = 0; s < 2; ++s) {
+            if (rows[s] == 1) continue;
+            uint32_t *const g_off = c->wr_off[s].as<uint32_t>();
+            uint8_t *const g_val = c->wr_val[s].as<uint8_t>();
+            e = launch_take(in_off[s], in_val[s], list[f], (uint32_t)m[f], g_off, g_val, c->tok_sums.as<uint32_t>(), c->stream);
+            if (e != hipSuccess) return hip_fail(e, "kernel launch (k_take_measure / k_token_scan / k_take_write)");
+            c->enqueued_ops += 5u;
+            if (s == 0) { sub.a_off = g_off; sub.a_val = g_val; sub.a_rows = m[f]; }
+            else { sub.b_off = g_off; sub.b_val = g_val; sub.b_rows = m[f]; }
+        }
+        if (f == 0) rc = token_max_scores(c, sub, bd, false, s_near, tmp);
+        else {
+            rc = two_pass_scores(c, sub, TP_PARTIAL, s_far0);
+            if (rc == STRSIM_OK) rc = token_max_scores(c, sub, bd, true, s_far1, tmp);
+        }
+        if (rc) return rc;
+    }
+    e = launch_wratio_combine(la, cls, pos, s_near, s_far0, s_far1);
+    if (e != hipSuccess) return hip_fail(e, "kernel launch (k_wratio_combine)");
+    c->enqueued_ops += 1u;
+    c->last_wratio_rows[0] = m[0];
+    c->last_wratio_rows[1] = m[1];
+    return STRSIM_OK;
+}
+
+// A pairwise call of one of the five: ids 18 .. 24 over the whole frame, WRatio routed.
+static int pairs_weighted(strsim_ctx *c, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
+                          const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t n)
+{
+    int rc = token_prepare(c);
+    if (rc) return rc;
+    const PairCols p{a_off, a_val, a_rows, b_off, b_val, b_rows, n};
+    if (measure == STRSIM_WRATIO) return pairs_wratio(c, p, out);
+    rc = token_bounds(c, a_off, a_rows, b_off, b_rows);
+    if (rc) return rc;
+    const ColBounds bd = token_col_bounds(c);
+    if (measure == STRSIM_PARTIAL_TOKEN_SORT_RATIO) return token_sort_scores(c, p, bd, TP_PARTIAL, out);
+    if (measure == STRSIM_PARTIAL_TOKEN_SET_RATIO) return partial_token_set_scores(c, p, bd, out);
+    rc = c->wr_score.reserve(n * sizeof(double));
+    if (rc) return rc;
+    return token_max_scores(c, p, bd, measure == STRSIM_PARTIAL_TOKEN_RATIO, out, c->wr_score.as<double>());
 }
 
 static int pairs_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
@@ -910,6 +1125,7 @@ static int pairs_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_off
     if (two_pass_measure(measure)) return pairs_osa(c, slot, measure, a_off, a_val, a_rows, b_off, b_val, b_rows, outs[0], n);
     if (measure == STRSIM_TOKEN_SORT_RATIO || measure == STRSIM_TOKEN_SET_RATIO)
         return pairs_token(c, slot, measure, a_off, a_val, a_rows, b_off, b_val, b_rows, outs[0], n);
+    if (weighted_measure(measure)) return pairs_weighted(c, measure, a_off, a_val, a_rows, b_off, b_val, b_rows, outs[0], n);
     const uint64_t nchunks = (n + 63) >> 6;
     // One launch (the lane kernel alone, the rest at retirement if it turns out to be needed) when the caller has opted in and the
     // context's last retired call left nothing behind its lane kernel.  Such a call owns a mask buffer until it is retired (there
@@ -1626,6 +1842,14 @@ uint64_t strsim_ctx_last_token_wave_rows(strsim_ctx_t *c)
     if (!c || !c->tok_status_host) return 0;
     const volatile uint32_t *w = c->tok_status_host->wave_rows;
     return (uint64_t)w[0] + w[1];
+}
+
+int strsim_ctx_last_wratio_rows(strsim_ctx_t *c, uint64_t *near_rows, uint64_t *far_rows)
+{
+    if (near_rows) *near_rows = c ? c->last_wratio_rows[0] : 0;
+    if (far_rows) *far_rows = c ? c->last_wratio_rows[1] : 0;
+    if (!c) { set_error("strsim_ctx_last_wratio_rows: ctx is NULL"); return STRSIM_ERR_ARG; }
+    return STRSIM_OK;
 }
 
 } // extern "C"

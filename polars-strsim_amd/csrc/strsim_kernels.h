@@ -161,6 +161,20 @@ hipError_t launch_token_scan(uint32_t *out_off, uint64_t rows, uint32_t *sums, h
 // out[i] = the rule of token_set_ratio over rec[i] and d32[i] = indel_distance(ab, ba)
 hipError_t launch_token_set_epilogue(const TokenSetRec *rec, const uint32_t *d32, double *out, uint64_t n, hipStream_t stream);
 
+// WRatio and the token compositions (strsim_wratio.h), measure ids 18 .. 26.  launch_wratio_classify: the class of each of a.n
+// pairs into cls, its position on the near or the far list into pos, the lists counted in st->rows (zeroed first).  launch_take: the
+// m rows `list` names of the column (off, val) as a column of their own -- lengths, launch_token_scan (sums: ceil(m / 4096) words),
+// copy; out_val holds the column's byte size.  launch_wratio_combine: a.out holds indel(a, b) and receives the rule's result.
+struct WratioStatus;
+hipError_t launch_wratio_classify(const LaunchArgs &a, uint8_t *cls, uint32_t *pos, uint32_t *list_near, uint32_t *list_far, WratioStatus *st);
+hipError_t launch_take(const uint32_t *off, const uint8_t *val, const uint32_t *list, uint32_t m, uint32_t *out_off, uint8_t *out_val,
+                       uint32_t *sums, hipStream_t stream);
+hipError_t launch_wratio_combine(const LaunchArgs &a, const uint8_t *cls, const uint32_t *pos, const double *s_near, const double *s_far0,
+                                 const double *s_far1);
+hipError_t launch_max_f64(const double *x, const double *y, double *out, uint64_t n, hipStream_t stream);
+// out[i] = the rule of partial_token_set_ratio over rec[i] and p[i] = partial_ratio(ab, ba)
+hipError_t launch_partial_token_set_epilogue(const TokenSetRec *rec, const double *p, double *out, uint64_t n, hipStream_t stream);
+
 // Nearest match by bounded edit distance (strsim_nearest_kernels.h), measure 0 (Levenshtein) or 6 (OSA).  The strings of both
 // sides are packed by launch_match_pack first; launch_nearest_order then puts them in length order on the device (histograms,
 // scan, scatter; the histograms must be zeroed), and launch_nearest_lane writes splits x nq x match_lane_k(k) partial lists in

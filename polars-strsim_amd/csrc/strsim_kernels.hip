@@ -33,6 +33,10 @@
 //   k_token_sort_* / k_token_set_*  token_sort_ratio and token_set_ratio (measures 14 and 16, strsim_token.h): tokenise, sort and
 //                     join (or merge as sets) every string into scratch columns that k_indel_lane / k_indel_wave then align;
 //                     ASCII strings of up to 64 bytes and 16 tokens per lane, the rest one string per wave.
+//   k_wratio_classify / k_take_* / k_wratio_combine  WRatio (measure 26, strsim_wratio.h): a row's class from the lengths of its
+//                     raw strings, the near and the far rows gathered into sub-frames for the token and the partial family, the
+//                     rule per row; k_max_f64 and k_partial_token_set_epilogue close token_ratio and the partial token ratios
+//                     (measures 18 .. 24), which are compositions of the kernels above.
 //   k_nearest_lane<TR, K> / k_extract_lane<K>  the two length-ordered searches, one sweep (search_sweep_lane,
 //                     strsim_nearest_kernels.h) under two rule sets: one query per lane in length order against wave-uniform
 //                     candidates, a candidate length window and a running bound per lane.  Nearest match by bounded edit
@@ -61,6 +65,7 @@
 #include "strsim_indel.h"
 #include "strsim_partial.h"
 #include "strsim_token.h"
+#include "strsim_wratio.h"
 #include "strsim_nearest.h"
 #include "strsim_extract.h"
 
@@ -675,6 +680,43 @@ hipError_t launch_token_scan(uint32_t *out_off, uint64_t rows, uint32_t *sums, h
 hipError_t launch_token_set_epilogue(const TokenSetRec *rec, const uint32_t *d32, double *out, uint64_t n, hipStream_t stream)
 {
     hipLaunchKernelGGL(k_token_set_epilogue, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, stream, rec, d32, out, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_wratio_classify(const LaunchArgs &a, uint8_t *cls, uint32_t *pos, uint32_t *list_near, uint32_t *list_far, WratioStatus *st)
+{
+    hipLaunchKernelGGL(k_wratio_classify, dim3((unsigned)((a.n + 255u) / 256u)), dim3(256), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB,
+                       a.rowsB, a.n, cls, pos, list_near, list_far, st);
+    return hipGetLastError();
+}
+
+hipError_t launch_take(const uint32_t *off, const uint8_t *val, const uint32_t *list, uint32_t m, uint32_t *out_off, uint8_t *out_val,
+                       uint32_t *sums, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_take_measure, dim3((unsigned)(((uint64_t)m + 255u) / 256u)), dim3(256), 0, stream, off, list, m, out_off);
+    hipError_t e = launch_token_scan(out_off, m, sums, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_take_write, dim3((unsigned)(((uint64_t)m * TAKE_LANES + 255u) / 256u)), dim3(256), 0, stream, off, val, list, m, out_off,
+                       out_val);
+    return hipGetLastError();
+}
+
+hipError_t launch_wratio_combine(const LaunchArgs &a, const uint8_t *cls, const uint32_t *pos, const double *s_near, const double *s_far0,
+                                 const double *s_far1)
+{
+    hipLaunchKernelGGL(k_wratio_combine, dim3((unsigned)((a.n + 255u) / 256u)), dim3(256), 0, a.stream, cls, pos, s_near, s_far0, s_far1, a.out, a.n);
+    return hipGetLastError();
+}
+
+hipError_t launch_max_f64(const double *x, const double *y, double *out, uint64_t n, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_max_f64, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, stream, x, y, out, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_partial_token_set_epilogue(const TokenSetRec *rec, const double *p, double *out, uint64_t n, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_partial_token_set_epilogue, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, stream, rec, p, out, n);
     return hipGetLastError();
 }
 

@@ -145,6 +145,42 @@ def token_set_ratio(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
     return _similarity("token_set_ratio", expr, other)
 
 
+def token_ratio(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
+    """rapidfuzz `fuzz.token_ratio` / 100: the larger of `token_sort_ratio` and `token_set_ratio` of the pair.
+    Not in the upstream polars-strsim."""
+    return _similarity("token_ratio", expr, other)
+
+
+def partial_token_sort_ratio(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
+    """rapidfuzz `fuzz.partial_token_sort_ratio` / 100: `partial_ratio` of the two strings with their tokens sorted (split, sorted
+    and joined as for `token_sort_ratio`).  Not in the upstream polars-strsim."""
+    return _similarity("partial_token_sort_ratio", expr, other)
+
+
+def partial_token_set_ratio(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
+    """rapidfuzz `fuzz.partial_token_set_ratio` / 100 over the sets of tokens: 0.0 when either string has no token, 1.0 when the
+    sets share a token, else `partial_ratio` of the two joined sorted differences.  Not in the upstream polars-strsim."""
+    return _similarity("partial_token_set_ratio", expr, other)
+
+
+def partial_token_ratio(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
+    """rapidfuzz `fuzz.partial_token_ratio` / 100: the larger of `partial_token_sort_ratio` and `partial_token_set_ratio`.
+    Not in the upstream polars-strsim."""
+    return _similarity("partial_token_ratio", expr, other)
+
+
+def wratio(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
+    """rapidfuzz `fuzz.WRatio` / 100, the default scorer of `process.extract`, without a processor (no lower-casing).
+
+    With lo and hi the shorter and the longer length in characters and r = `indel`: 0.0 when a string is empty; when
+    2 hi < 3 lo, max(r, `token_ratio` * 0.95); otherwise max(r, `partial_ratio` * ps, `partial_token_ratio` * 0.95 * ps) with
+    ps = 0.9 when hi <= 8 lo and 0.6 beyond.  `"this is a test"` against `"this is a new test!!!"` scores 0.855.  The GPU sorts
+    the rows into the two classes first and runs each family of scores over its own rows only.
+    Not in the upstream polars-strsim.
+    """
+    return _similarity("wratio", expr, other)
+
+
 def _distance(function_name: str, expr: IntoExpr, other: IntoExpr, max_distance: int | None) -> pl.Expr:
     args = [parse_into_expr(expr), other]
     if max_distance is not None:
@@ -191,6 +227,11 @@ __all__ = [
     "partial_ratio_alignment",
     "token_sort_ratio",
     "token_set_ratio",
+    "token_ratio",
+    "partial_token_sort_ratio",
+    "partial_token_set_ratio",
+    "partial_token_ratio",
+    "wratio",
     "levenshtein",
     "jaro",
     "jaro_winkler",

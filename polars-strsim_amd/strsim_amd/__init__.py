@@ -8,7 +8,7 @@ validity mask), as in README.md:69-70.
 """
 import numpy as np
 
-from ._lib import DISTANCE_MEASURES, DISTANCE_UNBOUNDED, ENTRY_POINT_ID, EXTRA_MEASURES, INDEL_MEASURES, MEASURES, MEASURE_ID, PARTIAL_MEASURES, TOKEN_MEASURES, LIB_PATH, STATUS, ShapeMismatch, StrsimError, lib
+from ._lib import DISTANCE_MEASURES, DISTANCE_UNBOUNDED, ENTRY_POINT_ID, EXTRA_MEASURES, INDEL_MEASURES, MEASURES, MEASURE_ID, PARTIAL_MEASURES, TOKEN_MEASURES, WEIGHTED_MEASURES, LIB_PATH, STATUS, ShapeMismatch, StrsimError, lib
 from .context import Codec, Context, device_count, pack_strings, split_offsets
 
 _default_ctx = None
@@ -144,6 +144,36 @@ def token_set_ratio(a, b, ctx=None):
     return similarity("token_set_ratio", a, b, ctx)
 
 
+def token_ratio(a, b, ctx=None):
+    """rapidfuzz's fuzz.token_ratio / 100: max(token_sort_ratio(a, b), token_set_ratio(a, b))."""
+    return similarity("token_ratio", a, b, ctx)
+
+
+def partial_token_sort_ratio(a, b, ctx=None):
+    """rapidfuzz's fuzz.partial_token_sort_ratio / 100: partial_ratio() of the two strings with their tokens sorted (split, sorted
+    and joined as for token_sort_ratio)."""
+    return similarity("partial_token_sort_ratio", a, b, ctx)
+
+
+def partial_token_set_ratio(a, b, ctx=None):
+    """rapidfuzz's fuzz.partial_token_set_ratio / 100 over the SETS of tokens: 0.0 when either string has no token, 1.0 when the
+    sets share a token, else partial_ratio() of the joined sorted differences."""
+    return similarity("partial_token_set_ratio", a, b, ctx)
+
+
+def partial_token_ratio(a, b, ctx=None):
+    """rapidfuzz's fuzz.partial_token_ratio / 100: max(partial_token_sort_ratio(a, b), partial_token_set_ratio(a, b))."""
+    return similarity("partial_token_ratio", a, b, ctx)
+
+
+def wratio(a, b, ctx=None):
+    """rapidfuzz's fuzz.WRatio / 100 (the default scorer of process.extract), without a processor.  With lo, hi the shorter and
+    the longer length in characters and r = indel(a, b): 0.0 when lo == 0; when 2 hi < 3 lo: max(r, token_ratio * 0.95);
+    otherwise, with ps = 0.9 when hi <= 8 lo and 0.6 beyond: max(r, partial_ratio * ps, (partial_token_ratio * 0.95) * ps).
+    The rows are classified on the GPU and each family runs over its own rows only (Context.last_wratio_rows())."""
+    return similarity("wratio", a, b, ctx)
+
+
 def token_sort(col, ctx=None):
     """The normalisation of token_sort_ratio on its own: a list of str or None -> a list of str or None, each string
     " ".join(sorted(s.split())) computed on the GPU.  indel(token_sort(a), token_sort(b)) is token_sort_ratio(a, b); best_match
@@ -199,7 +229,7 @@ def best_match(measure, queries, candidates, k=1, min_score=None, ctx=None):
     """For every query, its k best candidates by `measure`: (index int64 [N, k], score f64 [N, k]).  Slots in descending order
     of the score, ties to the lower candidate index; a candidate below min_score is not reported.  Empty slots -- and every slot
     of a null query -- are (-1, NaN).  Null candidates are never matched; indices refer to the caller's candidate positions."""
-    if measure in INDEL_MEASURES + PARTIAL_MEASURES + TOKEN_MEASURES:
+    if measure in INDEL_MEASURES + PARTIAL_MEASURES + TOKEN_MEASURES + WEIGHTED_MEASURES:
         raise ValueError(f"no best match by measure {measure!r} (one of {MEASURES})")
     ctx = ctx or default_context()
     Q, vq = _as_column(queries)
@@ -257,5 +287,6 @@ __all__ = ["best_match", "nearest", "Codec", "Context", "device_count", "pack_st
            "jaro_winkler", "jaccard", "sorensen_dice", "osa", "indel", "measure_supported", "distance", "levenshtein_distance", "osa_distance",
            "indel_distance", "INDEL_MEASURES", "partial_ratio", "partial_ratio_alignment", "PARTIAL_MEASURES",
            "token_sort_ratio", "token_set_ratio", "token_sort", "TOKEN_MEASURES",
+           "token_ratio", "partial_token_sort_ratio", "partial_token_set_ratio", "partial_token_ratio", "wratio", "WEIGHTED_MEASURES",
            "DISTANCE_MEASURES", "DISTANCE_UNBOUNDED", "MEASURES", "EXTRA_MEASURES", "MEASURE_ID", "STATUS", "ShapeMismatch", "StrsimError",
            "extract", "EXTRACT_SCORERS"]

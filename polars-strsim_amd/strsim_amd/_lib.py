@@ -30,6 +30,12 @@ MEASURE_ID["partial_ratio"] = 10
 TOKEN_MEASURES = ("token_sort_ratio", "token_set_ratio")
 MEASURE_ID["token_sort_ratio"] = 14
 MEASURE_ID["token_set_ratio"] = 16
+# token_ratio = 18, partial_token_sort_ratio = 20, partial_token_set_ratio = 22, partial_token_ratio = 24, wratio = STRSIM_WRATIO = 26
+# (the odd ids in between stay unassigned): compositions of the measures above, pairwise entry points only.  wratio is rapidfuzz's
+# WRatio / 100; the library classifies the rows on the device and runs each family of sub-scores over its own rows.
+WEIGHTED_MEASURES = ("token_ratio", "partial_token_sort_ratio", "partial_token_set_ratio", "partial_token_ratio", "wratio")
+for _i, _m in enumerate(WEIGHTED_MEASURES):
+    MEASURE_ID[_m] = 18 + 2 * _i
 ENTRY_POINT_ID = {"pairwise": 0, "best_match": 1, "codec": 2}  # strsim_entry_point_t
 # The measures strsim_distance_device / _host accept (integer edit distances), with their ids; STRSIM_DISTANCE_UNBOUNDED = no cutoff.
 DISTANCE_MEASURES = ("levenshtein", "osa")
@@ -101,7 +107,7 @@ def lib():
     L.strsim_ctx_destroy.argtypes = [vp]
     L.strsim_ctx_stream.restype = vp
     L.strsim_ctx_stream.argtypes = [vp]
-    for name in ("strsim_pairs_device", "strsim_pairs_host"):
+    for name in ("strsim_pairs_device", "strsim_pairs_device_small", "strsim_pairs_host"):
         f = getattr(L, name)
         f.restype = i32
         f.argtypes = [vp, i32, vp, vp, u64, vp, vp, u64, vp, u64]
@@ -123,6 +129,8 @@ def lib():
         f.argtypes = [vp, vp, vp, u64, vp, vp, u64]
     L.strsim_ctx_last_token_wave_rows.restype = u64
     L.strsim_ctx_last_token_wave_rows.argtypes = [vp]
+    L.strsim_ctx_last_wratio_rows.restype = i32
+    L.strsim_ctx_last_wratio_rows.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     for name in ("strsim_nearest_device", "strsim_nearest_host"):
         f = getattr(L, name)
         f.restype = i32

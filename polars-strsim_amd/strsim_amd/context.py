@@ -85,6 +85,13 @@ class Context:
         that call (synchronize())."""
         return int(lib().strsim_ctx_last_token_wave_rows(self._h))
 
+    def last_wratio_rows(self):
+        """-> (near, far): how the last completed wratio call routed its rows -- to the token family (2 hi < 3 lo in characters)
+        or to the partial family; rows in neither count had an empty string."""
+        near, far = C.c_uint64(), C.c_uint64()
+        check(lib().strsim_ctx_last_wratio_rows(self._h, C.byref(near), C.byref(far)))
+        return int(near.value), int(far.value)
+
     @property
     def last_late_rows(self):
         """Rows finished by a pass that the last synchronize() / retire_oldest() launched (slow rows of a one-launch call,
