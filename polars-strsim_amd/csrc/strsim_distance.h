@@ -9,7 +9,8 @@
 //   k_dist_lane<TR, LIT>  one pair per lane, both strings ASCII and <= 64 bytes: the lane class, bit-planes and text walk of
 //                         k_osa_lane; TR = 1 adds the transposition term (OSA), TR = 0 is Myers' step.  A pair whose lengths
 //                         differ by more than k is k + 1 without the DP.  Every other row goes to a work list.
-//   k_dist_wave<TR>       one pair per wave for the work list: any UTF-8, any length, the decode and pattern storage of k_osa_wave.
+//   k_dist_wave<TR>       one pair per wave for the work list: any UTF-8, any length, the decode and pattern storage of k_osa_wave
+//                         and its word step (osa_word_step).
 //                         With a cutoff only the words 0..y of a column are advanced (the block cutoff of Myers 1999, section 4,
 //                         as in edlib), y being the last word that may still hold a cell <= k (dist_column below).
 #pragma once
@@ -116,32 +117,8 @@ STRSIM_HD void dist_column(DistWord *st, int &y, uint32_t W, uint64_t k, uint64_
     }
     uint64_t add_c = 0ull, hp_c = 1ull, hn_c = 0ull, tr_c = 0ull;
     for (int w = 0; w <= y; ++w) {
-        const uint64_t Eq = eq((uint32_t)w);
         DistWord &s = st[w];
-        const uint64_t VP = s.VP, VN = s.VN;
-        uint64_t TRw = 0ull;
-        if constexpr (TR) {
-            const uint64_t t = ~s.D0p & Eq;
-            TRw = ((t << 1) | tr_c) & s.EQp;
-            tr_c = t >> 63;
-        }
-        const uint64_t x = Eq & VP;
-        const uint64_t s1 = x + VP;
-        const uint64_t s2 = s1 + add_c;
-        add_c = (uint64_t)(s1 < x) | (uint64_t)(s2 < s1);
-        const uint64_t D0 = (s2 ^ VP) | Eq | VN | TRw;
-        const uint64_t HP = VN | ~(D0 | VP);
-        const uint64_t HN = D0 & VP;
-        const uint64_t X = (HP << 1) | hp_c;
-        hp_c = HP >> 63;
-        const uint64_t Y = (HN << 1) | hn_c;
-        hn_c = HN >> 63;
-        s.VP = Y | ~(D0 | X);
-        s.VN = D0 & X;
-        if constexpr (TR) {
-            s.D0p = D0;
-            s.EQp = Eq;
-        }
+        osa_word_step<TR>(eq((uint32_t)w), s.VP, s.VN, s.D0p, s.EQp, add_c, hp_c, hn_c, tr_c);
         s.score = s.score + hp_c - hn_c;
     }
     if (bounded)
@@ -169,7 +146,7 @@ STRSIM_HD uint64_t dist_final(const DistWord *st, int y, uint32_t W, uint64_t m,
 
 // One pair per lane (k_osa_lane's classes and text walk).  TR: 1 = OSA, 0 = Levenshtein.  LIT as k_osa_lane.  A row whose
 // lengths differ by more than k is k + 1 without the DP, and a wave of such rows runs no columns.  Rows this kernel cannot take
-// are appended to `worklist` (st->wave_rows, st->max_len as in k_osa_lane); the status block is zeroed before the launch.
+// are appended to `worklist` (worklist_append of strsim_wave_util.h); the status block is zeroed before the launch.
 template <bool TR, int LIT>
 __global__ __launch_bounds__(256) void k_dist_lane(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ valA,
                                                    const uint32_t *__restrict__ offB, const uint8_t *__restrict__ valB, uint64_t n,
@@ -194,20 +171,7 @@ __global__ __launch_bounds__(256) void k_dist_lane(const uint32_t *__restrict__ 
         ascii = (osa_high_bits(wp) | osa_high_bits(wt)) == 0u;
     }
     const uint32_t cls = dist_lane_row(live, la, lb, ascii, k);
-    const bool slow = cls == DIST_ROW_WAVE;
-    const uint64_t sm = __ballot(slow);
-    if (sm) {
-        const uint32_t lane = threadIdx.x & 63u;
-        const uint32_t first = (uint32_t)__ffsll((unsigned long long)sm) - 1u;
-        const uint32_t bound = osa_wave_max(slow ? (la < lb ? la : lb) : 0u);
-        uint32_t base = 0u;
-        if (lane == first) {
-            base = atomicAdd(&st->wave_rows, (uint32_t)__popcll(sm));
-            atomicMax(&st->max_len, bound);
-        }
-        base = (uint32_t)__shfl((int)base, (int)first, 64);
-        if (slow) worklist[base + (uint32_t)__popcll(sm & ((1ull << lane) - 1ull))] = (uint32_t)row;
-    }
+    worklist_append<false>(cls == DIST_ROW_WAVE, row, la, lb, worklist, st);
     if (cls == DIST_ROW_CUT) out[row] = k + 1u;
     const bool run = cls == DIST_ROW_RUN;
     if (__ballot(run) == 0ull) return;
@@ -234,11 +198,7 @@ __global__ __launch_bounds__(64) void k_dist_wave(const uint32_t *__restrict__ o
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t count = st->wave_rows;
     for (uint32_t r = blockIdx.x; r < count; r += gridDim.x) {
-        const uint32_t row = worklist[r];
-        const uint64_t ia = rowsA == 1 ? 0 : row, ib = rowsB == 1 ? 0 : row;
-        const uint8_t *pa = valA + offA[ia], *pb = valB + offB[ib];
-        const uint32_t na = offA[ia + 1] - offA[ia], nb = offB[ib + 1] - offB[ib];
-        const uint32_t ca = osa_count_chars(pa, na), cb = osa_count_chars(pb, nb);
+        const auto [row, pa, pb, na, nb, ca, cb] = wave_pair(offA, valA, rowsA, offB, valB, rowsB, worklist[r]);
         const bool a_is_pat = ca <= cb;
         const uint8_t *pp = a_is_pat ? pa : pb, *tp = a_is_pat ? pb : pa;
         const uint32_t pbytes = a_is_pat ? na : nb, tbytes = a_is_pat ? nb : na;
@@ -255,33 +215,18 @@ __global__ __launch_bounds__(64) void k_dist_wave(const uint32_t *__restrict__ o
                 pat = scratch + (uint64_t)blockIdx.x * slot_words;
                 state = reinterpret_cast<DistWord *>(pat + (uint64_t)W * 64u);
             }
-            uint32_t pos = 0u;
-            for (uint32_t base = 0u; base < pbytes; base += 64u) {
-                const bool s = osa_is_start(pp, base + lane, pbytes);
-                const uint64_t sm = __ballot(s);
-                if (s) pat[pos + (uint32_t)__popcll(sm & ((1ull << lane) - 1ull))] = osa_decode_at(pp, base + lane, pbytes);
-                pos += (uint32_t)__popcll(sm);
-            }
+            wave_decode(pp, pbytes, pat, lane);
             for (uint32_t i = m + lane; i < W * 64u; i += 64u) pat[i] = 0xFFFFFFFFu;
             int y = dist_first_y(W, m, k, bounded);
             for (uint32_t w = lane; w < W; w += 64u) state[w] = DistWord{~0ull, 0ull, 0ull, 0ull, 64ull * (w + 1u)};
             __syncthreads();
             uint64_t c = 0u;
-            bool cut = false;
-            for (uint32_t base = 0u; base < tbytes && !cut; base += 64u) {
-                const bool s = osa_is_start(tp, base + lane, tbytes);
-                const uint32_t cv = s ? osa_decode_at(tp, base + lane, tbytes) : 0u;
-                uint64_t sm = __ballot(s);
-                while (sm) {
-                    const int src = __ffsll((unsigned long long)sm) - 1;
-                    sm &= sm - 1ull;
-                    const uint32_t ch = (uint32_t)__shfl((int)cv, src, 64);
-                    dist_column<TR>(state, y, W, k, c, bounded, [&](uint32_t w) { return (uint64_t)__ballot(pat[64u * w + lane] == ch); });
-                    ++c;
-                    if (y < 0 && c > k) { cut = true; break; } // no cell of this column is <= k (row 0 holds c)
-                }
-            }
-            d = cut ? (uint64_t)k + 1u : dist_final(state, y, W, m, nt, k);
+            const bool done = wave_each_char(tp, tbytes, lane, [&](uint32_t ch) {
+                dist_column<TR>(state, y, W, k, c, bounded, [&](uint32_t w) { return (uint64_t)__ballot(pat[64u * w + lane] == ch); });
+                ++c;
+                return !(y < 0 && c > k); // false: no cell of this column is <= k (row 0 holds c), the pair is decided
+            });
+            d = done ? dist_final(state, y, W, m, nt, k) : (uint64_t)k + 1u;
             __syncthreads(); // (the next row overwrites pat / state)
         }
         if (lane == 0u) out[row] = dist_clamp(d, k);

@@ -191,7 +191,7 @@ __device__ __forceinline__ uint32_t indel_lane_run(const uint8_t *__restrict__ p
 // One pair per lane.  LIT as k_osa_lane: 0 = row against row (the longer string is the pattern), 1 = a is a literal, 2 = b is (the
 // literal is the text, read through a wave-uniform address; the row is the pattern).  k: the distance cutoff (DIST_UNBOUNDED for
 // the similarity); a pair of ASCII strings whose lengths differ by more than k is k + 1 without any column.  Rows this kernel
-// cannot take are appended to `worklist` (st->wave_rows, st->max_len as in k_osa_lane); the status block is zeroed before the launch.
+// cannot take are appended to `worklist` (worklist_append of strsim_wave_util.h); the status block is zeroed before the launch.
 template <int LIT>
 __global__ __launch_bounds__(256) void k_indel_lane(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ valA,
                                                     const uint32_t *__restrict__ offB, const uint8_t *__restrict__ valB, uint64_t n,
@@ -230,21 +230,7 @@ __global__ __launch_bounds__(256) void k_indel_lane(const uint32_t *__restrict__
     else if (words == 3u) l = indel_lane_run<3, UNI>(pv, po, lp, tv, to, nt, lt_run, tmax, halves, hi);
     else l = indel_lane_run<4, UNI>(pv, po, lp, tv, to, nt, lt_run, tmax, halves, hi);
     const bool ok = fits && (hi & 0x80808080u) == 0u;
-    // rows for k_indel_wave (wave-aggregated append)
-    const bool slow = live && !ok;
-    const uint64_t sm = __ballot(slow);
-    if (sm) {
-        const uint32_t lane = threadIdx.x & 63u;
-        const uint32_t first = (uint32_t)__ffsll((unsigned long long)sm) - 1u;
-        const uint32_t bound = osa_wave_max(slow ? (la < lb ? la : lb) : 0u);
-        uint32_t base = 0u;
-        if (lane == first) {
-            base = atomicAdd(&st->wave_rows, (uint32_t)__popcll(sm));
-            atomicMax(&st->max_len, bound);
-        }
-        base = (uint32_t)__shfl((int)base, (int)first, 64);
-        if (slow) worklist[base + (uint32_t)__popcll(sm & ((1ull << lane) - 1ull))] = (uint32_t)row;
-    }
+    worklist_append<false>(live && !ok, row, la, lb, worklist, st); // rows for k_indel_wave
     if (ok) {
         const uint32_t d = la + lb - 2u * l;
         if (out32) out32[row] = cut ? k + 1u : dist_clamp(d, k);
@@ -264,19 +250,11 @@ __device__ __forceinline__ uint32_t indel_wave_reg(const uint32_t *pat, uint32_t
     uint64_t V[NW];
 #pragma unroll
     for (int w = 0; w < NW; ++w) V[w] = ~0ull;
-    for (uint32_t base = 0u; base < tbytes; base += 64u) {
-        const bool s = osa_is_start(tp, base + lane, tbytes);
-        const uint32_t cv = s ? osa_decode_at(tp, base + lane, tbytes) : 0u;
-        uint64_t sm = __ballot(s);
-        while (sm) {
-            const int src = __ffsll((unsigned long long)sm) - 1;
-            sm &= sm - 1ull;
-            const uint32_t ch = (uint32_t)__shfl((int)cv, src, 64);
-            uint64_t c = 0ull;
+    wave_each_char(tp, tbytes, lane, [&](uint32_t ch) {
+        uint64_t c = 0ull;
 #pragma unroll
-            for (int w = 0; w < NW; ++w) indel_word_step((uint64_t)__ballot(pv[w] == ch), V[w], c);
-        }
-    }
+        for (int w = 0; w < NW; ++w) indel_word_step((uint64_t)__ballot(pv[w] == ch), V[w], c);
+    });
     uint32_t l = 0u;
 #pragma unroll
     for (int w = 0; w < NW; ++w)
@@ -298,11 +276,7 @@ __global__ __launch_bounds__(64) void k_indel_wave(const uint32_t *__restrict__ 
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t count = st->wave_rows;
     for (uint32_t r = blockIdx.x; r < count; r += gridDim.x) {
-        const uint32_t row = worklist[r];
-        const uint64_t ia = rowsA == 1 ? 0 : row, ib = rowsB == 1 ? 0 : row;
-        const uint8_t *pa = valA + offA[ia], *pb = valB + offB[ib];
-        const uint32_t na = offA[ia + 1] - offA[ia], nb = offB[ib + 1] - offB[ib];
-        const uint32_t ca = osa_count_chars(pa, na), cb = osa_count_chars(pb, nb);
+        const auto [row, pa, pb, na, nb, ca, cb] = wave_pair(offA, valA, rowsA, offB, valB, rowsB, worklist[r]);
         const bool a_is_pat = ca <= cb;
         const uint8_t *pp = a_is_pat ? pa : pb, *tp = a_is_pat ? pb : pa;
         const uint32_t pbytes = a_is_pat ? na : nb, tbytes = a_is_pat ? nb : na;
@@ -318,14 +292,8 @@ __global__ __launch_bounds__(64) void k_indel_wave(const uint32_t *__restrict__ 
                 pat = scratch + (uint64_t)blockIdx.x * slot_words;
                 state = reinterpret_cast<uint64_t *>(pat + (uint64_t)W * 64u);
             }
-            // decode the pattern; values past m never match (no scalar value is 0xFFFFFFFF)
-            uint32_t pos = 0u;
-            for (uint32_t base = 0u; base < pbytes; base += 64u) {
-                const bool s = osa_is_start(pp, base + lane, pbytes);
-                const uint64_t sm = __ballot(s);
-                if (s) pat[pos + (uint32_t)__popcll(sm & ((1ull << lane) - 1ull))] = osa_decode_at(pp, base + lane, pbytes);
-                pos += (uint32_t)__popcll(sm);
-            }
+            // the pattern's values; those past m never match (no scalar value is 0xFFFFFFFF)
+            wave_decode(pp, pbytes, pat, lane);
             for (uint32_t i = m + lane; i < Wpad * 64u; i += 64u) pat[i] = 0xFFFFFFFFu;
             for (uint32_t w = lane; w < W; w += 64u) state[w] = ~0ull;
             __syncthreads();
@@ -333,22 +301,14 @@ __global__ __launch_bounds__(64) void k_indel_wave(const uint32_t *__restrict__ 
             else if (W == 2u) l = indel_wave_reg<2>(pat, m, tp, tbytes, lane);
             else if (64u * W <= INDEL_WAVE_REG_CPS) l = indel_wave_reg<4>(pat, m, tp, tbytes, lane);
             else {
-                for (uint32_t base = 0u; base < tbytes; base += 64u) {
-                    const bool s = osa_is_start(tp, base + lane, tbytes);
-                    const uint32_t cv = s ? osa_decode_at(tp, base + lane, tbytes) : 0u;
-                    uint64_t sm = __ballot(s);
-                    while (sm) {
-                        const int src = __ffsll((unsigned long long)sm) - 1;
-                        sm &= sm - 1ull;
-                        const uint32_t ch = (uint32_t)__shfl((int)cv, src, 64);
-                        uint64_t c = 0ull;
-                        for (uint32_t w = 0; w < W; ++w) {
-                            uint64_t V = state[w];
-                            indel_word_step((uint64_t)__ballot(pat[64u * w + lane] == ch), V, c);
-                            state[w] = V;
-                        }
+                wave_each_char(tp, tbytes, lane, [&](uint32_t ch) {
+                    uint64_t c = 0ull;
+                    for (uint32_t w = 0; w < W; ++w) {
+                        uint64_t V = state[w];
+                        indel_word_step((uint64_t)__ballot(pat[64u * w + lane] == ch), V, c);
+                        state[w] = V;
                     }
-                }
+                });
                 for (uint32_t w = 0; w < W; ++w) l += indel_word_lcs(state[w], w, m);
             }
             __syncthreads(); // (the next row overwrites pat / state)

@@ -12,16 +12,18 @@
 // Two tiers, both finished in stream order:
 //   k_osa_lane<LIT>  one pair per lane, both strings ASCII and <= 64 bytes; the pattern in seven bit-planes of 32 or 64 bits
 //                    (eq_mask of strsim_lane_core.h), the text walked byte by byte from registers.  Every other row is
-//                    appended to a work list.
+//                    appended to a work list (worklist_append of strsim_wave_util.h).
 //   k_osa_wave       one pair per wave for the work list: any UTF-8, any length.  Both strings are decoded to scalar values;
 //                    the shorter (in scalar values) is the pattern, held in LDS up to OSA_WAVE_LDS_CPS values and in the
 //                    context's scratch above that.  The match words of a text character are built 64 pattern values at a
 //                    time by a compare and a ballot; the words are then advanced one after the other with the four carries
-//                    between them (the add, HP << 1, HN << 1 and the TR << 1 term).
+//                    between them (the add, HP << 1, HN << 1 and the TR << 1 term): osa_word_step, which k_dist_wave
+//                    (strsim_distance.h) runs too.  The row set-up, the decode and the text walk are strsim_wave_util.h's.
 #pragma once
 #include <stdint.h>
 
 #include "strsim_lane_core.h"
+#include "strsim_wave_util.h"
 
 namespace strsim {
 
@@ -111,19 +113,84 @@ STRSIM_HD uint64_t osa_wave_slot_words(uint64_t m)
     return words * 64u + words * 8u;
 }
 
+// One column of the recurrence on one 64-row word of a longer pattern, for k_osa_wave (TR = true) and dist_column of
+// strsim_distance.h (TR = false: Myers' step, D0p / EQp / tr_c are left alone).  The words of a column are advanced low to high
+// with four carries between them: add_c of the add, hp_c / hn_c the bits HP << 1 and HN << 1 shift in (1 and 0 into word 0: the
+// top boundary row grows by one a column; on return the horizontal delta of the word's bottom row), tr_c the bit of ~D0p & Eq
+// that the TR term shifts in.  All four start a column as 0, 1, 0, 0.
+template <bool TR>
+STRSIM_HD void osa_word_step(uint64_t Eq, uint64_t &VP, uint64_t &VN, uint64_t &D0p, uint64_t &EQp, uint64_t &add_c, uint64_t &hp_c,
+                             uint64_t &hn_c, uint64_t &tr_c)
+{
+    const uint64_t vp = VP, vn = VN;
+    uint64_t TRw = 0ull;
+    if constexpr (TR) {
+        const uint64_t t = ~D0p & Eq;
+        TRw = ((t << 1) | tr_c) & EQp;
+        tr_c = t >> 63;
+    }
+    const uint64_t x = Eq & vp;
+    const uint64_t s1 = x + vp;
+    const uint64_t s2 = s1 + add_c;
+    add_c = (uint64_t)(s1 < x) | (uint64_t)(s2 < s1);
+    const uint64_t D0 = (s2 ^ vp) | Eq | vn | TRw;
+    const uint64_t HP = vn | ~(D0 | vp);
+    const uint64_t HN = D0 & vp;
+    const uint64_t X = (HP << 1) | hp_c;
+    hp_c = HP >> 63;
+    const uint64_t Y = (HN << 1) | hn_c;
+    hn_c = HN >> 63;
+    VP = Y | ~(D0 | X);
+    VN = D0 & X;
+    if constexpr (TR) {
+        D0p = D0;
+        EQp = Eq;
+    }
+}
+
+// k_osa_wave's state: four 64-bit words per mask word -- VP, VN, and D0 and Eq of the previous column.
+STRSIM_HD void osa_words_init(uint64_t *sw)
+{
+    sw[0] = ~0ull;
+    sw[1] = 0ull;
+    sw[2] = 0ull;
+    sw[3] = 0ull;
+}
+
+// One text column over the W words of that state; eq(w): the match word of pattern word w against the column's character.
+template <typename EqFn>
+STRSIM_HD void osa_words_column(uint64_t *state, uint32_t W, EqFn &&eq)
+{
+    uint64_t add_c = 0ull, hp_c = 1ull, hn_c = 0ull, tr_c = 0ull;
+    for (uint32_t w = 0; w < W; ++w) {
+        const uint64_t Eq = eq(w);
+        uint64_t *sw = state + 4 * w;
+        uint64_t VP = sw[0], VN = sw[1], D0p = sw[2], EQp = sw[3];
+        osa_word_step<true>(Eq, VP, VN, D0p, EQp, add_c, hp_c, hn_c, tr_c);
+        sw[0] = VP;
+        sw[1] = VN;
+        sw[2] = D0p;
+        sw[3] = EQp;
+    }
+}
+
+// The distance after the last of nt columns: the text length plus the vertical deltas of the m pattern rows.
+STRSIM_HD uint64_t osa_words_final(const uint64_t *state, uint32_t W, uint32_t m, uint32_t nt)
+{
+    uint64_t up = 0u, dn = 0u;
+    for (uint32_t w = 0; w < W; ++w) {
+        const uint32_t r = m - 64u * w;
+        const uint64_t rows = r >= 64u ? ~0ull : ((1ull << r) - 1ull);
+        up += (uint64_t)osa_popc((uint64_t)(state[4 * w] & rows));
+        dn += (uint64_t)osa_popc((uint64_t)(state[4 * w + 1] & rows));
+    }
+    return nt + up - dn;
+}
+
 #if defined(__HIPCC__) && !defined(STRSIM_OSA_NO_KERNELS)
 // ------------------------------------------------------------------------------------------------
 // device side
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t osa_wave_max(uint32_t v)
-{
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        const uint32_t o = (uint32_t)__shfl_xor((int)v, s, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
 
 // 64 bytes of vals[off, off + len) into w[0..15] (len <= 64); nothing outside the string is read, the rest is zero.
 __device__ __forceinline__ void osa_load64(const uint8_t *__restrict__ vals, uint32_t off, uint32_t len, uint32_t (&w)[16])
@@ -175,21 +242,7 @@ __global__ __launch_bounds__(256) void k_osa_lane(const uint32_t *__restrict__ o
         osa_load64(tv, to, lt, wt);
         ok = (osa_high_bits(wp) | osa_high_bits(wt)) == 0u;
     }
-    // rows for k_osa_wave (wave-aggregated append)
-    const bool slow = live && !ok;
-    const uint64_t sm = __ballot(slow);
-    if (sm) {
-        const uint32_t lane = threadIdx.x & 63u;
-        const uint32_t first = (uint32_t)__ffsll((unsigned long long)sm) - 1u;
-        const uint32_t bound = osa_wave_max(slow ? (la < lb ? la : lb) : 0u);
-        uint32_t base = 0u;
-        if (lane == first) {
-            base = atomicAdd(&st->wave_rows, (uint32_t)__popcll(sm));
-            atomicMax(&st->max_len, bound);
-        }
-        base = (uint32_t)__shfl((int)base, (int)first, 64);
-        if (slow) worklist[base + (uint32_t)__popcll(sm & ((1ull << lane) - 1ull))] = (uint32_t)row;
-    }
+    worklist_append<false>(live && !ok, row, la, lb, worklist, st); // rows for k_osa_wave
     if (__ballot(ok) == 0ull) return;
     const uint32_t tmax = osa_wave_max(ok ? lt : 0u);
     const uint32_t pmax = osa_wave_max(ok ? lp : 0u);
@@ -199,30 +252,6 @@ __global__ __launch_bounds__(256) void k_osa_lane(const uint32_t *__restrict__ o
     if (pmax <= 32u) d = osa_lane_core<uint32_t>(wt, lt, tmax, Plo, Phi, lp);
     else d = osa_lane_core<uint64_t>(wt, lt, tmax, Plo, Phi, lp);
     if (ok) out[row] = epilogue_osa(d, la, lb);
-}
-
-// Decode the UTF-8 character that starts at p[i] (i < len; bytes past len are not read).
-__device__ __forceinline__ uint32_t osa_decode_at(const uint8_t *__restrict__ p, uint32_t i, uint32_t len)
-{
-    const uint32_t b0 = p[i];
-    auto cont = [&](uint32_t k) { return i + k < len ? (uint32_t)(p[i + k] & 0x3Fu) : 0u; };
-    if (b0 < 0x80u) return b0;
-    if (b0 < 0xE0u) return ((b0 & 0x1Fu) << 6) | cont(1);
-    if (b0 < 0xF0u) return ((b0 & 0x0Fu) << 12) | (cont(1) << 6) | cont(2);
-    return ((b0 & 0x07u) << 18) | (cont(1) << 12) | (cont(2) << 6) | cont(3);
-}
-
-__device__ __forceinline__ bool osa_is_start(const uint8_t *__restrict__ p, uint32_t i, uint32_t len)
-{
-    return i < len && (p[i] & 0xC0u) != 0x80u;
-}
-
-// scalar values of p[0, len), counted by the wave
-__device__ __forceinline__ uint32_t osa_count_chars(const uint8_t *__restrict__ p, uint32_t len)
-{
-    uint32_t c = 0u;
-    for (uint32_t base = 0u; base < len; base += 64u) c += (uint32_t)__popcll(__ballot(osa_is_start(p, base + (threadIdx.x & 63u), len)));
-    return c;
 }
 
 // One pair per wave (blockDim.x = 64) for the rows k_osa_lane put on the work list (st->wave_rows of them).  scratch: gridDim.x
@@ -237,11 +266,7 @@ __global__ __launch_bounds__(64) void k_osa_wave(const uint32_t *__restrict__ of
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t count = st->wave_rows;
     for (uint32_t k = blockIdx.x; k < count; k += gridDim.x) {
-        const uint32_t row = worklist[k];
-        const uint64_t ia = rowsA == 1 ? 0 : row, ib = rowsB == 1 ? 0 : row;
-        const uint8_t *pa = valA + offA[ia], *pb = valB + offB[ib];
-        const uint32_t na = offA[ia + 1] - offA[ia], nb = offB[ib + 1] - offB[ib];
-        const uint32_t ca = osa_count_chars(pa, na), cb = osa_count_chars(pb, nb);
+        const auto [row, pa, pb, na, nb, ca, cb] = wave_pair(offA, valA, rowsA, offB, valB, rowsB, worklist[k]);
         const bool a_is_pat = ca <= cb;
         const uint8_t *pp = a_is_pat ? pa : pb, *tp = a_is_pat ? pb : pa;
         const uint32_t pbytes = a_is_pat ? na : nb, tbytes = a_is_pat ? nb : na;
@@ -255,66 +280,15 @@ __global__ __launch_bounds__(64) void k_osa_wave(const uint32_t *__restrict__ of
                 pat = scratch + (uint64_t)blockIdx.x * slot_words;
                 state = reinterpret_cast<uint64_t *>(pat + (uint64_t)W * 64u);
             }
-            // decode the pattern; values past m never match (no scalar value is 0xFFFFFFFF)
-            uint32_t pos = 0u;
-            for (uint32_t base = 0u; base < pbytes; base += 64u) {
-                const bool s = osa_is_start(pp, base + lane, pbytes);
-                const uint64_t sm = __ballot(s);
-                if (s) pat[pos + (uint32_t)__popcll(sm & ((1ull << lane) - 1ull))] = osa_decode_at(pp, base + lane, pbytes);
-                pos += (uint32_t)__popcll(sm);
-            }
+            // the pattern's values; those past m never match (no scalar value is 0xFFFFFFFF)
+            wave_decode(pp, pbytes, pat, lane);
             for (uint32_t i = m + lane; i < W * 64u; i += 64u) pat[i] = 0xFFFFFFFFu;
-            for (uint32_t w = lane; w < W; w += 64u) {
-                state[4 * w + 0] = ~0ull; // VP
-                state[4 * w + 1] = 0ull;  // VN
-                state[4 * w + 2] = 0ull;  // D0 of the previous column
-                state[4 * w + 3] = 0ull;  // Eq of the previous column
-            }
+            for (uint32_t w = lane; w < W; w += 64u) osa_words_init(state + 4 * w);
             __syncthreads();
-            for (uint32_t base = 0u; base < tbytes; base += 64u) {
-                const bool s = osa_is_start(tp, base + lane, tbytes);
-                const uint32_t cv = s ? osa_decode_at(tp, base + lane, tbytes) : 0u;
-                uint64_t sm = __ballot(s);
-                while (sm) {
-                    const int src = __ffsll((unsigned long long)sm) - 1;
-                    sm &= sm - 1ull;
-                    const uint32_t c = (uint32_t)__shfl((int)cv, src, 64);
-                    // the words of this column, low to high, with the carries between them
-                    uint64_t add_c = 0ull, hp_c = 1ull, hn_c = 0ull, tr_c = 0ull;
-                    for (uint32_t w = 0; w < W; ++w) {
-                        const uint64_t Eq = __ballot(pat[64u * w + lane] == c);
-                        uint64_t *sw = state + 4 * w;
-                        const uint64_t VP = sw[0], VN = sw[1], D0p = sw[2], EQp = sw[3];
-                        const uint64_t t = ~D0p & Eq;
-                        const uint64_t TR = ((t << 1) | tr_c) & EQp;
-                        tr_c = t >> 63;
-                        const uint64_t x = Eq & VP;
-                        const uint64_t s1 = x + VP;
-                        const uint64_t s2 = s1 + add_c;
-                        add_c = (uint64_t)(s1 < x) | (uint64_t)(s2 < s1);
-                        const uint64_t D0 = (s2 ^ VP) | Eq | VN | TR;
-                        const uint64_t HP = VN | ~(D0 | VP);
-                        const uint64_t HN = D0 & VP;
-                        const uint64_t X = (HP << 1) | hp_c;
-                        hp_c = HP >> 63;
-                        const uint64_t Y = (HN << 1) | hn_c;
-                        hn_c = HN >> 63;
-                        sw[0] = Y | ~(D0 | X);
-                        sw[1] = D0 & X;
-                        sw[2] = D0;
-                        sw[3] = Eq;
-                    }
-                }
-            }
-            // last column: the text length plus the vertical deltas of the m pattern rows
-            uint64_t up = 0u, dn = 0u;
-            for (uint32_t w = 0; w < W; ++w) {
-                const uint32_t r = m - 64u * w;
-                const uint64_t rows = r >= 64u ? ~0ull : ((1ull << r) - 1ull);
-                up += (uint64_t)__popcll(state[4 * w] & rows);
-                dn += (uint64_t)__popcll(state[4 * w + 1] & rows);
-            }
-            d = nt + up - dn;
+            wave_each_char(tp, tbytes, lane, [&](uint32_t c) {
+                osa_words_column(state, W, [&](uint32_t w) { return (uint64_t)__ballot(pat[64u * w + lane] == c); });
+            });
+            d = osa_words_final(state, W, m, nt);
             __syncthreads(); // (the next row overwrites pat / state)
         }
         if (lane == 0u) out[row] = epilogue_osa(d, ca, cb);

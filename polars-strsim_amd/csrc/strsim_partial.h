@@ -250,8 +250,8 @@ __device__ __forceinline__ void partial_store(double *__restrict__ out, uint32_t
 
 // One pair per lane.  LIT: 0 = row against row, 1 = a is a literal (rowsA == 1), 2 = b is; which of the two is the needle still
 // depends on each row's length, so a literal is loaded like a row (every lane reads the same address).  Rows this kernel cannot
-// take are appended to `worklist` as k_indel_lane does it (st->wave_rows, st->max_len bounds their needles); st->pad1[0] bounds
-// their haystacks (bytes).  The status block is zeroed before the launch.  ALIGN: span != nullptr.
+// take are appended to `worklist` (worklist_append<true> of strsim_wave_util.h: st->wave_rows, st->max_len bounds their needles,
+// st->pad1[0] their haystacks, in bytes).  The status block is zeroed before the launch.  ALIGN: span != nullptr.
 template <int LIT, bool ALIGN>
 __global__ __launch_bounds__(256) void k_partial_lane(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ valA,
                                                       const uint32_t *__restrict__ offB, const uint8_t *__restrict__ valB, uint64_t nrows,
@@ -293,23 +293,7 @@ __global__ __launch_bounds__(256) void k_partial_lane(const uint32_t *__restrict
         if (second) best = b2;
     }
     const bool ok = fits && (hi & 0x80808080u) == 0u;
-    // rows for k_partial_wave (wave-aggregated append)
-    const bool slow = live && !ok;
-    const uint64_t sm = __ballot(slow);
-    if (sm) {
-        const uint32_t lane = threadIdx.x & 63u;
-        const uint32_t first = (uint32_t)__ffsll((unsigned long long)sm) - 1u;
-        const uint32_t bound = osa_wave_max(slow ? (la < lb ? la : lb) : 0u);
-        const uint32_t hbound = osa_wave_max(slow ? (la < lb ? lb : la) : 0u);
-        uint32_t base = 0u;
-        if (lane == first) {
-            base = atomicAdd(&st->wave_rows, (uint32_t)__popcll(sm));
-            atomicMax(&st->max_len, bound);
-            atomicMax(&st->pad1[0], hbound);
-        }
-        base = (uint32_t)__shfl((int)base, (int)first, 64);
-        if (slow) worklist[base + (uint32_t)__popcll(sm & ((1ull << lane) - 1ull))] = (uint32_t)row;
-    }
+    worklist_append<true>(live && !ok, row, la, lb, worklist, st); // rows for k_partial_wave
     if (ok) {
         if (m == 0u) {
             partial_store(out, ALIGN ? span : nullptr, row, n == 0u ? 1.0 : 0.0, 0u, 0u, 0u, 0u);
@@ -336,18 +320,6 @@ __device__ __forceinline__ PartialWin partial_wave_reduce(PartialWin best, uint3
     return best;
 }
 
-// scalar values of p[0, bytes) into dst[0 ..), in order, by the wave
-__device__ __forceinline__ void partial_decode(const uint8_t *__restrict__ p, uint32_t bytes, uint32_t *dst, uint32_t lane)
-{
-    uint32_t pos = 0u;
-    for (uint32_t base = 0u; base < bytes; base += 64u) {
-        const bool s = osa_is_start(p, base + lane, bytes);
-        const uint64_t sm = __ballot(s);
-        if (s) dst[pos + (uint32_t)__popcll(sm & ((1ull << lane) - 1ull))] = osa_decode_at(p, base + lane, bytes);
-        pos += (uint32_t)__popcll(sm);
-    }
-}
-
 // P(needle, haystack) of one pair by the wave (m >= 1, n >= m scalar values); mem: partial_wave_words(m, n) words, 8-byte aligned;
 // s_pat: 64 words of LDS.  Every lane returns the winner.
 __device__ __forceinline__ PartialWin partial_wave_pair(const uint8_t *__restrict__ pp, uint32_t pbytes, uint32_t m,
@@ -356,24 +328,16 @@ __device__ __forceinline__ PartialWin partial_wave_pair(const uint8_t *__restric
 {
     PartialWin best = partial_floor();
     if (m <= 64u) {
-        partial_decode(pp, pbytes, s_pat, lane);
+        wave_decode(pp, pbytes, s_pat, lane);
         __syncthreads();
         const uint32_t pv = lane < m ? s_pat[lane] : 0xFFFFFFFFu; // (no scalar value is 0xFFFFFFFF)
         uint64_t *tab = reinterpret_cast<uint64_t *>(mem);
         uint32_t pos = 0u;
-        for (uint32_t base = 0u; base < tbytes; base += 64u) {
-            const bool s = osa_is_start(tp, base + lane, tbytes);
-            const uint32_t cv = s ? osa_decode_at(tp, base + lane, tbytes) : 0u;
-            uint64_t sm = __ballot(s);
-            while (sm) {
-                const int src = __ffsll((unsigned long long)sm) - 1;
-                sm &= sm - 1ull;
-                const uint32_t ch = (uint32_t)__shfl((int)cv, src, 64);
-                const uint64_t e = (uint64_t)__ballot(pv == ch);
-                if (lane == 0u) tab[pos] = e;
-                ++pos;
-            }
-        }
+        wave_each_char(tp, tbytes, lane, [&](uint32_t ch) {
+            const uint64_t e = (uint64_t)__ballot(pv == ch);
+            if (lane == 0u) tab[pos] = e;
+            ++pos;
+        });
         __syncthreads();
         // the proper prefixes: lane i takes t[0:i + 1]
         if (m >= 2u) {
@@ -396,8 +360,8 @@ __device__ __forceinline__ PartialWin partial_wave_pair(const uint8_t *__restric
         const uint32_t W = (m + 63u) / 64u;
         uint32_t *hay = mem, *pat = mem + n;
         uint64_t *V = reinterpret_cast<uint64_t *>(mem + ((n + 64u * W + 1u) & ~1u));
-        partial_decode(tp, tbytes, hay, lane);
-        partial_decode(pp, pbytes, pat, lane);
+        wave_decode(tp, tbytes, hay, lane);
+        wave_decode(pp, pbytes, pat, lane);
         for (uint32_t i = m + lane; i < W * 64u; i += 64u) pat[i] = 0xFFFFFFFFu;
         __syncthreads();
         // (every lane stores the same V words and reads back its own store)
@@ -425,11 +389,7 @@ __global__ __launch_bounds__(64) void k_partial_wave(const uint32_t *__restrict_
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t count = st->wave_rows;
     for (uint32_t r = blockIdx.x; r < count; r += gridDim.x) {
-        const uint32_t row = worklist[r];
-        const uint64_t ia = rowsA == 1 ? 0 : row, ib = rowsB == 1 ? 0 : row;
-        const uint8_t *pa = valA + offA[ia], *pb = valB + offB[ib];
-        const uint32_t na = offA[ia + 1] - offA[ia], nb = offB[ib + 1] - offB[ib];
-        const uint32_t ca = osa_count_chars(pa, na), cb = osa_count_chars(pb, nb);
+        const auto [row, pa, pb, na, nb, ca, cb] = wave_pair(offA, valA, rowsA, offB, valB, rowsB, worklist[r]);
         if (ca == 0u || cb == 0u) {
             if (lane == 0u) partial_store(out, ALIGN ? span : nullptr, row, (ca | cb) == 0u ? 1.0 : 0.0, 0u, 0u, 0u, 0u);
             continue;

@@ -321,19 +321,6 @@ struct TokenWaveWriter { // every lane of the wave is at the same token: the byt
     }
 };
 
-// wave-aggregated append of the lanes with `slow` to a work list
-__device__ __forceinline__ void token_append(bool slow, uint32_t row, uint32_t *__restrict__ list, uint32_t *count)
-{
-    const uint64_t sm = __ballot(slow);
-    if (sm == 0ull) return;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t first = (uint32_t)__ffsll((unsigned long long)sm) - 1u;
-    uint32_t base = 0u;
-    if (lane == first) base = atomicAdd(count, (uint32_t)__popcll(sm));
-    base = (uint32_t)__shfl((int)base, (int)first, 64);
-    if (slow) list[base + (uint32_t)__popcll(sm & ((1ull << lane) - 1ull))] = row;
-}
-
 // The longest row of a column and its first and last offset (side 0 or 1 of st; max_len zeroed before the launch).
 __global__ __launch_bounds__(TOKEN_THREADS) void k_token_bounds(const uint32_t *__restrict__ off, uint64_t rows, TokenStatus *st, int side)
 {
@@ -378,7 +365,7 @@ __global__ __launch_bounds__(TOKEN_THREADS) void k_token_sort_lane(const uint32_
             TokenCountWriter w;
             out_off[row + 1] = token_join(p, d, 0u, cnt, w);
         }
-        token_append(live && !ok, (uint32_t)row, list, count);
+        wave_append(live && !ok, (uint32_t)row, list, count);
     } else if (ok) {
         token_isort(p, d, 0u, cnt);
         TokenSerialWriter w{out_val + out_off[row]};
@@ -457,7 +444,7 @@ __global__ __launch_bounds__(TOKEN_THREADS) void k_token_set_lane(const uint32_t
     const bool ok = fits && (hi & 0x80u) == 0u && na <= TOKEN_LANE_MAX_TOKENS && nb <= TOKEN_LANE_MAX_TOKENS;
     if constexpr (!WRITE) {
         if (row == 0) { off_ab[0] = 0u; off_ba[0] = 0u; }
-        token_append(live && !ok, (uint32_t)row, list, count);
+        wave_append(live && !ok, (uint32_t)row, list, count);
     }
     if (!ok) return;
     token_isort(pa, d, 0u, na);

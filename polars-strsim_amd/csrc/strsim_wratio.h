@@ -122,21 +122,6 @@ __device__ __forceinline__ uint32_t wratio_chars_block(const uint8_t *p, uint32_
     return *s_acc;
 }
 
-// token_append that also tells the lane where its row went
-__device__ __forceinline__ uint32_t wratio_append(bool take, uint32_t row, uint32_t *__restrict__ list, uint32_t *count)
-{
-    const uint64_t sm = __ballot(take);
-    if (sm == 0ull) return 0u;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t first = (uint32_t)__ffsll((unsigned long long)sm) - 1u;
-    uint32_t base = 0u;
-    if (lane == first) base = atomicAdd(count, (uint32_t)__popcll(sm));
-    base = (uint32_t)__shfl((int)base, (int)first, 64);
-    const uint32_t pos = base + (uint32_t)__popcll(sm & ((1ull << lane) - 1ull));
-    if (take) list[pos] = row;
-    return pos;
-}
-
 // One pair per lane; rows_a / rows_b == 1: that side is a literal, counted once a workgroup.  cls[row] = the class, pos[row] = the
 // row's position on its list (near: list_near, counted in st->rows[0]; far: list_far, st->rows[1]; both zeroed before the launch).
 __global__ __launch_bounds__(WRATIO_THREADS) void k_wratio_classify(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ valA, uint64_t rows_a,
@@ -161,8 +146,8 @@ __global__ __launch_bounds__(WRATIO_THREADS) void k_wratio_classify(const uint32
         lb = live ? wratio_chars(valB + o, offB[row + 1] - o) : 0u;
     }
     const uint32_t c = live ? wratio_class(la, lb) : WRATIO_EMPTY;
-    const uint32_t pn = wratio_append(c == WRATIO_NEAR, (uint32_t)row, list_near, &st->rows[0]);
-    const uint32_t pf = wratio_append(c >= WRATIO_FAR8, (uint32_t)row, list_far, &st->rows[1]);
+    const uint32_t pn = wave_append(c == WRATIO_NEAR, (uint32_t)row, list_near, &st->rows[0]);
+    const uint32_t pf = wave_append(c >= WRATIO_FAR8, (uint32_t)row, list_far, &st->rows[1]);
     if (live) {
         cls[row] = (uint8_t)c;
         pos[row] = c == WRATIO_NEAR ? pn : pf;

@@ -1,5 +1,6 @@
 """Optimal string alignment (measure 6) without a GPU: the references against the known answers and each other, the host build of
-the one-pair-per-lane recurrence (strsim_osa.h) against them, strsim_measure_supported, and the plugin's field function."""
+the one-pair-per-lane recurrence and of the one-pair-per-wave word recurrence (strsim_osa.h) against them, strsim_measure_supported,
+and the plugin's field function."""
 import ctypes as C
 import os
 import random
@@ -33,6 +34,8 @@ def lane():
     L.osa_lane_distance.argtypes = [C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.c_uint32, C.c_int]
     L.osa_lane_score.restype = C.c_double
     L.osa_lane_score.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+    L.osa_words_distance.restype = C.c_uint64
+    L.osa_words_distance.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
     yield L
     d.cleanup()
 
@@ -122,6 +125,82 @@ def test_lane_recurrence_known_answers(lane):
         if all(ord(c) < 128 for c in a + b) and len(a) <= 64 and len(b) <= 64:
             for p, t in ((a, b), (b, a)):
                 assert lane.osa_lane_distance(p.encode(), len(p), t.encode(), len(t), len(t), 1) == d
+
+
+def _words_distance(lane, p, t):
+    x = np.array([ord(c) for c in p] or [0], dtype=np.uint32)
+    y = np.array([ord(c) for c in t] or [0], dtype=np.uint32)
+    return int(lane.osa_words_distance(x.ctypes.data, len(p), y.ctypes.data, len(t)))
+
+
+# pattern lengths around the 64-row words of k_osa_wave's state: one word, the last row of a word, the first of the next, three and
+# four words
+WORDS_PATTERN_LENGTHS = (1, 63, 64, 65, 127, 128, 129, 200)
+WORDS_ALPHABETS = ("ab\U0001F600", "abc\U00010348")  # three or four scalar values (one above 0xFFFF): matches and swaps are dense
+
+
+def test_words_recurrence_across_word_boundaries(lane, cref):
+    """The pattern over several 64-row words, the text from the pattern's length up to 260 values: a mutated copy of the pattern
+    (adjacent swaps, substitutions, insertions up to the length drawn) or unrelated values.  Exact distances against the C DP."""
+    rng = random.Random(66)
+    pairs = 0
+    for m in WORDS_PATTERN_LENGTHS:
+        for rep in range(36):
+            al = WORDS_ALPHABETS[rep & 1]
+            p = [rng.choice(al) for _ in range(m)]
+            n = rng.randint(m, min(260, m + 3)) if rep % 3 == 0 else rng.randint(m, 260)
+            if rep % 6 == 5:
+                t = [rng.choice(al) for _ in range(n)]
+            else:
+                t = list(p)
+                for _ in range(rng.randint(0, 1 + m // 8)):
+                    if len(t) >= 2:
+                        i = rng.randrange(len(t) - 1)
+                        t[i], t[i + 1] = t[i + 1], t[i]
+                for _ in range(rng.randint(0, 1 + m // 16)):
+                    t[rng.randrange(len(t))] = rng.choice(al)
+                while len(t) < n:
+                    t.insert(rng.randint(0, len(t)), rng.choice(al))
+            p, t = "".join(p), "".join(t)
+            assert _words_distance(lane, p, t) == cref.distance(p, t), (p, t)
+            pairs += 1
+    assert pairs == 288
+
+
+# (pattern, text, distance): one case per carry between the words of a column
+_X, _Y = "\U0001F600", "y"
+WORDS_CARRY_CASES = [
+    # tr_c: an adjacent swap whose two characters are pattern rows 63 | 64, and 127 | 128
+    ("a" * 63 + _X + _Y + "a" * 64, "a" * 63 + _Y + _X + "a" * 64, 1),
+    ("a" * 127 + _X + _Y + "a" * 71, "a" * 127 + _Y + _X + "a" * 71, 1),
+    ("a" * 127 + _X + _Y + "a" * 71, "a" * 63 + _Y + _X + "a" * 62 + _Y + _X + "a" * 71, 3),
+    # add_c: an insertion in front of a pattern of one repeated value: every row matches in every later column and the add
+    # carries through whole words of matches
+    ("a" * 200, _X + "a" * 200, 1),
+    ("a" * 200, "a" * 100 + _X + "a" * 100, 1),
+    # add_c: a match in row 61 or 62 followed by deletions up into rows 64 and 65 (the carry alone sets D0 there)
+    ("a" * 61 + "b" + "aa" + "b" + "a" * 35, "a" * 58 + "b" + "a" + "b" + "aa" + "b" + "a" * 36, 3),
+    # hp_c: nothing matches, D[i][j] = max(i, j): the +1 horizontal deltas of the rows above the diagonal cross every word
+    ("a" * 128, "b" * 130, 130),
+    # hn_c: the text's tail matches the pattern's tail after a block that matches nothing: -1 horizontal deltas in the rows
+    # on both sides of 63 | 64 and 127 | 128
+    ("b" + "a" * 127, "c" * 64 + "b" * 63 + "aa", 127),
+    ("bb" + "c" * 128, "a" * 64 + "b" + "c" * 127, 65),
+]
+
+
+@pytest.mark.parametrize("case", range(len(WORDS_CARRY_CASES)))
+def test_words_recurrence_carry_cases(lane, cref, case):
+    a, b, d = WORDS_CARRY_CASES[case]
+    p, t = (a, b) if len(a) <= len(b) else (b, a)
+    assert cref.distance(p, t) == d
+    assert _words_distance(lane, p, t) == d
+
+
+def test_words_recurrence_known_answers(lane):
+    for a, b, d, _, _ in R.KNOWN:
+        p, t = (a, b) if len(a) <= len(b) else (b, a)
+        assert _words_distance(lane, p, t) == d, (a, b)
 
 
 @pytest.fixture(scope="module")
