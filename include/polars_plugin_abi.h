@@ -164,6 +164,13 @@ POLARS_PLUGIN_DECLARE(nearest_osa)
 POLARS_PLUGIN_DECLARE(extract_ratio)
 POLARS_PLUGIN_DECLARE(extract_token_sort_ratio)
 
+/* default_process (not in the reference; rapidfuzz's utils.default_process made context-free, strsim_default_process_host of
+ * strsim_amd.h): ONE input, a string series in any of the three layouts; elementwise.  Output: N rows of Arrow Utf8 ("u": int32
+ * offsets -- the transform's 32-bit offsets are the buffer as it is; a result beyond 2^31 - 1 bytes is an error) named after
+ * input 0, one chunk, null where the input is null.  The field function declares "u".  The validity, offsets and values buffers
+ * belong to the array's release callback. */
+POLARS_PLUGIN_DECLARE(default_process)
+
 /* ---- diagnostics of this implementation (not part of the polars-ffi contract; the engine never calls them) ----
  * The plugin's staging -- pinned host memory and its device mirrors, per pipeline set -- is leased per call from one process-wide
  * pool under POLARS_STRSIM_STAGING_BUDGET_MB (csrc/plugin_pack.h: StagingPool; reference counterpart: the per-call scratch of

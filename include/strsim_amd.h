@@ -352,6 +352,61 @@ STRSIM_API int strsim_token_sort_host(strsim_ctx_t *ctx, const uint32_t *offsets
 STRSIM_API uint64_t strsim_ctx_last_token_wave_rows(strsim_ctx_t *ctx);
 
 /*
+ * default_process and processed scoring (found by dlsym: the ABI version stays 1.7, strsim_measure_supported does not describe
+ * them and no measure id is added).  default_process is rapidfuzz's utils.default_process made context-free: every scalar value c
+ * of a row is mapped by m -- m(c) = U+0020 when c is neither alphanumeric (Python's str.isalnum) nor "_", else the first scalar
+ * value of Python's c.lower() -- and U+0020 is then removed from both ends of the row; inner runs of spaces stay ("Apple, Inc."
+ * becomes "apple  inc").  It equals re.sub(r"(?ui)\W", " ", s).strip().lower() except in two places: U+03A3 maps to U+03C3 in
+ * every position (no final sigma), and U+0130 maps to "i" (its simple lower-case mapping, no U+0307 behind it).  m comes from a
+ * table generated from Python (strsim_default_process_unicode_version names its Unicode version); strsim_default_process_char
+ * returns m(cp) -- U+0020 for surrogates and values above U+10FFFF -- and, like the version call, needs no device.
+ *
+ * strsim_default_process_*: row i of the output column is default_process(row i); the same column layout, and any monotone offset
+ * base, as strsim_token_sort_*.  out_offsets holds rows + 1 words and starts at 0; out_values holds out_capacity bytes.  A
+ * processed row can be LONGER than its input (U+023A and U+023E grow from two bytes of UTF-8 to three):
+ * STRSIM_DEFAULT_PROCESS_CAPACITY(bytes) = bytes + bytes / 2 always suffices, the exact size is out_offsets[rows].  The device
+ * variant enqueues the measuring pass and the offset scan, waits once for the stream (the exact size, the column's bounds) and
+ * enqueues the writing pass: the output is complete in stream order.  A capacity below the exact size is STRSIM_ERR_ARG and
+ * nothing is written to out_values (out_offsets has been written); so is a column of more than (2^32 - 1) * 2 / 3 bytes, whose
+ * processed form might not fit 32-bit offsets.  Zero rows: out_offsets[0] = 0.  The arguments are checked first and the context
+ * last.  The host variant stages the column and is synchronous.  Rows of at most 64 ASCII bytes are rewritten one string per
+ * lane, every other row one string per wave (any UTF-8, any length); strsim_ctx_last_process_wave_rows counts the latter for the
+ * last call of the context (both sides of a processed-scoring call added up), valid when that call has returned.  The kernels
+ * read only the bytes the offsets describe and write only a row's own output bytes; on malformed UTF-8 the result is unspecified
+ * within those limits (a lead byte without all the continuation bytes it calls for counts as one space, so bytes + bytes / 2
+ * suffices for any bytes at all).  Scratch: 4 bytes of work list a row and 36 KB for the table.
+ *
+ * strsim_pairs_processed_*: `measure` over the processed columns -- bit for bit strsim_pairs_device(measure) over
+ * strsim_default_process_device of each side.  processor is STRSIM_PROCESS_DEFAULT; anything else is STRSIM_ERR_ARG, as is a
+ * measure the pairwise entry point refuses.  Both sides are processed into scratch of the context that no flow of the pairwise
+ * call uses (a literal stays a one-row literal): 4 bytes of offsets and 4 of work list a row and side, and the exact processed
+ * bytes of each side (+ 64); a failed reservation is STRSIM_ERR_OOM.  That scratch holds the input columns of the pairwise call,
+ * which a pending call's retirement reads again; so the call first retires every call of the context that is still pending, as the
+ * wrap of the ring does (a wait for the stream and their long-string or deferred passes; what they finished late is reported with
+ * the next strsim_ctx_synchronize / _retire_oldest; a failure there is STRSIM_ERR_EARLIER_CALL and this call is not enqueued) --
+ * calls can be enqueued back to back.  The call waits once for the stream for both sides' sizes,
+ * then runs strsim_pairs_device: what that documents for `measure` (further waits, strsim_ctx_synchronize, the counters) holds
+ * from there on.  The host variant stages both columns and is synchronous.
+ */
+#define STRSIM_PROCESS_DEFAULT 1
+#define STRSIM_DEFAULT_PROCESS_CAPACITY(bytes) ((uint64_t)(bytes) + (uint64_t)(bytes) / 2u)
+STRSIM_API uint32_t strsim_default_process_char(uint32_t cp);
+STRSIM_API const char *strsim_default_process_unicode_version(void);
+STRSIM_API int strsim_default_process_device(strsim_ctx_t *ctx, const uint32_t *offsets, const uint8_t *values, uint64_t rows,
+                                             uint32_t *out_offsets, uint8_t *out_values, uint64_t out_capacity);
+STRSIM_API int strsim_default_process_host(strsim_ctx_t *ctx, const uint32_t *offsets, const uint8_t *values, uint64_t rows,
+                                           uint32_t *out_offsets, uint8_t *out_values, uint64_t out_capacity);
+STRSIM_API int strsim_pairs_processed_device(strsim_ctx_t *ctx, int measure, int processor,
+                                             const uint32_t *a_offsets, const uint8_t *a_values, uint64_t a_rows,
+                                             const uint32_t *b_offsets, const uint8_t *b_values, uint64_t b_rows,
+                                             double *out, uint64_t out_rows);
+STRSIM_API int strsim_pairs_processed_host(strsim_ctx_t *ctx, int measure, int processor,
+                                           const uint32_t *a_offsets, const uint8_t *a_values, uint64_t a_rows,
+                                           const uint32_t *b_offsets, const uint8_t *b_values, uint64_t b_rows,
+                                           double *out, uint64_t out_rows);
+STRSIM_API uint64_t strsim_ctx_last_process_wave_rows(strsim_ctx_t *ctx);
+
+/*
  * STRSIM_TOKEN_RATIO .. STRSIM_WRATIO (ids 18 .. 26; strsim_measure_supported(id, STRSIM_ENTRY_PAIRWISE) detects them, the ABI
  * version stays 1.7).  Ids 18 .. 24 run the token transforms and the Indel / partial-ratio kernels over the whole frame.
  * STRSIM_WRATIO computes STRSIM_INDEL over every row into `out`, classifies the rows on the device and gathers the near rows and

@@ -153,6 +153,7 @@ void export_primitive(const char *format, const char *name, uint64_t n, void *da
 #include "plugin_partial.h"
 #include "plugin_nearest.h"
 #include "plugin_extract.h"
+#include "plugin_process.h"
 
 void run(int measure, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret, bool engine_parallel)
 {
@@ -547,6 +548,8 @@ POLARS_PLUGIN_DEFINE_NEAREST(levenshtein, STRSIM_LEVENSHTEIN)
 POLARS_PLUGIN_DEFINE_NEAREST(osa, STRSIM_OSA)
 POLARS_PLUGIN_DEFINE_EXTRACT(ratio, STRSIM_INDEL)
 POLARS_PLUGIN_DEFINE_EXTRACT(token_sort_ratio, STRSIM_TOKEN_SORT_RATIO)
+POLARS_PLUGIN_EXPORT(default_process, run_default_process(inputs, n_inputs, return_value),
+                     field_named_after_input0(input_fields, n_fields, return_value, [](ArrowSchema *s, const char *n) { fill_named_schema(s, "u", n); }))
 POLARS_PLUGIN_DEFINE_MATCH(levenshtein, STRSIM_LEVENSHTEIN)
 POLARS_PLUGIN_DEFINE_MATCH(jaro, STRSIM_JARO)
 POLARS_PLUGIN_DEFINE_MATCH(jaro_winkler, STRSIM_JARO_WINKLER)

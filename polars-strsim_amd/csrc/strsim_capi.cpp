@@ -24,6 +24,7 @@
 #include "strsim_partial.h"
 #include "strsim_token.h"
 #include "strsim_wratio.h"
+#include "strsim_process.h"
 #include "strsim_nearest.h"
 #include "strsim_extract.h"
 
@@ -197,6 +198,16 @@ struct strsim_ctx {
     WratioStatus *wr_status = nullptr;      // device
     WratioStatus *wr_status_host = nullptr; // pinned: the list counts, read behind the wait of token_bounds
     uint64_t last_wratio_rows[2] = {};      // strsim_ctx_last_wratio_rows
+
+    // ---- default_process and processed scoring (process_measure, process_write; strsim_process.h) ----
+    // buffers of their own: the pairwise flow that runs behind the transform uses every buffer above freely
+    DevBuf proc_off[2], proc_val[2]; // the processed columns of strsim_pairs_processed_device
+    DevBuf proc_list[2];             // work lists of the wave kernel (one word per row)
+    DevBuf proc_sums;                // block sums of the offset scan
+    DevBuf proc_table;               // the table of strsim_process_table.h (PROCESS_TABLE_BYTES), uploaded on first use
+    bool proc_table_ready = false;
+    TokenStatus *proc_status = nullptr;      // device: wave_rows, max_len, begin, end of each side
+    TokenStatus *proc_status_host = nullptr; // pinned: the same, and in pad[side] the processed bytes of each side
 };
 
 static int ctx_set_device(strsim_ctx *c) { HIP_TRY(hipSetDevice(c->device)); return STRSIM_OK; }
@@ -481,6 +492,8 @@ void strsim_ctx_destroy(strsim_ctx_t *c)
     if (c->tok_status_host) (void)hipHostFree(c->tok_status_host);
     if (c->wr_status) (void)hipFree(c->wr_status);
     if (c->wr_status_host) (void)hipHostFree(c->wr_status_host);
+    if (c->proc_status) (void)hipFree(c->proc_status);
+    if (c->proc_status_host) (void)hipHostFree(c->proc_status_host);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1850,6 +1863,270 @@ int strsim_ctx_last_wratio_rows(strsim_ctx_t *c, uint64_t *near_rows, uint64_t *
     if (far_rows) *far_rows = c ? c->last_wratio_rows[1] : 0;
     if (!c) { set_error("strsim_ctx_last_wratio_rows: ctx is NULL"); return STRSIM_ERR_ARG; }
     return STRSIM_OK;
+}
+
+} // extern "C"
+
+// ---- default_process and processed scoring (strsim_process.h) ----
+//
+// The transform of a column is the measuring pass, the offset scan and the writing pass.  Between the scan and the writing pass the
+// host learns how many bytes the processed column holds (the last offset) -- a processed row can be longer than its input, so only
+// that figure sizes the values exactly -- together with the column's bounds and the work-list count: one wait for the stream, for
+// both sides of a processed-scoring call.
+
+static ProcessTable process_host_table() { return ProcessTable{PROCESS_BLOCK, PROCESS_CLASS, PROCESS_DELTA}; }
+
+static int process_prepare(strsim_ctx *c, ProcessTable *t)
+{
+    int rc = ctx_set_device(c);
+    if (rc) return rc;
+    if (!c->proc_status) HIP_TRY(hipMalloc((void **)&c->proc_status, sizeof(TokenStatus)));
+    if (!c->proc_status_host) HIP_TRY(hipHostMalloc((void **)&c->proc_status_host, sizeof(TokenStatus), hipHostMallocDefault));
+    if (!c->proc_table_ready) {
+        rc = c->proc_table.reserve(PROCESS_TABLE_BYTES);
+        if (rc) return rc;
+        uint8_t *d = c->proc_table.as<uint8_t>();
+        // (static tables: pageable copies, complete for the host when the calls return)
+        HIP_TRY(hipMemcpy(d, PROCESS_BLOCK, sizeof(PROCESS_BLOCK), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d + PROCESS_TABLE_CLASS_AT, PROCESS_CLASS, sizeof(PROCESS_CLASS), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d + PROCESS_TABLE_DELTA_AT, PROCESS_DELTA, sizeof(PROCESS_DELTA), hipMemcpyHostToDevice));
+        c->proc_table_ready = true;
+    }
+    const uint8_t *d = c->proc_table.as<uint8_t>();
+    *t = ProcessTable{d, d + PROCESS_TABLE_CLASS_AT, reinterpret_cast<const int32_t *>(d + PROCESS_TABLE_DELTA_AT)};
+    // strsim_ctx_last_process_wave_rows describes THIS call from here on: one without rows, or one that fails before its wait,
+    // reports 0 (nothing on the stream writes this block now: every call that copies into it has waited for the copy)
+    c->proc_status_host->wave_rows[0] = c->proc_status_host->wave_rows[1] = 0u;
+    return STRSIM_OK;
+}
+
+// The pairwise call of an earlier strsim_pairs_processed_device may still be pending (a ring measure is retired by the caller, and
+// its long-string or deferred pass reads its input columns again then): those columns are proc_off / proc_val, which the next call
+// overwrites and may reallocate.  So every pending call is retired before they are touched -- a wait for the stream and the
+// retirement passes, exactly what the wrap of the ring does; what they finished late is kept for the caller's next
+// strsim_ctx_synchronize / strsim_ctx_retire_oldest.
+static int process_retire_pending(strsim_ctx *c, const char *who)
+{
+    bool pending = false;
+    for (int s = 0; s < strsim_ctx::RING; ++s) pending = pending || c->slot_pending[s];
+    if (!pending) return STRSIM_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const int rc = ctx_drain(c);
+    c->carry_late_rows += c->last_late_rows;
+    c->carry_long_rows += c->last_long_rows;
+    if (rc) {
+        const std::string why = strsim_last_error_message();
+        set_error("%s: retiring earlier pending calls failed (this call was not enqueued): %s", who, why.c_str());
+        return STRSIM_ERR_EARLIER_CALL;
+    }
+    return STRSIM_OK;
+}
+
+static int process_wave_grid(const strsim_ctx *c) { return c->num_cu * 8; }
+
+// Bounds, measuring pass and scan of one column (side 0 or 1 of c->proc_status, zeroed by the caller): out_off becomes the
+// processed column's offsets, and its last word is on its way to c->proc_status_host->pad[side].
+static int process_measure(strsim_ctx *c, int side, const ProcessTable &t, const uint32_t *off, const uint8_t *val, uint64_t rows, uint32_t *out_off)
+{
+    int rc = c->proc_list[side].reserve(rows * sizeof(uint32_t));
+    if (rc) return rc;
+    rc = c->proc_sums.reserve(((rows + 4095u) / 4096u) * sizeof(uint32_t));
+    if (rc) return rc;
+    HIP_TRY(launch_token_bounds(off, rows, c->proc_status, side, c->stream));
+    hipError_t e = launch_process(false, off, val, rows, out_off, nullptr, c->proc_list[side].as<uint32_t>(), &c->proc_status->wave_rows[side],
+                                  process_wave_grid(c), t, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "kernel launch (k_process_lane / _wave, measuring)");
+    e = launch_token_scan(out_off, rows, c->proc_sums.as<uint32_t>(), c->stream);
+    if (e != hipSuccess) return hip_fail(e, "kernel launch (k_token_scan)");
+    HIP_TRY(hipMemcpyAsync(&c->proc_status_host->pad[side], out_off + rows, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    c->enqueued_ops += 7u;
+    return STRSIM_OK;
+}
+
+// The wait of a call: the status words of both sides (not the pad words, which the copies above fill) reach the host.
+static int process_wait(strsim_ctx *c)
+{
+    HIP_TRY(hipMemcpyAsync(c->proc_status_host, c->proc_status, offsetof(TokenStatus, pad), hipMemcpyDeviceToHost, c->stream));
+    c->enqueued_ops += 1u;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return STRSIM_OK;
+}
+
+// A column whose processed form might not fit 32-bit offsets is refused (the scan would have wrapped).
+static int process_check_size(const char *who, const strsim_ctx *c, int side)
+{
+    const TokenStatus &st = *c->proc_status_host;
+    const uint64_t bytes = (uint64_t)st.end[side] - st.begin[side];
+    if (STRSIM_DEFAULT_PROCESS_CAPACITY(bytes) > 0xFFFFFFFFull) {
+        set_error("%s: a column of %llu bytes may not fit 32-bit offsets once processed; split the column (bytes + bytes / 2 <= 2^32 - 1)",
+                  who, (unsigned long long)bytes);
+        return STRSIM_ERR_ARG;
+    }
+    return STRSIM_OK;
+}
+
+static int process_write(strsim_ctx *c, int side, const ProcessTable &t, const uint32_t *off, const uint8_t *val, uint64_t rows, uint32_t *out_off,
+                         uint8_t *out_val)
+{
+    hipError_t e = launch_process(true, off, val, rows, out_off, out_val, c->proc_list[side].as<uint32_t>(), &c->proc_status->wave_rows[side],
+                                  process_wave_grid(c), t, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "kernel launch (k_process_lane / _wave, writing)");
+    c->enqueued_ops += 2u;
+    return STRSIM_OK;
+}
+
+static int process_column_check(const char *who, strsim_ctx_t *c, const uint32_t *off, const uint8_t *val, uint64_t rows, const uint32_t *out_off,
+                                const uint8_t *out_val)
+{
+    if (rows > 0xFFFFFFFFull) {
+        set_error("%s: %llu rows in one call; split the column (at most 2^32 - 1 rows per call)", who, (unsigned long long)rows);
+        return STRSIM_ERR_ARG;
+    }
+    if (!off || !out_off || (rows && (!val || !out_val))) { set_error("%s: NULL buffer", who); return STRSIM_ERR_ARG; }
+    if (!c) { set_error("%s: ctx is NULL", who); return STRSIM_ERR_ARG; }
+    return STRSIM_OK;
+}
+
+static int process_capacity_error(const char *who, uint64_t capacity, uint64_t total)
+{
+    set_error("%s: out_capacity=%llu but the processed column holds %llu bytes (bytes + bytes / 2 of the input always suffices)", who,
+              (unsigned long long)capacity, (unsigned long long)total);
+    return STRSIM_ERR_ARG;
+}
+
+static int pairs_processed_check(const char *who, strsim_ctx_t *c, int measure, int processor, const uint32_t *a_off, const uint8_t *a_val,
+                                 uint64_t a_rows, const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, const double *out, uint64_t out_rows,
+                                 uint64_t *n)
+{
+    if (processor != STRSIM_PROCESS_DEFAULT) {
+        set_error("%s: unknown processor %d (STRSIM_PROCESS_DEFAULT = 1 is the only one)", who, processor);
+        return STRSIM_ERR_ARG;
+    }
+    if (!measure_accepted(measure, STRSIM_ENTRY_PAIRWISE)) { set_error("%s: unknown measure %d", who, measure); return STRSIM_ERR_ARG; }
+    int rc = check_rows(who, a_rows, b_rows, out_rows, n);
+    if (rc) return rc;
+    if (*n && (!a_off || !a_val || !b_off || !b_val || !out)) { set_error("%s: NULL buffer", who); return STRSIM_ERR_ARG; }
+    if (!c) { set_error("%s: ctx is NULL", who); return STRSIM_ERR_ARG; }
+    return STRSIM_OK;
+}
+
+extern "C" {
+
+uint32_t strsim_default_process_char(uint32_t cp) { return process_map(cp, process_host_table()); }
+
+const char *strsim_default_process_unicode_version(void) { return STRSIM_PROCESS_UNICODE_VERSION; }
+
+int strsim_default_process_device(strsim_ctx_t *c, const uint32_t *off, const uint8_t *val, uint64_t rows, uint32_t *out_off, uint8_t *out_val,
+                                  uint64_t out_capacity)
+{
+    const char *const who = "strsim_default_process_device";
+    int rc = process_column_check(who, c, off, val, rows, out_off, out_val);
+    if (rc) return rc;
+    ProcessTable t;
+    rc = process_prepare(c, &t);
+    if (rc) return rc;
+    if (rows == 0) {
+        HIP_TRY(hipMemsetAsync(out_off, 0, sizeof(uint32_t), c->stream));
+        return STRSIM_OK;
+    }
+    HIP_TRY(hipMemsetAsync(c->proc_status, 0, sizeof(TokenStatus), c->stream));
+    c->enqueued_ops += 1u;
+    rc = process_measure(c, 0, t, off, val, rows, out_off);
+    if (rc == STRSIM_OK) rc = process_wait(c);
+    if (rc == STRSIM_OK) rc = process_check_size(who, c, 0);
+    if (rc) return rc;
+    const uint64_t total = c->proc_status_host->pad[0];
+    if (out_capacity < total) return process_capacity_error(who, out_capacity, total);
+    return process_write(c, 0, t, off, val, rows, out_off, out_val);
+}
+
+int strsim_default_process_host(strsim_ctx_t *c, const uint32_t *off, const uint8_t *val, uint64_t rows, uint32_t *out_off, uint8_t *out_val,
+                                uint64_t out_capacity)
+{
+    const char *const who = "strsim_default_process_host";
+    int rc = process_column_check(who, c, off, val, rows, out_off, out_val);
+    if (rc) return rc;
+    if (rows == 0) { out_off[0] = 0u; return STRSIM_OK; }
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    // stage[0..1]: the column; stage[2]: the new offsets; stage[3]: the new values
+    const uint64_t room = STRSIM_DEFAULT_PROCESS_CAPACITY((uint64_t)off[rows] - off[0]);
+    Staged s;
+    rc = ctx_stage(c, off, val, rows, nullptr, nullptr, 0, 0, &s);
+    if (rc == STRSIM_OK) rc = c->stage[2].reserve((rows + 1) * sizeof(uint32_t));
+    if (rc == STRSIM_OK) rc = c->stage[3].reserve(room + TOKEN_PAD);
+    if (rc) return rc;
+    uint32_t *const d_off = c->stage[2].as<uint32_t>();
+    uint8_t *const d_val = c->stage[3].as<uint8_t>();
+    rc = strsim_default_process_device(c, s.a_off, s.a_val, rows, d_off, d_val, room);
+    if (rc) return rc;
+    const uint64_t total = c->proc_status_host->pad[0];
+    if (out_capacity < total) return process_capacity_error(who, out_capacity, total);
+    HIP_TRY(hipMemcpyAsync(out_off, d_off, (rows + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (total) HIP_TRY(hipMemcpyAsync(out_val, d_val, total, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return STRSIM_OK;
+}
+
+int strsim_pairs_processed_device(strsim_ctx_t *c, int measure, int processor, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
+                                  const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t out_rows)
+{
+    const char *const who = "strsim_pairs_processed_device";
+    uint64_t n;
+    int rc = pairs_processed_check(who, c, measure, processor, a_off, a_val, a_rows, b_off, b_val, b_rows, out, out_rows, &n);
+    if (rc || n == 0) return rc;
+    ProcessTable t;
+    rc = process_prepare(c, &t);
+    if (rc == STRSIM_OK) rc = process_retire_pending(c, who);
+    if (rc) return rc;
+    const uint64_t rows[2] = {a_rows, b_rows};
+    const uint32_t *const in_off[2] = {a_off, b_off};
+    const uint8_t *const in_val[2] = {a_val, b_val};
+    for (int s = 0; s < 2; ++s) {
+        rc = c->proc_off[s].reserve((rows[s] + 1) * sizeof(uint32_t));
+        if (rc) return rc;
+    }
+    HIP_TRY(hipMemsetAsync(c->proc_status, 0, sizeof(TokenStatus), c->stream));
+    c->enqueued_ops += 1u;
+    for (int s = 0; s < 2; ++s) {
+        rc = process_measure(c, s, t, in_off[s], in_val[s], rows[s], c->proc_off[s].as<uint32_t>());
+        if (rc) return rc;
+    }
+    rc = process_wait(c); // the one wait of the transform: both sides' totals
+    for (int s = 0; s < 2 && rc == STRSIM_OK; ++s) rc = process_check_size(who, c, s);
+    for (int s = 0; s < 2 && rc == STRSIM_OK; ++s) rc = c->proc_val[s].reserve((size_t)c->proc_status_host->pad[s] + TOKEN_PAD);
+    for (int s = 0; s < 2 && rc == STRSIM_OK; ++s)
+        rc = process_write(c, s, t, in_off[s], in_val[s], rows[s], c->proc_off[s].as<uint32_t>(), c->proc_val[s].as<uint8_t>());
+    if (rc) return rc;
+    return strsim_pairs_device(c, measure, c->proc_off[0].as<uint32_t>(), c->proc_val[0].as<uint8_t>(), a_rows, c->proc_off[1].as<uint32_t>(),
+                               c->proc_val[1].as<uint8_t>(), b_rows, out, out_rows);
+}
+
+int strsim_pairs_processed_host(strsim_ctx_t *c, int measure, int processor, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
+                                const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t out_rows)
+{
+    uint64_t n;
+    int rc = pairs_processed_check("strsim_pairs_processed_host", c, measure, processor, a_off, a_val, a_rows, b_off, b_val, b_rows, out, out_rows, &n);
+    if (rc || n == 0) return rc;
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    Staged s;
+    rc = ctx_stage(c, a_off, a_val, a_rows, b_off, b_val, b_rows, n * 8, &s);
+    if (rc) return rc;
+    rc = strsim_pairs_processed_device(c, measure, processor, s.a_off, s.a_val, a_rows, s.b_off, s.b_val, b_rows, (double *)s.out, n);
+    if (rc) return rc;
+    rc = strsim_ctx_synchronize(c); // also runs the long-string pass, which writes into the staged output
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, s.out, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return STRSIM_OK;
+}
+
+uint64_t strsim_ctx_last_process_wave_rows(strsim_ctx_t *c)
+{
+    if (!c || !c->proc_status_host) return 0;
+    const volatile uint32_t *w = c->proc_status_host->wave_rows;
+    return (uint64_t)w[0] + w[1];
 }
 
 } // extern "C"

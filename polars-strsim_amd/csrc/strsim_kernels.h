@@ -161,6 +161,12 @@ hipError_t launch_token_scan(uint32_t *out_off, uint64_t rows, uint32_t *sums, h
 // out[i] = the rule of token_set_ratio over rec[i] and d32[i] = indel_distance(ab, ba)
 hipError_t launch_token_set_epilogue(const TokenSetRec *rec, const uint32_t *d32, double *out, uint64_t n, hipStream_t stream);
 
+// default_process (strsim_process.h): the passes of the column transform, as launch_token_sort's -- measuring (write = false), then
+// launch_token_scan over out_off, then writing (write = true) with the same list; t holds device pointers of the table.
+struct ProcessTable;
+hipError_t launch_process(bool write, const uint32_t *off, const uint8_t *val, uint64_t rows, uint32_t *out_off, uint8_t *out_val, uint32_t *list,
+                          uint32_t *count, int grid, const ProcessTable &t, hipStream_t stream);
+
 // WRatio and the token compositions (strsim_wratio.h), measure ids 18 .. 26.  launch_wratio_classify: the class of each of a.n
 // pairs into cls, its position on the near or the far list into pos, the lists counted in st->rows (zeroed first).  launch_take: the
 // m rows `list` names of the column (off, val) as a column of their own -- lengths, launch_token_scan (sums: ceil(m / 4096) words),

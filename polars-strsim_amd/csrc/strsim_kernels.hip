@@ -33,6 +33,8 @@
 //   k_token_sort_* / k_token_set_*  token_sort_ratio and token_set_ratio (measures 14 and 16, strsim_token.h): tokenise, sort and
 //                     join (or merge as sets) every string into scratch columns that k_indel_lane / k_indel_wave then align;
 //                     ASCII strings of up to 64 bytes and 16 tokens per lane, the rest one string per wave.
+//   k_process_lane / k_process_wave  default_process (strsim_process.h): the column transform in front of processed scoring, a
+//                                   measuring and a writing pass around the token transforms' offset scan
 //   k_wratio_classify / k_take_* / k_wratio_combine  WRatio (measure 26, strsim_wratio.h): a row's class from the lengths of its
 //                     raw strings, the near and the far rows gathered into sub-frames for the token and the partial family, the
 //                     rule per row; k_max_f64 and k_partial_token_set_epilogue close token_ratio and the partial token ratios
@@ -66,6 +68,7 @@
 #include "strsim_partial.h"
 #include "strsim_token.h"
 #include "strsim_wratio.h"
+#include "strsim_process.h"
 #include "strsim_nearest.h"
 #include "strsim_extract.h"
 
@@ -674,6 +677,20 @@ hipError_t launch_token_scan(uint32_t *out_off, uint64_t rows, uint32_t *sums, h
     hipLaunchKernelGGL(k_token_scan_sums, dim3(nb), dim3(256), 0, stream, out_off + 1, rows, sums);
     hipLaunchKernelGGL(k_token_scan_top, dim3(1), dim3(256), 0, stream, sums, nb);
     hipLaunchKernelGGL(k_token_scan_apply, dim3(nb), dim3(256), 0, stream, out_off + 1, rows, sums);
+    return hipGetLastError();
+}
+
+hipError_t launch_process(bool write, const uint32_t *off, const uint8_t *val, uint64_t rows, uint32_t *out_off, uint8_t *out_val, uint32_t *list,
+                          uint32_t *count, int grid, const ProcessTable &t, hipStream_t stream)
+{
+    const dim3 lane_grid((unsigned)((rows + 255u) / 256u));
+    if (write) {
+        hipLaunchKernelGGL(k_process_lane<true>, lane_grid, dim3(256), 0, stream, off, val, rows, out_off, out_val, list, count);
+        hipLaunchKernelGGL(k_process_wave<true>, dim3((unsigned)grid), dim3(64), 0, stream, off, val, out_off, out_val, list, count, t);
+    } else {
+        hipLaunchKernelGGL(k_process_lane<false>, lane_grid, dim3(256), 0, stream, off, val, rows, out_off, out_val, list, count);
+        hipLaunchKernelGGL(k_process_wave<false>, dim3((unsigned)grid), dim3(64), 0, stream, off, val, out_off, out_val, list, count, t);
+    }
     return hipGetLastError();
 }
 

@@ -215,7 +215,22 @@ def indel_distance(expr: IntoExpr, other: IntoExpr, max_distance: int | None = N
     return _distance("indel_distance", expr, other, max_distance)
 
 
+def default_process(expr: IntoExpr) -> pl.Expr:
+    """rapidfuzz `utils.default_process` on the GPU, String in and String out: every character that is neither alphanumeric nor
+    "_" becomes a space, the others are lower-cased, and spaces are removed from both ends (inner runs of spaces stay:
+    "Apple, Inc." -> "apple  inc").  `indel(default_process(a), default_process(b))` is rapidfuzz's
+    `fuzz.ratio(a, b, processor=utils.default_process)` / 100.  Character by character: U+03A3 is lower-cased to U+03C3 in every
+    position and U+0130 to "i".  Nulls stay null.  Not in the upstream polars-strsim."""
+    return register_plugin_function(
+        plugin_path=_PLUGIN_DIR,
+        function_name="default_process",
+        args=[parse_into_expr(expr, dtype=pl.Utf8)],
+        is_elementwise=True,
+    )
+
+
 __all__ = [
+    "default_process",
     "best_match",
     "nearest",
     "levenshtein_distance",

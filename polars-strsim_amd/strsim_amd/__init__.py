@@ -8,7 +8,7 @@ validity mask), as in README.md:69-70.
 """
 import numpy as np
 
-from ._lib import DISTANCE_MEASURES, DISTANCE_UNBOUNDED, ENTRY_POINT_ID, EXTRA_MEASURES, INDEL_MEASURES, MEASURES, MEASURE_ID, PARTIAL_MEASURES, TOKEN_MEASURES, WEIGHTED_MEASURES, LIB_PATH, STATUS, ShapeMismatch, StrsimError, lib
+from ._lib import PROCESSORS, DISTANCE_MEASURES, DISTANCE_UNBOUNDED, ENTRY_POINT_ID, EXTRA_MEASURES, INDEL_MEASURES, MEASURES, MEASURE_ID, PARTIAL_MEASURES, TOKEN_MEASURES, WEIGHTED_MEASURES, LIB_PATH, STATUS, ShapeMismatch, StrsimError, lib, processor_id
 from .context import Codec, Context, device_count, pack_strings, split_offsets
 
 _default_ctx = None
@@ -31,14 +31,17 @@ def _as_column(x):
     return vals, (None if valid.all() else valid)
 
 
-def similarity(measure, a, b, ctx=None):
-    """f64 numpy array (NaN where either input is null) for two columns / a column and a literal."""
+def similarity(measure, a, b, ctx=None, processor=None):
+    """f64 numpy array (NaN where either input is null) for two columns / a column and a literal.  processor=None compares the
+    strings as they are; "default_process" (PROCESSORS) first runs default_process() over both sides, on the GPU."""
+    if processor is not None:
+        processor_id(processor)
     ctx = ctx or default_context()
     A, va = _as_column(a)
     B, vb = _as_column(b)
     ao, av = pack_strings(A)
     bo, bv = pack_strings(B)
-    out = ctx.pairs_host(measure, ao, av, bo, bv)
+    out = ctx.pairs_host(measure, ao, av, bo, bv) if processor is None else ctx.pairs_processed_host(measure, ao, av, bo, bv, processor)
     out[_null_mask(out.size, va, vb)] = np.nan
     return out
 
@@ -96,21 +99,21 @@ def osa(a, b, ctx=None):
     return similarity("osa", a, b, ctx)
 
 
-def indel(a, b, ctx=None):
+def indel(a, b, ctx=None, processor=None):
     """Indel similarity: rapidfuzz's fuzz.ratio / 100 (Indel.normalized_similarity).  With l the length of the longest common
     subsequence, d = len(a) + len(b) - 2 l (insertions and deletions only: a substitution costs 2) and the score is
     1.0 - d / (len(a) + len(b)) over characters, 1.0 when both are empty."""
-    return similarity("indel", a, b, ctx)
+    return similarity("indel", a, b, ctx, processor)
 
 
-def partial_ratio(a, b, ctx=None):
+def partial_ratio(a, b, ctx=None, processor=None):
     """Partial ratio: rapidfuzz's fuzz.partial_ratio / 100.  The best indel() score of the shorter string (the needle, m
     characters) against a window of the longer one: its proper prefixes of 1 .. m-1 characters, every substring of m characters,
     its proper suffixes (the needle slid over the longer string one step at a time, overhanging either end).  Equal lengths: the
     larger of the two directions.  1.0 when both are empty, 0.0 when exactly one is.  It can be LOWER than indel(a, b): when the
     lengths differ the whole longer string is not one of the windows.  It is the maximum at every needle length (rapidfuzz's
     heuristic for needles of more than 64 characters is not followed)."""
-    return similarity("partial_ratio", a, b, ctx)
+    return similarity("partial_ratio", a, b, ctx, processor)
 
 
 def partial_ratio_alignment(a, b, ctx=None):
@@ -129,49 +132,49 @@ def partial_ratio_alignment(a, b, ctx=None):
     return score, np.ma.MaskedArray(span, mask=np.repeat(mask[:, None], 4, axis=1))
 
 
-def token_sort_ratio(a, b, ctx=None):
+def token_sort_ratio(a, b, ctx=None, processor=None):
     """rapidfuzz's fuzz.token_sort_ratio / 100: indel() of the two strings with their tokens sorted, bit for bit.  Tokens are split
     at whitespace -- exactly Python's str.isspace set, 29 code points -- as str.split() does, sorted as Python sorts str (by code
     point, a proper prefix first) and joined with one space; duplicates are kept.  Two strings without tokens give 1.0, exactly
     one gives 0.0.  No lower-casing and no other pre-processing."""
-    return similarity("token_sort_ratio", a, b, ctx)
+    return similarity("token_sort_ratio", a, b, ctx, processor)
 
 
-def token_set_ratio(a, b, ctx=None):
+def token_set_ratio(a, b, ctx=None, processor=None):
     """rapidfuzz's fuzz.token_set_ratio / 100 over the SETS of tokens (split as for token_sort_ratio): 0.0 when either string has
     no token, 1.0 when the sets share a token and one contains the other, else the best indel() among the pairs of
     sect, sect + " " + ab and sect + " " + ba -- the joined sorted intersection and the two differences."""
-    return similarity("token_set_ratio", a, b, ctx)
+    return similarity("token_set_ratio", a, b, ctx, processor)
 
 
-def token_ratio(a, b, ctx=None):
+def token_ratio(a, b, ctx=None, processor=None):
     """rapidfuzz's fuzz.token_ratio / 100: max(token_sort_ratio(a, b), token_set_ratio(a, b))."""
-    return similarity("token_ratio", a, b, ctx)
+    return similarity("token_ratio", a, b, ctx, processor)
 
 
-def partial_token_sort_ratio(a, b, ctx=None):
+def partial_token_sort_ratio(a, b, ctx=None, processor=None):
     """rapidfuzz's fuzz.partial_token_sort_ratio / 100: partial_ratio() of the two strings with their tokens sorted (split, sorted
     and joined as for token_sort_ratio)."""
-    return similarity("partial_token_sort_ratio", a, b, ctx)
+    return similarity("partial_token_sort_ratio", a, b, ctx, processor)
 
 
-def partial_token_set_ratio(a, b, ctx=None):
+def partial_token_set_ratio(a, b, ctx=None, processor=None):
     """rapidfuzz's fuzz.partial_token_set_ratio / 100 over the SETS of tokens: 0.0 when either string has no token, 1.0 when the
     sets share a token, else partial_ratio() of the joined sorted differences."""
-    return similarity("partial_token_set_ratio", a, b, ctx)
+    return similarity("partial_token_set_ratio", a, b, ctx, processor)
 
 
-def partial_token_ratio(a, b, ctx=None):
+def partial_token_ratio(a, b, ctx=None, processor=None):
     """rapidfuzz's fuzz.partial_token_ratio / 100: max(partial_token_sort_ratio(a, b), partial_token_set_ratio(a, b))."""
-    return similarity("partial_token_ratio", a, b, ctx)
+    return similarity("partial_token_ratio", a, b, ctx, processor)
 
 
-def wratio(a, b, ctx=None):
+def wratio(a, b, ctx=None, processor=None):
     """rapidfuzz's fuzz.WRatio / 100 (the default scorer of process.extract), without a processor.  With lo, hi the shorter and
     the longer length in characters and r = indel(a, b): 0.0 when lo == 0; when 2 hi < 3 lo: max(r, token_ratio * 0.95);
     otherwise, with ps = 0.9 when hi <= 8 lo and 0.6 beyond: max(r, partial_ratio * ps, (partial_token_ratio * 0.95) * ps).
     The rows are classified on the GPU and each family runs over its own rows only (Context.last_wratio_rows())."""
-    return similarity("wratio", a, b, ctx)
+    return similarity("wratio", a, b, ctx, processor)
 
 
 def token_sort(col, ctx=None):
@@ -181,6 +184,21 @@ def token_sort(col, ctx=None):
     ctx = ctx or default_context()
     X, valid = _as_column(col)
     off, val = ctx.token_sort_host(*pack_strings(X))
+    raw = val.tobytes()
+    out = [raw[int(off[i]):int(off[i + 1])].decode("utf-8") for i in range(len(X))]
+    if valid is not None:
+        out = [s if ok else None for s, ok in zip(out, valid)]
+    return out
+
+
+def default_process(col, ctx=None):
+    """rapidfuzz's utils.default_process on the GPU: a list of str or None -> a list of str or None.  Every character that is
+    neither alphanumeric nor "_" becomes a space, the others are lower-cased, and spaces are removed from both ends; inner runs of
+    spaces stay ("Apple, Inc." -> "apple  inc").  Character by character: U+03A3 is U+03C3 in every position and U+0130 is "i".
+    indel(default_process(a), default_process(b)) is indel(a, b, processor="default_process")."""
+    ctx = ctx or default_context()
+    X, valid = _as_column(col)
+    off, val = ctx.default_process_host(*pack_strings(X))
     raw = val.tobytes()
     out = [raw[int(off[i]):int(off[i + 1])].decode("utf-8") for i in range(len(X))]
     if valid is not None:
@@ -263,19 +281,26 @@ EXTRACT_SCORERS = ("ratio", "token_sort_ratio")
 _EXTRACT_SCORER_MEASURE = {"ratio": "indel", "indel": "indel", "token_sort_ratio": "token_sort_ratio"}
 
 
-def extract(scorer, queries, candidates, k=1, score_cutoff=None, ctx=None):
+def extract(scorer, queries, candidates, k=1, score_cutoff=None, ctx=None, processor=None):
     """For every query, its k best candidates by `scorer` ("ratio" -- "indel" is an alias -- or "token_sort_ratio",
     EXTRACT_SCORERS): (index int64 [N, k], score f64 [N, k]).  The score is indel(q, c) or token_sort_ratio(q, c), in [0, 1], bit
     for bit the pairwise call's.  Slots in descending order of the score, ties to the lower candidate index; a candidate below
     score_cutoff is not reported (None: no cutoff).  Empty slots -- and every slot of a null query -- are (-1, NaN).  Null
     candidates are never matched; indices refer to the caller's candidate positions.
-    rapidfuzz: process.extract(q, candidates, scorer=fuzz.ratio, score_cutoff=100 * score_cutoff, limit=k), scores / 100."""
+    rapidfuzz: process.extract(q, candidates, scorer=fuzz.ratio, score_cutoff=100 * score_cutoff, limit=k), scores / 100.
+    processor="default_process" runs default_process() over the queries and the candidates on the GPU and searches those
+    (rapidfuzz's processor=utils.default_process)."""
     if scorer not in _EXTRACT_SCORER_MEASURE:
         raise ValueError(f"no extract by scorer {scorer!r} (one of {EXTRACT_SCORERS})")
+    if processor is not None:
+        processor_id(processor)
     ctx = ctx or default_context()
     Q, vq = _as_column(queries)
     qo, qv = pack_strings(Q)
     co, cv, pos = _pack_candidates(candidates)
+    if processor is not None:
+        qo, qv = ctx.default_process_host(qo, qv)
+        co, cv = ctx.default_process_host(co, cv)
     idx, score = ctx.extract(_EXTRACT_SCORER_MEASURE[scorer], qo, qv, co, cv, k, score_cutoff)
     out = _remap_candidates(idx, pos, vq)
     if vq is not None:
@@ -283,7 +308,7 @@ def extract(scorer, queries, candidates, k=1, score_cutoff=None, ctx=None):
     return out, score
 
 
-__all__ = ["best_match", "nearest", "Codec", "Context", "device_count", "pack_strings", "split_offsets", "similarity", "levenshtein", "jaro",
+__all__ = ["default_process", "PROCESSORS", "best_match", "nearest", "Codec", "Context", "device_count", "pack_strings", "split_offsets", "similarity", "levenshtein", "jaro",
            "jaro_winkler", "jaccard", "sorensen_dice", "osa", "indel", "measure_supported", "distance", "levenshtein_distance", "osa_distance",
            "indel_distance", "INDEL_MEASURES", "partial_ratio", "partial_ratio_alignment", "PARTIAL_MEASURES",
            "token_sort_ratio", "token_set_ratio", "token_sort", "TOKEN_MEASURES",

@@ -37,6 +37,17 @@ WEIGHTED_MEASURES = ("token_ratio", "partial_token_sort_ratio", "partial_token_s
 for _i, _m in enumerate(WEIGHTED_MEASURES):
     MEASURE_ID[_m] = 18 + 2 * _i
 ENTRY_POINT_ID = {"pairwise": 0, "best_match": 1, "codec": 2}  # strsim_entry_point_t
+# Processors of the processed-scoring calls (strsim_pairs_processed_*): "default_process" = STRSIM_PROCESS_DEFAULT = 1, rapidfuzz's
+# utils.default_process made context-free.  None is "no processor".
+PROCESSORS = ("default_process",)
+PROCESSOR_ID = {"default_process": 1}
+
+
+def processor_id(processor):
+    """The id of a processor name; ValueError for anything that is not one (None, "no processor", is the caller's to handle)."""
+    if not isinstance(processor, str) or processor not in PROCESSOR_ID:
+        raise ValueError(f"unknown processor {processor!r} (None or one of {PROCESSORS})")
+    return PROCESSOR_ID[processor]
 # The measures strsim_distance_device / _host accept (integer edit distances), with their ids; STRSIM_DISTANCE_UNBOUNDED = no cutoff.
 DISTANCE_MEASURES = ("levenshtein", "osa")
 DISTANCE_UNBOUNDED = 0xFFFFFFFF
@@ -129,6 +140,20 @@ def lib():
         f.argtypes = [vp, vp, vp, u64, vp, vp, u64]
     L.strsim_ctx_last_token_wave_rows.restype = u64
     L.strsim_ctx_last_token_wave_rows.argtypes = [vp]
+    for name in ("strsim_default_process_device", "strsim_default_process_host"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, vp, vp, u64, vp, vp, u64]
+    for name in ("strsim_pairs_processed_device", "strsim_pairs_processed_host"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, i32, i32, vp, vp, u64, vp, vp, u64, vp, u64]
+    L.strsim_ctx_last_process_wave_rows.restype = u64
+    L.strsim_ctx_last_process_wave_rows.argtypes = [vp]
+    L.strsim_default_process_char.restype = C.c_uint32
+    L.strsim_default_process_char.argtypes = [C.c_uint32]
+    L.strsim_default_process_unicode_version.restype = C.c_char_p
+    L.strsim_default_process_unicode_version.argtypes = []
     L.strsim_ctx_last_wratio_rows.restype = i32
     L.strsim_ctx_last_wratio_rows.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     for name in ("strsim_nearest_device", "strsim_nearest_host"):

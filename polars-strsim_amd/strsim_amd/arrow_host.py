@@ -150,6 +150,43 @@ def call_plugin(name, a, b, layout="vu", names=("a", "b"), parallel=False, _prob
     return res
 
 
+def call_plugin_unary(name, a, layout="vu", input_name="a", _probe=None, out_type=None):
+    """Evaluate plugin expression `name` over ONE column (a list / pyarrow array / chunked array), as call_plugin does over two.
+    Returns a pyarrow ChunkedArray of `out_type` (default: string, what default_process returns)."""
+    out_type = pa.string() if out_type is None else out_type
+    L = _load()
+    fn = getattr(L, "_polars_plugin_" + name)
+    fn.restype = None
+    fn.argtypes = [C.POINTER(SeriesExport), C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(SeriesExport),
+                   C.POINTER(CallerContext)]
+    L._polars_plugin_get_last_error_message.restype = C.c_char_p
+    inputs = (SeriesExport * 1)()
+    chunks, dtype = _chunks(a, layout)
+    ex = _Exported(input_name, chunks, dtype)
+    ex.fill(inputs[0])
+    ret = SeriesExport()
+    ctx = CallerContext(0)
+    fn(inputs, 1, None, 0, C.byref(ret), C.byref(ctx))
+    if _probe is not None:
+        _probe["series_released"] = [ex.released]
+        _probe["arrays_released"] = [ex.arrays_released()]
+    if not ret.private_data:
+        raise PluginError("the plugin failed with message: " + L._polars_plugin_get_last_error_message().decode())
+    try:
+        out = [pa.Array._import_from_c(C.addressof(ret.arrays[i].contents), out_type) for i in range(ret.len)]
+        name_out = ret.field.contents.name.decode() if ret.field.contents.name else ""
+        fmt_out = ret.field.contents.format.decode() if ret.field.contents.format else ""
+        moved = all(not ret.arrays[i].contents.release for i in range(ret.len))  # (the importer took every array)
+    finally:
+        ret.release(C.byref(ret))
+    if _probe is not None:
+        _probe["name"] = name_out
+        _probe["format"] = fmt_out
+        _probe["series_released_after"] = not ret.private_data
+        _probe["arrays_moved"] = moved
+    return pa.chunked_array(out, type=out_type)
+
+
 def field_plugin(name, input_names=("a", "b")):
     """Planning-time output field of plugin expression `name` -> (field name, pyarrow type)."""
     L = _load()

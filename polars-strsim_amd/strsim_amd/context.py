@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import DISTANCE_UNBOUNDED, check, lib, measure_id
+from ._lib import DISTANCE_UNBOUNDED, check, lib, measure_id, processor_id
 
 
 def split_offsets(length, n):
@@ -84,6 +84,12 @@ class Context:
         wave, both columns added up; 0 when every row took the one-string-per-lane tier.  Valid once the stream has completed
         that call (synchronize())."""
         return int(lib().strsim_ctx_last_token_wave_rows(self._h))
+
+    @property
+    def last_process_wave_rows(self):
+        """Rows the last default_process_* / pairs_processed_* call rewrote one string per wave (non-ASCII, or longer than 64 bytes),
+        both columns added up; 0 when every row took the one-string-per-lane tier.  Valid when that call has returned."""
+        return int(lib().strsim_ctx_last_process_wave_rows(self._h))
 
     def last_wratio_rows(self):
         """-> (near, far): how the last completed wratio call routed its rows -- to the token family (2 hi < 3 lo in characters)
@@ -235,7 +241,64 @@ class Context:
                                              out_values.data_ptr(), out_values.numel()))
         return out_offsets, out_values
 
+    def default_process_device(self, offsets, values, out_offsets=None, out_values=None):
+        """default_process (strsim_default_process_device) of a device column laid out as for pairs_device -> (offsets int32
+        [rows + 1], values uint8): row i is lower-cased, every scalar value that is neither alphanumeric nor "_" becomes a space,
+        and spaces are removed from both ends.  A processed row can be longer than its input: out_values defaults to
+        bytes + bytes / 2, which always suffices; offsets[rows] is the exact size.  Complete in stream order; the call waits once
+        for the stream (between its measuring and its writing pass)."""
+        import torch
+        rows = offsets.numel() - 1
+        _check_device_column(offsets, values)
+        if out_offsets is None:
+            out_offsets = torch.empty(rows + 1, dtype=torch.int32, device=offsets.device)
+        if out_values is None:
+            out_values = torch.empty(max(values.numel() + values.numel() // 2, 1), dtype=torch.uint8, device=offsets.device)
+        _check_device_column(out_offsets, out_values)
+        assert out_offsets.numel() == rows + 1
+        check(lib().strsim_default_process_device(self._h, offsets.data_ptr(), values.data_ptr(), rows, out_offsets.data_ptr(),
+                                                  out_values.data_ptr(), out_values.numel()))
+        return out_offsets, out_values
+
+    def pairs_processed_device(self, measure, a_offsets, a_values, b_offsets, b_values, out=None, processor="default_process"):
+        """pairs_device over the processed columns (strsim_pairs_processed_device): both sides go through `processor` on the
+        device, into scratch of the context, and `measure` runs over the result -- bit for bit pairs_device(measure) over
+        default_process_device of each side.  Returns the f64 output tensor; complete after synchronize()."""
+        import torch
+        ra, rb = a_offsets.numel() - 1, b_offsets.numel() - 1
+        n = rb if ra == 1 else ra
+        _check_device_column(a_offsets, a_values)
+        _check_device_column(b_offsets, b_values)
+        if out is None:
+            out = torch.empty(n if (ra == rb or ra == 1 or rb == 1) else 0, dtype=torch.float64, device=a_offsets.device)
+        check(lib().strsim_pairs_processed_device(self._h, measure_id(measure), processor_id(processor),
+                                                  a_offsets.data_ptr(), a_values.data_ptr(), ra,
+                                                  b_offsets.data_ptr(), b_values.data_ptr(), rb,
+                                                  out.data_ptr(), out.numel()))
+        return out
+
     # ---- host-resident (numpy) ---------------------------------------------------------------------
+    def default_process_host(self, offsets, values):
+        """Synchronous default_process (strsim_default_process_host): numpy uint32 offsets + uint8 values in -> (uint32 offsets
+        from 0, uint8 values of offsets[-1] bytes)."""
+        off, val, rows = _host_column(offsets, values)
+        out_off = np.empty(rows + 1, dtype=np.uint32)
+        cap = int(off[rows]) - int(off[0])
+        cap += cap // 2
+        out_val = np.empty(max(cap, 1), dtype=np.uint8)
+        check(lib().strsim_default_process_host(self._h, off.ctypes.data, val.ctypes.data, rows, out_off.ctypes.data, out_val.ctypes.data, cap))
+        return out_off, out_val[:int(out_off[rows])]
+
+    def pairs_processed_host(self, measure, a_offsets, a_values, b_offsets, b_values, processor="default_process"):
+        """Synchronous processed scoring (strsim_pairs_processed_host): numpy uint32 offsets + uint8 values in, numpy f64 out."""
+        ao, av, ra = _host_column(a_offsets, a_values)
+        bo, bv, rb = _host_column(b_offsets, b_values)
+        n = _rows_out(ra, rb)
+        out = np.empty(n, dtype=np.float64)
+        check(lib().strsim_pairs_processed_host(self._h, measure_id(measure), processor_id(processor), ao.ctypes.data, av.ctypes.data, ra,
+                                                bo.ctypes.data, bv.ctypes.data, rb, out.ctypes.data, n))
+        return out
+
     def token_sort_host(self, offsets, values):
         """Synchronous token_sort transform (strsim_token_sort_host): numpy uint32 offsets + uint8 values in -> (uint32 offsets
         from 0, uint8 values of offsets[-1] bytes)."""
