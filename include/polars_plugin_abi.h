@@ -164,6 +164,19 @@ POLARS_PLUGIN_DECLARE(nearest_osa)
 POLARS_PLUGIN_DECLARE(extract_ratio)
 POLARS_PLUGIN_DECLARE(extract_token_sort_ratio)
 
+/* cdist: the scores of every query against every candidate (not in the reference; rapidfuzz's process.cdist with scores / 100, the
+ * matrix of strsim_cdist_host row by row): inputs 0 and 1 as extract (queries, candidates of any length M), an optional input 2 is
+ * score_cutoff, parsed as extract parses it; a score below it is 0.0.  Output: N rows of an Arrow LargeList<Float64> ("+L", child
+ * "item") named after input 0 -- row i is the list of the M scores of query i, in the order of input 1.  A null query gives a null
+ * list; a null candidate gives a null element (the child's validity) at its position in every list. */
+POLARS_PLUGIN_DECLARE(cdist_levenshtein)
+POLARS_PLUGIN_DECLARE(cdist_jaro)
+POLARS_PLUGIN_DECLARE(cdist_jaro_winkler)
+POLARS_PLUGIN_DECLARE(cdist_jaccard)
+POLARS_PLUGIN_DECLARE(cdist_sorensen_dice)
+POLARS_PLUGIN_DECLARE(cdist_ratio)
+POLARS_PLUGIN_DECLARE(cdist_token_sort_ratio)
+
 /* default_process (not in the reference; rapidfuzz's utils.default_process made context-free, strsim_default_process_host of
  * strsim_amd.h): ONE input, a string series in any of the three layouts; elementwise.  Output: N rows of Arrow Utf8 ("u": int32
  * offsets -- the transform's 32-bit offsets are the buffer as it is; a result beyond 2^31 - 1 bytes is an error) named after

@@ -495,6 +495,40 @@ STRSIM_API int strsim_extract_host(strsim_ctx_t *ctx, int scorer,
                                    const uint32_t *c_offsets, const uint8_t *c_values, uint64_t c_rows,
                                    uint32_t k, double score_cutoff, uint32_t *out_index, double *out_score);
 
+/*
+ * cdist: the full score matrix of queries x candidates -- rapidfuzz's process.cdist with scores / 100 (found by dlsym, like the
+ * search calls: the ABI version stays 1.7, and strsim_measure_supported does not describe these two entry points).  `measure` is
+ * one of the reference measures (ids 0 .. 4), STRSIM_INDEL (8) or STRSIM_TOKEN_SORT_RATIO (14); any other id is STRSIM_ERR_ARG.
+ * out is row-major f64 with leading dimension out_ld >= c_rows: out[i * out_ld + j] is bit for bit what
+ * strsim_pairs_device(measure, queries[i], candidates[j]) returns, except that a score < score_cutoff is stored as 0.0
+ * (rapidfuzz's rule; score_cutoff = -INFINITY or 0.0 changes nothing, a cutoff above 1.0 gives all zeros, NaN is STRSIM_ERR_ARG).
+ * Columns c_rows .. out_ld - 1 of every row are never written.
+ *
+ * q_rows <= 2^32 - 1, c_rows <= 2^32 - 2; q_rows == 0 or c_rows == 0 is a no-op.  out_ld < c_rows, a NULL buffer of a non-empty
+ * side or a NULL out of a non-empty matrix, a bad measure or a NaN cutoff: STRSIM_ERR_ARG.  The arguments are checked first, the
+ * context last (a NULL ctx is STRSIM_ERR_ARG too): no argument error needs a device.  Nulls are not seen here.
+ *
+ * Device-resident: the same column layout as strsim_pairs_device; out needs 8-byte alignment only.  Strings of at most 32 ASCII
+ * bytes are scored one query per lane against every candidate and the scores leave through a tile of LDS in whole rows; every
+ * pair with a longer or non-ASCII side goes through strsim_pairs_device (that string as the literal): a slow query straight into
+ * its row, a slow candidate into one scratch column of q_rows doubles that is then scattered into its column.  Measure 14 first
+ * normalises both columns on the device with the token_sort transform, as strsim_extract_device does.
+ * Waits for the stream: measure 14 waits once for the bounds of its columns; every call waits once for a read-back of how many
+ * strings fall outside the one-query-per-lane class.  Without such strings it then returns with the sweep enqueued: the matrix is
+ * complete after strsim_ctx_synchronize(), or in stream order.  With them it runs those pairs through strsim_pairs_device batch by
+ * batch, each of which waits for the stream.  Scratch the context cannot reserve is STRSIM_ERR_OOM.
+ */
+STRSIM_API int strsim_cdist_device(strsim_ctx_t *ctx, int measure,
+                                   const uint32_t *q_offsets, const uint8_t *q_values, uint64_t q_rows,
+                                   const uint32_t *c_offsets, const uint8_t *c_values, uint64_t c_rows,
+                                   double score_cutoff, double *out, uint64_t out_ld);
+
+/* The same with HOST-RESIDENT buffers (the column layout of strsim_pairs_host, out included); synchronous. */
+STRSIM_API int strsim_cdist_host(strsim_ctx_t *ctx, int measure,
+                                 const uint32_t *q_offsets, const uint8_t *q_values, uint64_t q_rows,
+                                 const uint32_t *c_offsets, const uint8_t *c_values, uint64_t c_rows,
+                                 double score_cutoff, double *out, uint64_t out_ld);
+
 /* Row partition used to shard a column over `n` GPUs/ranks: the reference's split_offsets
  * (strsim.rs:21-39).  Writes n (offset,len) pairs into out_offset_len[2*n]. */
 STRSIM_API void strsim_split_offsets(uint64_t len, uint64_t n, uint64_t *out_offset_len);

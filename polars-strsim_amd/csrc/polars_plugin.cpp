@@ -153,6 +153,7 @@ void export_primitive(const char *format, const char *name, uint64_t n, void *da
 #include "plugin_partial.h"
 #include "plugin_nearest.h"
 #include "plugin_extract.h"
+#include "plugin_cdist.h"
 #include "plugin_process.h"
 
 void run(int measure, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret, bool engine_parallel)
@@ -261,6 +262,9 @@ void _polars_plugin_strsim_coalesce_stats(uint64_t out[4]) { if (out) combiner()
     POLARS_PLUGIN_EXPORT(nearest_##name, run_nearest(id, inputs, n_inputs, return_value), STRUCT_FIELD(NEAREST_STRUCT))
 #define POLARS_PLUGIN_DEFINE_EXTRACT(name, id) \
     POLARS_PLUGIN_EXPORT(extract_##name, run_extract(id, inputs, n_inputs, return_value), STRUCT_FIELD(MATCH_STRUCT))
+#define POLARS_PLUGIN_DEFINE_CDIST(name, id)                                      \
+    POLARS_PLUGIN_EXPORT(cdist_##name, run_cdist(id, inputs, n_inputs, return_value), \
+                         field_named_after_input0(input_fields, n_fields, return_value, fill_list_f64_schema))
 #define POLARS_PLUGIN_DEFINE_MATCH(name, id) \
     POLARS_PLUGIN_EXPORT(best_match_##name, run_best_match(id, inputs, n_inputs, return_value), STRUCT_FIELD(MATCH_STRUCT))
 
@@ -548,6 +552,13 @@ POLARS_PLUGIN_DEFINE_NEAREST(levenshtein, STRSIM_LEVENSHTEIN)
 POLARS_PLUGIN_DEFINE_NEAREST(osa, STRSIM_OSA)
 POLARS_PLUGIN_DEFINE_EXTRACT(ratio, STRSIM_INDEL)
 POLARS_PLUGIN_DEFINE_EXTRACT(token_sort_ratio, STRSIM_TOKEN_SORT_RATIO)
+POLARS_PLUGIN_DEFINE_CDIST(levenshtein, STRSIM_LEVENSHTEIN)
+POLARS_PLUGIN_DEFINE_CDIST(jaro, STRSIM_JARO)
+POLARS_PLUGIN_DEFINE_CDIST(jaro_winkler, STRSIM_JARO_WINKLER)
+POLARS_PLUGIN_DEFINE_CDIST(jaccard, STRSIM_JACCARD)
+POLARS_PLUGIN_DEFINE_CDIST(sorensen_dice, STRSIM_SORENSEN_DICE)
+POLARS_PLUGIN_DEFINE_CDIST(ratio, STRSIM_INDEL)
+POLARS_PLUGIN_DEFINE_CDIST(token_sort_ratio, STRSIM_TOKEN_SORT_RATIO)
 POLARS_PLUGIN_EXPORT(default_process, run_default_process(inputs, n_inputs, return_value),
                      field_named_after_input0(input_fields, n_fields, return_value, [](ArrowSchema *s, const char *n) { fill_named_schema(s, "u", n); }))
 POLARS_PLUGIN_DEFINE_MATCH(levenshtein, STRSIM_LEVENSHTEIN)

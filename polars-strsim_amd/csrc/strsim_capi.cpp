@@ -27,6 +27,7 @@
 #include "strsim_process.h"
 #include "strsim_nearest.h"
 #include "strsim_extract.h"
+#include "strsim_cdist.h"
 
 namespace strsim {
 
@@ -171,6 +172,11 @@ struct strsim_ctx {
     DevBuf extract_ws, extract_scratch, extract_tab;
     bool extract_tab_ready = false;
     DevBuf extract_off[2], extract_val[2];
+    // strsim_cdist_device: the packed strings and slow lists, the fallback's score columns and the device copy of the Indel score
+    // table (strsim_cdist.h) -- buffers of its own, for the same reason; scorer 14 normalises into extract_off / extract_val,
+    // which no flow inside a cdist call uses
+    DevBuf cdist_ws, cdist_scratch, cdist_tab;
+    bool cdist_tab_ready = false;
 
     // ---- two-pass measures (two_pass: pairs_osa, distance_device_impl, partial_device_impl) ----
     DevBuf osa_list;                 // the work list of the wave kernel (one word per row)
@@ -2294,6 +2300,168 @@ int strsim_extract_host(strsim_ctx_t *c, int scorer, const uint32_t *q_off, cons
             return strsim_extract_device(c, scorer, s.a_off, s.a_val, q_rows, s.b_off, s.b_val, c_rows, k, score_cutoff, d_index, d_score);
         },
         [&] { return strsim_ctx_synchronize(c); });
+}
+
+} // extern "C"
+
+// ---- cdist: the full score matrix (strsim_cdist.h, strsim_cdist_kernels.h) ----
+
+static bool cdist_measure(int m) { return (m >= STRSIM_LEVENSHTEIN && m <= STRSIM_SORENSEN_DICE) || m == STRSIM_INDEL || m == STRSIM_TOKEN_SORT_RATIO; }
+
+static int cdist_check(const char *who, strsim_ctx_t *c, int measure, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows,
+                       const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, double score_cutoff, const double *out, uint64_t out_ld)
+{
+    if (!cdist_measure(measure)) {
+        set_error("%s: measure %d is not a measure of cdist (the reference measures 0 .. 4, STRSIM_INDEL = 8 or STRSIM_TOKEN_SORT_RATIO = 14)", who,
+                  measure);
+        return STRSIM_ERR_ARG;
+    }
+    if (score_cutoff != score_cutoff) { set_error("%s: score_cutoff is NaN", who); return STRSIM_ERR_ARG; }
+    if (q_rows > 0xFFFFFFFFull) { set_error("%s: %llu queries (at most 2^32 - 1)", who, (unsigned long long)q_rows); return STRSIM_ERR_ARG; }
+    if (c_rows > 0xFFFFFFFEull) { set_error("%s: %llu candidates (at most 2^32 - 2)", who, (unsigned long long)c_rows); return STRSIM_ERR_ARG; }
+    if (out_ld < c_rows) {
+        set_error("%s: out_ld=%llu is less than the %llu candidates of a row", who, (unsigned long long)out_ld, (unsigned long long)c_rows);
+        return STRSIM_ERR_ARG;
+    }
+    if (q_rows && (!q_off || !q_val)) { set_error("%s: NULL query buffer", who); return STRSIM_ERR_ARG; }
+    if (c_rows && (!c_off || !c_val)) { set_error("%s: NULL candidate buffer", who); return STRSIM_ERR_ARG; }
+    if (q_rows && c_rows && !out) { set_error("%s: NULL output buffer", who); return STRSIM_ERR_ARG; }
+    if (!c) { set_error("%s: ctx is NULL", who); return STRSIM_ERR_ARG; }
+    return STRSIM_OK;
+}
+
+// The Indel score table of strsim_cdist.h, built once per process.
+static const double *cdist_indel_table()
+{
+    static const double *const t = [] {
+        double *n = new double[CDIST_TAB_N];
+        cdist_build_indel_table(n);
+        return n;
+    }();
+    return t;
+}
+
+// The matrix of one pairwise measure (0 .. 4 or STRSIM_INDEL) over two columns (for STRSIM_TOKEN_SORT_RATIO: the normalised ones).
+static int cdist_matrix(strsim_ctx *c, int measure, const uint32_t *q_off, const uint8_t *q_val, uint32_t nq, const uint32_t *c_off,
+                        const uint8_t *c_val, uint32_t nc, double cutoff, double *out, uint64_t ld)
+{
+    const char *const who = "strsim_cdist_device";
+    hipStream_t st = c->stream;
+    const double *tab = c->qtab;
+    if (measure == STRSIM_INDEL) {
+        if (!c->cdist_tab_ready) {
+            int rc = c->cdist_tab.reserve(CDIST_TAB_N * sizeof(double));
+            if (rc) return rc;
+            HIP_TRY(hipMemcpyAsync(c->cdist_tab.p, cdist_indel_table(), CDIST_TAB_N * sizeof(double), hipMemcpyHostToDevice, st));
+            c->cdist_tab_ready = true;
+        }
+        tab = c->cdist_tab.as<double>();
+    }
+    SearchPack p; // (tail: the two slow counts)
+    int rc = search_pack(c, c->cdist_ws, 256, 8, q_off, q_val, nq, c_off, c_val, nc, &p);
+    if (rc) return rc;
+    c->enqueued_ops += 4u;
+    // fast x fast; a pair with a slow side is written as 0.0 here and by the fallback below, which is enqueued behind this grid
+    if (p.q_slow < nq && p.c_slow < nc) {
+        const uint32_t splits = cdist_splits(nq, nc, c->num_cu);
+        const uint32_t per = (uint32_t)(((uint64_t)nc + splits - 1) / splits);
+        const uint32_t nsplit = (uint32_t)(((uint64_t)nc + per - 1) / per);
+        HIP_TRY(launch_cdist_lane(measure, CdistLaneArgs{p.qw, p.qm, nq, p.cw, p.cm, nc, nsplit, per, tab, cutoff, out, ld, st}));
+        c->enqueued_ops += 1u;
+    }
+    const uint32_t q_slow = p.q_slow, c_slow = p.c_slow;
+    if (!q_slow && !c_slow) return STRSIM_OK;
+
+    // every pair with a slow side: strsim_pairs_device with that side as the literal (search_fallback's argument order), batch by
+    // batch; a batch is waited for (the long-string pass of a pairwise call writes from strsim_ctx_synchronize)
+    const uint32_t calls = (uint32_t)fallback_calls(nq, nc);
+    const std::unique_ptr<uint32_t[]> host_list(new (std::nothrow) uint32_t[(size_t)q_slow + c_slow + 1]);
+    if (!host_list) { set_error("%s: out of host memory", who); return STRSIM_ERR_OOM; }
+    if (q_slow) HIP_TRY(hipMemcpyAsync(host_list.get(), p.qs, (size_t)q_slow * 4, hipMemcpyDeviceToHost, st));
+    if (c_slow) HIP_TRY(hipMemcpyAsync(host_list.get() + q_slow, p.cs, (size_t)c_slow * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (uint32_t b0 = 0; b0 < q_slow; b0 += calls) { // a slow query against every candidate: straight into its row
+        const uint32_t nb = q_slow - b0 < calls ? q_slow - b0 : calls;
+        for (uint32_t b = 0; b < nb; ++b) {
+            const uint32_t i = host_list[b0 + b];
+            rc = strsim_pairs_device(c, measure, q_off + i, q_val, 1, c_off, c_val, nc, out + cdist_index(i, ld, 0), nc);
+            if (rc) return rc;
+        }
+        rc = strsim_ctx_synchronize(c);
+        if (rc) return rc;
+        if (cutoff > 0.0) HIP_TRY(launch_cdist_cutoff(out, p.qs + b0, nb, nc, ld, cutoff, st));
+    }
+    if (c_slow) {
+        rc = c->cdist_scratch.reserve((size_t)calls * nq * sizeof(double));
+        if (rc) return rc;
+    }
+    double *const col = c->cdist_scratch.as<double>();
+    for (uint32_t b0 = 0; b0 < c_slow; b0 += calls) { // a slow candidate against every query: a scratch column, then its column
+        const uint32_t nb = c_slow - b0 < calls ? c_slow - b0 : calls;
+        for (uint32_t b = 0; b < nb; ++b) {
+            rc = strsim_pairs_device(c, measure, c_off + host_list[q_slow + b0 + b], c_val, 1, q_off, q_val, nq, col + (size_t)b * nq, nq);
+            if (rc) return rc;
+        }
+        rc = strsim_ctx_synchronize(c);
+        if (rc) return rc;
+        HIP_TRY(launch_cdist_put_col(col, p.cs + b0, nb, p.qm, nq, cutoff, out, ld, st));
+    }
+    return STRSIM_OK;
+}
+
+extern "C" {
+
+int strsim_cdist_device(strsim_ctx_t *c, int measure, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows, const uint32_t *c_off,
+                        const uint8_t *c_val, uint64_t c_rows, double score_cutoff, double *out, uint64_t out_ld)
+{
+    int rc = cdist_check("strsim_cdist_device", c, measure, q_off, q_val, q_rows, c_off, c_val, c_rows, score_cutoff, out, out_ld);
+    if (rc || q_rows == 0 || c_rows == 0) return rc;
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    const uint32_t nq = (uint32_t)q_rows, nc = (uint32_t)c_rows;
+    if (measure == STRSIM_TOKEN_SORT_RATIO) {
+        // both sides through the token_sort transform into the context's own columns, as strsim_extract_device; one wait (the bounds)
+        rc = token_prepare(c);
+        if (rc) return rc;
+        rc = token_bounds(c, q_off, q_rows, c_off, c_rows);
+        if (rc) return rc;
+        const TokenStatus ts = *c->tok_status_host;
+        const uint32_t *const in_off[2] = {q_off, c_off};
+        const uint8_t *const in_val[2] = {q_val, c_val};
+        const uint64_t rows[2] = {q_rows, c_rows};
+        for (int s = 0; s < 2; ++s) {
+            rc = c->extract_off[s].reserve((rows[s] + 1) * sizeof(uint32_t));
+            if (rc == STRSIM_OK) rc = c->extract_val[s].reserve((uint64_t)ts.end[s] - ts.begin[s] + TOKEN_PAD);
+            if (rc == STRSIM_OK)
+                rc = token_sort_column(c, s, in_off[s], in_val[s], rows[s], ts.max_len[s], c->extract_off[s].as<uint32_t>(),
+                                       c->extract_val[s].as<uint8_t>());
+            if (rc) return rc;
+        }
+        rc = token_copy_counts(c);
+        if (rc) return rc;
+        q_off = c->extract_off[0].as<uint32_t>(); q_val = c->extract_val[0].as<uint8_t>();
+        c_off = c->extract_off[1].as<uint32_t>(); c_val = c->extract_val[1].as<uint8_t>();
+        measure = STRSIM_INDEL;
+    }
+    return cdist_matrix(c, measure, q_off, q_val, nq, c_off, c_val, nc, score_cutoff, out, out_ld);
+}
+
+int strsim_cdist_host(strsim_ctx_t *c, int measure, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows, const uint32_t *c_off,
+                      const uint8_t *c_val, uint64_t c_rows, double score_cutoff, double *out, uint64_t out_ld)
+{
+    int rc = cdist_check("strsim_cdist_host", c, measure, q_off, q_val, q_rows, c_off, c_val, c_rows, score_cutoff, out, out_ld);
+    if (rc || q_rows == 0 || c_rows == 0) return rc;
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    const size_t row_bytes = (size_t)c_rows * sizeof(double);
+    Staged s;
+    rc = ctx_stage(c, q_off, q_val, q_rows, c_off, c_val, c_rows, (size_t)q_rows * row_bytes + 16, &s);
+    if (rc) return rc;
+    double *const d_out = reinterpret_cast<double *>(s.out);
+    rc = strsim_cdist_device(c, measure, s.a_off, s.a_val, q_rows, s.b_off, s.b_val, c_rows, score_cutoff, d_out, c_rows);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy2DAsync(out, (size_t)out_ld * sizeof(double), d_out, row_bytes, row_bytes, (size_t)q_rows, hipMemcpyDeviceToHost, c->stream));
+    return strsim_ctx_synchronize(c);
 }
 
 } // extern "C"

@@ -223,5 +223,24 @@ struct ExtractLaneArgs {
 };
 hipError_t launch_extract_lane(const ExtractLaneArgs &a);
 
+// The full score matrix (strsim_cdist_kernels.h), measures 0 .. 4 and 8 (Indel).  Both sides packed by launch_match_pack;
+// launch_cdist_lane writes out[i * ld + j] for every pair of split s's candidates [s * per, ...), 0.0 where a side is outside the
+// lane class.  tab: the quotient table (measures 0 .. 2), the Indel score table of strsim_cdist.h (8), unused otherwise.
+// launch_cdist_put_col: nb columns of nq pairwise scores into columns clist[b], the rows of slow queries left alone;
+// launch_cdist_cutoff: the cutoff rule over rows qlist[b].
+struct CdistLaneArgs {
+    const uint32_t *qwords, *qmeta; uint32_t nq;
+    const uint32_t *cwords, *cmeta; uint32_t nc;
+    uint32_t splits, per;
+    const double *tab;
+    double cutoff;
+    double *out; uint64_t ld;
+    hipStream_t stream;
+};
+hipError_t launch_cdist_lane(int measure, const CdistLaneArgs &a);
+hipError_t launch_cdist_put_col(const double *scores, const uint32_t *clist, uint32_t nb, const uint32_t *qmeta, uint32_t nq, double cutoff,
+                                double *out, uint64_t ld, hipStream_t stream);
+hipError_t launch_cdist_cutoff(double *out, const uint32_t *qlist, uint32_t nb, uint32_t nc, uint64_t ld, double cutoff, hipStream_t stream);
+
 } // namespace strsim
 

@@ -44,6 +44,8 @@
 //                     candidates, a candidate length window and a running bound per lane.  Nearest match by bounded edit
 //                     distance (NearestRules, strsim_nearest.h); top-k by Indel similarity with a score cutoff, scores ordered
 //                     through a rank table in LDS (ExtractRules, strsim_extract.h; strsim_extract_kernels.h).
+//   k_cdist_lane<M>   the full score matrix (strsim_cdist.h, strsim_cdist_kernels.h): k_match_lane's sweep with every score kept,
+//                     staged per wave in a tile of LDS and written out row-wise; k_cdist_put_col / k_cdist_cutoff close its fallback.
 //   k_huge_pairs<M>   strings beyond WAVE_CAP, scratch in global memory, launched from strsim_ctx_synchronize() only
 //                     when such rows were counted; Levenshtein: the block step in stripes of 64 blocks, any length.
 //
@@ -71,6 +73,7 @@
 #include "strsim_process.h"
 #include "strsim_nearest.h"
 #include "strsim_extract.h"
+#include "strsim_cdist.h"
 
 namespace strsim {
 
@@ -88,6 +91,7 @@ struct OutPtrs {
 #include "strsim_match.h"
 #include "strsim_nearest_kernels.h"
 #include "strsim_extract_kernels.h"
+#include "strsim_cdist_kernels.h"
 
 #include "strsim_kernel_wide.h"
 #include "strsim_kernel_utf8.h"
@@ -541,6 +545,44 @@ hipError_t launch_extract_lane(const ExtractLaneArgs &a)
         hipLaunchKernelGGL(k_extract_lane<decltype(K)::value>, dim3(match_grid(s.nq), s.splits), dim3(MATCH_BLOCK), 0, s.stream, s.qwords, s.qmeta,
                            s.qperm, s.qstart, s.nq, s.swords, s.smeta, s.sidx, s.cstart, a.tab, a.rlimit, s.pscore, s.pidx);
     });
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// cdist (strsim_cdist_kernels.h)
+// ------------------------------------------------------------------------------------------------
+template <int M>
+static void launch_cdist_lane_m(const CdistLaneArgs &a)
+{
+    hipLaunchKernelGGL(k_cdist_lane<M>, dim3((unsigned)(((uint64_t)a.nq + CDIST_BLOCK - 1) / CDIST_BLOCK), a.splits), dim3(CDIST_BLOCK), 0, a.stream, a.qwords, a.qmeta, a.nq, a.cwords,
+                       a.cmeta, a.nc, a.per, a.tab, a.cutoff, a.out, a.ld);
+}
+
+hipError_t launch_cdist_lane(int measure, const CdistLaneArgs &a)
+{
+    switch (measure) {
+    case LEVENSHTEIN: launch_cdist_lane_m<LEVENSHTEIN>(a); break;
+    case JARO: launch_cdist_lane_m<JARO>(a); break;
+    case JARO_WINKLER: launch_cdist_lane_m<JARO_WINKLER>(a); break;
+    case JACCARD: launch_cdist_lane_m<JACCARD>(a); break;
+    case SORENSEN_DICE: launch_cdist_lane_m<SORENSEN_DICE>(a); break;
+    default: launch_cdist_lane_m<INDEL>(a); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_cdist_put_col(const double *scores, const uint32_t *clist, uint32_t nb, const uint32_t *qmeta, uint32_t nq, double cutoff,
+                                double *out, uint64_t ld, hipStream_t stream)
+{
+    if (nb == 0u || nq == 0u) return hipSuccess;
+    hipLaunchKernelGGL(k_cdist_put_col, dim3(match_grid(nq), nb), dim3(MATCH_BLOCK), 0, stream, scores, clist, qmeta, nq, cutoff, out, ld);
+    return hipGetLastError();
+}
+
+hipError_t launch_cdist_cutoff(double *out, const uint32_t *qlist, uint32_t nb, uint32_t nc, uint64_t ld, double cutoff, hipStream_t stream)
+{
+    if (nb == 0u || nc == 0u) return hipSuccess;
+    hipLaunchKernelGGL(k_cdist_cutoff, dim3(match_grid(nc), nb), dim3(MATCH_BLOCK), 0, stream, out, qlist, nc, ld, cutoff);
     return hipGetLastError();
 }
 

@@ -313,3 +313,28 @@ def extract(expr: IntoExpr, candidates: IntoExpr, scorer: str = "ratio", score_c
         args=args,
         is_elementwise=False,
     )
+
+
+# (a statement of its own: the list above closes with "extract")
+__all__ += ["cdist"]
+
+_CDIST_MEASURES = ("levenshtein", "jaro", "jaro_winkler", "jaccard", "sorensen_dice", "ratio", "token_sort_ratio")
+
+
+def cdist(expr: IntoExpr, candidates: IntoExpr, measure: str = "ratio", score_cutoff: float | None = None) -> pl.Expr:
+    """The scores of every row of `expr` against all rows of `candidates` (any length M) by `measure` (one of the five reference
+    measures, "ratio" or "token_sort_ratio"): a List(Float64) of M scores per row, in the order of `candidates`; a score below
+    score_cutoff is 0.0 (None: no cutoff).  A null row gives a null list and a null candidate a null element.  rapidfuzz's
+    process.cdist, row by row; for "ratio" and "token_sort_ratio" the score is fuzz.ratio / fuzz.token_sort_ratio / 100, in [0, 1],
+    and so is score_cutoff.  Not in the upstream polars-strsim."""
+    if measure not in _CDIST_MEASURES:
+        raise ValueError(f"unknown measure {measure!r}; expected one of {_CDIST_MEASURES}")
+    args = [parse_into_expr(expr, dtype=pl.Utf8), parse_into_expr(candidates, dtype=pl.Utf8)]
+    if score_cutoff is not None:
+        args.append(pl.lit(score_cutoff, dtype=pl.Float64))
+    return register_plugin_function(
+        plugin_path=_PLUGIN_DIR,
+        function_name="cdist_" + measure,
+        args=args,
+        is_elementwise=False,
+    )

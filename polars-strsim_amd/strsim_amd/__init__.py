@@ -308,10 +308,42 @@ def extract(scorer, queries, candidates, k=1, score_cutoff=None, ctx=None, proce
     return out, score
 
 
+CDIST_MEASURES = MEASURES + ("ratio", "token_sort_ratio")
+_CDIST_MEASURE = {**{m: m for m in MEASURES}, "ratio": "indel", "indel": "indel", "token_sort_ratio": "token_sort_ratio"}
+
+
+def cdist(measure, queries, candidates, score_cutoff=None, ctx=None, processor=None):
+    """The full score matrix of queries x candidates by `measure` (one of the reference measures, "ratio" -- "indel" is an alias
+    -- or "token_sort_ratio", CDIST_MEASURES): f64 [N, M], element (i, j) the score of (queries[i], candidates[j]) in [0, 1], bit
+    for bit the pairwise call's, in the caller's candidate positions.  A score below score_cutoff is 0.0 (None: no cutoff).  The
+    row of a null query is NaN and the column of a null candidate is NaN.
+    rapidfuzz: process.cdist(queries, candidates, scorer=fuzz.ratio, score_cutoff=100 * score_cutoff) / 100.
+    processor="default_process" runs default_process() over the queries and the candidates on the GPU first (rapidfuzz's
+    processor=utils.default_process)."""
+    if not isinstance(measure, str) or measure not in _CDIST_MEASURE:
+        raise ValueError(f"no cdist by measure {measure!r} (one of {CDIST_MEASURES})")
+    if processor is not None:
+        processor_id(processor)
+    ctx = ctx or default_context()
+    Q, vq = _as_column(queries)
+    qo, qv = pack_strings(Q)
+    cand = list(candidates)
+    co, cv, pos = _pack_candidates(cand)
+    if processor is not None:
+        qo, qv = ctx.default_process_host(qo, qv)
+        co, cv = ctx.default_process_host(co, cv)
+    out = np.full((len(Q), len(cand)), np.nan, dtype=np.float64)
+    if len(Q) and len(pos):
+        out[:, pos] = ctx.cdist(_CDIST_MEASURE[measure], qo, qv, co, cv, score_cutoff)
+    if vq is not None:
+        out[~vq] = np.nan
+    return out
+
+
 __all__ = ["default_process", "PROCESSORS", "best_match", "nearest", "Codec", "Context", "device_count", "pack_strings", "split_offsets", "similarity", "levenshtein", "jaro",
            "jaro_winkler", "jaccard", "sorensen_dice", "osa", "indel", "measure_supported", "distance", "levenshtein_distance", "osa_distance",
            "indel_distance", "INDEL_MEASURES", "partial_ratio", "partial_ratio_alignment", "PARTIAL_MEASURES",
            "token_sort_ratio", "token_set_ratio", "token_sort", "TOKEN_MEASURES",
            "token_ratio", "partial_token_sort_ratio", "partial_token_set_ratio", "partial_token_ratio", "wratio", "WEIGHTED_MEASURES",
            "DISTANCE_MEASURES", "DISTANCE_UNBOUNDED", "MEASURES", "EXTRA_MEASURES", "MEASURE_ID", "STATUS", "ShapeMismatch", "StrsimError",
-           "extract", "EXTRACT_SCORERS"]
+           "extract", "EXTRACT_SCORERS", "cdist", "CDIST_MEASURES"]

@@ -164,6 +164,10 @@ def lib():
         f = getattr(L, name)
         f.restype = i32
         f.argtypes = [vp, i32, vp, vp, u64, vp, vp, u64, C.c_uint32, C.c_double, vp, vp]
+    for name in ("strsim_cdist_device", "strsim_cdist_host"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, i32, vp, vp, u64, vp, vp, u64, C.c_double, vp, u64]
     L.strsim_measure_supported.restype = C.c_uint32
     L.strsim_measure_supported.argtypes = [i32, i32]
     L.strsim_pairs_device_all.restype = i32

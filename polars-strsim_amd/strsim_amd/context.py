@@ -391,6 +391,36 @@ class Context:
                                         co.ctypes.data, cv.ctypes.data, nc, int(k), cut, index.ctypes.data, score.ctypes.data))
         return index, score
 
+    def cdist(self, measure, q_offsets, q_values, c_offsets, c_values, score_cutoff=None, out=None):
+        """The full score matrix (strsim_cdist_host for numpy columns, strsim_cdist_device for torch tensors on this context's
+        device): uint32 offsets + uint8 values of the queries and the candidates -> f64 [rows, candidates], element (i, j) bit for
+        bit the pairwise score of (queries[i], candidates[j]) by one of the reference measures, "indel" or "token_sort_ratio"; a
+        score below score_cutoff is stored as 0.0 (None: no cutoff).  `out`: a 2-D f64 array / tensor of that shape to fill, with
+        unit stride along a row and any row stride >= candidates (what lies between two rows is never written).  Device inputs give
+        a device output, complete in stream order."""
+        cut = -np.inf if score_cutoff is None else float(score_cutoff)
+        if not isinstance(q_offsets, np.ndarray) and hasattr(q_offsets, "data_ptr"):
+            import torch
+            nq, nc = max(q_offsets.numel() - 1, 0), max(c_offsets.numel() - 1, 0)
+            if out is None:
+                out = torch.empty((nq, nc), dtype=torch.float64, device=q_offsets.device)
+            if out.dtype != torch.float64 or tuple(out.shape) != (nq, nc) or (nc > 1 and out.stride(1) != 1):
+                raise ValueError(f"out must be a float64 tensor of shape ({nq}, {nc}) with unit stride along a row")
+            ld = out.stride(0) if nq > 1 else nc
+            check(lib().strsim_cdist_device(self._h, measure_id(measure), q_offsets.data_ptr(), q_values.data_ptr(), nq,
+                                            c_offsets.data_ptr(), c_values.data_ptr(), nc, cut, out.data_ptr(), max(ld, nc)))
+            return out
+        qo, qv, nq = _host_column(q_offsets, q_values)
+        co, cv, nc = _host_column(c_offsets, c_values)
+        if out is None:
+            out = np.empty((nq, nc), dtype=np.float64)
+        if out.dtype != np.float64 or out.shape != (nq, nc) or (nc > 1 and out.strides[1] != 8) or (nq > 1 and out.strides[0] % 8):
+            raise ValueError(f"out must be a float64 array of shape ({nq}, {nc}) with unit stride along a row")
+        ld = out.strides[0] // 8 if nq > 1 else nc
+        check(lib().strsim_cdist_host(self._h, measure_id(measure), qo.ctypes.data, qv.ctypes.data, nq,
+                                      co.ctypes.data, cv.ctypes.data, nc, cut, out.ctypes.data, max(ld, nc)))
+        return out
+
 
 class Codec:
     """Lossless 16-bit transport codec for one measure's result column (include/strsim_amd.h: strsim_codec_*)."""
