@@ -160,7 +160,7 @@ struct strsim_ctx {
     uint64_t fault_retire_at = 0;      // STRSIM_FAULT_RETIRE_AT (0 = never)
     uint64_t retired = 0;
 
-    // ---- search calls (search_pack / search_fallback; strsim_best_match_device, strsim_nearest_device) ----
+    // ---- search calls (search_pack / slow_walk / search_fallback_merge; strsim_best_match_device, strsim_nearest_device) ----
     // packed strings + slow lists + partial lists (nearest: also the length order and the merged scores), the fallback's score
     // (nearest: and distance) batches, and a pinned word pair for the two slow counts
     DevBuf match_ws, match_scratch;
@@ -520,7 +520,14 @@ void strsim_split_offsets(uint64_t len, uint64_t n, uint64_t *out)
 
 } // extern "C"
 
-// ---- argument checks and staging shared by the entry points ----
+// ---- columns, argument checks and staging shared by the entry points ----
+
+// A string column as every function below the entry points takes it: rows + 1 Arrow offsets, the values they index, the rows.
+struct Col {
+    const uint32_t *off; const uint8_t *val; uint64_t rows;
+};
+// Row i of a column as a column of its own: the literal of a pairwise or distance call.
+static Col literal(const Col &col, uint32_t i) { return Col{col.off + i, col.val, 1}; }
 
 // Shape rule of parallel_apply, strsim.rs:48-52: the rows a call of two columns produces.
 static int shape_rows(uint64_t a_rows, uint64_t b_rows, uint64_t *n)
@@ -561,17 +568,32 @@ static int elementwise_check(const char *who, strsim_ctx *c, uint64_t a_rows, ui
     return STRSIM_OK;
 }
 
+// What the searches and cdist check alike: the row limits of the two sides and the NULL test of the candidate side.  Each family
+// keeps its own tests of the query side and the outputs, which it words and places differently.
+static int search_rows_check(const char *who, const Col &q, const Col &cnd)
+{
+    if (q.rows > 0xFFFFFFFFull) { set_error("%s: %llu queries (at most 2^32 - 1)", who, (unsigned long long)q.rows); return STRSIM_ERR_ARG; }
+    if (cnd.rows > 0xFFFFFFFEull) { set_error("%s: %llu candidates (at most 2^32 - 2)", who, (unsigned long long)cnd.rows); return STRSIM_ERR_ARG; }
+    return STRSIM_OK;
+}
+static int candidate_buffers_check(const char *who, const Col &cnd)
+{
+    if (cnd.rows && (!cnd.off || !cnd.val)) { set_error("%s: NULL candidate buffer", who); return STRSIM_ERR_ARG; }
+    return STRSIM_OK;
+}
+
 // The checks of the search families behind their measure test (best match: min_score may not be NaN; nearest passes 0; extract
 // tests its score_cutoff itself).
-static int search_check(const char *who, strsim_ctx *c, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows, const uint32_t *c_off,
-                        const uint8_t *c_val, uint64_t c_rows, uint32_t k, uint32_t max_k, double min_score, const void *out_a, const void *out_b)
+static int search_check(const char *who, strsim_ctx *c, const Col &q, const Col &cnd, uint32_t k, uint32_t max_k, double min_score,
+                        const void *out_a, const void *out_b)
 {
     if (k < 1u || k > max_k) { set_error("%s: k=%u is outside 1..%u", who, k, max_k); return STRSIM_ERR_ARG; }
     if (min_score != min_score) { set_error("%s: min_score is NaN", who); return STRSIM_ERR_ARG; }
-    if (q_rows > 0xFFFFFFFFull) { set_error("%s: %llu queries (at most 2^32 - 1)", who, (unsigned long long)q_rows); return STRSIM_ERR_ARG; }
-    if (c_rows > 0xFFFFFFFEull) { set_error("%s: %llu candidates (at most 2^32 - 2)", who, (unsigned long long)c_rows); return STRSIM_ERR_ARG; }
-    if (q_rows && (!q_off || !q_val || !out_a || !out_b)) { set_error("%s: NULL query or output buffer", who); return STRSIM_ERR_ARG; }
-    if (c_rows && (!c_off || !c_val)) { set_error("%s: NULL candidate buffer", who); return STRSIM_ERR_ARG; }
+    int rc = search_rows_check(who, q, cnd);
+    if (rc) return rc;
+    if (q.rows && (!q.off || !q.val || !out_a || !out_b)) { set_error("%s: NULL query or output buffer", who); return STRSIM_ERR_ARG; }
+    rc = candidate_buffers_check(who, cnd);
+    if (rc) return rc;
     if (!c) { set_error("%s: ctx is NULL", who); return STRSIM_ERR_ARG; }
     return STRSIM_OK;
 }
@@ -580,30 +602,57 @@ static int search_check(const char *who, strsim_ctx *c, const uint32_t *q_off, c
 // and out_bytes of stage[4] for the results.  The caller's offset base is kept and the values go up from byte 0 of the caller's
 // buffer, so every offset the kernels can form, 0 included, is inside the device copy.  The second column may have no rows.
 struct Staged {
-    const uint32_t *a_off; const uint8_t *a_val;
-    const uint32_t *b_off; const uint8_t *b_val;
+    Col a, b;
     uint8_t *out;
 };
-static int ctx_stage(strsim_ctx *c, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off, const uint8_t *b_val,
-                     uint64_t b_rows, size_t out_bytes, Staged *s)
+static Col dev_col(const DevBuf &off, const DevBuf &val, uint64_t rows) { return Col{off.as<uint32_t>(), val.as<uint8_t>(), rows}; }
+static const Col NO_COL{nullptr, nullptr, 0};
+
+static int ctx_stage(strsim_ctx *c, const Col &a, const Col &b, size_t out_bytes, Staged *s)
 {
-    const size_t a_bytes = a_off[a_rows], b_bytes = b_rows ? b_off[b_rows] : 0;
-    const size_t need[5] = {(a_rows + 1) * 4, a_bytes + 1, (b_rows + 1) * 4, b_bytes + 1, out_bytes};
+    const size_t a_bytes = a.off[a.rows], b_bytes = b.rows ? b.off[b.rows] : 0;
+    const size_t need[5] = {(a.rows + 1) * 4, a_bytes + 1, (b.rows + 1) * 4, b_bytes + 1, out_bytes};
     for (int i = 0; i < 5; ++i) {
         int rc = c->stage[i].reserve(need[i]);
         if (rc) return rc;
     }
-    HIP_TRY(hipMemcpyAsync(c->stage[0].p, a_off, need[0], hipMemcpyHostToDevice, c->stream));
-    if (a_bytes) HIP_TRY(hipMemcpyAsync(c->stage[1].p, a_val, a_bytes, hipMemcpyHostToDevice, c->stream));
-    if (b_rows) {
-        HIP_TRY(hipMemcpyAsync(c->stage[2].p, b_off, need[2], hipMemcpyHostToDevice, c->stream));
-        if (b_bytes) HIP_TRY(hipMemcpyAsync(c->stage[3].p, b_val, b_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->stage[0].p, a.off, need[0], hipMemcpyHostToDevice, c->stream));
+    if (a_bytes) HIP_TRY(hipMemcpyAsync(c->stage[1].p, a.val, a_bytes, hipMemcpyHostToDevice, c->stream));
+    if (b.rows) {
+        HIP_TRY(hipMemcpyAsync(c->stage[2].p, b.off, need[2], hipMemcpyHostToDevice, c->stream));
+        if (b_bytes) HIP_TRY(hipMemcpyAsync(c->stage[3].p, b.val, b_bytes, hipMemcpyHostToDevice, c->stream));
     }
-    *s = Staged{c->stage[0].as<uint32_t>(), c->stage[1].as<uint8_t>(), c->stage[2].as<uint32_t>(), c->stage[3].as<uint8_t>(), c->stage[4].as<uint8_t>()};
+    *s = Staged{dev_col(c->stage[0], c->stage[1], a.rows), dev_col(c->stage[2], c->stage[3], b.rows), c->stage[4].as<uint8_t>()};
     return STRSIM_OK;
 }
 
 static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// The *_host entry point of an element-wise family behind its check (`checked`: what the check returned; n: the rows of the call):
+// both columns staged, the device implementation on the staged columns with its output a (a_bytes) and, where the family has one, its
+// output b (b_bytes, at a 256-byte boundary behind a) in stage[4], the copies back and the wait for them.  settle() runs between the
+// device implementation and the copies: a pairwise family retires its call there (strsim_ctx_synchronize -- the long-string pass
+// writes into the staged output from it), a distance family has nothing to do.
+template <class Device, class Settle>
+static int elementwise_host(strsim_ctx *c, int checked, const Col &a, const Col &b, uint64_t n, void *out_a, size_t a_bytes, void *out_b,
+                            size_t b_bytes, Device device, Settle settle)
+{
+    if (checked || n == 0) return checked;
+    int rc = ctx_set_device(c);
+    if (rc) return rc;
+    Staged s;
+    rc = ctx_stage(c, a, b, b_bytes ? up256(a_bytes) + b_bytes : a_bytes, &s);
+    if (rc) return rc;
+    uint8_t *const d_a = s.out, *const d_b = s.out + up256(a_bytes);
+    rc = device(s, d_a, d_b);
+    if (rc == STRSIM_OK) rc = settle();
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out_a, d_a, a_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (b_bytes) HIP_TRY(hipMemcpyAsync(out_b, d_b, b_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return STRSIM_OK;
+}
+static int nothing_to_settle() { return STRSIM_OK; }
 
 // Take a ticket for the call in `slot` and clear the host copy of its status block.
 static void slot_begin(strsim_ctx *c, int slot)
@@ -723,26 +772,31 @@ static int two_pass(strsim_ctx *c, const LaunchArgs &la, const TwoPassCall &t, i
     return STRSIM_OK;
 }
 
-static LaunchArgs two_pass_args(strsim_ctx *c, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
-                                const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t n, DevStatus *status)
+// The one place that copies columns into a LaunchArgs; everything else is zero.
+static LaunchArgs two_pass_args(strsim_ctx *c, const Col &a, const Col &b, double *out, uint64_t n, DevStatus *status)
 {
     LaunchArgs la{};
-    la.offA = a_off; la.valA = a_val; la.rowsA = a_rows;
-    la.offB = b_off; la.valB = b_val; la.rowsB = b_rows;
+    la.offA = a.off; la.valA = a.val; la.rowsA = a.rows;
+    la.offB = b.off; la.valB = b.val; la.rowsB = b.rows;
     la.out = out; la.n = n;
     la.status = status; la.stream = c->stream;
     return la;
 }
 
+// The two columns of a pairwise call and the rows it produces.
+struct PairCols {
+    Col a, b;
+    uint64_t n;
+};
+
 // A pairwise call of a two-pass measure (OSA: strsim_osa.h, Indel: strsim_indel.h, partial ratio: strsim_partial.h).  It occupies
 // a ring slot like any other (its status block carries the ticket and the work-list count) and has nothing to do at retirement.
-static int pairs_osa(strsim_ctx *c, int slot, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
-                     const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t n)
+static int pairs_osa(strsim_ctx *c, int slot, int measure, const PairCols &p, double *out)
 {
-    int rc = c->osa_list.reserve(n * sizeof(uint32_t));
+    int rc = c->osa_list.reserve(p.n * sizeof(uint32_t));
     if (rc) return rc;
     slot_begin(c, slot);
-    const LaunchArgs la = two_pass_args(c, a_off, a_val, a_rows, b_off, b_val, b_rows, out, n, c->status + slot);
+    const LaunchArgs la = two_pass_args(c, p.a, p.b, out, p.n, c->status + slot);
     const TwoPassKind kind = measure == STRSIM_PARTIAL_RATIO ? TP_PARTIAL : measure == STRSIM_INDEL ? TP_INDEL : TP_OSA;
     rc = two_pass(c, la, TwoPassCall{kind, measure, DIST_UNBOUNDED, nullptr, nullptr}, slot);
     if (rc) return rc;
@@ -769,14 +823,14 @@ static int token_prepare(strsim_ctx *c)
     return STRSIM_OK;
 }
 
-// The bounds of one or two columns into c->tok_status_host (b_off == nullptr: one column); waits for the stream.
-static int token_bounds(strsim_ctx *c, const uint32_t *a_off, uint64_t a_rows, const uint32_t *b_off, uint64_t b_rows)
+// The bounds of one or two columns into c->tok_status_host (b == nullptr: one column); waits for the stream.
+static int token_bounds(strsim_ctx *c, const Col &a, const Col *b)
 {
     HIP_TRY(hipMemsetAsync(c->tok_status, 0, sizeof(TokenStatus), c->stream));
-    HIP_TRY(launch_token_bounds(a_off, a_rows, c->tok_status, 0, c->stream));
-    if (b_off) HIP_TRY(launch_token_bounds(b_off, b_rows, c->tok_status, 1, c->stream));
+    HIP_TRY(launch_token_bounds(a.off, a.rows, c->tok_status, 0, c->stream));
+    if (b) HIP_TRY(launch_token_bounds(b->off, b->rows, c->tok_status, 1, c->stream));
     HIP_TRY(hipMemcpyAsync(c->tok_status_host, c->tok_status, sizeof(TokenStatus), hipMemcpyDeviceToHost, c->stream));
-    c->enqueued_ops += b_off ? 4u : 3u;
+    c->enqueued_ops += b ? 4u : 3u;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return STRSIM_OK;
 }
@@ -806,9 +860,9 @@ static int token_copy_counts(strsim_ctx *c)
 
 // The sort form of one column into (out_off, out_val): out_off holds rows + 1 words, out_val the column's byte size.  max_len: the
 // column's longest row (token_bounds).  side: which work list and counter (zeroed by token_bounds) the column uses.
-static int token_sort_column(strsim_ctx *c, int side, const uint32_t *off, const uint8_t *val, uint64_t rows, uint32_t max_len,
-                             uint32_t *out_off, uint8_t *out_val)
+static int token_sort_column(strsim_ctx *c, int side, const Col &col, uint32_t max_len, uint32_t *out_off, uint8_t *out_val)
 {
+    const uint64_t rows = col.rows;
     int rc = c->tok_list[side].reserve(rows * sizeof(uint32_t));
     if (rc) return rc;
     rc = c->tok_sums.reserve(((rows + 4095u) / 4096u) * sizeof(uint32_t));
@@ -819,23 +873,18 @@ static int token_sort_column(strsim_ctx *c, int side, const uint32_t *off, const
     rc = token_wave_scratch(c, token_max_tokens(max_len), &grid, &scratch, &slot_words);
     if (rc) return rc;
     uint32_t *const list = c->tok_list[side].as<uint32_t>(), *const count = &c->tok_status->wave_rows[side];
-    hipError_t e = launch_token_sort(false, off, val, rows, out_off, out_val, list, count, grid, scratch, slot_words, c->stream);
+    hipError_t e = launch_token_sort(false, col.off, col.val, rows, out_off, out_val, list, count, grid, scratch, slot_words, c->stream);
     if (e != hipSuccess) return hip_fail(e, "kernel launch (k_token_sort_lane / _wave, measuring)");
     e = launch_token_scan(out_off, rows, c->tok_sums.as<uint32_t>(), c->stream);
     if (e != hipSuccess) return hip_fail(e, "kernel launch (k_token_scan)");
-    e = launch_token_sort(true, off, val, rows, out_off, out_val, list, count, grid, scratch, slot_words, c->stream);
+    e = launch_token_sort(true, col.off, col.val, rows, out_off, out_val, list, count, grid, scratch, slot_words, c->stream);
     if (e != hipSuccess) return hip_fail(e, "kernel launch (k_token_sort_lane / _wave, writing)");
     c->enqueued_ops += 7u;
     return STRSIM_OK;
 }
 
-// The two columns of a pairwise call, and what sizes their scratch: upper bounds of each column's bytes and longest row (token_bounds
-// of the columns themselves, or of the columns a sub-frame was gathered from).
-struct PairCols {
-    const uint32_t *a_off; const uint8_t *a_val; uint64_t a_rows;
-    const uint32_t *b_off; const uint8_t *b_val; uint64_t b_rows;
-    uint64_t n;
-};
+// What sizes the scratch of a pair of columns: upper bounds of each column's bytes and longest row (token_bounds of the columns
+// themselves, or of the columns a sub-frame was gathered from).
 struct ColBounds {
     uint64_t bytes[2];
     uint32_t max_len[2];
@@ -847,20 +896,30 @@ static ColBounds token_col_bounds(const strsim_ctx *c)
     return ColBounds{{(uint64_t)st.end[0] - st.begin[0], (uint64_t)st.end[1] - st.begin[1]}, {st.max_len[0], st.max_len[1]}};
 }
 
-// The sort form of both columns into c->tok_off / c->tok_val (a literal stays one row); the work-list counters are zero on entry.
-static int token_sort_columns(strsim_ctx *c, const PairCols &p, const ColBounds &bd)
+// The sort form of two columns with the bounds bd into (off[s], val[s]), which *a and *b name afterwards (a literal stays one row; a
+// side without rows -- the candidates of a search that has none -- is left as it is).  The work-list counters are zero on entry.
+static int token_sort_columns(strsim_ctx *c, Col *a, Col *b, const ColBounds &bd, DevBuf (&off)[2], DevBuf (&val)[2])
 {
-    const uint64_t rows[2] = {p.a_rows, p.b_rows};
-    const uint32_t *const in_off[2] = {p.a_off, p.b_off};
-    const uint8_t *const in_val[2] = {p.a_val, p.b_val};
+    Col *const side[2] = {a, b};
     for (int s = 0; s < 2; ++s) {
-        int rc = c->tok_off[s].reserve((rows[s] + 1) * sizeof(uint32_t));
-        if (rc == STRSIM_OK) rc = c->tok_val[s].reserve(bd.bytes[s] + TOKEN_PAD);
-        if (rc == STRSIM_OK)
-            rc = token_sort_column(c, s, in_off[s], in_val[s], rows[s], bd.max_len[s], c->tok_off[s].as<uint32_t>(), c->tok_val[s].as<uint8_t>());
+        if (!side[s]->rows) continue;
+        int rc = off[s].reserve((side[s]->rows + 1) * sizeof(uint32_t));
+        if (rc == STRSIM_OK) rc = val[s].reserve(bd.bytes[s] + TOKEN_PAD);
+        if (rc == STRSIM_OK) rc = token_sort_column(c, s, *side[s], bd.max_len[s], off[s].as<uint32_t>(), val[s].as<uint8_t>());
         if (rc) return rc;
+        *side[s] = dev_col(off[s], val[s], side[s]->rows);
     }
     return token_copy_counts(c);
+}
+
+// The same for the two sides of a search or of cdist: their bounds are read here (the call's one wait beyond the search's),
+// and the columns are the context's extract_off / extract_val.
+static int token_sort_search_columns(strsim_ctx *c, Col *q, Col *cnd)
+{
+    int rc = token_prepare(c);
+    if (rc == STRSIM_OK) rc = token_bounds(c, *q, cnd->rows ? cnd : nullptr);
+    if (rc) return rc;
+    return token_sort_columns(c, q, cnd, token_col_bounds(c), c->extract_off, c->extract_val);
 }
 
 // The set form of p.n pairs: ab and ba into c->tok_off / c->tok_val at full length, the records into *rec, and room for the uint32
@@ -869,10 +928,10 @@ static int token_set_columns(strsim_ctx *c, const PairCols &p, const ColBounds &
 {
     const uint64_t n = p.n;
     // a difference is never longer than its string; a literal's is materialised for every row
-    const uint64_t cap[2] = {p.a_rows == 1 ? n * bd.bytes[0] : bd.bytes[0], p.b_rows == 1 ? n * bd.bytes[1] : bd.bytes[1]};
+    const uint64_t cap[2] = {p.a.rows == 1 ? n * bd.bytes[0] : bd.bytes[0], p.b.rows == 1 ? n * bd.bytes[1] : bd.bytes[1]};
     if (cap[0] > 0xFFFFFFFFull || cap[1] > 0xFFFFFFFFull) {
         set_error("strsim_pairs_device: token_set_ratio with a literal of %llu bytes against %llu rows exceeds 32-bit offsets; split the column",
-                  (unsigned long long)(p.a_rows == 1 ? bd.bytes[0] : bd.bytes[1]), (unsigned long long)n);
+                  (unsigned long long)(p.a.rows == 1 ? bd.bytes[0] : bd.bytes[1]), (unsigned long long)n);
         return STRSIM_ERR_ARG;
     }
     int rc = STRSIM_OK;
@@ -895,7 +954,7 @@ static int token_set_columns(strsim_ctx *c, const PairCols &p, const ColBounds &
     uint8_t *const val_ab = c->tok_val[0].as<uint8_t>(), *const val_ba = c->tok_val[1].as<uint8_t>();
     TokenSetRec *const rec = c->tok_rec.as<TokenSetRec>();
     uint32_t *const list = c->tok_list[0].as<uint32_t>(), *const count = &c->tok_status->wave_rows[0];
-    LaunchArgs in = two_pass_args(c, p.a_off, p.a_val, p.a_rows, p.b_off, p.b_val, p.b_rows, nullptr, n, nullptr);
+    LaunchArgs in = two_pass_args(c, p.a, p.b, nullptr, n, nullptr);
     hipError_t e = launch_token_set(false, in, off_ab, val_ab, off_ba, val_ba, rec, list, count, grid, scratch, slot_words);
     if (e != hipSuccess) return hip_fail(e, "kernel launch (k_token_set_lane / _wave, measuring)");
     e = launch_token_scan(off_ab, n, c->tok_sums.as<uint32_t>(), c->stream);
@@ -918,8 +977,7 @@ static int token_set_scores(strsim_ctx *c, const PairCols &p, const ColBounds &b
     if (rc) return rc;
     rc = dist_prepare(c, p.n);
     if (rc) return rc;
-    const LaunchArgs la = two_pass_args(c, c->tok_off[0].as<uint32_t>(), c->tok_val[0].as<uint8_t>(), p.n, c->tok_off[1].as<uint32_t>(),
-                                        c->tok_val[1].as<uint8_t>(), p.n, nullptr, p.n, c->dist_status);
+    const LaunchArgs la = two_pass_args(c, dev_col(c->tok_off[0], c->tok_val[0], p.n), dev_col(c->tok_off[1], c->tok_val[1], p.n), nullptr, p.n, c->dist_status);
     rc = two_pass(c, la, TwoPassCall{TP_INDEL, STRSIM_INDEL, DIST_UNBOUNDED, d32, nullptr}, -1);
     if (rc) return rc;
     const hipError_t e = launch_token_set_epilogue(rec, d32, out, p.n, c->stream);
@@ -931,20 +989,18 @@ static int token_set_scores(strsim_ctx *c, const PairCols &p, const ColBounds &b
 // A pairwise call of a token measure.  Sort form: both columns normalised into scratch (a literal stays one row), then the Indel
 // flow into the caller's out, in this call's ring slot.  Set form: ab and ba into scratch at full length, the Indel flow with the
 // unbounded integer distance, then the epilogue; it takes no ring slot (nothing is left to do at retirement).
-static int pairs_token(strsim_ctx *c, int slot, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
-                       const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t n)
+static int pairs_token(strsim_ctx *c, int slot, int measure, const PairCols &p, double *out)
 {
     int rc = token_prepare(c);
     if (rc) return rc;
-    rc = token_bounds(c, a_off, a_rows, b_off, b_rows);
+    rc = token_bounds(c, p.a, &p.b);
     if (rc) return rc;
     const ColBounds bd = token_col_bounds(c);
-    const PairCols p{a_off, a_val, a_rows, b_off, b_val, b_rows, n};
     if (measure == STRSIM_TOKEN_SET_RATIO) return token_set_scores(c, p, bd, out);
-    rc = token_sort_columns(c, p, bd);
+    PairCols t = p;
+    rc = token_sort_columns(c, &t.a, &t.b, bd, c->tok_off, c->tok_val);
     if (rc) return rc;
-    return pairs_osa(c, slot, STRSIM_INDEL, c->tok_off[0].as<uint32_t>(), c->tok_val[0].as<uint8_t>(), a_rows, c->tok_off[1].as<uint32_t>(),
-                     c->tok_val[1].as<uint8_t>(), b_rows, out, n);
+    return pairs_osa(c, slot, STRSIM_INDEL, t, out);
 }
 
 // ---- token_ratio, the partial token ratios and WRatio (strsim_wratio.h) ----
@@ -966,7 +1022,7 @@ static int two_pass_scores(strsim_ctx *c, const PairCols &p, TwoPassKind kind, d
 {
     int rc = dist_prepare(c, p.n);
     if (rc) return rc;
-    const LaunchArgs la = two_pass_args(c, p.a_off, p.a_val, p.a_rows, p.b_off, p.b_val, p.b_rows, out, p.n, c->dist_status);
+    const LaunchArgs la = two_pass_args(c, p.a, p.b, out, p.n, c->dist_status);
     if (kind == TP_PARTIAL) return two_pass(c, la, TwoPassCall{TP_PARTIAL, STRSIM_PARTIAL_RATIO, 0u, nullptr, nullptr}, -1);
     return two_pass(c, la, TwoPassCall{TP_INDEL, STRSIM_INDEL, DIST_UNBOUNDED, nullptr, nullptr}, -1);
 }
@@ -974,11 +1030,10 @@ static int two_pass_scores(strsim_ctx *c, const PairCols &p, TwoPassKind kind, d
 // token_sort_ratio (TP_INDEL) or partial_token_sort_ratio (TP_PARTIAL) into out
 static int token_sort_scores(strsim_ctx *c, const PairCols &p, const ColBounds &bd, TwoPassKind kind, double *out)
 {
+    PairCols t = p;
     int rc = token_zero_counts(c);
-    if (rc == STRSIM_OK) rc = token_sort_columns(c, p, bd);
+    if (rc == STRSIM_OK) rc = token_sort_columns(c, &t.a, &t.b, bd, c->tok_off, c->tok_val);
     if (rc) return rc;
-    const PairCols t{c->tok_off[0].as<uint32_t>(), c->tok_val[0].as<uint8_t>(), p.a_rows, c->tok_off[1].as<uint32_t>(), c->tok_val[1].as<uint8_t>(),
-                     p.b_rows, p.n};
     return two_pass_scores(c, t, kind, out);
 }
 
@@ -990,8 +1045,7 @@ static int partial_token_set_scores(strsim_ctx *c, const PairCols &p, const ColB
     int rc = token_zero_counts(c);
     if (rc == STRSIM_OK) rc = token_set_columns(c, p, bd, &rec, &d32);
     if (rc) return rc;
-    const PairCols t{c->tok_off[0].as<uint32_t>(), c->tok_val[0].as<uint8_t>(), p.n, c->tok_off[1].as<uint32_t>(), c->tok_val[1].as<uint8_t>(), p.n,
-                     p.n};
+    const PairCols t{dev_col(c->tok_off[0], c->tok_val[0], p.n), dev_col(c->tok_off[1], c->tok_val[1], p.n), p.n};
     rc = two_pass_scores(c, t, TP_PARTIAL, out);
     if (rc) return rc;
     const hipError_t e = launch_partial_token_set_epilogue(rec, out, out, p.n, c->stream);
@@ -1038,13 +1092,13 @@ static int pairs_wratio(strsim_ctx *c, const PairCols &p, double *out)
     uint8_t *const cls = c->wr_cls.as<uint8_t>();
     uint32_t *const pos = c->wr_pos.as<uint32_t>();
     uint32_t *const list[2] = {c->wr_list[0].as<uint32_t>(), c->wr_list[1].as<uint32_t>()};
-    const LaunchArgs la = two_pass_args(c, p.a_off, p.a_val, p.a_rows, p.b_off, p.b_val, p.b_rows, out, n, nullptr);
+    const LaunchArgs la = two_pass_args(c, p.a, p.b, out, n, nullptr);
     HIP_TRY(hipMemsetAsync(c->wr_status, 0, sizeof(WratioStatus), c->stream));
     hipError_t e = launch_wratio_classify(la, cls, pos, list[0], list[1], c->wr_status);
     if (e != hipSuccess) return hip_fail(e, "kernel launch (k_wratio_classify)");
     HIP_TRY(hipMemcpyAsync(c->wr_status_host, c->wr_status, sizeof(WratioStatus), hipMemcpyDeviceToHost, c->stream));
     c->enqueued_ops += 3u;
-    rc = token_bounds(c, p.a_off, p.a_rows, p.b_off, p.b_rows); // (the list counts ride on this wait)
+    rc = token_bounds(c, p.a, &p.b); // (the list counts ride on this wait)
     if (rc) return rc;
     const ColBounds bd = token_col_bounds(c);
     const uint64_t m[2] = {c->wr_status_host->rows[0], c->wr_status_host->rows[1]};
@@ -1052,28 +1106,25 @@ static int pairs_wratio(strsim_ctx *c, const PairCols &p, double *out)
     // sub-scores: token_ratio of the near rows | partial_ratio, partial_token_ratio of the far rows | one column of the longer list
     rc = c->wr_score.reserve((m[0] + 2u * m[1] + longer) * sizeof(double));
     if (rc == STRSIM_OK) rc = c->tok_sums.reserve(((longer + 4095u) / 4096u) * sizeof(uint32_t));
-    const uint64_t rows[2] = {p.a_rows, p.b_rows};
+    const Col *const side[2] = {&p.a, &p.b};
     for (int s = 0; s < 2 && rc == STRSIM_OK; ++s) {
-        if (rows[s] == 1) continue; // a literal is not gathered
+        if (side[s]->rows == 1) continue; // a literal is not gathered
         rc = c->wr_off[s].reserve((longer + 1) * sizeof(uint32_t));
         if (rc == STRSIM_OK) rc = c->wr_val[s].reserve(bd.bytes[s] + TOKEN_PAD);
     }
     if (rc) return rc;
     double *const s_near = c->wr_score.as<double>(), *const s_far0 = s_near + m[0], *const s_far1 = s_far0 + m[1], *const tmp = s_far1 + m[1];
-    const uint32_t *const in_off[2] = {p.a_off, p.b_off};
-    const uint8_t *const in_val[2] = {p.a_val, p.b_val};
     for (int f = 0; f < 2; ++f) {
         if (m[f] == 0) continue; // a family without rows launches nothing
-        PairCols sub{p.a_off, p.a_val, p.a_rows, p.b_off, p.b_val, p.b_rows, m[f]};
+        PairCols sub{p.a, p.b, m[f]};
+        Col *const sub_side[2] = {&sub.a, &sub.b};
         for (int s = 0; s < 2; ++s) {
-            if (rows[s] == 1) continue;
-            uint32_t *const g_off = c->wr_off[s].as<uint32_t>();
-            uint8_t *const g_val = c->wr_val[s].as<uint8_t>();
-            e = launch_take(in_off[s], in_val[s], list[f], (uint32_t)m[f], g_off, g_val, c->tok_sums.as<uint32_t>(), c->stream);
+            if (side[s]->rows == 1) continue;
+            e = launch_take(side[s]->off, side[s]->val, list[f], (uint32_t)m[f], c->wr_off[s].as<uint32_t>(), c->wr_val[s].as<uint8_t>(),
+                            c->tok_sums.as<uint32_t>(), c->stream);
             if (e != hipSuccess) return hip_fail(e, "kernel launch (k_take_measure / k_token_scan / k_take_write)");
             c->enqueued_ops += 5u;
-            if (s == 0) { sub.a_off = g_off; sub.a_val = g_val; sub.a_rows = m[f]; }
-            else { sub.b_off = g_off; sub.b_val = g_val; sub.b_rows = m[f]; }
+            *sub_side[s] = dev_col(c->wr_off[s], c->wr_val[s], m[f]);
         }
         if (f == 0) rc = token_max_scores(c, sub, bd, false, s_near, tmp);
         else {
@@ -1091,26 +1142,22 @@ static int pairs_wratio(strsim_ctx *c, const PairCols &p, double *out)
 }
 
 // A pairwise call of one of the five: ids 18 .. 24 over the whole frame, WRatio routed.
-static int pairs_weighted(strsim_ctx *c, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
-                          const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t n)
+static int pairs_weighted(strsim_ctx *c, int measure, const PairCols &p, double *out)
 {
     int rc = token_prepare(c);
     if (rc) return rc;
-    const PairCols p{a_off, a_val, a_rows, b_off, b_val, b_rows, n};
     if (measure == STRSIM_WRATIO) return pairs_wratio(c, p, out);
-    rc = token_bounds(c, a_off, a_rows, b_off, b_rows);
+    rc = token_bounds(c, p.a, &p.b);
     if (rc) return rc;
     const ColBounds bd = token_col_bounds(c);
     if (measure == STRSIM_PARTIAL_TOKEN_SORT_RATIO) return token_sort_scores(c, p, bd, TP_PARTIAL, out);
     if (measure == STRSIM_PARTIAL_TOKEN_SET_RATIO) return partial_token_set_scores(c, p, bd, out);
-    rc = c->wr_score.reserve(n * sizeof(double));
+    rc = c->wr_score.reserve(p.n * sizeof(double));
     if (rc) return rc;
     return token_max_scores(c, p, bd, measure == STRSIM_PARTIAL_TOKEN_RATIO, out, c->wr_score.as<double>());
 }
 
-static int pairs_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
-                             const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, double *const *outs,
-                             uint64_t out_rows, bool eager = false)
+static int pairs_device_impl(strsim_ctx_t *c, int measure, const Col &a, const Col &b, double *const *outs, uint64_t out_rows, bool eager = false)
 {
     const bool all = measure == STRSIM_NUM_MEASURES;
     if (!c) { set_error("strsim_pairs_device: ctx is NULL"); return STRSIM_ERR_ARG; }
@@ -1119,9 +1166,9 @@ static int pairs_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_off
         return STRSIM_ERR_ARG;
     }
     uint64_t n;
-    int rc = check_rows("strsim_pairs_device", a_rows, b_rows, out_rows, &n);
+    int rc = check_rows("strsim_pairs_device", a.rows, b.rows, out_rows, &n);
     if (rc || n == 0) return rc;
-    if (!a_off || !b_off || !outs) { set_error("strsim_pairs_device: NULL buffer"); return STRSIM_ERR_ARG; }
+    if (!a.off || !b.off || !outs) { set_error("strsim_pairs_device: NULL buffer"); return STRSIM_ERR_ARG; }
     for (int q = 0; q < (all ? STRSIM_NUM_MEASURES : 1); ++q)
         if (!outs[q]) { set_error("strsim_pairs_device: NULL output buffer"); return STRSIM_ERR_ARG; }
     rc = ctx_set_device(c);
@@ -1141,10 +1188,10 @@ static int pairs_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_off
             return STRSIM_ERR_EARLIER_CALL;
         }
     }
-    if (two_pass_measure(measure)) return pairs_osa(c, slot, measure, a_off, a_val, a_rows, b_off, b_val, b_rows, outs[0], n);
-    if (measure == STRSIM_TOKEN_SORT_RATIO || measure == STRSIM_TOKEN_SET_RATIO)
-        return pairs_token(c, slot, measure, a_off, a_val, a_rows, b_off, b_val, b_rows, outs[0], n);
-    if (weighted_measure(measure)) return pairs_weighted(c, measure, a_off, a_val, a_rows, b_off, b_val, b_rows, outs[0], n);
+    const PairCols p{a, b, n};
+    if (two_pass_measure(measure)) return pairs_osa(c, slot, measure, p, outs[0]);
+    if (measure == STRSIM_TOKEN_SORT_RATIO || measure == STRSIM_TOKEN_SET_RATIO) return pairs_token(c, slot, measure, p, outs[0]);
+    if (weighted_measure(measure)) return pairs_weighted(c, measure, p, outs[0]);
     const uint64_t nchunks = (n + 63) >> 6;
     // One launch (the lane kernel alone, the rest at retirement if it turns out to be needed) when the caller has opted in and the
     // context's last retired call left nothing behind its lane kernel.  Such a call owns a mask buffer until it is retired (there
@@ -1164,14 +1211,9 @@ static int pairs_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_off
     slot_begin(c, slot);
     c->status_host[slot].lane_left = LANE_LEFT_UNKNOWN;
 
-    LaunchArgs la;
-    la.offA = a_off; la.valA = a_val; la.rowsA = a_rows;
-    la.offB = b_off; la.valB = b_val; la.rowsB = b_rows;
-    la.out = outs[0]; la.n = n;
-    la.slowmask = mask; la.status = c->status + slot; la.stream = c->stream;
+    LaunchArgs la = two_pass_args(c, a, b, outs[0], n, c->status + slot);
+    la.slowmask = mask;
     la.sched = c->sched + 4 * slot;
-    la.publish_host = nullptr;
-    la.publish_ticket = 0u;
     la.worklist = reinterpret_cast<uint32_t *>(mask + 2 * nchunks);
     la.qtab = c->qtab;
     la.stage_grid = c->num_cu * c->stage_wg_per_cu;
@@ -1245,29 +1287,36 @@ static int pairs_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_off
     return STRSIM_OK;
 }
 
+// strsim_pairs_device (eager: strsim_pairs_device_small), which the flows below call with a literal or with columns of their own.
+static int pairs_device(strsim_ctx *c, int measure, const Col &a, const Col &b, double *out, uint64_t out_rows, bool eager = false)
+{
+    if (measure == STRSIM_NUM_MEASURES) {
+        set_error("%s: unknown measure %d", eager ? "strsim_pairs_device_small" : "strsim_pairs_device", measure);
+        return STRSIM_ERR_ARG;
+    }
+    double *outs[1] = {out};
+    return pairs_device_impl(c, measure, a, b, out ? outs : nullptr, out_rows, eager);
+}
+
 extern "C" {
 
 int strsim_pairs_device(strsim_ctx_t *c, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
                         const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t out_rows)
 {
-    if (measure == STRSIM_NUM_MEASURES) { set_error("strsim_pairs_device: unknown measure %d", measure); return STRSIM_ERR_ARG; }
-    double *outs[1] = {out};
-    return pairs_device_impl(c, measure, a_off, a_val, a_rows, b_off, b_val, b_rows, out ? outs : nullptr, out_rows);
+    return pairs_device(c, measure, Col{a_off, a_val, a_rows}, Col{b_off, b_val, b_rows}, out, out_rows);
 }
 
 int strsim_pairs_device_small(strsim_ctx_t *c, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
                               const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t out_rows)
 {
-    if (measure == STRSIM_NUM_MEASURES) { set_error("strsim_pairs_device_small: unknown measure %d", measure); return STRSIM_ERR_ARG; }
-    double *outs[1] = {out};
-    return pairs_device_impl(c, measure, a_off, a_val, a_rows, b_off, b_val, b_rows, out ? outs : nullptr, out_rows, true);
+    return pairs_device(c, measure, Col{a_off, a_val, a_rows}, Col{b_off, b_val, b_rows}, out, out_rows, true);
 }
 
 int strsim_pairs_device_all(strsim_ctx_t *c, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
                             const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, double *const outs[5],
                             uint64_t out_rows)
 {
-    return pairs_device_impl(c, STRSIM_NUM_MEASURES, a_off, a_val, a_rows, b_off, b_val, b_rows, outs, out_rows);
+    return pairs_device_impl(c, STRSIM_NUM_MEASURES, Col{a_off, a_val, a_rows}, Col{b_off, b_val, b_rows}, outs, out_rows);
 }
 
 int strsim_ctx_synchronize(strsim_ctx_t *c)
@@ -1325,21 +1374,21 @@ int strsim_pairs_host(strsim_ctx_t *c, int measure, const uint32_t *a_off, const
                       const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t out_rows)
 {
     if (!c) { set_error("strsim_pairs_host: ctx is NULL"); return STRSIM_ERR_ARG; }
+    const Col a{a_off, a_val, a_rows}, b{b_off, b_val, b_rows};
     uint64_t n;
     int rc = shape_rows(a_rows, b_rows, &n);
     if (rc) return rc;
     if (out_rows != n) { set_error("strsim_pairs_host: out_rows mismatch"); return STRSIM_ERR_ARG; }
     if (n == 0) return STRSIM_OK;
     if (!a_off || !b_off || !out) { set_error("strsim_pairs_host: NULL buffer"); return STRSIM_ERR_ARG; }
-    rc = ctx_set_device(c);
-    if (rc) return rc;
     const size_t abytes = (size_t)a_off[a_rows] - a_off[0], bbytes = (size_t)b_off[b_rows] - b_off[0];
     if (n <= c->host_direct_rows && abytes <= HOST_DIRECT_BYTES && bbytes <= HOST_DIRECT_BYTES) {
+        rc = ctx_set_device(c);
+        if (rc) return rc;
         // Small call: gather the five buffers in one pinned block and let the kernels work on it in place through the
         // device's mapping of host memory -- no copy engine, whose hand-overs (four H2D, one D2H) are most of a small call.
-        auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-        const size_t o_aoff = 0, o_aval = o_aoff + up((a_rows + 1) * 4), o_boff = o_aval + up(abytes + 64),
-                     o_bval = o_boff + up((b_rows + 1) * 4), o_out = o_bval + up(bbytes + 64), total = o_out + up(n * 8);
+        const size_t o_aoff = 0, o_aval = o_aoff + up256((a_rows + 1) * 4), o_boff = o_aval + up256(abytes + 64),
+                     o_bval = o_boff + up256((b_rows + 1) * 4), o_out = o_bval + up256(bbytes + 64), total = o_out + up256(n * 8);
         if (total > c->pin_cap) {
             if (c->pin) { HIP_TRY(hipHostFree(c->pin)); c->pin = nullptr; c->pin_cap = 0; }
             const size_t want = total + total / 4 + 4096;
@@ -1369,16 +1418,10 @@ int strsim_pairs_host(strsim_ctx_t *c, int measure, const uint32_t *a_off, const
         memcpy(out, h + o_out, n * 8);
         return STRSIM_OK;
     }
-    Staged s;
-    rc = ctx_stage(c, a_off, a_val, a_rows, b_off, b_val, b_rows, n * 8, &s);
-    if (rc) return rc;
-    rc = strsim_pairs_device(c, measure, s.a_off, s.a_val, a_rows, s.b_off, s.b_val, b_rows, (double *)s.out, n);
-    if (rc) return rc;
-    rc = strsim_ctx_synchronize(c); // also runs the long-string pass, which writes into the staged output
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, s.out, n * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return STRSIM_OK;
+    return elementwise_host(
+        c, STRSIM_OK, a, b, n, out, n * 8, nullptr, 0,
+        [&](const Staged &s, uint8_t *d_out, uint8_t *) { return pairs_device(c, measure, s.a, s.b, (double *)d_out, n); },
+        [&] { return strsim_ctx_synchronize(c); });
 }
 
 int strsim_ctx_timing_enable(strsim_ctx_t *c, int enable)
@@ -1448,8 +1491,8 @@ static constexpr uint64_t MATCH_FALLBACK_SCORES = (uint64_t)1 << 24;
 // The part of a search call's workspace that both families lay out alike: both sides packed by k_match_pack (32-byte words +
 // meta) and their slow lists; `tail` is the family's own, and starts with the two slow counts.
 struct SearchPack {
-    const uint32_t *q_off; const uint8_t *q_val; uint32_t nq; // the call's columns
-    const uint32_t *c_off; const uint8_t *c_val; uint32_t nc;
+    Col q, c;        // the call's columns
+    uint32_t nq, nc; // their rows
     uint32_t *qw, *qm, *cw, *cm, *qs, *cs;
     uint8_t *tail;
     uint32_t q_slow, c_slow; // strings k_match_pack could not pack
@@ -1457,23 +1500,23 @@ struct SearchPack {
 
 // Reserve `ws` for the common part + tail_bytes, zero the first zero_bytes of the tail, pack both sides and read the two slow
 // counts back: they decide what runs (the only wait of a call without slow strings).
-static int search_pack(strsim_ctx *c, DevBuf &ws, size_t tail_bytes, size_t zero_bytes, const uint32_t *q_off, const uint8_t *q_val,
-                       uint32_t nq, const uint32_t *c_off, const uint8_t *c_val, uint32_t nc, SearchPack *p)
+static int search_pack(strsim_ctx *c, DevBuf &ws, size_t tail_bytes, size_t zero_bytes, const Col &q, const Col &cnd, SearchPack *p)
 {
+    const uint32_t nq = (uint32_t)q.rows, nc = (uint32_t)cnd.rows;
     const size_t o_qw = 0, o_qm = o_qw + up256((size_t)nq * 32), o_cw = o_qm + up256((size_t)nq * 4), o_cm = o_cw + up256((size_t)nc * 32),
                  o_qs = o_cm + up256((size_t)nc * 4), o_cs = o_qs + up256((size_t)nq * 4), o_tail = o_cs + up256((size_t)nc * 4);
     int rc = ws.reserve(o_tail + tail_bytes);
     if (rc) return rc;
     if (!c->match_counts_host) HIP_TRY(hipHostMalloc((void **)&c->match_counts_host, 64, hipHostMallocDefault));
     uint8_t *const b = ws.as<uint8_t>();
-    p->q_off = q_off; p->q_val = q_val; p->nq = nq; p->c_off = c_off; p->c_val = c_val; p->nc = nc;
+    p->q = q; p->c = cnd; p->nq = nq; p->nc = nc;
     p->qw = (uint32_t *)(b + o_qw); p->qm = (uint32_t *)(b + o_qm); p->cw = (uint32_t *)(b + o_cw); p->cm = (uint32_t *)(b + o_cm);
     p->qs = (uint32_t *)(b + o_qs); p->cs = (uint32_t *)(b + o_cs); p->tail = b + o_tail;
     uint32_t *const cnt = (uint32_t *)p->tail;
     hipStream_t st = c->stream;
     HIP_TRY(hipMemsetAsync(cnt, 0, zero_bytes, st));
-    HIP_TRY(launch_match_pack(q_off, q_val, nq, p->qw, p->qm, p->qs, cnt, st));
-    HIP_TRY(launch_match_pack(c_off, c_val, nc, p->cw, p->cm, p->cs, cnt + 1, st));
+    HIP_TRY(launch_match_pack(q.off, q.val, nq, p->qw, p->qm, p->qs, cnt, st));
+    HIP_TRY(launch_match_pack(cnd.off, cnd.val, nc, p->cw, p->cm, p->cs, cnt + 1, st));
     HIP_TRY(hipMemcpyAsync(c->match_counts_host, cnt, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     p->q_slow = c->match_counts_host[0];
@@ -1487,64 +1530,65 @@ static uint64_t fallback_calls(uint32_t nq, uint32_t nc)
     return std::min(std::max<uint64_t>(calls, 1), MATCH_FALLBACK_CALLS);
 }
 
-// Every pair with a slow side: that side as the literal of a pairwise call against the other column, `calls` of them per batch,
-// folded into the list (fs, fi).  score(lit_off, lit_val, col_off, col_val, rows, b) enqueues literal b of a batch;
-// finish(scores) leaves the batch's `scores` scores, row b at b * rows, in `batch` for the fold.
-template <class Score, class Finish>
-static int search_fallback(strsim_ctx *c, const char *who, const SearchPack &p, uint32_t k, uint32_t kp, double min_score, uint64_t calls,
-                           const double *batch, double *fs, uint32_t *fi, Score score, Finish finish)
+// Every pair with a slow side: that side as the literal of a call against the other column, `calls` of them per batch -- the slow
+// queries against every candidate, then the slow candidates against every query.  score(side, literal, column, b) enqueues literal b
+// of a batch; done(side, b0, nb) ends the batch of the slow strings b0 .. b0 + nb - 1 of side 0 (p.qs) or 1 (p.cs).
+template <class Score, class Done>
+static int slow_walk(strsim_ctx *c, const char *who, const SearchPack &p, uint64_t calls, Score score, Done done)
 {
     hipStream_t st = c->stream;
-    const uint32_t nq = p.nq, nc = p.nc;
-    HIP_TRY(launch_match_clear(fs, fi, (uint64_t)nq * kp, st));
-    const uint32_t q_slow = p.q_slow, c_slow = p.c_slow;
-    const std::unique_ptr<uint32_t[]> host_list(new (std::nothrow) uint32_t[(size_t)q_slow + c_slow + 1]);
+    const uint32_t slow[2] = {p.q_slow, p.c_slow};
+    const std::unique_ptr<uint32_t[]> host_list(new (std::nothrow) uint32_t[(size_t)slow[0] + slow[1] + 1]);
     if (!host_list) { set_error("%s: out of host memory", who); return STRSIM_ERR_OOM; }
-    if (q_slow) HIP_TRY(hipMemcpyAsync(host_list.get(), p.qs, (size_t)q_slow * 4, hipMemcpyDeviceToHost, st));
-    if (c_slow) HIP_TRY(hipMemcpyAsync(host_list.get() + q_slow, p.cs, (size_t)c_slow * 4, hipMemcpyDeviceToHost, st));
+    if (slow[0]) HIP_TRY(hipMemcpyAsync(host_list.get(), p.qs, (size_t)slow[0] * 4, hipMemcpyDeviceToHost, st));
+    if (slow[1]) HIP_TRY(hipMemcpyAsync(host_list.get() + slow[0], p.cs, (size_t)slow[1] * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    for (uint32_t b0 = 0; b0 < q_slow; b0 += (uint32_t)calls) { // a slow query against every candidate
-        const uint32_t nb = (uint32_t)(q_slow - b0 < calls ? q_slow - b0 : calls);
-        for (uint32_t b = 0; b < nb; ++b) {
-            int r = score(p.q_off + host_list[b0 + b], p.q_val, p.c_off, p.c_val, nc, b);
+    const Col *const col[2] = {&p.q, &p.c};
+    for (int side = 0; side < 2; ++side) {
+        const uint32_t *const list = host_list.get() + (side ? slow[0] : 0u);
+        for (uint32_t b0 = 0; b0 < slow[side]; b0 += (uint32_t)calls) {
+            const uint32_t nb = (uint32_t)(slow[side] - b0 < calls ? slow[side] - b0 : calls);
+            for (uint32_t b = 0; b < nb; ++b) {
+                int r = score(side, literal(*col[side], list[b0 + b]), *col[1 - side], b);
+                if (r) return r;
+            }
+            int r = done(side, b0, nb);
             if (r) return r;
         }
-        int r = finish((uint64_t)nb * nc);
-        if (r) return r;
-        HIP_TRY(launch_match_fold_cols(k, batch, p.qs + b0, nb, nc, min_score, fs, fi, st));
-    }
-    for (uint32_t b0 = 0; b0 < c_slow; b0 += (uint32_t)calls) { // a slow candidate against every query (the fast ones are kept)
-        const uint32_t nb = (uint32_t)(c_slow - b0 < calls ? c_slow - b0 : calls);
-        for (uint32_t b = 0; b < nb; ++b) {
-            int r = score(p.c_off + host_list[q_slow + b0 + b], p.c_val, p.q_off, p.q_val, nq, b);
-            if (r) return r;
-        }
-        int r = finish((uint64_t)nb * nq);
-        if (r) return r;
-        HIP_TRY(launch_match_fold_rows(k, batch, p.cs + b0, nb, p.qm, nq, min_score, fs, fi, st));
     }
     return STRSIM_OK;
 }
 
-// The end of every search call: when `fallback` and a side has slow strings, every pair with a slow side goes through
-// search_fallback, its batches in `scratch` (pair_bytes per pair, the f64 scores first), into list `used`; then the lists are
-// merged.  score / finish read their batch pointers from `scratch` when they run: it is reserved only here.
+// The end of every search call: when `fallback` and a side has slow strings, every pair with a slow side goes through slow_walk,
+// its batches in `scratch` (pair_bytes per pair, the f64 scores first), folded into list `used` (the fast ones of a slow candidate's
+// queries are kept); then the lists are merged.  finish(scores) leaves a batch's `scores` scores, row b at b * rows, at the front of
+// `scratch` for the fold; score / finish read their batch pointers from `scratch` when they run: it is reserved only here.
 template <class Score, class Finish>
 static int search_fallback_merge(strsim_ctx *c, const char *who, const SearchPack &p, uint32_t k, double min_score, bool fallback,
                                  DevBuf &scratch, size_t pair_bytes, uint32_t used, double *lscore, uint32_t *lidx, uint32_t *out_index,
                                  double *out_score, Score score, Finish finish)
 {
     const uint32_t kp = (uint32_t)match_lane_k(k);
+    hipStream_t st = c->stream;
     if (fallback && p.nc && (p.q_slow || p.c_slow)) {
         const uint64_t calls = fallback_calls(p.nq, p.nc);
         int rc = scratch.reserve((size_t)(calls * std::max(p.nq, p.nc) * pair_bytes));
         if (rc) return rc;
-        const size_t o = (size_t)used * p.nq * kp;
-        rc = search_fallback(c, who, p, k, kp, min_score, calls, scratch.as<double>(), lscore + o, lidx + o, score, finish);
+        const double *const batch = scratch.as<double>();
+        double *const fs = lscore + (size_t)used * p.nq * kp;
+        uint32_t *const fi = lidx + (size_t)used * p.nq * kp;
+        HIP_TRY(launch_match_clear(fs, fi, (uint64_t)p.nq * kp, st));
+        rc = slow_walk(c, who, p, calls, score, [&](int side, uint32_t b0, uint32_t nb) -> int {
+            int r = finish((uint64_t)nb * (side ? p.nq : p.nc));
+            if (r) return r;
+            if (side == 0) HIP_TRY(launch_match_fold_cols(k, batch, p.qs + b0, nb, p.nc, min_score, fs, fi, st));
+            else HIP_TRY(launch_match_fold_rows(k, batch, p.cs + b0, nb, p.qm, p.nq, min_score, fs, fi, st));
+            return STRSIM_OK;
+        });
         if (rc) return rc;
         ++used;
     }
-    HIP_TRY(launch_match_merge(k, lscore, lidx, used, p.nq, out_index, out_score, c->stream));
+    HIP_TRY(launch_match_merge(k, lscore, lidx, used, p.nq, out_index, out_score, st));
     return STRSIM_OK;
 }
 
@@ -1558,9 +1602,9 @@ struct OrderedSearch {
     bool fast;          // the length order is in place and the lane kernel has work: lists 0 .. splits - 1 are its
 };
 // `sweep`: the family admits a sweep at all (extract under a cutoff above 1.0 does not).
-static int ordered_search_pack(strsim_ctx *c, DevBuf &ws, size_t extra_bytes, bool sweep, const uint32_t *q_off, const uint8_t *q_val,
-                               uint32_t nq, const uint32_t *c_off, const uint8_t *c_val, uint32_t nc, uint32_t k, OrderedSearch *o)
+static int ordered_search_pack(strsim_ctx *c, DevBuf &ws, size_t extra_bytes, bool sweep, const Col &q, const Col &cnd, uint32_t k, OrderedSearch *o)
 {
+    const uint32_t nq = (uint32_t)q.rows, nc = (uint32_t)cnd.rows;
     const uint32_t kp = (uint32_t)match_lane_k(k);
     const uint32_t splits = nc ? match_splits(nq, nc, kp, c->num_cu) : 0u;
     const size_t lists = ((size_t)splits + 1) * nq * kp;
@@ -1568,7 +1612,7 @@ static int ordered_search_pack(strsim_ctx *c, DevBuf &ws, size_t extra_bytes, bo
                  o_ls = o_si + up256((size_t)nc * 4), o_li = o_ls + up256(lists * 8), o_ex = o_li + up256(lists * 4);
     SearchPack &p = o->p;
     // (of the small block, the counts and histograms are zeroed)
-    int rc = search_pack(c, ws, o_ex + extra_bytes, 4 * 88, q_off, q_val, nq, c_off, c_val, nc, &p);
+    int rc = search_pack(c, ws, o_ex + extra_bytes, 4 * 88, q, cnd, &p);
     if (rc) return rc;
     uint32_t *const small = (uint32_t *)p.tail;
     uint32_t *const qhist = small + 8, *const chist = qhist + 40, *const qstart = chist + 40, *const cstart = qstart + 40,
@@ -1590,15 +1634,14 @@ static int ordered_search_pack(strsim_ctx *c, DevBuf &ws, size_t extra_bytes, bo
 // The *_host entry point of a search family behind its check (`checked`: what the check returned): both columns staged, the
 // device entry point on the staged columns with outputs a then b in stage[4], the two copies back and the family's wait.
 template <class A, class B, class Device, class Wait>
-static int search_host(strsim_ctx *c, int checked, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows, const uint32_t *c_off,
-                       const uint8_t *c_val, uint64_t c_rows, uint32_t k, A *out_a, B *out_b, Device device, Wait wait)
+static int search_host(strsim_ctx *c, int checked, const Col &q, const Col &cnd, uint32_t k, A *out_a, B *out_b, Device device, Wait wait)
 {
-    if (checked || q_rows == 0) return checked;
+    if (checked || q.rows == 0) return checked;
     int rc = ctx_set_device(c);
     if (rc) return rc;
-    const size_t ob = q_rows * (size_t)k;
+    const size_t ob = q.rows * (size_t)k;
     Staged s;
-    rc = ctx_stage(c, q_off, q_val, q_rows, c_off, c_val, c_rows, ob * (sizeof(A) + sizeof(B)) + 256, &s);
+    rc = ctx_stage(c, q, cnd, ob * (sizeof(A) + sizeof(B)) + 256, &s);
     if (rc) return rc;
     A *const d_a = reinterpret_cast<A *>(s.out);
     B *const d_b = reinterpret_cast<B *>(s.out + up256(ob * sizeof(A)));
@@ -1609,12 +1652,11 @@ static int search_host(strsim_ctx *c, int checked, const uint32_t *q_off, const 
     return wait();
 }
 
-static int best_match_check(const char *who, strsim_ctx_t *c, int measure, const uint32_t *q_off, const uint8_t *q_val,
-                            uint64_t q_rows, const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, uint32_t k,
-                            double min_score, const void *out_index, const void *out_score)
+static int best_match_check(const char *who, strsim_ctx_t *c, int measure, const Col &q, const Col &cnd, uint32_t k, double min_score,
+                            const void *out_index, const void *out_score)
 {
     if (!measure_accepted(measure, STRSIM_ENTRY_BEST_MATCH)) { set_error("%s: unknown measure %d", who, measure); return STRSIM_ERR_ARG; }
-    return search_check(who, c, q_off, q_val, q_rows, c_off, c_val, c_rows, k, STRSIM_BEST_MATCH_MAX_K, min_score, out_index, out_score);
+    return search_check(who, c, q, cnd, k, STRSIM_BEST_MATCH_MAX_K, min_score, out_index, out_score);
 }
 
 extern "C" {
@@ -1623,8 +1665,8 @@ int strsim_best_match_device(strsim_ctx_t *c, int measure, const uint32_t *q_off
                              const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, uint32_t k, double min_score,
                              uint32_t *out_index, double *out_score)
 {
-    int rc = best_match_check("strsim_best_match_device", c, measure, q_off, q_val, q_rows, c_off, c_val, c_rows, k, min_score,
-                              out_index, out_score);
+    const Col q{q_off, q_val, q_rows}, cnd{c_off, c_val, c_rows};
+    int rc = best_match_check("strsim_best_match_device", c, measure, q, cnd, k, min_score, out_index, out_score);
     if (rc || q_rows == 0) return rc;
     rc = ctx_set_device(c);
     if (rc) return rc;
@@ -1636,7 +1678,7 @@ int strsim_best_match_device(strsim_ctx_t *c, int measure, const uint32_t *q_off
     const size_t lists = ((size_t)nsplit + 1) * nq * kp;
     const size_t o_ls = 256, o_li = o_ls + up256(lists * 8);
     SearchPack p;
-    rc = search_pack(c, c->match_ws, o_li + up256(lists * 4), 8, q_off, q_val, nq, c_off, c_val, nc, &p);
+    rc = search_pack(c, c->match_ws, o_li + up256(lists * 4), 8, q, cnd, &p);
     if (rc) return rc;
     double *const lscore = (double *)(p.tail + o_ls);
     uint32_t *const lidx = (uint32_t *)(p.tail + o_li);
@@ -1651,8 +1693,8 @@ int strsim_best_match_device(strsim_ctx_t *c, int measure, const uint32_t *q_off
     // every pair with a slow side: strsim_pairs_device with that side as the literal, batch by batch, folded into list `used`
     return search_fallback_merge(
         c, "strsim_best_match_device", p, k, min_score, true, c->match_scratch, 8, used, lscore, lidx, out_index, out_score,
-        [&](const uint32_t *lit_off, const uint8_t *lit_val, const uint32_t *off, const uint8_t *val, uint32_t rows, uint32_t b) {
-            return strsim_pairs_device(c, measure, lit_off, lit_val, 1, off, val, rows, c->match_scratch.as<double>() + (size_t)b * rows, rows);
+        [&](int, const Col &lit, const Col &col, uint32_t b) {
+            return pairs_device(c, measure, lit, col, c->match_scratch.as<double>() + (size_t)b * col.rows, col.rows);
         },
         [&](uint64_t) { return strsim_ctx_synchronize(c); });
 }
@@ -1661,11 +1703,11 @@ int strsim_best_match_host(strsim_ctx_t *c, int measure, const uint32_t *q_off, 
                            const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, uint32_t k, double min_score,
                            uint32_t *out_index, double *out_score)
 {
+    const Col q{q_off, q_val, q_rows}, cnd{c_off, c_val, c_rows};
     return search_host(
-        c, best_match_check("strsim_best_match_host", c, measure, q_off, q_val, q_rows, c_off, c_val, c_rows, k, min_score, out_index, out_score),
-        q_off, q_val, q_rows, c_off, c_val, c_rows, k, out_score, out_index,
+        c, best_match_check("strsim_best_match_host", c, measure, q, cnd, k, min_score, out_index, out_score), q, cnd, k, out_score, out_index,
         [&](const Staged &s, double *d_score, uint32_t *d_index) {
-            return strsim_best_match_device(c, measure, s.a_off, s.a_val, q_rows, s.b_off, s.b_val, c_rows, k, min_score, d_index, d_score);
+            return strsim_best_match_device(c, measure, s.a.off, s.a.val, q_rows, s.b.off, s.b.val, c_rows, k, min_score, d_index, d_score);
         },
         [&] { return strsim_ctx_synchronize(c); });
 }
@@ -1674,15 +1716,13 @@ int strsim_best_match_host(strsim_ctx_t *c, int measure, const uint32_t *q_off, 
 
 // ---- bounded distances (strsim_distance.h) ----
 
-static int distance_check(const char *who, strsim_ctx_t *c, int measure, const uint32_t *a_off, const uint8_t *a_val,
-                          uint64_t a_rows, const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, const uint32_t *out,
-                          uint64_t out_rows)
+static int distance_check(const char *who, strsim_ctx_t *c, int measure, const Col &a, const Col &b, const uint32_t *out, uint64_t out_rows)
 {
     if (measure != STRSIM_LEVENSHTEIN && measure != STRSIM_OSA && measure != STRSIM_INDEL) {
         set_error("%s: measure %d has no distance (STRSIM_LEVENSHTEIN, STRSIM_OSA or STRSIM_INDEL)", who, measure);
         return STRSIM_ERR_ARG;
     }
-    return elementwise_check(who, c, a_rows, b_rows, out_rows, a_off && a_val && b_off && b_val && out);
+    return elementwise_check(who, c, a.rows, b.rows, out_rows, a.off && a.val && b.off && b.val && out);
 }
 
 // The status block of a distance or alignment call and its pinned read-back, and the work list for n rows.
@@ -1698,13 +1738,20 @@ static int dist_prepare(strsim_ctx *c, uint64_t n)
 }
 
 // k_dist_lane, then k_dist_wave (Indel: k_indel_lane / k_indel_wave with the uint32 output, strsim_indel.h).
-static int distance_device_impl(strsim_ctx_t *c, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
-                                const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, uint32_t k, uint32_t *out, uint64_t n)
+static int distance_device_impl(strsim_ctx_t *c, int measure, const Col &a, const Col &b, uint32_t k, uint32_t *out, uint64_t n)
 {
     int rc = dist_prepare(c, n);
     if (rc) return rc;
-    const LaunchArgs la = two_pass_args(c, a_off, a_val, a_rows, b_off, b_val, b_rows, nullptr, n, c->dist_status);
+    const LaunchArgs la = two_pass_args(c, a, b, nullptr, n, c->dist_status);
     return two_pass(c, la, TwoPassCall{measure == STRSIM_INDEL ? TP_INDEL : TP_DIST, measure, k, out, nullptr}, -1);
+}
+
+// strsim_distance_device, which the fallback of the nearest search calls with a literal.
+static int distance_device(strsim_ctx *c, int measure, const Col &a, const Col &b, uint32_t max_distance, uint32_t *out, uint64_t out_rows)
+{
+    int rc = distance_check("strsim_distance_device", c, measure, a, b, out, out_rows);
+    if (rc || out_rows == 0) return rc;
+    return distance_device_impl(c, measure, a, b, max_distance, out, out_rows);
 }
 
 extern "C" {
@@ -1713,28 +1760,18 @@ int strsim_distance_device(strsim_ctx_t *c, int measure, const uint32_t *a_off, 
                            const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, uint32_t max_distance, uint32_t *out,
                            uint64_t out_rows)
 {
-    int rc = distance_check("strsim_distance_device", c, measure, a_off, a_val, a_rows, b_off, b_val, b_rows, out, out_rows);
-    if (rc || out_rows == 0) return rc;
-    return distance_device_impl(c, measure, a_off, a_val, a_rows, b_off, b_val, b_rows, max_distance, out, out_rows);
+    return distance_device(c, measure, Col{a_off, a_val, a_rows}, Col{b_off, b_val, b_rows}, max_distance, out, out_rows);
 }
 
 int strsim_distance_host(strsim_ctx_t *c, int measure, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
                          const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, uint32_t max_distance, uint32_t *out,
                          uint64_t out_rows)
 {
-    int rc = distance_check("strsim_distance_host", c, measure, a_off, a_val, a_rows, b_off, b_val, b_rows, out, out_rows);
-    if (rc || out_rows == 0) return rc;
-    rc = ctx_set_device(c);
-    if (rc) return rc;
-    const uint64_t n = out_rows;
-    Staged s;
-    rc = ctx_stage(c, a_off, a_val, a_rows, b_off, b_val, b_rows, n * 4, &s);
-    if (rc) return rc;
-    rc = distance_device_impl(c, measure, s.a_off, s.a_val, a_rows, s.b_off, s.b_val, b_rows, max_distance, (uint32_t *)s.out, n);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, s.out, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return STRSIM_OK;
+    const Col a{a_off, a_val, a_rows}, b{b_off, b_val, b_rows};
+    return elementwise_host(
+        c, distance_check("strsim_distance_host", c, measure, a, b, out, out_rows), a, b, out_rows, out, out_rows * 4, nullptr, 0,
+        [&](const Staged &s, uint8_t *d_out, uint8_t *) { return distance_device_impl(c, measure, s.a, s.b, max_distance, (uint32_t *)d_out, out_rows); },
+        nothing_to_settle);
 }
 
 } // extern "C"
@@ -1742,12 +1779,11 @@ int strsim_distance_host(strsim_ctx_t *c, int measure, const uint32_t *a_off, co
 // ---- partial ratio with its alignment (strsim_partial.h) ----
 
 // k_partial_lane<ALIGN>, then k_partial_wave<ALIGN>.
-static int partial_device_impl(strsim_ctx_t *c, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
-                               const uint8_t *b_val, uint64_t b_rows, double *out_score, uint32_t *out_span, uint64_t n)
+static int partial_device_impl(strsim_ctx_t *c, const Col &a, const Col &b, double *out_score, uint32_t *out_span, uint64_t n)
 {
     int rc = dist_prepare(c, n);
     if (rc) return rc;
-    const LaunchArgs la = two_pass_args(c, a_off, a_val, a_rows, b_off, b_val, b_rows, out_score, n, c->dist_status);
+    const LaunchArgs la = two_pass_args(c, a, b, out_score, n, c->dist_status);
     return two_pass(c, la, TwoPassCall{TP_PARTIAL, STRSIM_PARTIAL_RATIO, 0u, nullptr, out_span}, -1);
 }
 
@@ -1758,44 +1794,62 @@ int strsim_partial_alignment_device(strsim_ctx_t *c, const uint32_t *a_off, cons
 {
     int rc = elementwise_check("strsim_partial_alignment_device", c, a_rows, b_rows, out_rows, a_off && a_val && b_off && b_val && out_score && out_span);
     if (rc || out_rows == 0) return rc;
-    return partial_device_impl(c, a_off, a_val, a_rows, b_off, b_val, b_rows, out_score, out_span, out_rows);
+    return partial_device_impl(c, Col{a_off, a_val, a_rows}, Col{b_off, b_val, b_rows}, out_score, out_span, out_rows);
 }
 
 int strsim_partial_alignment_host(strsim_ctx_t *c, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
                                   const uint8_t *b_val, uint64_t b_rows, double *out_score, uint32_t *out_span, uint64_t out_rows)
 {
-    int rc = elementwise_check("strsim_partial_alignment_host", c, a_rows, b_rows, out_rows, a_off && a_val && b_off && b_val && out_score && out_span);
-    if (rc || out_rows == 0) return rc;
-    rc = ctx_set_device(c);
-    if (rc) return rc;
-    const uint64_t n = out_rows;
-    const size_t span_at = up256(n * 8);
-    Staged s;
-    rc = ctx_stage(c, a_off, a_val, a_rows, b_off, b_val, b_rows, span_at + n * 16, &s);
-    if (rc) return rc;
-    double *const d_score = reinterpret_cast<double *>(s.out);
-    uint32_t *const d_span = reinterpret_cast<uint32_t *>(s.out + span_at);
-    rc = partial_device_impl(c, s.a_off, s.a_val, a_rows, s.b_off, s.b_val, b_rows, d_score, d_span, n);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out_score, d_score, n * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(out_span, d_span, n * 16, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return STRSIM_OK;
+    const int checked = elementwise_check("strsim_partial_alignment_host", c, a_rows, b_rows, out_rows, a_off && a_val && b_off && b_val && out_score && out_span);
+    return elementwise_host(
+        c, checked, Col{a_off, a_val, a_rows}, Col{b_off, b_val, b_rows}, out_rows, out_score, out_rows * 8, out_span, out_rows * 16,
+        [&](const Staged &s, uint8_t *d_score, uint8_t *d_span) { return partial_device_impl(c, s.a, s.b, (double *)d_score, (uint32_t *)d_span, out_rows); },
+        nothing_to_settle);
 }
 
 } // extern "C"
 
 // ---- the token_sort transform itself (strsim_token.h) ----
 
-static int token_sort_check(const char *who, strsim_ctx_t *c, const uint32_t *off, const uint8_t *val, uint64_t rows, const uint32_t *out_off,
-                            const uint8_t *out_val)
+// The checks of the two column transforms (token_sort here, default_process below).
+static int transform_check(const char *who, strsim_ctx_t *c, const Col &col, const uint32_t *out_off, const uint8_t *out_val)
 {
-    if (rows > 0xFFFFFFFFull) {
-        set_error("%s: %llu rows in one call; split the column (at most 2^32 - 1 rows per call)", who, (unsigned long long)rows);
+    if (col.rows > 0xFFFFFFFFull) {
+        set_error("%s: %llu rows in one call; split the column (at most 2^32 - 1 rows per call)", who, (unsigned long long)col.rows);
         return STRSIM_ERR_ARG;
     }
-    if (!off || !out_off || (rows && (!val || !out_val))) { set_error("%s: NULL buffer", who); return STRSIM_ERR_ARG; }
+    if (!col.off || !out_off || (col.rows && (!col.val || !out_val))) { set_error("%s: NULL buffer", who); return STRSIM_ERR_ARG; }
     if (!c) { set_error("%s: ctx is NULL", who); return STRSIM_ERR_ARG; }
+    return STRSIM_OK;
+}
+
+// The *_host entry point of a transform behind its checks: the column staged (stage[0..1]), rows + 1 new offsets in stage[2] and room
+// for `room` bytes of new values in stage[3], transform(column, offsets, values, &total) on them, the new column copied back.  A
+// transform that learns the new column's byte size sets *total; otherwise it is read from the offsets once they are back.
+static constexpr uint64_t TOTAL_UNKNOWN = ~(uint64_t)0;
+template <class Transform>
+static int transform_host(strsim_ctx *c, const Col &col, uint64_t room, uint32_t *out_off, uint8_t *out_val, Transform transform)
+{
+    if (col.rows == 0) { out_off[0] = 0u; return STRSIM_OK; }
+    int rc = ctx_set_device(c);
+    if (rc) return rc;
+    Staged s;
+    rc = ctx_stage(c, col, NO_COL, 0, &s);
+    if (rc == STRSIM_OK) rc = c->stage[2].reserve((col.rows + 1) * sizeof(uint32_t));
+    if (rc == STRSIM_OK) rc = c->stage[3].reserve(room + TOKEN_PAD);
+    if (rc) return rc;
+    uint32_t *const d_off = c->stage[2].as<uint32_t>();
+    uint8_t *const d_val = c->stage[3].as<uint8_t>();
+    uint64_t total = TOTAL_UNKNOWN;
+    rc = transform(s.a, d_off, d_val, &total);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out_off, d_off, (col.rows + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (total == TOTAL_UNKNOWN) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        total = out_off[col.rows];
+    }
+    if (total) HIP_TRY(hipMemcpyAsync(out_val, d_val, total, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return STRSIM_OK;
 }
 
@@ -1804,7 +1858,8 @@ extern "C" {
 int strsim_token_sort_device(strsim_ctx_t *c, const uint32_t *off, const uint8_t *val, uint64_t rows, uint32_t *out_off, uint8_t *out_val,
                              uint64_t out_capacity)
 {
-    int rc = token_sort_check("strsim_token_sort_device", c, off, val, rows, out_off, out_val);
+    const Col col{off, val, rows};
+    int rc = transform_check("strsim_token_sort_device", c, col, out_off, out_val);
     if (rc) return rc;
     rc = token_prepare(c);
     if (rc) return rc;
@@ -1812,16 +1867,15 @@ int strsim_token_sort_device(strsim_ctx_t *c, const uint32_t *off, const uint8_t
         HIP_TRY(hipMemsetAsync(out_off, 0, sizeof(uint32_t), c->stream));
         return STRSIM_OK;
     }
-    rc = token_bounds(c, off, rows, nullptr, 0);
+    rc = token_bounds(c, col, nullptr);
     if (rc) return rc;
-    const TokenStatus st = *c->tok_status_host;
-    const uint64_t bytes = (uint64_t)st.end[0] - st.begin[0];
-    if (out_capacity < bytes) {
+    const ColBounds bd = token_col_bounds(c);
+    if (out_capacity < bd.bytes[0]) {
         set_error("strsim_token_sort_device: out_capacity=%llu but the column holds %llu bytes (its byte size always suffices)",
-                  (unsigned long long)out_capacity, (unsigned long long)bytes);
+                  (unsigned long long)out_capacity, (unsigned long long)bd.bytes[0]);
         return STRSIM_ERR_ARG;
     }
-    rc = token_sort_column(c, 0, off, val, rows, st.max_len[0], out_off, out_val);
+    rc = token_sort_column(c, 0, col, bd.max_len[0], out_off, out_val);
     if (rc) return rc;
     return token_copy_counts(c);
 }
@@ -1829,7 +1883,8 @@ int strsim_token_sort_device(strsim_ctx_t *c, const uint32_t *off, const uint8_t
 int strsim_token_sort_host(strsim_ctx_t *c, const uint32_t *off, const uint8_t *val, uint64_t rows, uint32_t *out_off, uint8_t *out_val,
                            uint64_t out_capacity)
 {
-    int rc = token_sort_check("strsim_token_sort_host", c, off, val, rows, out_off, out_val);
+    const Col col{off, val, rows};
+    int rc = transform_check("strsim_token_sort_host", c, col, out_off, out_val);
     if (rc) return rc;
     const uint64_t bytes = (uint64_t)off[rows] - off[0];
     if (out_capacity < bytes) {
@@ -1837,23 +1892,9 @@ int strsim_token_sort_host(strsim_ctx_t *c, const uint32_t *off, const uint8_t *
                   (unsigned long long)out_capacity, (unsigned long long)bytes);
         return STRSIM_ERR_ARG;
     }
-    if (rows == 0) { out_off[0] = 0u; return STRSIM_OK; }
-    rc = ctx_set_device(c);
-    if (rc) return rc;
-    // stage[0..1]: the column; stage[2]: the new offsets; stage[3]: the new values
-    Staged s;
-    rc = ctx_stage(c, off, val, rows, nullptr, nullptr, 0, 0, &s);
-    if (rc == STRSIM_OK) rc = c->stage[2].reserve((rows + 1) * sizeof(uint32_t));
-    if (rc == STRSIM_OK) rc = c->stage[3].reserve(bytes + TOKEN_PAD);
-    if (rc) return rc;
-    uint32_t *const d_off = c->stage[2].as<uint32_t>();
-    uint8_t *const d_val = c->stage[3].as<uint8_t>();
-    rc = strsim_token_sort_device(c, s.a_off, s.a_val, rows, d_off, d_val, bytes);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out_off, d_off, (rows + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (out_off[rows]) HIP_TRY(hipMemcpy(out_val, d_val, out_off[rows], hipMemcpyDeviceToHost));
-    return STRSIM_OK;
+    return transform_host(c, col, bytes, out_off, out_val, [&](const Col &d, uint32_t *d_off, uint8_t *d_val, uint64_t *) {
+        return strsim_token_sort_device(c, d.off, d.val, rows, d_off, d_val, bytes);
+    });
 }
 
 uint64_t strsim_ctx_last_token_wave_rows(strsim_ctx_t *c)
@@ -1932,14 +1973,15 @@ static int process_wave_grid(const strsim_ctx *c) { return c->num_cu * 8; }
 
 // Bounds, measuring pass and scan of one column (side 0 or 1 of c->proc_status, zeroed by the caller): out_off becomes the
 // processed column's offsets, and its last word is on its way to c->proc_status_host->pad[side].
-static int process_measure(strsim_ctx *c, int side, const ProcessTable &t, const uint32_t *off, const uint8_t *val, uint64_t rows, uint32_t *out_off)
+static int process_measure(strsim_ctx *c, int side, const ProcessTable &t, const Col &col, uint32_t *out_off)
 {
+    const uint64_t rows = col.rows;
     int rc = c->proc_list[side].reserve(rows * sizeof(uint32_t));
     if (rc) return rc;
     rc = c->proc_sums.reserve(((rows + 4095u) / 4096u) * sizeof(uint32_t));
     if (rc) return rc;
-    HIP_TRY(launch_token_bounds(off, rows, c->proc_status, side, c->stream));
-    hipError_t e = launch_process(false, off, val, rows, out_off, nullptr, c->proc_list[side].as<uint32_t>(), &c->proc_status->wave_rows[side],
+    HIP_TRY(launch_token_bounds(col.off, rows, c->proc_status, side, c->stream));
+    hipError_t e = launch_process(false, col.off, col.val, rows, out_off, nullptr, c->proc_list[side].as<uint32_t>(), &c->proc_status->wave_rows[side],
                                   process_wave_grid(c), t, c->stream);
     if (e != hipSuccess) return hip_fail(e, "kernel launch (k_process_lane / _wave, measuring)");
     e = launch_token_scan(out_off, rows, c->proc_sums.as<uint32_t>(), c->stream);
@@ -1971,25 +2013,12 @@ static int process_check_size(const char *who, const strsim_ctx *c, int side)
     return STRSIM_OK;
 }
 
-static int process_write(strsim_ctx *c, int side, const ProcessTable &t, const uint32_t *off, const uint8_t *val, uint64_t rows, uint32_t *out_off,
-                         uint8_t *out_val)
+static int process_write(strsim_ctx *c, int side, const ProcessTable &t, const Col &col, uint32_t *out_off, uint8_t *out_val)
 {
-    hipError_t e = launch_process(true, off, val, rows, out_off, out_val, c->proc_list[side].as<uint32_t>(), &c->proc_status->wave_rows[side],
+    hipError_t e = launch_process(true, col.off, col.val, col.rows, out_off, out_val, c->proc_list[side].as<uint32_t>(), &c->proc_status->wave_rows[side],
                                   process_wave_grid(c), t, c->stream);
     if (e != hipSuccess) return hip_fail(e, "kernel launch (k_process_lane / _wave, writing)");
     c->enqueued_ops += 2u;
-    return STRSIM_OK;
-}
-
-static int process_column_check(const char *who, strsim_ctx_t *c, const uint32_t *off, const uint8_t *val, uint64_t rows, const uint32_t *out_off,
-                                const uint8_t *out_val)
-{
-    if (rows > 0xFFFFFFFFull) {
-        set_error("%s: %llu rows in one call; split the column (at most 2^32 - 1 rows per call)", who, (unsigned long long)rows);
-        return STRSIM_ERR_ARG;
-    }
-    if (!off || !out_off || (rows && (!val || !out_val))) { set_error("%s: NULL buffer", who); return STRSIM_ERR_ARG; }
-    if (!c) { set_error("%s: ctx is NULL", who); return STRSIM_ERR_ARG; }
     return STRSIM_OK;
 }
 
@@ -2000,18 +2029,17 @@ static int process_capacity_error(const char *who, uint64_t capacity, uint64_t t
     return STRSIM_ERR_ARG;
 }
 
-static int pairs_processed_check(const char *who, strsim_ctx_t *c, int measure, int processor, const uint32_t *a_off, const uint8_t *a_val,
-                                 uint64_t a_rows, const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, const double *out, uint64_t out_rows,
-                                 uint64_t *n)
+static int pairs_processed_check(const char *who, strsim_ctx_t *c, int measure, int processor, const Col &a, const Col &b, const double *out,
+                                 uint64_t out_rows, uint64_t *n)
 {
     if (processor != STRSIM_PROCESS_DEFAULT) {
         set_error("%s: unknown processor %d (STRSIM_PROCESS_DEFAULT = 1 is the only one)", who, processor);
         return STRSIM_ERR_ARG;
     }
     if (!measure_accepted(measure, STRSIM_ENTRY_PAIRWISE)) { set_error("%s: unknown measure %d", who, measure); return STRSIM_ERR_ARG; }
-    int rc = check_rows(who, a_rows, b_rows, out_rows, n);
+    int rc = check_rows(who, a.rows, b.rows, out_rows, n);
     if (rc) return rc;
-    if (*n && (!a_off || !a_val || !b_off || !b_val || !out)) { set_error("%s: NULL buffer", who); return STRSIM_ERR_ARG; }
+    if (*n && (!a.off || !a.val || !b.off || !b.val || !out)) { set_error("%s: NULL buffer", who); return STRSIM_ERR_ARG; }
     if (!c) { set_error("%s: ctx is NULL", who); return STRSIM_ERR_ARG; }
     return STRSIM_OK;
 }
@@ -2026,7 +2054,8 @@ int strsim_default_process_device(strsim_ctx_t *c, const uint32_t *off, const ui
                                   uint64_t out_capacity)
 {
     const char *const who = "strsim_default_process_device";
-    int rc = process_column_check(who, c, off, val, rows, out_off, out_val);
+    const Col col{off, val, rows};
+    int rc = transform_check(who, c, col, out_off, out_val);
     if (rc) return rc;
     ProcessTable t;
     rc = process_prepare(c, &t);
@@ -2037,95 +2066,75 @@ int strsim_default_process_device(strsim_ctx_t *c, const uint32_t *off, const ui
     }
     HIP_TRY(hipMemsetAsync(c->proc_status, 0, sizeof(TokenStatus), c->stream));
     c->enqueued_ops += 1u;
-    rc = process_measure(c, 0, t, off, val, rows, out_off);
+    rc = process_measure(c, 0, t, col, out_off);
     if (rc == STRSIM_OK) rc = process_wait(c);
     if (rc == STRSIM_OK) rc = process_check_size(who, c, 0);
     if (rc) return rc;
     const uint64_t total = c->proc_status_host->pad[0];
     if (out_capacity < total) return process_capacity_error(who, out_capacity, total);
-    return process_write(c, 0, t, off, val, rows, out_off, out_val);
+    return process_write(c, 0, t, col, out_off, out_val);
 }
 
 int strsim_default_process_host(strsim_ctx_t *c, const uint32_t *off, const uint8_t *val, uint64_t rows, uint32_t *out_off, uint8_t *out_val,
                                 uint64_t out_capacity)
 {
     const char *const who = "strsim_default_process_host";
-    int rc = process_column_check(who, c, off, val, rows, out_off, out_val);
+    const Col col{off, val, rows};
+    int rc = transform_check(who, c, col, out_off, out_val);
     if (rc) return rc;
-    if (rows == 0) { out_off[0] = 0u; return STRSIM_OK; }
-    rc = ctx_set_device(c);
-    if (rc) return rc;
-    // stage[0..1]: the column; stage[2]: the new offsets; stage[3]: the new values
     const uint64_t room = STRSIM_DEFAULT_PROCESS_CAPACITY((uint64_t)off[rows] - off[0]);
-    Staged s;
-    rc = ctx_stage(c, off, val, rows, nullptr, nullptr, 0, 0, &s);
-    if (rc == STRSIM_OK) rc = c->stage[2].reserve((rows + 1) * sizeof(uint32_t));
-    if (rc == STRSIM_OK) rc = c->stage[3].reserve(room + TOKEN_PAD);
-    if (rc) return rc;
-    uint32_t *const d_off = c->stage[2].as<uint32_t>();
-    uint8_t *const d_val = c->stage[3].as<uint8_t>();
-    rc = strsim_default_process_device(c, s.a_off, s.a_val, rows, d_off, d_val, room);
-    if (rc) return rc;
-    const uint64_t total = c->proc_status_host->pad[0];
-    if (out_capacity < total) return process_capacity_error(who, out_capacity, total);
-    HIP_TRY(hipMemcpyAsync(out_off, d_off, (rows + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    if (total) HIP_TRY(hipMemcpyAsync(out_val, d_val, total, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return STRSIM_OK;
+    return transform_host(c, col, room, out_off, out_val, [&](const Col &d, uint32_t *d_off, uint8_t *d_val, uint64_t *total) {
+        const int r = strsim_default_process_device(c, d.off, d.val, rows, d_off, d_val, room);
+        if (r) return r;
+        *total = c->proc_status_host->pad[0]; // (the device call has waited for it)
+        return out_capacity < *total ? process_capacity_error(who, out_capacity, *total) : STRSIM_OK;
+    });
 }
 
 int strsim_pairs_processed_device(strsim_ctx_t *c, int measure, int processor, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
                                   const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t out_rows)
 {
     const char *const who = "strsim_pairs_processed_device";
+    const Col a{a_off, a_val, a_rows}, b{b_off, b_val, b_rows};
     uint64_t n;
-    int rc = pairs_processed_check(who, c, measure, processor, a_off, a_val, a_rows, b_off, b_val, b_rows, out, out_rows, &n);
+    int rc = pairs_processed_check(who, c, measure, processor, a, b, out, out_rows, &n);
     if (rc || n == 0) return rc;
     ProcessTable t;
     rc = process_prepare(c, &t);
     if (rc == STRSIM_OK) rc = process_retire_pending(c, who);
     if (rc) return rc;
-    const uint64_t rows[2] = {a_rows, b_rows};
-    const uint32_t *const in_off[2] = {a_off, b_off};
-    const uint8_t *const in_val[2] = {a_val, b_val};
+    const Col *const side[2] = {&a, &b};
     for (int s = 0; s < 2; ++s) {
-        rc = c->proc_off[s].reserve((rows[s] + 1) * sizeof(uint32_t));
+        rc = c->proc_off[s].reserve((side[s]->rows + 1) * sizeof(uint32_t));
         if (rc) return rc;
     }
     HIP_TRY(hipMemsetAsync(c->proc_status, 0, sizeof(TokenStatus), c->stream));
     c->enqueued_ops += 1u;
     for (int s = 0; s < 2; ++s) {
-        rc = process_measure(c, s, t, in_off[s], in_val[s], rows[s], c->proc_off[s].as<uint32_t>());
+        rc = process_measure(c, s, t, *side[s], c->proc_off[s].as<uint32_t>());
         if (rc) return rc;
     }
     rc = process_wait(c); // the one wait of the transform: both sides' totals
     for (int s = 0; s < 2 && rc == STRSIM_OK; ++s) rc = process_check_size(who, c, s);
     for (int s = 0; s < 2 && rc == STRSIM_OK; ++s) rc = c->proc_val[s].reserve((size_t)c->proc_status_host->pad[s] + TOKEN_PAD);
     for (int s = 0; s < 2 && rc == STRSIM_OK; ++s)
-        rc = process_write(c, s, t, in_off[s], in_val[s], rows[s], c->proc_off[s].as<uint32_t>(), c->proc_val[s].as<uint8_t>());
+        rc = process_write(c, s, t, *side[s], c->proc_off[s].as<uint32_t>(), c->proc_val[s].as<uint8_t>());
     if (rc) return rc;
-    return strsim_pairs_device(c, measure, c->proc_off[0].as<uint32_t>(), c->proc_val[0].as<uint8_t>(), a_rows, c->proc_off[1].as<uint32_t>(),
-                               c->proc_val[1].as<uint8_t>(), b_rows, out, out_rows);
+    return pairs_device(c, measure, dev_col(c->proc_off[0], c->proc_val[0], a_rows), dev_col(c->proc_off[1], c->proc_val[1], b_rows), out, out_rows);
 }
 
 int strsim_pairs_processed_host(strsim_ctx_t *c, int measure, int processor, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
                                 const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t out_rows)
 {
-    uint64_t n;
-    int rc = pairs_processed_check("strsim_pairs_processed_host", c, measure, processor, a_off, a_val, a_rows, b_off, b_val, b_rows, out, out_rows, &n);
-    if (rc || n == 0) return rc;
-    rc = ctx_set_device(c);
-    if (rc) return rc;
-    Staged s;
-    rc = ctx_stage(c, a_off, a_val, a_rows, b_off, b_val, b_rows, n * 8, &s);
-    if (rc) return rc;
-    rc = strsim_pairs_processed_device(c, measure, processor, s.a_off, s.a_val, a_rows, s.b_off, s.b_val, b_rows, (double *)s.out, n);
-    if (rc) return rc;
-    rc = strsim_ctx_synchronize(c); // also runs the long-string pass, which writes into the staged output
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, s.out, n * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return STRSIM_OK;
+    const Col a{a_off, a_val, a_rows}, b{b_off, b_val, b_rows};
+    uint64_t n = 0;
+    const int checked = pairs_processed_check("strsim_pairs_processed_host", c, measure, processor, a, b, out, out_rows, &n);
+    return elementwise_host(
+        c, checked, a, b, n, out, n * 8, nullptr, 0,
+        [&](const Staged &s, uint8_t *d_out, uint8_t *) {
+            return strsim_pairs_processed_device(c, measure, processor, s.a.off, s.a.val, a_rows, s.b.off, s.b.val, b_rows, (double *)d_out, n);
+        },
+        [&] { return strsim_ctx_synchronize(c); });
 }
 
 uint64_t strsim_ctx_last_process_wave_rows(strsim_ctx_t *c)
@@ -2139,15 +2148,14 @@ uint64_t strsim_ctx_last_process_wave_rows(strsim_ctx_t *c)
 
 // ---- nearest match (strsim_nearest.h, strsim_nearest_kernels.h) ----
 
-static int nearest_check(const char *who, strsim_ctx_t *c, int measure, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows,
-                         const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, uint32_t k, const void *out_index,
+static int nearest_check(const char *who, strsim_ctx_t *c, int measure, const Col &q, const Col &cnd, uint32_t k, const void *out_index,
                          const void *out_distance)
 {
     if (measure != STRSIM_LEVENSHTEIN && measure != STRSIM_OSA) {
         set_error("%s: measure %d has no distance (STRSIM_LEVENSHTEIN or STRSIM_OSA)", who, measure);
         return STRSIM_ERR_ARG;
     }
-    return search_check(who, c, q_off, q_val, q_rows, c_off, c_val, c_rows, k, STRSIM_NEAREST_MAX_K, 0.0, out_index, out_distance);
+    return search_check(who, c, q, cnd, k, STRSIM_NEAREST_MAX_K, 0.0, out_index, out_distance);
 }
 
 extern "C" {
@@ -2156,14 +2164,15 @@ int strsim_nearest_device(strsim_ctx_t *c, int measure, const uint32_t *q_off, c
                           const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, uint32_t k, uint32_t max_distance,
                           uint32_t *out_index, uint32_t *out_distance)
 {
-    int rc = nearest_check("strsim_nearest_device", c, measure, q_off, q_val, q_rows, c_off, c_val, c_rows, k, out_index, out_distance);
+    const Col q{q_off, q_val, q_rows}, cnd{c_off, c_val, c_rows};
+    int rc = nearest_check("strsim_nearest_device", c, measure, q, cnd, k, out_index, out_distance);
     if (rc || q_rows == 0) return rc;
     rc = ctx_set_device(c);
     if (rc) return rc;
     const uint32_t nq = (uint32_t)q_rows, nc = (uint32_t)c_rows;
     const size_t ob = (size_t)nq * k;
     OrderedSearch o; // (extra: the merged scores)
-    rc = ordered_search_pack(c, c->nearest_ws, up256(ob * 8), true, q_off, q_val, nq, c_off, c_val, nc, k, &o);
+    rc = ordered_search_pack(c, c->nearest_ws, up256(ob * 8), true, q, cnd, k, &o);
     if (rc) return rc;
     if (o.fast) HIP_TRY(launch_nearest_lane(measure, NearestLaneArgs{o.lane, max_distance}));
     // every pair with a slow side: strsim_distance_device with that side as the literal (its length prefilter and block cutoff
@@ -2175,8 +2184,8 @@ int strsim_nearest_device(strsim_ctx_t *c, int measure, const uint32_t *q_off, c
     rc = search_fallback_merge(
         c, "strsim_nearest_device", o.p, k, -(double)max_distance /* a cut pair comes back as max_distance + 1 */, true, c->nearest_scratch, 12,
         o.fast ? o.lane.splits : 0u, o.lane.pscore, o.lane.pidx, out_index, mscore,
-        [&](const uint32_t *lit_off, const uint8_t *lit_val, const uint32_t *off, const uint8_t *val, uint32_t rows, uint32_t b) {
-            return strsim_distance_device(c, measure, lit_off, lit_val, 1, off, val, rows, max_distance, dist() + (size_t)b * rows, rows);
+        [&](int, const Col &lit, const Col &col, uint32_t b) {
+            return distance_device(c, measure, lit, col, max_distance, dist() + (size_t)b * col.rows, col.rows);
         },
         [&](uint64_t count) -> int { HIP_TRY(launch_nearest_scores(dist(), count, c->nearest_scratch.as<double>(), st)); return STRSIM_OK; });
     if (rc) return rc;
@@ -2188,11 +2197,11 @@ int strsim_nearest_host(strsim_ctx_t *c, int measure, const uint32_t *q_off, con
                         const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, uint32_t k, uint32_t max_distance,
                         uint32_t *out_index, uint32_t *out_distance)
 {
+    const Col q{q_off, q_val, q_rows}, cnd{c_off, c_val, c_rows};
     return search_host(
-        c, nearest_check("strsim_nearest_host", c, measure, q_off, q_val, q_rows, c_off, c_val, c_rows, k, out_index, out_distance), q_off, q_val,
-        q_rows, c_off, c_val, c_rows, k, out_index, out_distance,
+        c, nearest_check("strsim_nearest_host", c, measure, q, cnd, k, out_index, out_distance), q, cnd, k, out_index, out_distance,
         [&](const Staged &s, uint32_t *d_index, uint32_t *d_dist) {
-            return strsim_nearest_device(c, measure, s.a_off, s.a_val, q_rows, s.b_off, s.b_val, c_rows, k, max_distance, d_index, d_dist);
+            return strsim_nearest_device(c, measure, s.a.off, s.a.val, q_rows, s.b.off, s.b.val, c_rows, k, max_distance, d_index, d_dist);
         },
         [&]() -> int { HIP_TRY(hipStreamSynchronize(c->stream)); return STRSIM_OK; });
 }
@@ -2201,8 +2210,7 @@ int strsim_nearest_host(strsim_ctx_t *c, int measure, const uint32_t *q_off, con
 
 // ---- extract: top-k by Indel similarity with a score cutoff (strsim_extract.h, strsim_extract_kernels.h) ----
 
-static int extract_check(const char *who, strsim_ctx_t *c, int scorer, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows,
-                         const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, uint32_t k, double score_cutoff,
+static int extract_check(const char *who, strsim_ctx_t *c, int scorer, const Col &q, const Col &cnd, uint32_t k, double score_cutoff,
                          const void *out_index, const void *out_score)
 {
     if (scorer != STRSIM_INDEL && scorer != STRSIM_TOKEN_SORT_RATIO) {
@@ -2210,7 +2218,7 @@ static int extract_check(const char *who, strsim_ctx_t *c, int scorer, const uin
         return STRSIM_ERR_ARG;
     }
     if (score_cutoff != score_cutoff) { set_error("%s: score_cutoff is NaN", who); return STRSIM_ERR_ARG; }
-    return search_check(who, c, q_off, q_val, q_rows, c_off, c_val, c_rows, k, STRSIM_EXTRACT_MAX_K, score_cutoff, out_index, out_score);
+    return search_check(who, c, q, cnd, k, STRSIM_EXTRACT_MAX_K, score_cutoff, out_index, out_score);
 }
 
 // The rank table of strsim_extract.h, built once per process.
@@ -2225,8 +2233,7 @@ static const ExtractTable &extract_table()
 }
 
 // The search over two columns of Indel scores (for STRSIM_TOKEN_SORT_RATIO: the normalised ones).
-static int extract_search(strsim_ctx *c, const uint32_t *q_off, const uint8_t *q_val, uint32_t nq, const uint32_t *c_off, const uint8_t *c_val,
-                          uint32_t nc, uint32_t k, double score_cutoff, uint32_t *out_index, double *out_score)
+static int extract_search(strsim_ctx *c, const Col &q, const Col &cnd, uint32_t k, double score_cutoff, uint32_t *out_index, double *out_score)
 {
     const ExtractTable &tab = extract_table();
     hipStream_t st = c->stream;
@@ -2238,7 +2245,7 @@ static int extract_search(strsim_ctx *c, const uint32_t *q_off, const uint8_t *q
     }
     const uint32_t rlimit = extract_rank_limit(tab, score_cutoff); // 0: the cutoff is above 1.0 and nothing is reported
     OrderedSearch o;
-    int rc = ordered_search_pack(c, c->extract_ws, 0, rlimit != 0u, q_off, q_val, nq, c_off, c_val, nc, k, &o);
+    int rc = ordered_search_pack(c, c->extract_ws, 0, rlimit != 0u, q, cnd, k, &o);
     if (rc) return rc;
     if (o.fast) HIP_TRY(launch_extract_lane(ExtractLaneArgs{o.lane, c->extract_tab.as<ExtractTable>(), rlimit}));
     // every pair with a slow side: strsim_pairs_device(STRSIM_INDEL) with that side as the literal, batch by batch, folded into
@@ -2246,8 +2253,8 @@ static int extract_search(strsim_ctx *c, const uint32_t *q_off, const uint8_t *q
     return search_fallback_merge(
         c, "strsim_extract_device", o.p, k, score_cutoff, rlimit != 0u, c->extract_scratch, 8, o.fast ? o.lane.splits : 0u, o.lane.pscore,
         o.lane.pidx, out_index, out_score,
-        [&](const uint32_t *lit_off, const uint8_t *lit_val, const uint32_t *off, const uint8_t *val, uint32_t rows, uint32_t b) {
-            return strsim_pairs_device(c, STRSIM_INDEL, lit_off, lit_val, 1, off, val, rows, c->extract_scratch.as<double>() + (size_t)b * rows, rows);
+        [&](int, const Col &lit, const Col &col, uint32_t b) {
+            return pairs_device(c, STRSIM_INDEL, lit, col, c->extract_scratch.as<double>() + (size_t)b * col.rows, col.rows);
         },
         [&](uint64_t) { return strsim_ctx_synchronize(c); });
 }
@@ -2258,46 +2265,25 @@ int strsim_extract_device(strsim_ctx_t *c, int scorer, const uint32_t *q_off, co
                           const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, uint32_t k, double score_cutoff,
                           uint32_t *out_index, double *out_score)
 {
-    int rc = extract_check("strsim_extract_device", c, scorer, q_off, q_val, q_rows, c_off, c_val, c_rows, k, score_cutoff, out_index, out_score);
+    Col q{q_off, q_val, q_rows}, cnd{c_off, c_val, c_rows};
+    int rc = extract_check("strsim_extract_device", c, scorer, q, cnd, k, score_cutoff, out_index, out_score);
     if (rc || q_rows == 0) return rc;
     rc = ctx_set_device(c);
     if (rc) return rc;
-    const uint32_t nq = (uint32_t)q_rows, nc = (uint32_t)c_rows;
-    if (scorer == STRSIM_TOKEN_SORT_RATIO) {
-        // both sides through the token_sort transform into the context's own columns, on the device; one wait (the bounds)
-        rc = token_prepare(c);
-        if (rc) return rc;
-        rc = token_bounds(c, q_off, q_rows, nc ? c_off : nullptr, c_rows);
-        if (rc) return rc;
-        const TokenStatus ts = *c->tok_status_host;
-        const uint32_t *const in_off[2] = {q_off, c_off};
-        const uint8_t *const in_val[2] = {q_val, c_val};
-        const uint64_t rows[2] = {q_rows, c_rows};
-        for (int s = 0; s < 2 && rows[s]; ++s) {
-            rc = c->extract_off[s].reserve((rows[s] + 1) * sizeof(uint32_t));
-            if (rc == STRSIM_OK) rc = c->extract_val[s].reserve((uint64_t)ts.end[s] - ts.begin[s] + TOKEN_PAD);
-            if (rc == STRSIM_OK)
-                rc = token_sort_column(c, s, in_off[s], in_val[s], rows[s], ts.max_len[s], c->extract_off[s].as<uint32_t>(),
-                                       c->extract_val[s].as<uint8_t>());
-            if (rc) return rc;
-        }
-        rc = token_copy_counts(c);
-        if (rc) return rc;
-        q_off = c->extract_off[0].as<uint32_t>(); q_val = c->extract_val[0].as<uint8_t>();
-        if (nc) { c_off = c->extract_off[1].as<uint32_t>(); c_val = c->extract_val[1].as<uint8_t>(); }
-    }
-    return extract_search(c, q_off, q_val, nq, c_off, c_val, nc, k, score_cutoff, out_index, out_score);
+    // token_sort_ratio: both sides through the token_sort transform into the context's own columns, on the device
+    if (scorer == STRSIM_TOKEN_SORT_RATIO && (rc = token_sort_search_columns(c, &q, &cnd)) != STRSIM_OK) return rc;
+    return extract_search(c, q, cnd, k, score_cutoff, out_index, out_score);
 }
 
 int strsim_extract_host(strsim_ctx_t *c, int scorer, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows,
                         const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, uint32_t k, double score_cutoff,
                         uint32_t *out_index, double *out_score)
 {
+    const Col q{q_off, q_val, q_rows}, cnd{c_off, c_val, c_rows};
     return search_host(
-        c, extract_check("strsim_extract_host", c, scorer, q_off, q_val, q_rows, c_off, c_val, c_rows, k, score_cutoff, out_index, out_score), q_off,
-        q_val, q_rows, c_off, c_val, c_rows, k, out_score, out_index,
+        c, extract_check("strsim_extract_host", c, scorer, q, cnd, k, score_cutoff, out_index, out_score), q, cnd, k, out_score, out_index,
         [&](const Staged &s, double *d_score, uint32_t *d_index) {
-            return strsim_extract_device(c, scorer, s.a_off, s.a_val, q_rows, s.b_off, s.b_val, c_rows, k, score_cutoff, d_index, d_score);
+            return strsim_extract_device(c, scorer, s.a.off, s.a.val, q_rows, s.b.off, s.b.val, c_rows, k, score_cutoff, d_index, d_score);
         },
         [&] { return strsim_ctx_synchronize(c); });
 }
@@ -2308,8 +2294,8 @@ int strsim_extract_host(strsim_ctx_t *c, int scorer, const uint32_t *q_off, cons
 
 static bool cdist_measure(int m) { return (m >= STRSIM_LEVENSHTEIN && m <= STRSIM_SORENSEN_DICE) || m == STRSIM_INDEL || m == STRSIM_TOKEN_SORT_RATIO; }
 
-static int cdist_check(const char *who, strsim_ctx_t *c, int measure, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows,
-                       const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, double score_cutoff, const double *out, uint64_t out_ld)
+static int cdist_check(const char *who, strsim_ctx_t *c, int measure, const Col &q, const Col &cnd, double score_cutoff, const double *out,
+                       uint64_t out_ld)
 {
     if (!cdist_measure(measure)) {
         set_error("%s: measure %d is not a measure of cdist (the reference measures 0 .. 4, STRSIM_INDEL = 8 or STRSIM_TOKEN_SORT_RATIO = 14)", who,
@@ -2317,15 +2303,16 @@ static int cdist_check(const char *who, strsim_ctx_t *c, int measure, const uint
         return STRSIM_ERR_ARG;
     }
     if (score_cutoff != score_cutoff) { set_error("%s: score_cutoff is NaN", who); return STRSIM_ERR_ARG; }
-    if (q_rows > 0xFFFFFFFFull) { set_error("%s: %llu queries (at most 2^32 - 1)", who, (unsigned long long)q_rows); return STRSIM_ERR_ARG; }
-    if (c_rows > 0xFFFFFFFEull) { set_error("%s: %llu candidates (at most 2^32 - 2)", who, (unsigned long long)c_rows); return STRSIM_ERR_ARG; }
-    if (out_ld < c_rows) {
-        set_error("%s: out_ld=%llu is less than the %llu candidates of a row", who, (unsigned long long)out_ld, (unsigned long long)c_rows);
+    int rc = search_rows_check(who, q, cnd);
+    if (rc) return rc;
+    if (out_ld < cnd.rows) {
+        set_error("%s: out_ld=%llu is less than the %llu candidates of a row", who, (unsigned long long)out_ld, (unsigned long long)cnd.rows);
         return STRSIM_ERR_ARG;
     }
-    if (q_rows && (!q_off || !q_val)) { set_error("%s: NULL query buffer", who); return STRSIM_ERR_ARG; }
-    if (c_rows && (!c_off || !c_val)) { set_error("%s: NULL candidate buffer", who); return STRSIM_ERR_ARG; }
-    if (q_rows && c_rows && !out) { set_error("%s: NULL output buffer", who); return STRSIM_ERR_ARG; }
+    if (q.rows && (!q.off || !q.val)) { set_error("%s: NULL query buffer", who); return STRSIM_ERR_ARG; }
+    rc = candidate_buffers_check(who, cnd);
+    if (rc) return rc;
+    if (q.rows && cnd.rows && !out) { set_error("%s: NULL output buffer", who); return STRSIM_ERR_ARG; }
     if (!c) { set_error("%s: ctx is NULL", who); return STRSIM_ERR_ARG; }
     return STRSIM_OK;
 }
@@ -2342,11 +2329,10 @@ static const double *cdist_indel_table()
 }
 
 // The matrix of one pairwise measure (0 .. 4 or STRSIM_INDEL) over two columns (for STRSIM_TOKEN_SORT_RATIO: the normalised ones).
-static int cdist_matrix(strsim_ctx *c, int measure, const uint32_t *q_off, const uint8_t *q_val, uint32_t nq, const uint32_t *c_off,
-                        const uint8_t *c_val, uint32_t nc, double cutoff, double *out, uint64_t ld)
+static int cdist_matrix(strsim_ctx *c, int measure, const Col &q, const Col &cnd, double cutoff, double *out, uint64_t ld)
 {
-    const char *const who = "strsim_cdist_device";
     hipStream_t st = c->stream;
+    const uint32_t nq = (uint32_t)q.rows, nc = (uint32_t)cnd.rows;
     const double *tab = c->qtab;
     if (measure == STRSIM_INDEL) {
         if (!c->cdist_tab_ready) {
@@ -2358,7 +2344,7 @@ static int cdist_matrix(strsim_ctx *c, int measure, const uint32_t *q_off, const
         tab = c->cdist_tab.as<double>();
     }
     SearchPack p; // (tail: the two slow counts)
-    int rc = search_pack(c, c->cdist_ws, 256, 8, q_off, q_val, nq, c_off, c_val, nc, &p);
+    int rc = search_pack(c, c->cdist_ws, 256, 8, q, cnd, &p);
     if (rc) return rc;
     c->enqueued_ops += 4u;
     // fast x fast; a pair with a slow side is written as 0.0 here and by the fallback below, which is enqueued behind this grid
@@ -2369,44 +2355,30 @@ static int cdist_matrix(strsim_ctx *c, int measure, const uint32_t *q_off, const
         HIP_TRY(launch_cdist_lane(measure, CdistLaneArgs{p.qw, p.qm, nq, p.cw, p.cm, nc, nsplit, per, tab, cutoff, out, ld, st}));
         c->enqueued_ops += 1u;
     }
-    const uint32_t q_slow = p.q_slow, c_slow = p.c_slow;
-    if (!q_slow && !c_slow) return STRSIM_OK;
+    if (!p.q_slow && !p.c_slow) return STRSIM_OK;
 
-    // every pair with a slow side: strsim_pairs_device with that side as the literal (search_fallback's argument order), batch by
-    // batch; a batch is waited for (the long-string pass of a pairwise call writes from strsim_ctx_synchronize)
-    const uint32_t calls = (uint32_t)fallback_calls(nq, nc);
-    const std::unique_ptr<uint32_t[]> host_list(new (std::nothrow) uint32_t[(size_t)q_slow + c_slow + 1]);
-    if (!host_list) { set_error("%s: out of host memory", who); return STRSIM_ERR_OOM; }
-    if (q_slow) HIP_TRY(hipMemcpyAsync(host_list.get(), p.qs, (size_t)q_slow * 4, hipMemcpyDeviceToHost, st));
-    if (c_slow) HIP_TRY(hipMemcpyAsync(host_list.get() + q_slow, p.cs, (size_t)c_slow * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (uint32_t b0 = 0; b0 < q_slow; b0 += calls) { // a slow query against every candidate: straight into its row
-        const uint32_t nb = q_slow - b0 < calls ? q_slow - b0 : calls;
-        for (uint32_t b = 0; b < nb; ++b) {
-            const uint32_t i = host_list[b0 + b];
-            rc = strsim_pairs_device(c, measure, q_off + i, q_val, 1, c_off, c_val, nc, out + cdist_index(i, ld, 0), nc);
-            if (rc) return rc;
-        }
-        rc = strsim_ctx_synchronize(c);
-        if (rc) return rc;
-        if (cutoff > 0.0) HIP_TRY(launch_cdist_cutoff(out, p.qs + b0, nb, nc, ld, cutoff, st));
-    }
-    if (c_slow) {
+    // every pair with a slow side: strsim_pairs_device with that side as the literal, batch by batch (slow_walk) -- a slow query straight
+    // into its row, a slow candidate into a scratch column and from there into its column; a batch is waited for (the long-string
+    // pass of a pairwise call writes from strsim_ctx_synchronize)
+    const uint64_t calls = fallback_calls(nq, nc);
+    if (p.c_slow) {
         rc = c->cdist_scratch.reserve((size_t)calls * nq * sizeof(double));
         if (rc) return rc;
     }
     double *const col = c->cdist_scratch.as<double>();
-    for (uint32_t b0 = 0; b0 < c_slow; b0 += calls) { // a slow candidate against every query: a scratch column, then its column
-        const uint32_t nb = c_slow - b0 < calls ? c_slow - b0 : calls;
-        for (uint32_t b = 0; b < nb; ++b) {
-            rc = strsim_pairs_device(c, measure, c_off + host_list[q_slow + b0 + b], c_val, 1, q_off, q_val, nq, col + (size_t)b * nq, nq);
-            if (rc) return rc;
-        }
-        rc = strsim_ctx_synchronize(c);
-        if (rc) return rc;
-        HIP_TRY(launch_cdist_put_col(col, p.cs + b0, nb, p.qm, nq, cutoff, out, ld, st));
-    }
-    return STRSIM_OK;
+    return slow_walk(
+        c, "strsim_cdist_device", p, calls,
+        [&](int side, const Col &lit, const Col &other, uint32_t b) { // (a literal's row: where its offsets start in its column)
+            double *const to = side == 0 ? out + cdist_index((uint32_t)(lit.off - q.off), ld, 0) : col + (size_t)b * nq;
+            return pairs_device(c, measure, lit, other, to, other.rows);
+        },
+        [&](int side, uint32_t b0, uint32_t nb) -> int {
+            const int r = strsim_ctx_synchronize(c);
+            if (r) return r;
+            if (side == 1) HIP_TRY(launch_cdist_put_col(col, p.cs + b0, nb, p.qm, nq, cutoff, out, ld, st));
+            else if (cutoff > 0.0) HIP_TRY(launch_cdist_cutoff(out, p.qs + b0, nb, nc, ld, cutoff, st));
+            return STRSIM_OK;
+        });
 }
 
 extern "C" {
@@ -2414,51 +2386,33 @@ extern "C" {
 int strsim_cdist_device(strsim_ctx_t *c, int measure, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows, const uint32_t *c_off,
                         const uint8_t *c_val, uint64_t c_rows, double score_cutoff, double *out, uint64_t out_ld)
 {
-    int rc = cdist_check("strsim_cdist_device", c, measure, q_off, q_val, q_rows, c_off, c_val, c_rows, score_cutoff, out, out_ld);
+    Col q{q_off, q_val, q_rows}, cnd{c_off, c_val, c_rows};
+    int rc = cdist_check("strsim_cdist_device", c, measure, q, cnd, score_cutoff, out, out_ld);
     if (rc || q_rows == 0 || c_rows == 0) return rc;
     rc = ctx_set_device(c);
     if (rc) return rc;
-    const uint32_t nq = (uint32_t)q_rows, nc = (uint32_t)c_rows;
-    if (measure == STRSIM_TOKEN_SORT_RATIO) {
-        // both sides through the token_sort transform into the context's own columns, as strsim_extract_device; one wait (the bounds)
-        rc = token_prepare(c);
+    if (measure == STRSIM_TOKEN_SORT_RATIO) { // both sides through the token_sort transform, as in strsim_extract_device; then their Indel scores
+        rc = token_sort_search_columns(c, &q, &cnd);
         if (rc) return rc;
-        rc = token_bounds(c, q_off, q_rows, c_off, c_rows);
-        if (rc) return rc;
-        const TokenStatus ts = *c->tok_status_host;
-        const uint32_t *const in_off[2] = {q_off, c_off};
-        const uint8_t *const in_val[2] = {q_val, c_val};
-        const uint64_t rows[2] = {q_rows, c_rows};
-        for (int s = 0; s < 2; ++s) {
-            rc = c->extract_off[s].reserve((rows[s] + 1) * sizeof(uint32_t));
-            if (rc == STRSIM_OK) rc = c->extract_val[s].reserve((uint64_t)ts.end[s] - ts.begin[s] + TOKEN_PAD);
-            if (rc == STRSIM_OK)
-                rc = token_sort_column(c, s, in_off[s], in_val[s], rows[s], ts.max_len[s], c->extract_off[s].as<uint32_t>(),
-                                       c->extract_val[s].as<uint8_t>());
-            if (rc) return rc;
-        }
-        rc = token_copy_counts(c);
-        if (rc) return rc;
-        q_off = c->extract_off[0].as<uint32_t>(); q_val = c->extract_val[0].as<uint8_t>();
-        c_off = c->extract_off[1].as<uint32_t>(); c_val = c->extract_val[1].as<uint8_t>();
         measure = STRSIM_INDEL;
     }
-    return cdist_matrix(c, measure, q_off, q_val, nq, c_off, c_val, nc, score_cutoff, out, out_ld);
+    return cdist_matrix(c, measure, q, cnd, score_cutoff, out, out_ld);
 }
 
 int strsim_cdist_host(strsim_ctx_t *c, int measure, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows, const uint32_t *c_off,
                       const uint8_t *c_val, uint64_t c_rows, double score_cutoff, double *out, uint64_t out_ld)
 {
-    int rc = cdist_check("strsim_cdist_host", c, measure, q_off, q_val, q_rows, c_off, c_val, c_rows, score_cutoff, out, out_ld);
+    const Col q{q_off, q_val, q_rows}, cnd{c_off, c_val, c_rows};
+    int rc = cdist_check("strsim_cdist_host", c, measure, q, cnd, score_cutoff, out, out_ld);
     if (rc || q_rows == 0 || c_rows == 0) return rc;
     rc = ctx_set_device(c);
     if (rc) return rc;
     const size_t row_bytes = (size_t)c_rows * sizeof(double);
     Staged s;
-    rc = ctx_stage(c, q_off, q_val, q_rows, c_off, c_val, c_rows, (size_t)q_rows * row_bytes + 16, &s);
+    rc = ctx_stage(c, q, cnd, (size_t)q_rows * row_bytes + 16, &s);
     if (rc) return rc;
     double *const d_out = reinterpret_cast<double *>(s.out);
-    rc = strsim_cdist_device(c, measure, s.a_off, s.a_val, q_rows, s.b_off, s.b_val, c_rows, score_cutoff, d_out, c_rows);
+    rc = strsim_cdist_device(c, measure, s.a.off, s.a.val, q_rows, s.b.off, s.b.val, c_rows, score_cutoff, d_out, c_rows);
     if (rc) return rc;
     HIP_TRY(hipMemcpy2DAsync(out, (size_t)out_ld * sizeof(double), d_out, row_bytes, row_bytes, (size_t)q_rows, hipMemcpyDeviceToHost, c->stream));
     return strsim_ctx_synchronize(c);

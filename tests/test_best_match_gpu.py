@@ -109,6 +109,16 @@ def test_lengths_around_32_non_ascii_and_long_strings(ctx, measure, k):
     _check(ctx, measure, E, E[::-1], k)   # slow x slow
 
 
+@pytest.mark.parametrize("side", ["queries", "candidates", "both"])
+@pytest.mark.parametrize("k", [1, 3])
+def test_more_slow_strings_than_one_batch(ctx, side, k):
+    # 37 slow queries and 21 slow candidates (gen.batch_boundary_frame): the fallback folds three batches of slow queries and
+    # two of slow candidates into its list
+    Q, Cs = gen.batch_boundary_frame(171, side)
+    for measure in MEASURES:
+        _check(ctx, measure, Q, Cs, k)
+
+
 @pytest.mark.parametrize("measure", ["levenshtein", "jaro_winkler"])
 def test_candidate_split_and_merge_20k(ctx, measure):
     # 20 k x 20 k: the candidates are split over many workgroups and merged; 200 of the queries are held to the oracle

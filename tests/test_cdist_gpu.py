@@ -169,6 +169,33 @@ def test_cdist_gpu_slow_strings(ctx, measure, side, cut):
     _assert_same(_run(ctx, measure, Q, Cs, cut), R.cdist(measure, Q, Cs, cut), "%s %s" % (measure, side))
 
 
+@functools.lru_cache(maxsize=None)
+def _batch_boundary_frame(measure, side):
+    Q, Cs = gen.batch_boundary_frame(161, side)
+    M = R.score_matrix(measure, Q, Cs)
+    M.setflags(write=False)
+    return Q, Cs, M
+
+
+@pytest.mark.parametrize("side", ["queries", "candidates", "both"])
+@pytest.mark.parametrize("cut", ["zero", "between"])
+def test_cdist_gpu_more_slow_strings_than_one_batch(ctx, side, cut):
+    # 37 slow queries and 21 slow candidates (gen.batch_boundary_frame): the fallback walks three batches of rows and two of
+    # columns, so the row cutoff and the column scatter run on a batch that is not the first.  "between": a cutoff strictly
+    # between two attained scores, so the pairs at the lower one are zeroed and those at the upper one are kept.
+    for measure in MEASURES:
+        Q, Cs, M = _batch_boundary_frame(measure, side)
+        c = 0.0
+        if cut == "between":
+            v = np.unique(M)
+            lo, hi = float(v[len(v) // 2 - 1]), float(v[len(v) // 2])
+            c = (lo + hi) / 2
+            assert lo < c < hi
+        exp = R.apply_cutoff(M, c)
+        assert cut == "zero" or ((exp == 0.0) & (M != 0.0)).any()
+        _assert_same(_run(ctx, measure, Q, Cs, c), exp, "%s %s cutoff %r" % (measure, side, c))
+
+
 def test_cdist_gpu_every_string_slow(ctx):
     Q, Cs = ["é" * 3, "y" * 33], ["è", "z" * 34, "é" * 3]
     for measure in MEASURES:

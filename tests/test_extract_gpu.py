@@ -214,6 +214,18 @@ def test_extract_gpu_slow_strings(ctx, scorer, side):
             _check(ctx, scorer, Q, Cs, k, cut, M)
 
 
+@pytest.mark.parametrize("scorer", SCORERS)
+@pytest.mark.parametrize("side", ["queries", "candidates", "both"])
+@pytest.mark.parametrize("k", [1, 3])
+def test_extract_gpu_more_slow_strings_than_one_batch(ctx, scorer, side, k):
+    # 37 slow queries and 21 slow candidates (gen.batch_boundary_frame): the fallback folds three batches of slow queries and
+    # two of slow candidates into its list
+    Q, Cs = gen.batch_boundary_frame(191, side)
+    M = R.score_matrix(scorer, Q, Cs)
+    for cut in (0.5, None):
+        _check(ctx, scorer, Q, Cs, k, cut, M)
+
+
 def test_extract_gpu_token_sort_normalises_on_the_device(ctx):
     # permuted tokens, runs of whitespace, multi-byte whitespace code points (U+3000), tokenless strings.  Raw strings longer than
     # 32 bytes whose normalised form is a lane-path string (runs of spaces), raw strings of at most 32 bytes that k_match_pack

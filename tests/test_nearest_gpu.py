@@ -145,6 +145,17 @@ def test_nearest_gpu_slow_strings(ctx, measure, side):
             _check(ctx, measure, Q, Cs, k, md)
 
 
+@pytest.mark.parametrize("side", ["queries", "candidates", "both"])
+@pytest.mark.parametrize("k", [1, 3])
+def test_nearest_gpu_more_slow_strings_than_one_batch(ctx, side, k):
+    # 37 slow queries and 21 slow candidates (gen.batch_boundary_frame): the fallback folds three batches of slow queries and
+    # two of slow candidates into its list
+    Q, Cs = gen.batch_boundary_frame(181, side)
+    for measure in MEASURES:
+        for md in (3, None):
+            _check(ctx, measure, Q, Cs, k, md)
+
+
 @pytest.mark.parametrize("measure", MEASURES)
 def test_nearest_gpu_near_duplicates_dynamic_bound(ctx, measure):
     # frame (b) small: most queries have a candidate within 3 edits, so the bound of a full list cuts the sweep short
