@@ -10,6 +10,8 @@
 #                    OSA / distance kernels whose headers it includes (their figures must not move when strsim_wratio.h changes)
 #         extract -- the kernel of strsim_extract_device and the nearest / best-match kernels it reuses
 #         cdist   -- the kernels of strsim_cdist_device and the best-match kernels beside them (k_match_lane: the same sweep with a list)
+#         join    -- the kernels of strsim_join_device, the pack and length-order kernels it reuses and k_extract_lane beside them (the
+#                    same sweep with a list)
 ROOT=$(cd "$(dirname "$0")/.." && pwd); OUT=${TMPDIR:-/tmp}/strsim_co; mkdir -p $OUT
 case "$1" in
     wratio) FILTER='k_wratio_|k_take_|k_max_f64|k_token_|k_partial_|k_indel_|k_osa_|k_dist_' ;;
@@ -17,6 +19,7 @@ case "$1" in
     partial) FILTER='k_partial_|k_indel_|k_osa_|k_dist_' ;;
     extract) FILTER='k_extract_|k_nearest_hist|k_nearest_scan|k_nearest_scatter|k_match_pack|k_match_clear|k_match_fold|k_match_merge' ;;
     cdist) FILTER='k_cdist_|k_match_pack|k_match_lane' ;;
+    join) FILTER='k_join_|k_extract_|k_nearest_hist|k_nearest_scan|k_nearest_scatter|k_match_pack' ;;
     nearest) FILTER='k_nearest_|k_match_pack|k_match_clear|k_match_fold|k_match_merge' ;;
     *) FILTER=${1:-.} ;;
 esac

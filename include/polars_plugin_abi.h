@@ -177,6 +177,15 @@ POLARS_PLUGIN_DECLARE(cdist_sorensen_dice)
 POLARS_PLUGIN_DECLARE(cdist_ratio)
 POLARS_PLUGIN_DECLARE(cdist_token_sort_ratio)
 
+/* join: every candidate that scores at least score_cutoff (not in the reference; the pairs rapidfuzz's process.cdist leaves non-zero
+ * under a score_cutoff, strsim_join_host): inputs 0 and 1 as extract (queries, candidates of any length), an optional input 2 is
+ * score_cutoff, parsed as extract parses it (a null or absent input: every pair).  Output: N rows of an Arrow
+ * LargeList<Struct{index: UInt32, score: Float64}> ("+L", child "item") named after input 0 -- row i is the list of the hits of query
+ * i in ascending candidate index (its row in input 1), nothing truncated; a query without a hit gives an empty list.  A null query
+ * gives a null list; null candidates are never matched. */
+POLARS_PLUGIN_DECLARE(join_ratio)
+POLARS_PLUGIN_DECLARE(join_token_sort_ratio)
+
 /* default_process (not in the reference; rapidfuzz's utils.default_process made context-free, strsim_default_process_host of
  * strsim_amd.h): ONE input, a string series in any of the three layouts; elementwise.  Output: N rows of Arrow Utf8 ("u": int32
  * offsets -- the transform's 32-bit offsets are the buffer as it is; a result beyond 2^31 - 1 bytes is an error) named after

@@ -529,6 +529,54 @@ STRSIM_API int strsim_cdist_host(strsim_ctx_t *ctx, int measure,
                                  const uint32_t *c_offsets, const uint8_t *c_values, uint64_t c_rows,
                                  double score_cutoff, double *out, uint64_t out_ld);
 
+/*
+ * Threshold join: every pair (query i, candidate j) with score(i, j) >= score_cutoff, as CSR -- the question of record linkage and
+ * deduplication, "which pairs score at least 0.85" (found by dlsym, like the search calls and cdist: the ABI version stays 1.7, and
+ * strsim_measure_supported does not describe these two entry points).  `scorer` is STRSIM_INDEL (8) or STRSIM_TOKEN_SORT_RATIO
+ * (14), extract's two; score(i, j) is bit for bit what strsim_pairs_device(scorer, queries[i], candidates[j]) returns.  With
+ * STRSIM_JOIN_UPPER in `flags` only pairs with j > i are reported: pass one column as both sides for a self-join.
+ *
+ * Output.  out_indptr[0] = 0, out_indptr[i + 1] - out_indptr[i] is the number of hits of query i, and they sit at out_index /
+ * out_score[out_indptr[i] .. out_indptr[i + 1]) in ASCENDING CANDIDATE INDEX: one canonical order, which does not depend on how the
+ * work was split or visited and compares equal run to run.
+ * Capacity.  *out_nnz (HOST memory) and all of out_indptr are always written, and exact.  out_index and out_score (capacity
+ * elements each) are written iff nnz <= capacity; otherwise not one element of either is touched and the call still returns
+ * STRSIM_OK: the caller compares *out_nnz with capacity, allocates and calls again.  capacity == 0 with NULL out_index / out_score
+ * is the count-only form.
+ * score_cutoff = -INFINITY or 0.0 reports every pair (cdist as CSR), a cutoff above 1.0 nothing (no sweep is launched); NaN is
+ * STRSIM_ERR_ARG.
+ *
+ * q_rows <= 2^32 - 1, c_rows <= 2^32 - 2; q_rows == 0 writes out_indptr[0] = 0 and *out_nnz = 0, c_rows == 0 gives all-zero counts.
+ * An unknown scorer, unknown flag bits, a NULL buffer of a non-empty side, a NULL out_nnz or out_indptr, a non-zero capacity with a
+ * NULL output: STRSIM_ERR_ARG.  The arguments are checked first, the context last (a NULL ctx is STRSIM_ERR_ARG too): no argument
+ * error needs a device.  Nulls are not seen here: a caller drops null candidates and maps the indices back.
+ *
+ * Device-resident: the same column layout as strsim_pairs_device.  Strings of at most 32 ASCII bytes are swept one query per lane
+ * in length order, visiting only the candidate lengths whose best possible score can reach the cutoff -- once to count the hits of
+ * every row, then, when they fit, once more to store them; the rows are then sorted by candidate index.  Every pair with a longer or
+ * non-ASCII side goes through strsim_pairs_device(STRSIM_INDEL) (that string as the literal); those scores are kept for the second
+ * pass up to 128 MB, beyond that both passes make the calls.  Scorer 14 first
+ * normalises both columns on the device, as strsim_extract_device does.
+ * Waits for the stream: scorer 14 waits once for the bounds of its columns; every call waits once for a read-back of how many
+ * strings fall outside the one-query-per-lane class and once for nnz.  Without such strings it then returns with the fill and the
+ * sort enqueued: out_index / out_score are complete after strsim_ctx_synchronize(), or in stream order.  With them it runs those
+ * pairs through strsim_pairs_device batch by batch, each of which waits for the stream.  Scratch the context cannot reserve is
+ * STRSIM_ERR_OOM.
+ */
+#define STRSIM_JOIN_UPPER 1u /* report only pairs with j > i (self-join / dedup: pass the same column twice) */
+STRSIM_API int strsim_join_device(strsim_ctx_t *ctx, int scorer,
+                                  const uint32_t *q_offsets, const uint8_t *q_values, uint64_t q_rows,
+                                  const uint32_t *c_offsets, const uint8_t *c_values, uint64_t c_rows,
+                                  double score_cutoff, uint32_t flags, uint64_t capacity,
+                                  uint64_t *out_indptr, uint32_t *out_index, double *out_score, uint64_t *out_nnz);
+
+/* The same with HOST-RESIDENT buffers (the column layout of strsim_pairs_host, every output included); synchronous. */
+STRSIM_API int strsim_join_host(strsim_ctx_t *ctx, int scorer,
+                                const uint32_t *q_offsets, const uint8_t *q_values, uint64_t q_rows,
+                                const uint32_t *c_offsets, const uint8_t *c_values, uint64_t c_rows,
+                                double score_cutoff, uint32_t flags, uint64_t capacity,
+                                uint64_t *out_indptr, uint32_t *out_index, double *out_score, uint64_t *out_nnz);
+
 /* Row partition used to shard a column over `n` GPUs/ranks: the reference's split_offsets
  * (strsim.rs:21-39).  Writes n (offset,len) pairs into out_offset_len[2*n]. */
 STRSIM_API void strsim_split_offsets(uint64_t len, uint64_t n, uint64_t *out_offset_len);

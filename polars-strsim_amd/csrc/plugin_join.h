@@ -1,0 +1,160 @@
+// plugin_join.h -- the join_ratio / join_token_sort_ratio plugin functions: every candidate of a query row that scores at least
+// score_cutoff, as an Arrow LargeList<Struct{index: UInt32, score: Float64}> (one list of hits per query, in ascending candidate
+// index).  Included by polars_plugin.cpp inside its anonymous namespace, after plugin_cdist.h: the struct export of plugin_match.h
+// under the list export of plugin_cdist.h.
+//
+// Inputs as extract's (plugin_extract.h): input 0 the queries (N rows, the output has N rows), input 1 the candidates (any M; null
+// candidates are dropped before the call and the indices map back to rows of input 1, so they are never matched); an optional
+// input 2 is score_cutoff, parsed by extract_cutoff (null or absent: every pair).  A null query gives a null list; a query without
+// a hit gives an empty one.  The call is strsim_join_host: once to count (capacity 0), once more with exactly nnz slots.
+#pragma once
+
+// the nullable LargeList<Struct{index, score}> named `name` (its child: "item")
+void fill_list_struct_schema(ArrowSchema *s, const char *name)
+{
+    memset(s, 0, sizeof *s);
+    std::unique_ptr<ListSchemaPriv> p(new ListSchemaPriv{});
+    p->name = strdup(name ? name : "");
+    p->child = static_cast<ArrowSchema *>(calloc(1, sizeof(ArrowSchema)));
+    if (!p->name || !p->child) { free(p->name); free(p->child); throw std::bad_alloc(); }
+    try {
+        fill_struct_schema(p->child, "item", MATCH_STRUCT);
+    } catch (...) {
+        free(p->name); free(p->child);
+        throw;
+    }
+    p->children[0] = p->child;
+    s->format = "+L";
+    s->name = p->name;
+    s->flags = ARROW_FLAG_NULLABLE;
+    s->n_children = 1;
+    s->children = p->children;
+    s->release = release_list_schema;
+    s->private_data = p.release();
+}
+
+// Every buffer and box of a join result, allocated before any of it is handed over; until then the destructor frees them.
+struct JoinOwned {
+    void *index = nullptr, *score = nullptr, *offsets = nullptr, *valid = nullptr;
+    void *box[6] = {}; // the two primitive arrays, the struct array, the list array, the schema, the array pointers
+    JoinOwned(uint64_t n, bool list_nulls)
+    {
+        offsets = alloc64((n + 1) * sizeof(int64_t));
+        if (list_nulls) valid = alloc64((n + 63) / 64 * 8);
+        for (int b = 0; b < 4; ++b)
+            if (!(box[b] = calloc(1, sizeof(ArrowArray)))) throw std::bad_alloc();
+        if (!(box[4] = calloc(1, sizeof(ArrowSchema))) || !(box[5] = calloc(1, sizeof(ArrowArray *)))) throw std::bad_alloc();
+    }
+    void room(uint64_t nnz)
+    {
+        index = alloc64(nnz * sizeof(uint32_t));
+        score = alloc64(nnz * sizeof(double));
+    }
+    ~JoinOwned()
+    {
+        free(index); free(score); free(offsets); free(valid);
+        for (void *x : box) free(x);
+    }
+};
+
+// Hands the buffers of `own` to `ret` as one LargeList<Struct{index, score}> chunk of n lists (nnz structs in the child) named `name`.
+void export_list_struct(JoinOwned &own, uint64_t n, uint64_t nnz, int64_t list_nulls, const char *name, SeriesExport *ret)
+{
+    ArrowSchema *const schema = static_cast<ArrowSchema *>(own.box[4]);
+    ArrowArray **const arrays = static_cast<ArrowArray **>(own.box[5]);
+    std::unique_ptr<ChildPriv> ci(new ChildPriv{own.index, nullptr, {nullptr, own.index}});
+    std::unique_ptr<ChildPriv> cs(new ChildPriv{own.score, nullptr, {nullptr, own.score}});
+    std::unique_ptr<StructPriv> st(new StructPriv{2, {}, nullptr, {nullptr}});
+    std::unique_ptr<ListPriv> lp(new ListPriv{own.offsets, own.valid, nullptr, {}, {own.valid, own.offsets}});
+    std::unique_ptr<SeriesPriv> sp(new SeriesPriv{schema, arrays, 1});
+    fill_list_struct_schema(schema, name); // (the last step that may throw)
+    // ---- from here on nothing allocates or throws: hand every buffer and box to the result
+    ChildPriv *const cp[2] = {ci.release(), cs.release()};
+    for (int i = 0; i < 2; ++i) {
+        ArrowArray *const ch = static_cast<ArrowArray *>(own.box[i]);
+        ch->length = (int64_t)nnz;
+        ch->n_buffers = 2;
+        ch->buffers = cp[i]->bufs;
+        ch->release = release_child_array;
+        ch->private_data = cp[i];
+        st->child[i] = ch;
+    }
+    ArrowArray *const sa = static_cast<ArrowArray *>(own.box[2]);
+    sa->length = (int64_t)nnz;
+    sa->n_buffers = 1;
+    sa->n_children = 2;
+    sa->buffers = st->bufs;
+    sa->children = st->child;
+    sa->release = release_struct_array;
+    sa->private_data = st.release();
+    lp->child = sa;
+    lp->children[0] = sa;
+    ArrowArray *const arr = static_cast<ArrowArray *>(own.box[3]);
+    arr->length = (int64_t)n;
+    arr->null_count = list_nulls;
+    arr->n_buffers = 2;
+    arr->n_children = 1;
+    arr->buffers = lp->bufs;
+    arr->children = lp->children;
+    arr->release = release_list_array;
+    arr->private_data = lp.release();
+    arrays[0] = arr;
+    own.index = own.score = own.offsets = own.valid = nullptr;
+    for (void *&x : own.box) x = nullptr;
+    ret->field = schema;
+    ret->arrays = arrays;
+    ret->len = 1;
+    ret->release = release_series;
+    ret->private_data = sp.release();
+}
+
+void run_join(int scorer, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret)
+{
+    if (n_inputs != 2 && n_inputs != 3)
+        fail("join: expected 2 input series (queries, candidates) and an optional score_cutoff, got " + std::to_string(n_inputs));
+    const SearchInputs in("join", inputs, n_inputs, false);
+    const double cutoff = extract_cutoff(inputs, n_inputs);
+    const uint64_t n = in.q.rows;
+    const Packed p(in.q, in.c, true);
+    const uint64_t m = p.b_rows();
+    JoinOwned own(n, in.q.any_null);
+    std::vector<uint64_t> indptr(n + 1, 0);
+    uint64_t nnz = 0;
+    if (n) {
+        // staging and workspace of the count call, then of the fill: strings and offsets, indptr, packed strings, length order and
+        // counts, the fallback's columns; the outputs once nnz is known
+        PipeLease lease(2 * p.staged_bytes() + 16 * n + 84 * (n + m) + 4 * 65 * n + 16 * 8 * std::max(n, m));
+        strsim_ctx_t *const ctx = leased_context(lease);
+        if (strsim_join_host(ctx, scorer, p.ao.data(), p.av.data(), n, p.bo.data(), p.bv.data(), m, cutoff, 0u, 0, indptr.data(), nullptr, nullptr,
+                             &nnz) != STRSIM_OK)
+            fail(strsim_last_error_message());
+        own.room(nnz);
+        if (nnz && strsim_join_host(ctx, scorer, p.ao.data(), p.av.data(), n, p.bo.data(), p.bv.data(), m, cutoff, 0u, nnz, indptr.data(),
+                                    static_cast<uint32_t *>(own.index), static_cast<double *>(own.score), &nnz) != STRSIM_OK)
+            fail(strsim_last_error_message());
+    } else {
+        own.room(0);
+    }
+    // the hits of a null query (scored as the empty string) are dropped: the lists are compacted in place
+    uint32_t *const index = static_cast<uint32_t *>(own.index);
+    double *const score = static_cast<double *>(own.score);
+    int64_t *const off = static_cast<int64_t *>(own.offsets);
+    uint8_t *const valid = static_cast<uint8_t *>(own.valid);
+    if (valid) memset(valid, 0, (n + 63) / 64 * 8);
+    int64_t list_nulls = 0;
+    uint64_t at = 0;
+    off[0] = 0;
+    for (uint64_t r = 0; r < n; ++r) {
+        if (row_valid(in.q, r)) {
+            if (valid) valid[r >> 3] |= (uint8_t)(1u << (r & 7));
+            for (uint64_t x = indptr[r]; x < indptr[r + 1]; ++x, ++at) {
+                index[at] = p.pos[index[x]];
+                score[at] = score[x];
+            }
+        } else {
+            ++list_nulls;
+        }
+        off[r + 1] = (int64_t)at;
+    }
+    export_list_struct(own, n, at, list_nulls, in.q.name.c_str(), ret);
+}

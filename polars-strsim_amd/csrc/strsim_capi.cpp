@@ -28,6 +28,7 @@
 #include "strsim_nearest.h"
 #include "strsim_extract.h"
 #include "strsim_cdist.h"
+#include "strsim_join.h"
 
 namespace strsim {
 
@@ -177,6 +178,10 @@ struct strsim_ctx {
     // which no flow inside a cdist call uses
     DevBuf cdist_ws, cdist_scratch, cdist_tab;
     bool cdist_tab_ready = false;
+    // strsim_join_device: the packed strings, slow lists, length order, counts and cursors, and the fallback's score columns --
+    // buffers of its own, for the same reason; it reads extract_tab (the rank table, never rewritten) and scorer 14 normalises into
+    // extract_off / extract_val, which no flow inside a join call uses
+    DevBuf join_ws, join_scratch;
 
     // ---- two-pass measures (two_pass: pairs_osa, distance_device_impl, partial_device_impl) ----
     DevBuf osa_list;                 // the work list of the wave kernel (one word per row)
@@ -2415,6 +2420,219 @@ int strsim_cdist_host(strsim_ctx_t *c, int measure, const uint32_t *q_off, const
     rc = strsim_cdist_device(c, measure, s.a.off, s.a.val, q_rows, s.b.off, s.b.val, c_rows, score_cutoff, d_out, c_rows);
     if (rc) return rc;
     HIP_TRY(hipMemcpy2DAsync(out, (size_t)out_ld * sizeof(double), d_out, row_bytes, row_bytes, (size_t)q_rows, hipMemcpyDeviceToHost, c->stream));
+    return strsim_ctx_synchronize(c);
+}
+
+} // extern "C"
+
+// ---- threshold join: every pair at or above a score cutoff, as CSR (strsim_join.h, strsim_join_kernels.h) ----
+
+static int join_check(const char *who, strsim_ctx_t *c, int scorer, const Col &q, const Col &cnd, double score_cutoff, uint32_t flags,
+                      uint64_t capacity, const uint64_t *out_indptr, const uint32_t *out_index, const double *out_score, const uint64_t *out_nnz)
+{
+    if (scorer != STRSIM_INDEL && scorer != STRSIM_TOKEN_SORT_RATIO) {
+        set_error("%s: scorer %d is not a scorer of join (STRSIM_INDEL = 8 or STRSIM_TOKEN_SORT_RATIO = 14)", who, scorer);
+        return STRSIM_ERR_ARG;
+    }
+    if (score_cutoff != score_cutoff) { set_error("%s: score_cutoff is NaN", who); return STRSIM_ERR_ARG; }
+    if (flags & ~STRSIM_JOIN_UPPER) { set_error("%s: unknown flags 0x%x (STRSIM_JOIN_UPPER = 1)", who, flags); return STRSIM_ERR_ARG; }
+    int rc = search_rows_check(who, q, cnd);
+    if (rc) return rc;
+    if (q.rows && (!q.off || !q.val)) { set_error("%s: NULL query buffer", who); return STRSIM_ERR_ARG; }
+    rc = candidate_buffers_check(who, cnd);
+    if (rc) return rc;
+    if (!out_nnz) { set_error("%s: out_nnz is NULL", who); return STRSIM_ERR_ARG; }
+    if (!out_indptr) { set_error("%s: out_indptr is NULL", who); return STRSIM_ERR_ARG; }
+    if (capacity && (!out_index || !out_score)) {
+        set_error("%s: capacity=%llu with a NULL output buffer", who, (unsigned long long)capacity);
+        return STRSIM_ERR_ARG;
+    }
+    if (!c) { set_error("%s: ctx is NULL", who); return STRSIM_ERR_ARG; }
+    return STRSIM_OK;
+}
+
+// The join over two columns of Indel scores (for STRSIM_TOKEN_SORT_RATIO: the normalised ones), q.rows >= 1.  Waits for the stream:
+// once for the slow counts (search_pack), once for nnz; the fallback waits for every batch of its pairwise calls (in the count pass,
+// and again in the fill when their scores were too many to keep).
+static int join_pairs(strsim_ctx *c, const Col &q, const Col &cnd, double cutoff, uint32_t flags, uint64_t capacity, uint64_t *out_indptr,
+                      uint32_t *out_index, double *out_score, uint64_t *out_nnz)
+{
+    const ExtractTable &tab = extract_table();
+    hipStream_t st = c->stream;
+    const uint32_t nq = (uint32_t)q.rows, nc = (uint32_t)cnd.rows;
+    const uint32_t upper = flags & STRSIM_JOIN_UPPER;
+    const uint32_t rlimit = extract_rank_limit(tab, cutoff); // 0: the cutoff is above 1.0 and nothing is reported
+    *out_nnz = 0;
+    if (rlimit == 0u || nc == 0u) { // no hit anywhere: no sweep
+        HIP_TRY(hipMemsetAsync(out_indptr, 0, ((size_t)nq + 1) * sizeof(uint64_t), st));
+        c->enqueued_ops += 1u;
+        return STRSIM_OK;
+    }
+    if (!c->extract_tab_ready) {
+        int rc = c->extract_tab.reserve(sizeof(ExtractTable));
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(c->extract_tab.p, &tab, sizeof(ExtractTable), hipMemcpyHostToDevice, st));
+        c->extract_tab_ready = true;
+    }
+    // the tail of the workspace: the small block of ordered_search_pack (slow counts, histograms, bucket starts, cursors; its last
+    // two words: nnz), the query permutation, the candidates in length order, (splits + 1) counts and one cursor per query, the
+    // block sums of the scan and the hit map of the sweeps
+    const uint32_t splits = join_splits(nq, nc, c->num_cu);
+    const size_t o_qp = 1024, o_sw = o_qp + up256((size_t)nq * 4), o_sm = o_sw + up256((size_t)nc * 32), o_si = o_sm + up256((size_t)nc * 4),
+                 o_cnt = o_si + up256((size_t)nc * 4), o_cur = o_cnt + up256(((size_t)splits + 1) * nq * 4), o_sums = o_cur + up256((size_t)nq * 4),
+                 o_map = o_sums + up256((size_t)join_scan_blocks(nq) * 8);
+    const uint32_t map_shift = join_map_shift(nq, nc, splits);
+    const uint64_t map_words = join_map_words(nc, splits, map_shift);
+    const size_t o_end = o_map + up256((size_t)(((uint64_t)nq + 63u) / 64u * map_words * 4u));
+    SearchPack p;
+    int rc = search_pack(c, c->join_ws, o_end, 4 * 88, q, cnd, &p);
+    if (rc) return rc;
+    c->enqueued_ops += 4u;
+    uint32_t *const small = (uint32_t *)p.tail;
+    uint32_t *const qhist = small + 8, *const chist = qhist + 40, *const qstart = chist + 40, *const cstart = qstart + 40,
+                   *const qcur = cstart + 40, *const ccur = qcur + 40;
+    uint32_t *const qperm = (uint32_t *)(p.tail + o_qp), *const sw = (uint32_t *)(p.tail + o_sw), *const sm = (uint32_t *)(p.tail + o_sm),
+                   *const si = (uint32_t *)(p.tail + o_si), *const cnt = (uint32_t *)(p.tail + o_cnt), *const cur = (uint32_t *)(p.tail + o_cur);
+    uint64_t *const sums = (uint64_t *)(p.tail + o_sums);
+    const bool fast = p.q_slow < nq && p.c_slow < nc;
+    const bool slow = p.q_slow || p.c_slow;
+    const uint32_t ns = fast ? splits : 0u; // lists of the sweep; list ns is the fallback's
+    uint32_t *const fb = cnt + (size_t)ns * nq;
+    JoinLaneArgs la{p.qw, p.qm, qperm, qstart, nq, sw, sm, si, cstart, splits, c->extract_tab.as<ExtractTable>(), rlimit, upper, cnt,
+                    (uint32_t *)(p.tail + o_map), map_words, map_shift, out_indptr, out_index, out_score, st};
+    JoinSlowArgs sa{c->join_scratch.as<double>(), nullptr, 0u, p.qm, nq, nc, cutoff, upper, fb, cur, out_indptr, out_index, out_score, st};
+    const uint64_t calls = fallback_calls(nq, nc);
+    // every pair with a slow side: strsim_pairs_device(STRSIM_INDEL) with that side as the literal, batch by batch (slow_walk), a batch
+    // waited for and then counted into the fallback's list.  The columns of scores are kept for the fill when they fit
+    // JOIN_KEEP_SCORES doubles (the slow queries' columns first, then the slow candidates'); otherwise a batch reuses the scratch and
+    // the fill walks, scores and waits again.
+    const uint64_t slow_scores = (uint64_t)p.q_slow * nc + (uint64_t)p.c_slow * nq;
+    const bool keep = slow_scores <= JOIN_KEEP_SCORES;
+    auto kept_column = [&](int side, uint64_t b) { // column b of a side's kept scores
+        return c->join_scratch.as<double>() + (side ? (size_t)p.q_slow * nc : (size_t)0) + (size_t)b * (side ? nq : nc);
+    };
+    uint64_t walked[2] = {0, 0}; // slow strings of each side whose batch is done
+    auto slow_pass = [&](bool fill) -> int {
+        if (fill && keep) { // no pairwise call, no wait: the kept columns, at most 32 768 per launch (grid.y)
+            for (int side = 0; side < 2; ++side) {
+                const uint32_t n = side ? p.c_slow : p.q_slow;
+                for (uint32_t b0 = 0; b0 < n; b0 += 32768u) {
+                    sa.scores = kept_column(side, b0);
+                    sa.list = (side ? p.cs : p.qs) + b0;
+                    sa.nb = n - b0 < 32768u ? n - b0 : 32768u;
+                    HIP_TRY(launch_join_slow(side, true, sa));
+                    c->enqueued_ops += 1u;
+                }
+            }
+            return STRSIM_OK;
+        }
+        return slow_walk(
+            c, "strsim_join_device", p, calls,
+            [&](int side, const Col &lit, const Col &other, uint32_t b) {
+                double *const to = keep ? kept_column(side, walked[side] + b) : c->join_scratch.as<double>() + (size_t)b * other.rows;
+                return pairs_device(c, STRSIM_INDEL, lit, other, to, other.rows);
+            },
+            [&](int side, uint32_t b0, uint32_t nb) -> int {
+                const int r = strsim_ctx_synchronize(c);
+                if (r) return r;
+                sa.scores = keep ? kept_column(side, b0) : c->join_scratch.as<double>();
+                sa.list = (side ? p.cs : p.qs) + b0;
+                sa.nb = nb;
+                HIP_TRY(launch_join_slow(side, fill, sa));
+                c->enqueued_ops += 1u;
+                walked[side] = (uint64_t)b0 + nb;
+                return STRSIM_OK;
+            });
+    };
+
+    // count
+    HIP_TRY(hipMemsetAsync(fb, 0, (size_t)nq * 4, st));
+    c->enqueued_ops += 1u;
+    if (fast) {
+        NearestOrderArgs oa{p.qm, nq, p.cw, p.cm, nc, qhist, chist, qstart, cstart, qcur, ccur, qperm, sw, sm, si, st};
+        HIP_TRY(launch_nearest_order(oa));
+        HIP_TRY(launch_join_lane(false, la));
+        c->enqueued_ops += 6u;
+    }
+    if (slow) {
+        rc = c->join_scratch.reserve((size_t)(keep ? slow_scores : calls * std::max(nq, nc)) * sizeof(double));
+        if (rc) return rc;
+        rc = slow_pass(false);
+        if (rc) return rc;
+    }
+    // counts -> indptr, and nnz back: the call's second wait
+    HIP_TRY(launch_join_indptr(cnt, nq, ns + 1u, out_indptr, sums, st));
+    uint64_t *const nnz_host = reinterpret_cast<uint64_t *>(c->match_counts_host) + 1; // (search_pack's pinned block: 64 bytes)
+    HIP_TRY(hipMemcpyAsync(nnz_host, out_indptr + nq, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    c->enqueued_ops += 5u;
+    const uint64_t nnz = *nnz_host;
+    *out_nnz = nnz;
+    if (nnz == 0u || nnz > capacity) return STRSIM_OK; // count only: not one element of out_index / out_score is touched
+
+    // fill: the same sweep over the same order, then the fallback again, then every row by candidate index
+    if (fast) {
+        HIP_TRY(launch_join_lane(true, la));
+        c->enqueued_ops += 1u;
+    }
+    if (slow) {
+        HIP_TRY(hipMemsetAsync(cur, 0, (size_t)nq * 4, st));
+        c->enqueued_ops += 1u;
+        rc = slow_pass(true);
+        if (rc) return rc;
+    }
+    HIP_TRY(launch_join_sort_rows(out_indptr, nq, nc, out_index, out_score, st));
+    c->enqueued_ops += nc < 2u ? 0u : nc > JOIN_SORT_WAVE_MAX ? 2u : 1u;
+    return STRSIM_OK;
+}
+
+extern "C" {
+
+int strsim_join_device(strsim_ctx_t *c, int scorer, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows, const uint32_t *c_off,
+                       const uint8_t *c_val, uint64_t c_rows, double score_cutoff, uint32_t flags, uint64_t capacity, uint64_t *out_indptr,
+                       uint32_t *out_index, double *out_score, uint64_t *out_nnz)
+{
+    Col q{q_off, q_val, q_rows}, cnd{c_off, c_val, c_rows};
+    int rc = join_check("strsim_join_device", c, scorer, q, cnd, score_cutoff, flags, capacity, out_indptr, out_index, out_score, out_nnz);
+    if (rc) return rc;
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    if (q_rows == 0) {
+        *out_nnz = 0;
+        HIP_TRY(hipMemsetAsync(out_indptr, 0, sizeof(uint64_t), c->stream));
+        return STRSIM_OK;
+    }
+    // token_sort_ratio: both sides through the token_sort transform, as in strsim_extract_device (its bounds wait); then their Indel scores
+    if (scorer == STRSIM_TOKEN_SORT_RATIO && c_rows && (rc = token_sort_search_columns(c, &q, &cnd)) != STRSIM_OK) return rc;
+    return join_pairs(c, q, cnd, score_cutoff, flags, capacity, out_indptr, out_index, out_score, out_nnz);
+}
+
+int strsim_join_host(strsim_ctx_t *c, int scorer, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows, const uint32_t *c_off,
+                     const uint8_t *c_val, uint64_t c_rows, double score_cutoff, uint32_t flags, uint64_t capacity, uint64_t *out_indptr,
+                     uint32_t *out_index, double *out_score, uint64_t *out_nnz)
+{
+    const Col q{q_off, q_val, q_rows}, cnd{c_off, c_val, c_rows};
+    int rc = join_check("strsim_join_host", c, scorer, q, cnd, score_cutoff, flags, capacity, out_indptr, out_index, out_score, out_nnz);
+    if (rc) return rc;
+    *out_nnz = 0;
+    out_indptr[0] = 0;
+    if (q_rows == 0) return STRSIM_OK;
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    const size_t ptr_bytes = up256(((size_t)q_rows + 1) * sizeof(uint64_t)), idx_bytes = up256((size_t)capacity * sizeof(uint32_t));
+    Staged s;
+    rc = ctx_stage(c, q, cnd, ptr_bytes + idx_bytes + (size_t)capacity * sizeof(double) + 256, &s);
+    if (rc) return rc;
+    uint64_t *const d_ptr = reinterpret_cast<uint64_t *>(s.out);
+    uint32_t *const d_idx = capacity ? reinterpret_cast<uint32_t *>(s.out + ptr_bytes) : nullptr;
+    double *const d_score = capacity ? reinterpret_cast<double *>(s.out + ptr_bytes + idx_bytes) : nullptr;
+    rc = strsim_join_device(c, scorer, s.a.off, s.a.val, q_rows, s.b.off, s.b.val, c_rows, score_cutoff, flags, capacity, d_ptr, d_idx, d_score, out_nnz);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out_indptr, d_ptr, ((size_t)q_rows + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (*out_nnz && *out_nnz <= capacity) {
+        HIP_TRY(hipMemcpyAsync(out_index, d_idx, (size_t)*out_nnz * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(out_score, d_score, (size_t)*out_nnz * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
     return strsim_ctx_synchronize(c);
 }
 

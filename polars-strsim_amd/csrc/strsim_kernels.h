@@ -242,5 +242,36 @@ hipError_t launch_cdist_put_col(const double *scores, const uint32_t *clist, uin
                                 double *out, uint64_t ld, hipStream_t stream);
 hipError_t launch_cdist_cutoff(double *out, const uint32_t *qlist, uint32_t nb, uint32_t nc, uint64_t ld, double cutoff, hipStream_t stream);
 
+// Threshold join (strsim_join_kernels.h; the rules are in strsim_join.h).  Both sides packed by launch_match_pack and put in length
+// order by launch_nearest_order, once per call.  launch_join_lane(false) stores the hits of (split, query i) at cnt[split * nq + i];
+// launch_join_indptr turns the `lists` counts of every query (the splits, then the fallback's list) into their prefix in place and
+// the totals into indptr (nq + 1 words; sums: join_scan_blocks(nq) words); launch_join_lane(true) stores every hit inside the segment
+// the counts gave it.  launch_join_slow: nb columns of pairwise scores of slow queries (side 0: nc scores each) or slow candidates
+// (side 1: nq scores each) counted into / stored in the fallback's list fb (nq words; cur: nq cursors, zeroed before the fill).
+// launch_join_sort_rows: every row by candidate index.
+struct JoinLaneArgs {
+    const uint32_t *qwords, *qmeta, *qperm, *qstart; uint32_t nq;
+    const uint32_t *swords, *smeta, *sidx, *cstart;
+    uint32_t splits;
+    const ExtractTable *tab; uint32_t rlimit, upper;
+    uint32_t *cnt;
+    uint32_t *map; uint64_t map_words; uint32_t map_shift; // the hit map: ceil(nq / 64) x map_words words
+    const uint64_t *indptr;
+    uint32_t *out_index; double *out_score;
+    hipStream_t stream;
+};
+hipError_t launch_join_lane(bool fill, const JoinLaneArgs &a);
+hipError_t launch_join_indptr(uint32_t *cnt, uint32_t nq, uint32_t lists, uint64_t *indptr, uint64_t *sums, hipStream_t stream);
+struct JoinSlowArgs {
+    const double *scores; const uint32_t *list; uint32_t nb;
+    const uint32_t *qmeta; uint32_t nq, nc;
+    double cutoff; uint32_t upper;
+    uint32_t *fb, *cur; const uint64_t *indptr;
+    uint32_t *out_index; double *out_score;
+    hipStream_t stream;
+};
+hipError_t launch_join_slow(int side, bool fill, const JoinSlowArgs &a);
+hipError_t launch_join_sort_rows(const uint64_t *indptr, uint32_t nq, uint32_t nc, uint32_t *index, double *score, hipStream_t stream);
+
 } // namespace strsim
 

@@ -74,6 +74,7 @@
 #include "strsim_nearest.h"
 #include "strsim_extract.h"
 #include "strsim_cdist.h"
+#include "strsim_join.h"
 
 namespace strsim {
 
@@ -92,6 +93,7 @@ struct OutPtrs {
 #include "strsim_nearest_kernels.h"
 #include "strsim_extract_kernels.h"
 #include "strsim_cdist_kernels.h"
+#include "strsim_join_kernels.h"
 
 #include "strsim_kernel_wide.h"
 #include "strsim_kernel_utf8.h"
@@ -583,6 +585,63 @@ hipError_t launch_cdist_cutoff(double *out, const uint32_t *qlist, uint32_t nb, 
 {
     if (nb == 0u || nc == 0u) return hipSuccess;
     hipLaunchKernelGGL(k_cdist_cutoff, dim3(match_grid(nc), nb), dim3(MATCH_BLOCK), 0, stream, out, qlist, nc, ld, cutoff);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// threshold join (strsim_join_kernels.h)
+// ------------------------------------------------------------------------------------------------
+hipError_t launch_join_lane(bool fill, const JoinLaneArgs &a)
+{
+    const dim3 grid(match_grid(a.nq), a.splits);
+    if (fill)
+        hipLaunchKernelGGL(k_join_lane<true>, grid, dim3(MATCH_BLOCK), 0, a.stream, a.qwords, a.qmeta, a.qperm, a.qstart, a.nq, a.swords, a.smeta,
+                           a.sidx, a.cstart, a.tab, a.rlimit, a.upper, a.cnt, a.map, a.map_words, a.map_shift, a.indptr, a.out_index, a.out_score);
+    else
+        hipLaunchKernelGGL(k_join_lane<false>, grid, dim3(MATCH_BLOCK), 0, a.stream, a.qwords, a.qmeta, a.qperm, a.qstart, a.nq, a.swords, a.smeta,
+                           a.sidx, a.cstart, a.tab, a.rlimit, a.upper, a.cnt, a.map, a.map_words, a.map_shift, a.indptr, a.out_index, a.out_score);
+    return hipGetLastError();
+}
+
+hipError_t launch_join_indptr(uint32_t *cnt, uint32_t nq, uint32_t lists, uint64_t *indptr, uint64_t *sums, hipStream_t stream)
+{
+    const unsigned nb = (unsigned)join_scan_blocks(nq);
+    hipLaunchKernelGGL(k_join_totals, dim3(match_grid(nq)), dim3(MATCH_BLOCK), 0, stream, cnt, nq, lists, indptr);
+    hipLaunchKernelGGL(k_join_scan_sums, dim3(nb), dim3(JOIN_SCAN_BLOCK), 0, stream, indptr + 1, (uint64_t)nq, sums);
+    hipLaunchKernelGGL(k_join_scan_top, dim3(1), dim3(JOIN_SCAN_BLOCK), 0, stream, sums, (uint64_t)nb);
+    hipLaunchKernelGGL(k_join_scan_apply, dim3(nb), dim3(JOIN_SCAN_BLOCK), 0, stream, indptr + 1, (uint64_t)nq, sums);
+    return hipGetLastError();
+}
+
+template <int SIDE>
+static void launch_join_slow_side(bool fill, const JoinSlowArgs &a)
+{
+    const uint32_t rows = SIDE == 0 ? a.nc : a.nq;
+    const dim3 grid(match_grid(rows), a.nb);
+    if (fill)
+        hipLaunchKernelGGL((k_join_slow<SIDE, true>), grid, dim3(MATCH_BLOCK), 0, a.stream, a.scores, a.list, a.qmeta, rows, a.cutoff, a.upper, a.fb,
+                           a.cur, a.indptr, a.out_index, a.out_score);
+    else
+        hipLaunchKernelGGL((k_join_slow<SIDE, false>), grid, dim3(MATCH_BLOCK), 0, a.stream, a.scores, a.list, a.qmeta, rows, a.cutoff, a.upper, a.fb,
+                           a.cur, a.indptr, a.out_index, a.out_score);
+}
+
+hipError_t launch_join_slow(int side, bool fill, const JoinSlowArgs &a)
+{
+    if (a.nb == 0u || a.nq == 0u || a.nc == 0u) return hipSuccess;
+    if (side == 0) launch_join_slow_side<0>(fill, a);
+    else launch_join_slow_side<1>(fill, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_join_sort_rows(const uint64_t *indptr, uint32_t nq, uint32_t nc, uint32_t *index, double *score, hipStream_t stream)
+{
+    if (nq == 0u || nc < 2u) return hipSuccess;
+    const uint32_t per = JOIN_SORT_BLOCK / 64u;
+    hipLaunchKernelGGL(k_join_sort_rows<false>, dim3((unsigned)(((uint64_t)nq + per - 1u) / per)), dim3(JOIN_SORT_BLOCK), 0, stream, indptr, nq, index,
+                       score);
+    if (nc > JOIN_SORT_WAVE_MAX) // (a row has at most nc hits)
+        hipLaunchKernelGGL(k_join_sort_rows<true>, dim3(nq < 4096u ? nq : 4096u), dim3(JOIN_SORT_BLOCK), 0, stream, indptr, nq, index, score);
     return hipGetLastError();
 }
 

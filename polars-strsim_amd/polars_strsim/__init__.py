@@ -338,3 +338,28 @@ def cdist(expr: IntoExpr, candidates: IntoExpr, measure: str = "ratio", score_cu
         args=args,
         is_elementwise=False,
     )
+
+
+# (a statement of its own again)
+__all__ += ["join"]
+
+_JOIN_SCORERS = ("ratio", "token_sort_ratio")
+
+
+def join(expr: IntoExpr, candidates: IntoExpr, scorer: str = "ratio", score_cutoff: float | None = None) -> pl.Expr:
+    """Every row of `candidates` (any length) that scores at least score_cutoff against the row of `expr`, by `scorer` ("ratio" or
+    "token_sort_ratio"): a List(Struct{index: UInt32, score: Float64}) per row, in ascending candidate index, nothing truncated (a
+    name with 40 duplicates lists all 40); None reports every candidate.  A null row gives a null list, a row without a hit an empty
+    one; null candidates are never matched.  The score is fuzz.ratio / fuzz.token_sort_ratio / 100, in [0, 1], and so is
+    score_cutoff.  Not in the upstream polars-strsim."""
+    if scorer not in _JOIN_SCORERS:
+        raise ValueError(f"unknown scorer {scorer!r}; expected one of {_JOIN_SCORERS}")
+    args = [parse_into_expr(expr, dtype=pl.Utf8), parse_into_expr(candidates, dtype=pl.Utf8)]
+    if score_cutoff is not None:
+        args.append(pl.lit(score_cutoff, dtype=pl.Float64))
+    return register_plugin_function(
+        plugin_path=_PLUGIN_DIR,
+        function_name="join_" + scorer,
+        args=args,
+        is_elementwise=False,
+    )

@@ -340,10 +340,66 @@ def cdist(measure, queries, candidates, score_cutoff=None, ctx=None, processor=N
     return out
 
 
+JOIN_SCORERS = ("ratio", "token_sort_ratio")
+_JOIN_SCORER_MEASURE = _EXTRACT_SCORER_MEASURE
+
+
+def join(scorer, queries, candidates, score_cutoff, upper=False, ctx=None, processor=None):
+    """Threshold join: every pair (query i, candidate j) whose score by `scorer` ("ratio" -- "indel" is an alias -- or
+    "token_sort_ratio", JOIN_SCORERS) is >= score_cutoff, as CSR: (indptr int64 [N + 1], index int64 [nnz], score f64 [nnz]).  The
+    hits of query i are index / score[indptr[i]:indptr[i + 1]], in ascending candidate position; the score is in [0, 1], bit for bit
+    the pairwise call's.  Nothing is truncated: a query with 40 duplicates has 40 hits.  score_cutoff=None reports every pair.
+    upper=True reports only j > i: with the same list on both sides that is each unordered pair once, never a row with itself
+    (dedupe_pairs).  A null query has an empty row and null candidates are never matched; indices refer to the caller's candidate
+    positions.  processor="default_process" runs default_process() over both sides on the GPU first.
+    rapidfuzz: the pairs process.cdist(queries, candidates, scorer=fuzz.ratio, score_cutoff=100 * score_cutoff) leaves non-zero."""
+    if not isinstance(scorer, str) or scorer not in _JOIN_SCORER_MEASURE:
+        raise ValueError(f"no join by scorer {scorer!r} (one of {JOIN_SCORERS})")
+    if processor is not None:
+        processor_id(processor)
+    ctx = ctx or default_context()
+    Q, vq = _as_column(queries)
+    qo, qv = pack_strings(Q)
+    cand = list(candidates)
+    if upper:
+        # j > i compares positions: the null candidates keep theirs (as empty strings) and their hits are dropped below
+        vc = np.array([c is not None for c in cand], dtype=bool)
+        co, cv = pack_strings([c if c is not None else "" for c in cand])
+        pos = np.arange(len(cand), dtype=np.int64)
+    else:
+        vc = None
+        co, cv, pos = _pack_candidates(cand)
+    if processor is not None:
+        qo, qv = ctx.default_process_host(qo, qv)
+        co, cv = ctx.default_process_host(co, cv)
+    indptr, idx, score = ctx.join(_JOIN_SCORER_MEASURE[scorer], qo, qv, co, cv, score_cutoff, upper)
+    indptr = np.asarray(indptr).astype(np.int64)
+    index = pos[np.asarray(idx).astype(np.int64)] if len(idx) else np.zeros(0, dtype=np.int64)
+    score = np.asarray(score, dtype=np.float64)
+    keep = np.ones(index.size, dtype=bool)
+    rows = np.repeat(np.arange(len(Q), dtype=np.int64), np.diff(indptr))
+    if vq is not None:
+        keep &= vq[rows]
+    if vc is not None and not vc.all():
+        keep &= vc[index]
+    if not keep.all():
+        index, score = index[keep], score[keep]
+        indptr = np.concatenate(([0], np.cumsum(np.bincount(rows[keep], minlength=len(Q))))).astype(np.int64)
+    return indptr, index, score
+
+
+def dedupe_pairs(scorer, column, score_cutoff, ctx=None, processor=None):
+    """The near-duplicates of one column: the self-join join(scorer, column, column, score_cutoff, upper=True) as COO -- (i int64
+    [nnz], j int64 [nnz], score f64 [nnz]) with i < j, every unordered pair at or above score_cutoff once, ordered by i, then j."""
+    column = list(column)
+    indptr, index, score = join(scorer, column, column, score_cutoff, upper=True, ctx=ctx, processor=processor)
+    return np.repeat(np.arange(len(column), dtype=np.int64), np.diff(indptr)), index, score
+
+
 __all__ = ["default_process", "PROCESSORS", "best_match", "nearest", "Codec", "Context", "device_count", "pack_strings", "split_offsets", "similarity", "levenshtein", "jaro",
            "jaro_winkler", "jaccard", "sorensen_dice", "osa", "indel", "measure_supported", "distance", "levenshtein_distance", "osa_distance",
            "indel_distance", "INDEL_MEASURES", "partial_ratio", "partial_ratio_alignment", "PARTIAL_MEASURES",
            "token_sort_ratio", "token_set_ratio", "token_sort", "TOKEN_MEASURES",
            "token_ratio", "partial_token_sort_ratio", "partial_token_set_ratio", "partial_token_ratio", "wratio", "WEIGHTED_MEASURES",
            "DISTANCE_MEASURES", "DISTANCE_UNBOUNDED", "MEASURES", "EXTRA_MEASURES", "MEASURE_ID", "STATUS", "ShapeMismatch", "StrsimError",
-           "extract", "EXTRACT_SCORERS", "cdist", "CDIST_MEASURES"]
+           "extract", "EXTRACT_SCORERS", "cdist", "CDIST_MEASURES", "join", "dedupe_pairs", "JOIN_SCORERS"]

@@ -51,6 +51,7 @@ def processor_id(processor):
 # The measures strsim_distance_device / _host accept (integer edit distances), with their ids; STRSIM_DISTANCE_UNBOUNDED = no cutoff.
 DISTANCE_MEASURES = ("levenshtein", "osa")
 DISTANCE_UNBOUNDED = 0xFFFFFFFF
+JOIN_UPPER = 1  # STRSIM_JOIN_UPPER: only pairs with j > i
 
 STATUS = {0: "OK", 1: "ERR_SHAPE", 2: "ERR_ARG", 3: "ERR_NO_DEVICE", 4: "ERR_HIP", 5: "ERR_OOM", 6: "ERR_DTYPE",
           7: "ERR_INTERNAL", 8: "ERR_EARLIER_CALL"}
@@ -168,6 +169,10 @@ def lib():
         f = getattr(L, name)
         f.restype = i32
         f.argtypes = [vp, i32, vp, vp, u64, vp, vp, u64, C.c_double, vp, u64]
+    for name in ("strsim_join_device", "strsim_join_host"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, i32, vp, vp, u64, vp, vp, u64, C.c_double, C.c_uint32, u64, vp, vp, vp, C.POINTER(u64)]
     L.strsim_measure_supported.restype = C.c_uint32
     L.strsim_measure_supported.argtypes = [i32, i32]
     L.strsim_pairs_device_all.restype = i32

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import DISTANCE_UNBOUNDED, check, lib, measure_id, processor_id
+from ._lib import DISTANCE_UNBOUNDED, JOIN_UPPER, StrsimError, check, lib, measure_id, processor_id
 
 
 def split_offsets(length, n):
@@ -420,6 +420,48 @@ class Context:
         check(lib().strsim_cdist_host(self._h, measure_id(measure), qo.ctypes.data, qv.ctypes.data, nq,
                                       co.ctypes.data, cv.ctypes.data, nc, cut, out.ctypes.data, max(ld, nc)))
         return out
+
+    def join(self, scorer, q_offsets, q_values, c_offsets, c_values, score_cutoff=None, upper=False, capacity=None, count_only=False):
+        """Threshold join (strsim_join_host for numpy columns, strsim_join_device for torch tensors on this context's device): every
+        pair (i, j) with score >= score_cutoff by "indel" or "token_sort_ratio" (None: every pair), as CSR -> (indptr [rows + 1],
+        index [nnz], score f64 [nnz]); the hits of query i are index / score[indptr[i]:indptr[i + 1]], in ascending candidate index,
+        the score bit for bit the pairwise call's.  upper=True reports only j > i (pass one column twice: a self-join).  The call is
+        made with `capacity` slots (None: a guess from the rows) and, when the hits do not fit, once more with exactly nnz.
+        count_only=True makes the count-only call and returns indptr alone.  numpy in: uint64 / uint32 / f64 arrays out; device
+        tensors in: int64 / int32 / f64 tensors out, complete in stream order."""
+        cut = -np.inf if score_cutoff is None else float(score_cutoff)
+        flags = JOIN_UPPER if upper else 0
+        nnz = C.c_uint64(0)
+        device = not isinstance(q_offsets, np.ndarray) and hasattr(q_offsets, "data_ptr")
+        if device:
+            import torch
+            nq, nc = max(q_offsets.numel() - 1, 0), max(c_offsets.numel() - 1, 0)
+            cols = (q_offsets.data_ptr(), q_values.data_ptr(), nq, c_offsets.data_ptr(), c_values.data_ptr(), nc)
+            fn = lib().strsim_join_device
+            indptr = torch.empty(nq + 1, dtype=torch.int64, device=q_offsets.device)
+            new = lambda n, dt: torch.empty(n, dtype={"i": torch.int32, "f": torch.float64}[dt], device=q_offsets.device)
+            ptr = lambda t: t.data_ptr()
+        else:
+            qo, qv, nq = _host_column(q_offsets, q_values)
+            co, cv, nc = _host_column(c_offsets, c_values)
+            nq, nc = max(nq, 0), max(nc, 0)
+            cols = (qo.ctypes.data, qv.ctypes.data, nq, co.ctypes.data, cv.ctypes.data, nc)
+            fn = lib().strsim_join_host
+            indptr = np.empty(nq + 1, dtype=np.uint64)
+            new = lambda n, dt: np.empty(n, dtype={"i": np.uint32, "f": np.float64}[dt])
+            ptr = lambda a: a.ctypes.data
+        if count_only:
+            check(fn(self._h, measure_id(scorer), *cols, cut, flags, 0, ptr(indptr), None, None, C.byref(nnz)))
+            return indptr
+        cap = 4 * nq + 1024 if capacity is None else int(capacity)
+        for _ in range(2):
+            index, score = new(cap, "i"), new(cap, "f")
+            check(fn(self._h, measure_id(scorer), *cols, cut, flags, cap, ptr(indptr), ptr(index) if cap else None,
+                     ptr(score) if cap else None, C.byref(nnz)))
+            if nnz.value <= cap:
+                return indptr, index[:nnz.value], score[:nnz.value]
+            cap = nnz.value  # the hits did not fit: nothing was written; once more with the exact size
+        raise StrsimError(7, f"strsim_join: nnz changed between two calls on the same columns ({nnz.value} > {cap})")
 
 
 class Codec:
