@@ -186,6 +186,15 @@ POLARS_PLUGIN_DECLARE(cdist_token_sort_ratio)
 POLARS_PLUGIN_DECLARE(join_ratio)
 POLARS_PLUGIN_DECLARE(join_token_sort_ratio)
 
+/* match_join: the same by one of the five reference measures (strsim_match_join_host): every candidate whose score by the measure
+ * is at least min_score.  Inputs, the optional input 2 (here min_score; it is parsed as join's score_cutoff and the messages about
+ * it say score_cutoff), the null rules and the LargeList<Struct{index: UInt32, score: Float64}> result are join_ratio's. */
+POLARS_PLUGIN_DECLARE(match_join_levenshtein)
+POLARS_PLUGIN_DECLARE(match_join_jaro)
+POLARS_PLUGIN_DECLARE(match_join_jaro_winkler)
+POLARS_PLUGIN_DECLARE(match_join_jaccard)
+POLARS_PLUGIN_DECLARE(match_join_sorensen_dice)
+
 /* default_process (not in the reference; rapidfuzz's utils.default_process made context-free, strsim_default_process_host of
  * strsim_amd.h): ONE input, a string series in any of the three layouts; elementwise.  Output: N rows of Arrow Utf8 ("u": int32
  * offsets -- the transform's 32-bit offsets are the buffer as it is; a result beyond 2^31 - 1 bytes is an error) named after

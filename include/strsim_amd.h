@@ -577,6 +577,40 @@ STRSIM_API int strsim_join_host(strsim_ctx_t *ctx, int scorer,
                                 double score_cutoff, uint32_t flags, uint64_t capacity,
                                 uint64_t *out_indptr, uint32_t *out_index, double *out_score, uint64_t *out_nnz);
 
+/*
+ * Threshold join by the five reference measures: every pair (query i, candidate j) with score(i, j) >= min_score, as CSR -- "every
+ * pair of names with Jaro-Winkler >= 0.9" without the N x M matrix of cdist and without best_match's limit of 16 candidates (found
+ * by dlsym, like strsim_join_*: the ABI version stays 1.7 and strsim_measure_supported does not describe these two entry points).
+ * `measure` is one of the reference measures, STRSIM_LEVENSHTEIN (0) .. STRSIM_SORENSEN_DICE (4); score(i, j) is bit for bit what
+ * strsim_pairs_device(measure, queries[i], candidates[j]) returns, and a hit is the f64 comparison score >= min_score.
+ *
+ * Everything else is the contract of strsim_join_device, word for word: STRSIM_JOIN_UPPER in `flags` keeps only j > i; the result
+ * is CSR with every row in ascending candidate index; *out_nnz (host memory) and all of out_indptr are always written, and exact;
+ * out_index and out_score (capacity elements each) are written iff nnz <= capacity, otherwise not one element of either is touched
+ * and the call still returns STRSIM_OK; capacity == 0 with NULL out_index / out_score is the count-only form.  min_score = -INFINITY
+ * or 0.0 reports every pair, a value above 1.0 nothing (no sweep is launched, one clear of out_indptr is enqueued); NaN is
+ * STRSIM_ERR_ARG.  The limits on the rows, the argument errors and their order (arguments first, the context last) and the waits
+ * are those of strsim_join_device too.
+ *
+ * Device-resident: strings of at most 32 ASCII bytes are swept one query per lane in length order, visiting only the candidate
+ * lengths at which the measure's own best score for the two lengths reaches min_score (a table of 33 x 33 bits the host builds per
+ * call and passes as a kernel argument) -- once to count, then, when the hits fit, once more to store them; the rows are then
+ * sorted by candidate index.  Every pair with a longer or non-ASCII side goes through strsim_pairs_device(measure) with that string
+ * as the literal, as in strsim_join_device.
+ */
+STRSIM_API int strsim_match_join_device(strsim_ctx_t *ctx, int measure,
+                                        const uint32_t *q_offsets, const uint8_t *q_values, uint64_t q_rows,
+                                        const uint32_t *c_offsets, const uint8_t *c_values, uint64_t c_rows,
+                                        double min_score, uint32_t flags, uint64_t capacity,
+                                        uint64_t *out_indptr, uint32_t *out_index, double *out_score, uint64_t *out_nnz);
+
+/* The same with HOST-RESIDENT buffers (the column layout of strsim_pairs_host, every output included); synchronous. */
+STRSIM_API int strsim_match_join_host(strsim_ctx_t *ctx, int measure,
+                                      const uint32_t *q_offsets, const uint8_t *q_values, uint64_t q_rows,
+                                      const uint32_t *c_offsets, const uint8_t *c_values, uint64_t c_rows,
+                                      double min_score, uint32_t flags, uint64_t capacity,
+                                      uint64_t *out_indptr, uint32_t *out_index, double *out_score, uint64_t *out_nnz);
+
 /* Row partition used to shard a column over `n` GPUs/ranks: the reference's split_offsets
  * (strsim.rs:21-39).  Writes n (offset,len) pairs into out_offset_len[2*n]. */
 STRSIM_API void strsim_split_offsets(uint64_t len, uint64_t n, uint64_t *out_offset_len);

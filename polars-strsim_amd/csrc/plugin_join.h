@@ -7,6 +7,9 @@
 // candidates are dropped before the call and the indices map back to rows of input 1, so they are never matched); an optional
 // input 2 is score_cutoff, parsed by extract_cutoff (null or absent: every pair).  A null query gives a null list; a query without
 // a hit gives an empty one.  The call is strsim_join_host: once to count (capacity 0), once more with exactly nnz slots.
+//
+// The match_join_<measure> functions (the five reference measures; input 2 is min_score) are the same flow over
+// strsim_match_join_host: run_join takes the host entry point to call.
 #pragma once
 
 // the nullable LargeList<Struct{index, score}> named `name` (its child: "item")
@@ -108,7 +111,11 @@ void export_list_struct(JoinOwned &own, uint64_t n, uint64_t nnz, int64_t list_n
     ret->private_data = sp.release();
 }
 
-void run_join(int scorer, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret)
+// strsim_join_host or strsim_match_join_host
+typedef int (*JoinHostFn)(strsim_ctx_t *, int, const uint32_t *, const uint8_t *, uint64_t, const uint32_t *, const uint8_t *, uint64_t, double, uint32_t,
+                          uint64_t, uint64_t *, uint32_t *, double *, uint64_t *);
+
+void run_join(JoinHostFn join_host, int scorer, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret)
 {
     if (n_inputs != 2 && n_inputs != 3)
         fail("join: expected 2 input series (queries, candidates) and an optional score_cutoff, got " + std::to_string(n_inputs));
@@ -125,12 +132,12 @@ void run_join(int scorer, SeriesExport *inputs, size_t n_inputs, SeriesExport *r
         // counts, the fallback's columns; the outputs once nnz is known
         PipeLease lease(2 * p.staged_bytes() + 16 * n + 84 * (n + m) + 4 * 65 * n + 16 * 8 * std::max(n, m));
         strsim_ctx_t *const ctx = leased_context(lease);
-        if (strsim_join_host(ctx, scorer, p.ao.data(), p.av.data(), n, p.bo.data(), p.bv.data(), m, cutoff, 0u, 0, indptr.data(), nullptr, nullptr,
-                             &nnz) != STRSIM_OK)
+        if (join_host(ctx, scorer, p.ao.data(), p.av.data(), n, p.bo.data(), p.bv.data(), m, cutoff, 0u, 0, indptr.data(), nullptr, nullptr, &nnz) !=
+            STRSIM_OK)
             fail(strsim_last_error_message());
         own.room(nnz);
-        if (nnz && strsim_join_host(ctx, scorer, p.ao.data(), p.av.data(), n, p.bo.data(), p.bv.data(), m, cutoff, 0u, nnz, indptr.data(),
-                                    static_cast<uint32_t *>(own.index), static_cast<double *>(own.score), &nnz) != STRSIM_OK)
+        if (nnz && join_host(ctx, scorer, p.ao.data(), p.av.data(), n, p.bo.data(), p.bv.data(), m, cutoff, 0u, nnz, indptr.data(),
+                             static_cast<uint32_t *>(own.index), static_cast<double *>(own.score), &nnz) != STRSIM_OK)
             fail(strsim_last_error_message());
     } else {
         own.room(0);

@@ -267,7 +267,10 @@ void _polars_plugin_strsim_coalesce_stats(uint64_t out[4]) { if (out) combiner()
     POLARS_PLUGIN_EXPORT(cdist_##name, run_cdist(id, inputs, n_inputs, return_value), \
                          field_named_after_input0(input_fields, n_fields, return_value, fill_list_f64_schema))
 #define POLARS_PLUGIN_DEFINE_JOIN(name, id)                                     \
-    POLARS_PLUGIN_EXPORT(join_##name, run_join(id, inputs, n_inputs, return_value), \
+    POLARS_PLUGIN_EXPORT(join_##name, run_join(strsim_join_host, id, inputs, n_inputs, return_value), \
+                         field_named_after_input0(input_fields, n_fields, return_value, fill_list_struct_schema))
+#define POLARS_PLUGIN_DEFINE_MATCH_JOIN(name, id)                                                             \
+    POLARS_PLUGIN_EXPORT(match_join_##name, run_join(strsim_match_join_host, id, inputs, n_inputs, return_value), \
                          field_named_after_input0(input_fields, n_fields, return_value, fill_list_struct_schema))
 #define POLARS_PLUGIN_DEFINE_MATCH(name, id) \
     POLARS_PLUGIN_EXPORT(best_match_##name, run_best_match(id, inputs, n_inputs, return_value), STRUCT_FIELD(MATCH_STRUCT))
@@ -565,6 +568,11 @@ POLARS_PLUGIN_DEFINE_CDIST(ratio, STRSIM_INDEL)
 POLARS_PLUGIN_DEFINE_CDIST(token_sort_ratio, STRSIM_TOKEN_SORT_RATIO)
 POLARS_PLUGIN_DEFINE_JOIN(ratio, STRSIM_INDEL)
 POLARS_PLUGIN_DEFINE_JOIN(token_sort_ratio, STRSIM_TOKEN_SORT_RATIO)
+POLARS_PLUGIN_DEFINE_MATCH_JOIN(levenshtein, STRSIM_LEVENSHTEIN)
+POLARS_PLUGIN_DEFINE_MATCH_JOIN(jaro, STRSIM_JARO)
+POLARS_PLUGIN_DEFINE_MATCH_JOIN(jaro_winkler, STRSIM_JARO_WINKLER)
+POLARS_PLUGIN_DEFINE_MATCH_JOIN(jaccard, STRSIM_JACCARD)
+POLARS_PLUGIN_DEFINE_MATCH_JOIN(sorensen_dice, STRSIM_SORENSEN_DICE)
 POLARS_PLUGIN_EXPORT(default_process, run_default_process(inputs, n_inputs, return_value),
                      field_named_after_input0(input_fields, n_fields, return_value, [](ArrowSchema *s, const char *n) { fill_named_schema(s, "u", n); }))
 POLARS_PLUGIN_DEFINE_MATCH(levenshtein, STRSIM_LEVENSHTEIN)

@@ -29,6 +29,7 @@
 #include "strsim_extract.h"
 #include "strsim_cdist.h"
 #include "strsim_join.h"
+#include "strsim_match_join.h"
 
 namespace strsim {
 
@@ -2427,14 +2428,26 @@ int strsim_cdist_host(strsim_ctx_t *c, int measure, const uint32_t *q_off, const
 
 // ---- threshold join: every pair at or above a score cutoff, as CSR (strsim_join.h, strsim_join_kernels.h) ----
 
-static int join_check(const char *who, strsim_ctx_t *c, int scorer, const Col &q, const Col &cnd, double score_cutoff, uint32_t flags,
-                      uint64_t capacity, const uint64_t *out_indptr, const uint32_t *out_index, const double *out_score, const uint64_t *out_nnz)
+// What the two families of entry points word differently: which ids they take, the sentence that refuses another (one %s, one %d)
+// and the name of the cutoff.
+struct JoinWords {
+    bool (*accepts)(int);
+    const char *refusal, *cutoff;
+};
+static const JoinWords JOIN_WORDS = {[](int id) { return id == STRSIM_INDEL || id == STRSIM_TOKEN_SORT_RATIO; },
+                                     "%s: scorer %d is not a scorer of join (STRSIM_INDEL = 8 or STRSIM_TOKEN_SORT_RATIO = 14)", "score_cutoff"};
+static const JoinWords MATCH_JOIN_WORDS = {[](int id) { return id >= STRSIM_LEVENSHTEIN && id <= STRSIM_SORENSEN_DICE; },
+                                           "%s: measure %d is not a measure of match_join (the reference measures 0 .. 4)", "min_score"};
+
+static int join_check(const JoinWords &words, const char *who, strsim_ctx_t *c, int scorer, const Col &q, const Col &cnd, double score_cutoff,
+                      uint32_t flags, uint64_t capacity, const uint64_t *out_indptr, const uint32_t *out_index, const double *out_score,
+                      const uint64_t *out_nnz)
 {
-    if (scorer != STRSIM_INDEL && scorer != STRSIM_TOKEN_SORT_RATIO) {
-        set_error("%s: scorer %d is not a scorer of join (STRSIM_INDEL = 8 or STRSIM_TOKEN_SORT_RATIO = 14)", who, scorer);
+    if (!words.accepts(scorer)) {
+        set_error(words.refusal, who, scorer);
         return STRSIM_ERR_ARG;
     }
-    if (score_cutoff != score_cutoff) { set_error("%s: score_cutoff is NaN", who); return STRSIM_ERR_ARG; }
+    if (score_cutoff != score_cutoff) { set_error("%s: %s is NaN", who, words.cutoff); return STRSIM_ERR_ARG; }
     if (flags & ~STRSIM_JOIN_UPPER) { set_error("%s: unknown flags 0x%x (STRSIM_JOIN_UPPER = 1)", who, flags); return STRSIM_ERR_ARG; }
     int rc = search_rows_check(who, q, cnd);
     if (rc) return rc;
@@ -2451,28 +2464,30 @@ static int join_check(const char *who, strsim_ctx_t *c, int scorer, const Col &q
     return STRSIM_OK;
 }
 
-// The join over two columns of Indel scores (for STRSIM_TOKEN_SORT_RATIO: the normalised ones), q.rows >= 1.  Waits for the stream:
-// once for the slow counts (search_pack), once for nnz; the fallback waits for every batch of its pairwise calls (in the count pass,
-// and again in the fill when their scores were too many to keep).
-static int join_pairs(strsim_ctx *c, const Col &q, const Col &cnd, double cutoff, uint32_t flags, uint64_t capacity, uint64_t *out_indptr,
-                      uint32_t *out_index, double *out_score, uint64_t *out_nnz)
+// The join over two columns, q.rows >= 1, by the scores of one pairwise measure.  What a family of entry points brings: `who` (for
+// the fallback's errors), `nothing` (the cutoff is above every score: no sweep), ready() (the sweep's table on the device; called
+// only when there is a sweep to come), sweep(fill, args) (the launcher of its lane sweep) and slow_measure (of the fallback's
+// strsim_pairs_device calls).  strsim_join_*: Indel ranks (for STRSIM_TOKEN_SORT_RATIO over the normalised columns);
+// strsim_match_join_*: the f64 score of a reference measure.  Waits for the stream: once for the slow counts (search_pack), once
+// for nnz; the fallback waits for every batch of its pairwise calls (in the count pass, and again in the fill when their scores
+// were too many to keep).
+template <class Ready, class Sweep>
+static int join_pairs(strsim_ctx *c, const char *who, const Col &q, const Col &cnd, double cutoff, uint32_t flags, uint64_t capacity,
+                      uint64_t *out_indptr, uint32_t *out_index, double *out_score, uint64_t *out_nnz, bool nothing, Ready ready, Sweep sweep,
+                      int slow_measure)
 {
-    const ExtractTable &tab = extract_table();
     hipStream_t st = c->stream;
     const uint32_t nq = (uint32_t)q.rows, nc = (uint32_t)cnd.rows;
     const uint32_t upper = flags & STRSIM_JOIN_UPPER;
-    const uint32_t rlimit = extract_rank_limit(tab, cutoff); // 0: the cutoff is above 1.0 and nothing is reported
     *out_nnz = 0;
-    if (rlimit == 0u || nc == 0u) { // no hit anywhere: no sweep
+    if (nothing || nc == 0u) { // no hit anywhere: no sweep
         HIP_TRY(hipMemsetAsync(out_indptr, 0, ((size_t)nq + 1) * sizeof(uint64_t), st));
         c->enqueued_ops += 1u;
         return STRSIM_OK;
     }
-    if (!c->extract_tab_ready) {
-        int rc = c->extract_tab.reserve(sizeof(ExtractTable));
+    {
+        const int rc = ready();
         if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(c->extract_tab.p, &tab, sizeof(ExtractTable), hipMemcpyHostToDevice, st));
-        c->extract_tab_ready = true;
     }
     // the tail of the workspace: the small block of ordered_search_pack (slow counts, histograms, bucket starts, cursors; its last
     // two words: nnz), the query permutation, the candidates in length order, (splits + 1) counts and one cursor per query, the
@@ -2498,11 +2513,11 @@ static int join_pairs(strsim_ctx *c, const Col &q, const Col &cnd, double cutoff
     const bool slow = p.q_slow || p.c_slow;
     const uint32_t ns = fast ? splits : 0u; // lists of the sweep; list ns is the fallback's
     uint32_t *const fb = cnt + (size_t)ns * nq;
-    JoinLaneArgs la{p.qw, p.qm, qperm, qstart, nq, sw, sm, si, cstart, splits, c->extract_tab.as<ExtractTable>(), rlimit, upper, cnt,
+    JoinLaneArgs la{p.qw, p.qm, qperm, qstart, nq, sw, sm, si, cstart, splits, nullptr, 0u, upper, cnt, // (tab, rlimit: sweep's to set)
                     (uint32_t *)(p.tail + o_map), map_words, map_shift, out_indptr, out_index, out_score, st};
     JoinSlowArgs sa{c->join_scratch.as<double>(), nullptr, 0u, p.qm, nq, nc, cutoff, upper, fb, cur, out_indptr, out_index, out_score, st};
     const uint64_t calls = fallback_calls(nq, nc);
-    // every pair with a slow side: strsim_pairs_device(STRSIM_INDEL) with that side as the literal, batch by batch (slow_walk), a batch
+    // every pair with a slow side: strsim_pairs_device(slow_measure) with that side as the literal, batch by batch (slow_walk), a batch
     // waited for and then counted into the fallback's list.  The columns of scores are kept for the fill when they fit
     // JOIN_KEEP_SCORES doubles (the slow queries' columns first, then the slow candidates'); otherwise a batch reuses the scratch and
     // the fill walks, scores and waits again.
@@ -2527,10 +2542,10 @@ static int join_pairs(strsim_ctx *c, const Col &q, const Col &cnd, double cutoff
             return STRSIM_OK;
         }
         return slow_walk(
-            c, "strsim_join_device", p, calls,
+            c, who, p, calls,
             [&](int side, const Col &lit, const Col &other, uint32_t b) {
                 double *const to = keep ? kept_column(side, walked[side] + b) : c->join_scratch.as<double>() + (size_t)b * other.rows;
-                return pairs_device(c, STRSIM_INDEL, lit, other, to, other.rows);
+                return pairs_device(c, slow_measure, lit, other, to, other.rows);
             },
             [&](int side, uint32_t b0, uint32_t nb) -> int {
                 const int r = strsim_ctx_synchronize(c);
@@ -2551,7 +2566,7 @@ static int join_pairs(strsim_ctx *c, const Col &q, const Col &cnd, double cutoff
     if (fast) {
         NearestOrderArgs oa{p.qm, nq, p.cw, p.cm, nc, qhist, chist, qstart, cstart, qcur, ccur, qperm, sw, sm, si, st};
         HIP_TRY(launch_nearest_order(oa));
-        HIP_TRY(launch_join_lane(false, la));
+        HIP_TRY(sweep(false, la));
         c->enqueued_ops += 6u;
     }
     if (slow) {
@@ -2572,7 +2587,7 @@ static int join_pairs(strsim_ctx *c, const Col &q, const Col &cnd, double cutoff
 
     // fill: the same sweep over the same order, then the fallback again, then every row by candidate index
     if (fast) {
-        HIP_TRY(launch_join_lane(true, la));
+        HIP_TRY(sweep(true, la));
         c->enqueued_ops += 1u;
     }
     if (slow) {
@@ -2586,6 +2601,37 @@ static int join_pairs(strsim_ctx *c, const Col &q, const Col &cnd, double cutoff
     return STRSIM_OK;
 }
 
+// The host-resident form of a join entry point: the columns staged, `device_call` on them, the results copied back.
+typedef int (*JoinDeviceFn)(strsim_ctx_t *, int, const uint32_t *, const uint8_t *, uint64_t, const uint32_t *, const uint8_t *, uint64_t, double, uint32_t,
+                            uint64_t, uint64_t *, uint32_t *, double *, uint64_t *);
+static int join_host(JoinDeviceFn device_call, const JoinWords &words, const char *who, strsim_ctx_t *c, int scorer, const Col &q, const Col &cnd,
+                     double score_cutoff, uint32_t flags, uint64_t capacity, uint64_t *out_indptr, uint32_t *out_index, double *out_score,
+                     uint64_t *out_nnz)
+{
+    int rc = join_check(words, who, c, scorer, q, cnd, score_cutoff, flags, capacity, out_indptr, out_index, out_score, out_nnz);
+    if (rc) return rc;
+    *out_nnz = 0;
+    out_indptr[0] = 0;
+    if (q.rows == 0) return STRSIM_OK;
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    const size_t ptr_bytes = up256(((size_t)q.rows + 1) * sizeof(uint64_t)), idx_bytes = up256((size_t)capacity * sizeof(uint32_t));
+    Staged s;
+    rc = ctx_stage(c, q, cnd, ptr_bytes + idx_bytes + (size_t)capacity * sizeof(double) + 256, &s);
+    if (rc) return rc;
+    uint64_t *const d_ptr = reinterpret_cast<uint64_t *>(s.out);
+    uint32_t *const d_idx = capacity ? reinterpret_cast<uint32_t *>(s.out + ptr_bytes) : nullptr;
+    double *const d_score = capacity ? reinterpret_cast<double *>(s.out + ptr_bytes + idx_bytes) : nullptr;
+    rc = device_call(c, scorer, s.a.off, s.a.val, q.rows, s.b.off, s.b.val, cnd.rows, score_cutoff, flags, capacity, d_ptr, d_idx, d_score, out_nnz);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out_indptr, d_ptr, ((size_t)q.rows + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (*out_nnz && *out_nnz <= capacity) {
+        HIP_TRY(hipMemcpyAsync(out_index, d_idx, (size_t)*out_nnz * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(out_score, d_score, (size_t)*out_nnz * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
+    return strsim_ctx_synchronize(c);
+}
+
 extern "C" {
 
 int strsim_join_device(strsim_ctx_t *c, int scorer, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows, const uint32_t *c_off,
@@ -2593,7 +2639,7 @@ int strsim_join_device(strsim_ctx_t *c, int scorer, const uint32_t *q_off, const
                        uint32_t *out_index, double *out_score, uint64_t *out_nnz)
 {
     Col q{q_off, q_val, q_rows}, cnd{c_off, c_val, c_rows};
-    int rc = join_check("strsim_join_device", c, scorer, q, cnd, score_cutoff, flags, capacity, out_indptr, out_index, out_score, out_nnz);
+    int rc = join_check(JOIN_WORDS, "strsim_join_device", c, scorer, q, cnd, score_cutoff, flags, capacity, out_indptr, out_index, out_score, out_nnz);
     if (rc) return rc;
     rc = ctx_set_device(c);
     if (rc) return rc;
@@ -2604,36 +2650,65 @@ int strsim_join_device(strsim_ctx_t *c, int scorer, const uint32_t *q_off, const
     }
     // token_sort_ratio: both sides through the token_sort transform, as in strsim_extract_device (its bounds wait); then their Indel scores
     if (scorer == STRSIM_TOKEN_SORT_RATIO && c_rows && (rc = token_sort_search_columns(c, &q, &cnd)) != STRSIM_OK) return rc;
-    return join_pairs(c, q, cnd, score_cutoff, flags, capacity, out_indptr, out_index, out_score, out_nnz);
+    const ExtractTable &tab = extract_table();
+    const uint32_t rlimit = extract_rank_limit(tab, score_cutoff); // 0: the cutoff is above 1.0 and nothing is reported
+    return join_pairs(
+        c, "strsim_join_device", q, cnd, score_cutoff, flags, capacity, out_indptr, out_index, out_score, out_nnz, rlimit == 0u,
+        [&]() -> int {
+            if (c->extract_tab_ready) return STRSIM_OK;
+            const int r = c->extract_tab.reserve(sizeof(ExtractTable));
+            if (r) return r;
+            HIP_TRY(hipMemcpyAsync(c->extract_tab.p, &tab, sizeof(ExtractTable), hipMemcpyHostToDevice, c->stream));
+            c->extract_tab_ready = true;
+            return STRSIM_OK;
+        },
+        [&](bool fill, JoinLaneArgs &a) {
+            a.tab = c->extract_tab.as<ExtractTable>();
+            a.rlimit = rlimit;
+            return launch_join_lane(fill, a);
+        },
+        STRSIM_INDEL);
 }
 
 int strsim_join_host(strsim_ctx_t *c, int scorer, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows, const uint32_t *c_off,
                      const uint8_t *c_val, uint64_t c_rows, double score_cutoff, uint32_t flags, uint64_t capacity, uint64_t *out_indptr,
                      uint32_t *out_index, double *out_score, uint64_t *out_nnz)
 {
+    return join_host(strsim_join_device, JOIN_WORDS, "strsim_join_host", c, scorer, Col{q_off, q_val, q_rows}, Col{c_off, c_val, c_rows}, score_cutoff,
+                     flags, capacity, out_indptr, out_index, out_score, out_nnz);
+}
+
+// ---- threshold join by the five reference measures (strsim_match_join.h, strsim_match_join_kernels.h): join_pairs with another sweep ----
+
+int strsim_match_join_device(strsim_ctx_t *c, int measure, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows, const uint32_t *c_off,
+                             const uint8_t *c_val, uint64_t c_rows, double min_score, uint32_t flags, uint64_t capacity, uint64_t *out_indptr,
+                             uint32_t *out_index, double *out_score, uint64_t *out_nnz)
+{
     const Col q{q_off, q_val, q_rows}, cnd{c_off, c_val, c_rows};
-    int rc = join_check("strsim_join_host", c, scorer, q, cnd, score_cutoff, flags, capacity, out_indptr, out_index, out_score, out_nnz);
+    int rc = join_check(MATCH_JOIN_WORDS, "strsim_match_join_device", c, measure, q, cnd, min_score, flags, capacity, out_indptr, out_index, out_score,
+                        out_nnz);
     if (rc) return rc;
-    *out_nnz = 0;
-    out_indptr[0] = 0;
-    if (q_rows == 0) return STRSIM_OK;
     rc = ctx_set_device(c);
     if (rc) return rc;
-    const size_t ptr_bytes = up256(((size_t)q_rows + 1) * sizeof(uint64_t)), idx_bytes = up256((size_t)capacity * sizeof(uint32_t));
-    Staged s;
-    rc = ctx_stage(c, q, cnd, ptr_bytes + idx_bytes + (size_t)capacity * sizeof(double) + 256, &s);
-    if (rc) return rc;
-    uint64_t *const d_ptr = reinterpret_cast<uint64_t *>(s.out);
-    uint32_t *const d_idx = capacity ? reinterpret_cast<uint32_t *>(s.out + ptr_bytes) : nullptr;
-    double *const d_score = capacity ? reinterpret_cast<double *>(s.out + ptr_bytes + idx_bytes) : nullptr;
-    rc = strsim_join_device(c, scorer, s.a.off, s.a.val, q_rows, s.b.off, s.b.val, c_rows, score_cutoff, flags, capacity, d_ptr, d_idx, d_score, out_nnz);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out_indptr, d_ptr, ((size_t)q_rows + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (*out_nnz && *out_nnz <= capacity) {
-        HIP_TRY(hipMemcpyAsync(out_index, d_idx, (size_t)*out_nnz * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(out_score, d_score, (size_t)*out_nnz * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (q_rows == 0) {
+        *out_nnz = 0;
+        HIP_TRY(hipMemsetAsync(out_indptr, 0, sizeof(uint64_t), c->stream));
+        return STRSIM_OK;
     }
-    return strsim_ctx_synchronize(c);
+    MatchJoinNeed need; // which candidate lengths a query of each length visits: 33 words, a kernel argument
+    const bool some = match_join_need_mask(measure, min_score, need);
+    return join_pairs(
+        c, "strsim_match_join_device", q, cnd, min_score, flags, capacity, out_indptr, out_index, out_score, out_nnz, !some,
+        []() -> int { return STRSIM_OK; }, // (the quotient table is the context's, on the device since the context was made)
+        [&](bool fill, JoinLaneArgs &a) { return launch_match_join_lane(measure, fill, a, c->qtab, need, min_score); }, measure);
+}
+
+int strsim_match_join_host(strsim_ctx_t *c, int measure, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows, const uint32_t *c_off,
+                           const uint8_t *c_val, uint64_t c_rows, double min_score, uint32_t flags, uint64_t capacity, uint64_t *out_indptr,
+                           uint32_t *out_index, double *out_score, uint64_t *out_nnz)
+{
+    return join_host(strsim_match_join_device, MATCH_JOIN_WORDS, "strsim_match_join_host", c, measure, Col{q_off, q_val, q_rows},
+                     Col{c_off, c_val, c_rows}, min_score, flags, capacity, out_indptr, out_index, out_score, out_nnz);
 }
 
 } // extern "C"

@@ -273,5 +273,11 @@ struct JoinSlowArgs {
 hipError_t launch_join_slow(int side, bool fill, const JoinSlowArgs &a);
 hipError_t launch_join_sort_rows(const uint64_t *indptr, uint32_t nq, uint32_t nc, uint32_t *index, double *score, hipStream_t stream);
 
+// Threshold join by a reference measure 0 .. 4 (strsim_match_join_kernels.h; the rule is in strsim_match_join.h): the sweep that
+// stands where launch_join_lane stands, everything around it is the join's.  Of `a`, tab and rlimit are not read; qtab: the quotient
+// table (measures 0 .. 2), need: the lengths a query of each length visits, passed by value.
+struct MatchJoinNeed;
+hipError_t launch_match_join_lane(int measure, bool fill, const JoinLaneArgs &a, const double *qtab, const MatchJoinNeed &need, double min_score);
+
 } // namespace strsim
 

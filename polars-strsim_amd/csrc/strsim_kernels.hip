@@ -75,6 +75,7 @@
 #include "strsim_extract.h"
 #include "strsim_cdist.h"
 #include "strsim_join.h"
+#include "strsim_match_join.h"
 
 namespace strsim {
 
@@ -94,6 +95,7 @@ struct OutPtrs {
 #include "strsim_extract_kernels.h"
 #include "strsim_cdist_kernels.h"
 #include "strsim_join_kernels.h"
+#include "strsim_match_join_kernels.h"
 
 #include "strsim_kernel_wide.h"
 #include "strsim_kernel_utf8.h"
@@ -642,6 +644,35 @@ hipError_t launch_join_sort_rows(const uint64_t *indptr, uint32_t nq, uint32_t n
                        score);
     if (nc > JOIN_SORT_WAVE_MAX) // (a row has at most nc hits)
         hipLaunchKernelGGL(k_join_sort_rows<true>, dim3(nq < 4096u ? nq : 4096u), dim3(JOIN_SORT_BLOCK), 0, stream, indptr, nq, index, score);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// threshold join by the reference measures (strsim_match_join_kernels.h)
+// ------------------------------------------------------------------------------------------------
+template <int M>
+static void launch_match_join_lane_m(bool fill, const JoinLaneArgs &a, const double *qtab, const MatchJoinNeed &need, double min_score)
+{
+    const dim3 grid(match_grid(a.nq), a.splits);
+    if (fill)
+        hipLaunchKernelGGL((k_match_join_lane<M, true>), grid, dim3(MATCH_BLOCK), 0, a.stream, a.qwords, a.qmeta, a.qperm, a.qstart, a.nq, a.swords,
+                           a.smeta, a.sidx, a.cstart, qtab, need, min_score, a.upper, a.cnt, a.map, a.map_words, a.map_shift, a.indptr, a.out_index,
+                           a.out_score);
+    else
+        hipLaunchKernelGGL((k_match_join_lane<M, false>), grid, dim3(MATCH_BLOCK), 0, a.stream, a.qwords, a.qmeta, a.qperm, a.qstart, a.nq, a.swords,
+                           a.smeta, a.sidx, a.cstart, qtab, need, min_score, a.upper, a.cnt, a.map, a.map_words, a.map_shift, a.indptr, a.out_index,
+                           a.out_score);
+}
+
+hipError_t launch_match_join_lane(int measure, bool fill, const JoinLaneArgs &a, const double *qtab, const MatchJoinNeed &need, double min_score)
+{
+    switch (measure) {
+    case LEVENSHTEIN: launch_match_join_lane_m<LEVENSHTEIN>(fill, a, qtab, need, min_score); break;
+    case JARO: launch_match_join_lane_m<JARO>(fill, a, qtab, need, min_score); break;
+    case JARO_WINKLER: launch_match_join_lane_m<JARO_WINKLER>(fill, a, qtab, need, min_score); break;
+    case JACCARD: launch_match_join_lane_m<JACCARD>(fill, a, qtab, need, min_score); break;
+    default: launch_match_join_lane_m<SORENSEN_DICE>(fill, a, qtab, need, min_score); break;
+    }
     return hipGetLastError();
 }
 

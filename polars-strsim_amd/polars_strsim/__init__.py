@@ -363,3 +363,27 @@ def join(expr: IntoExpr, candidates: IntoExpr, scorer: str = "ratio", score_cuto
         args=args,
         is_elementwise=False,
     )
+
+
+# (a statement of its own again)
+__all__ += ["match_join"]
+
+_MATCH_JOIN_MEASURES = ("levenshtein", "jaro", "jaro_winkler", "jaccard", "sorensen_dice")
+
+
+def match_join(expr: IntoExpr, candidates: IntoExpr, measure: str = "jaro_winkler", min_score: float | None = None) -> pl.Expr:
+    """Every row of `candidates` (any length) that scores at least min_score against the row of `expr`, by `measure` (one of the
+    five measures of this package): a List(Struct{index: UInt32, score: Float64}) per row, in ascending candidate index, nothing
+    truncated; None reports every candidate.  A null row gives a null list, a row without a hit an empty one; null candidates are
+    never matched.  The score is the pairwise function's, bit for bit.  Not in the upstream polars-strsim."""
+    if measure not in _MATCH_JOIN_MEASURES:
+        raise ValueError(f"unknown measure {measure!r}; expected one of {_MATCH_JOIN_MEASURES}")
+    args = [parse_into_expr(expr, dtype=pl.Utf8), parse_into_expr(candidates, dtype=pl.Utf8)]
+    if min_score is not None:
+        args.append(pl.lit(min_score, dtype=pl.Float64))
+    return register_plugin_function(
+        plugin_path=_PLUGIN_DIR,
+        function_name="match_join_" + measure,
+        args=args,
+        is_elementwise=False,
+    )

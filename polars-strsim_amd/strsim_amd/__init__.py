@@ -355,6 +355,11 @@ def join(scorer, queries, candidates, score_cutoff, upper=False, ctx=None, proce
     rapidfuzz: the pairs process.cdist(queries, candidates, scorer=fuzz.ratio, score_cutoff=100 * score_cutoff) leaves non-zero."""
     if not isinstance(scorer, str) or scorer not in _JOIN_SCORER_MEASURE:
         raise ValueError(f"no join by scorer {scorer!r} (one of {JOIN_SCORERS})")
+    return _join_lists(lambda c: c.join, _JOIN_SCORER_MEASURE[scorer], queries, candidates, score_cutoff, upper, ctx, processor)
+
+
+def _join_lists(call, measure, queries, candidates, cutoff, upper, ctx, processor):
+    """join() and match_join() over Python lists: call(ctx) is the context's method; nulls, `upper` and the processor alike"""
     if processor is not None:
         processor_id(processor)
     ctx = ctx or default_context()
@@ -372,7 +377,7 @@ def join(scorer, queries, candidates, score_cutoff, upper=False, ctx=None, proce
     if processor is not None:
         qo, qv = ctx.default_process_host(qo, qv)
         co, cv = ctx.default_process_host(co, cv)
-    indptr, idx, score = ctx.join(_JOIN_SCORER_MEASURE[scorer], qo, qv, co, cv, score_cutoff, upper)
+    indptr, idx, score = call(ctx)(measure, qo, qv, co, cv, cutoff, upper)
     indptr = np.asarray(indptr).astype(np.int64)
     index = pos[np.asarray(idx).astype(np.int64)] if len(idx) else np.zeros(0, dtype=np.int64)
     score = np.asarray(score, dtype=np.float64)
@@ -396,10 +401,33 @@ def dedupe_pairs(scorer, column, score_cutoff, ctx=None, processor=None):
     return np.repeat(np.arange(len(column), dtype=np.int64), np.diff(indptr)), index, score
 
 
+MATCH_JOIN_MEASURES = MEASURES
+
+
+def match_join(measure, queries, candidates, min_score, upper=False, ctx=None, processor=None):
+    """Threshold join by one of the five reference measures (MATCH_JOIN_MEASURES): every pair (query i, candidate j) whose score
+    by `measure` is >= min_score, as CSR: (indptr int64 [N + 1], index int64 [nnz], score f64 [nnz]) -- "every pair of names with
+    Jaro-Winkler >= 0.9" without cdist's N x M matrix and without best_match's limit on k.  The hits of query i are index /
+    score[indptr[i]:indptr[i + 1]], in ascending candidate position; the score is bit for bit the pairwise call's.  min_score=None
+    reports every pair.  upper, the nulls and processor="default_process" are join()'s."""
+    if not isinstance(measure, str) or measure not in MATCH_JOIN_MEASURES:
+        raise ValueError(f"no match_join by measure {measure!r} (one of {MATCH_JOIN_MEASURES})")
+    return _join_lists(lambda c: c.match_join, measure, queries, candidates, min_score, upper, ctx, processor)
+
+
+def match_dedupe_pairs(measure, column, min_score, ctx=None, processor=None):
+    """The near-duplicates of one column by a reference measure: the self-join match_join(measure, column, column, min_score,
+    upper=True) as COO -- (i int64 [nnz], j int64 [nnz], score f64 [nnz]) with i < j, ordered by i, then j."""
+    column = list(column)
+    indptr, index, score = match_join(measure, column, column, min_score, upper=True, ctx=ctx, processor=processor)
+    return np.repeat(np.arange(len(column), dtype=np.int64), np.diff(indptr)), index, score
+
+
 __all__ = ["default_process", "PROCESSORS", "best_match", "nearest", "Codec", "Context", "device_count", "pack_strings", "split_offsets", "similarity", "levenshtein", "jaro",
            "jaro_winkler", "jaccard", "sorensen_dice", "osa", "indel", "measure_supported", "distance", "levenshtein_distance", "osa_distance",
            "indel_distance", "INDEL_MEASURES", "partial_ratio", "partial_ratio_alignment", "PARTIAL_MEASURES",
            "token_sort_ratio", "token_set_ratio", "token_sort", "TOKEN_MEASURES",
            "token_ratio", "partial_token_sort_ratio", "partial_token_set_ratio", "partial_token_ratio", "wratio", "WEIGHTED_MEASURES",
            "DISTANCE_MEASURES", "DISTANCE_UNBOUNDED", "MEASURES", "EXTRA_MEASURES", "MEASURE_ID", "STATUS", "ShapeMismatch", "StrsimError",
-           "extract", "EXTRACT_SCORERS", "cdist", "CDIST_MEASURES", "join", "dedupe_pairs", "JOIN_SCORERS"]
+           "extract", "EXTRACT_SCORERS", "cdist", "CDIST_MEASURES", "join", "dedupe_pairs", "JOIN_SCORERS",
+           "match_join", "match_dedupe_pairs", "MATCH_JOIN_MEASURES"]

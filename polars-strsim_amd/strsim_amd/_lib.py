@@ -169,7 +169,7 @@ def lib():
         f = getattr(L, name)
         f.restype = i32
         f.argtypes = [vp, i32, vp, vp, u64, vp, vp, u64, C.c_double, vp, u64]
-    for name in ("strsim_join_device", "strsim_join_host"):
+    for name in ("strsim_join_device", "strsim_join_host", "strsim_match_join_device", "strsim_match_join_host"):
         f = getattr(L, name)
         f.restype = i32
         f.argtypes = [vp, i32, vp, vp, u64, vp, vp, u64, C.c_double, C.c_uint32, u64, vp, vp, vp, C.POINTER(u64)]

@@ -429,6 +429,16 @@ class Context:
         made with `capacity` slots (None: a guess from the rows) and, when the hits do not fit, once more with exactly nnz.
         count_only=True makes the count-only call and returns indptr alone.  numpy in: uint64 / uint32 / f64 arrays out; device
         tensors in: int64 / int32 / f64 tensors out, complete in stream order."""
+        return self._join("strsim_join", scorer, q_offsets, q_values, c_offsets, c_values, score_cutoff, upper, capacity, count_only)
+
+    def match_join(self, measure, q_offsets, q_values, c_offsets, c_values, min_score=None, upper=False, capacity=None, count_only=False):
+        """Threshold join by one of the five reference measures (strsim_match_join_host for numpy columns, strsim_match_join_device
+        for torch tensors on this context's device): every pair (i, j) with score >= min_score (None: every pair), as CSR.  The
+        result, `upper`, the capacity protocol and count_only are join()'s."""
+        return self._join("strsim_match_join", measure, q_offsets, q_values, c_offsets, c_values, min_score, upper, capacity, count_only)
+
+    def _join(self, entry, scorer, q_offsets, q_values, c_offsets, c_values, score_cutoff, upper, capacity, count_only):
+        """join() and match_join(): the entry points `entry`_device / `entry`_host under the capacity protocol"""
         cut = -np.inf if score_cutoff is None else float(score_cutoff)
         flags = JOIN_UPPER if upper else 0
         nnz = C.c_uint64(0)
@@ -437,7 +447,7 @@ class Context:
             import torch
             nq, nc = max(q_offsets.numel() - 1, 0), max(c_offsets.numel() - 1, 0)
             cols = (q_offsets.data_ptr(), q_values.data_ptr(), nq, c_offsets.data_ptr(), c_values.data_ptr(), nc)
-            fn = lib().strsim_join_device
+            fn = getattr(lib(), entry + "_device")
             indptr = torch.empty(nq + 1, dtype=torch.int64, device=q_offsets.device)
             new = lambda n, dt: torch.empty(n, dtype={"i": torch.int32, "f": torch.float64}[dt], device=q_offsets.device)
             ptr = lambda t: t.data_ptr()
@@ -446,7 +456,7 @@ class Context:
             co, cv, nc = _host_column(c_offsets, c_values)
             nq, nc = max(nq, 0), max(nc, 0)
             cols = (qo.ctypes.data, qv.ctypes.data, nq, co.ctypes.data, cv.ctypes.data, nc)
-            fn = lib().strsim_join_host
+            fn = getattr(lib(), entry + "_host")
             indptr = np.empty(nq + 1, dtype=np.uint64)
             new = lambda n, dt: np.empty(n, dtype={"i": np.uint32, "f": np.float64}[dt])
             ptr = lambda a: a.ctypes.data
@@ -461,8 +471,7 @@ class Context:
             if nnz.value <= cap:
                 return indptr, index[:nnz.value], score[:nnz.value]
             cap = nnz.value  # the hits did not fit: nothing was written; once more with the exact size
-        raise StrsimError(7, f"strsim_join: nnz changed between two calls on the same columns ({nnz.value} > {cap})")
-
+        raise StrsimError(7, f"{entry}: nnz changed between two calls on the same columns ({nnz.value} > {cap})")
 
 class Codec:
     """Lossless 16-bit transport codec for one measure's result column (include/strsim_amd.h: strsim_codec_*)."""
