@@ -14,6 +14,8 @@
 #                    same sweep with a list)
 #         match_join -- the ten k_match_join_lane kernels of strsim_match_join_device, k_match_lane beside them (the same scoring with
 #                    a list) and the join kernels around the sweep
+#         cluster -- the kernels of strsim_components_device (strsim_cluster_device adds none: it runs the join's) and the join's
+#                    scan kernels they reuse
 ROOT=$(cd "$(dirname "$0")/.." && pwd); OUT=${TMPDIR:-/tmp}/strsim_co; mkdir -p $OUT
 case "$1" in
     wratio) FILTER='k_wratio_|k_take_|k_max_f64|k_token_|k_partial_|k_indel_|k_osa_|k_dist_' ;;
@@ -23,6 +25,7 @@ case "$1" in
     cdist) FILTER='k_cdist_|k_match_pack|k_match_lane' ;;
     join) FILTER='k_join_|k_extract_|k_nearest_hist|k_nearest_scan|k_nearest_scatter|k_match_pack' ;;
     match_join) FILTER='k_match_join_|k_match_lane|k_join_|k_nearest_hist|k_nearest_scan|k_nearest_scatter|k_match_pack' ;;
+    cluster) FILTER='k_components_|k_join_scan_' ;;
     nearest) FILTER='k_nearest_|k_match_pack|k_match_clear|k_match_fold|k_match_merge' ;;
     *) FILTER=${1:-.} ;;
 esac

@@ -195,6 +195,20 @@ POLARS_PLUGIN_DECLARE(match_join_jaro_winkler)
 POLARS_PLUGIN_DECLARE(match_join_jaccard)
 POLARS_PLUGIN_DECLARE(match_join_sorensen_dice)
 
+/* cluster: the duplicate groups of ONE column (not in the reference; strsim_cluster_host: the self-join of the column at
+ * min_score, then the connected components of its hits).  Input 0 is a string series of any number of chunks, clustered as one
+ * column; input 1 is the Float64 literal min_score (required: one non-null value, not NaN -- without it the call fails with
+ * "cluster: expected 2 input series (the column and the Float64 literal min_score), got 1").  Output: N rows of UInt32 ("I") named
+ * after input 0 -- row r holds the row of the first member of r's group.  A null row gives null and never joins anything.  Groups
+ * chain: a ~ b and b ~ c put a and c together even where they do not match each other. */
+POLARS_PLUGIN_DECLARE(cluster_ratio)
+POLARS_PLUGIN_DECLARE(cluster_token_sort_ratio)
+POLARS_PLUGIN_DECLARE(cluster_levenshtein)
+POLARS_PLUGIN_DECLARE(cluster_jaro)
+POLARS_PLUGIN_DECLARE(cluster_jaro_winkler)
+POLARS_PLUGIN_DECLARE(cluster_jaccard)
+POLARS_PLUGIN_DECLARE(cluster_sorensen_dice)
+
 /* default_process (not in the reference; rapidfuzz's utils.default_process made context-free, strsim_default_process_host of
  * strsim_amd.h): ONE input, a string series in any of the three layouts; elementwise.  Output: N rows of Arrow Utf8 ("u": int32
  * offsets -- the transform's 32-bit offsets are the buffer as it is; a result beyond 2^31 - 1 bytes is an error) named after

@@ -611,6 +611,54 @@ STRSIM_API int strsim_match_join_host(strsim_ctx_t *ctx, int measure,
                                       double min_score, uint32_t flags, uint64_t capacity,
                                       uint64_t *out_indptr, uint32_t *out_index, double *out_score, uint64_t *out_nnz);
 
+/*
+ * Connected components of a CSR graph: one label per row -- the last stage of deduplication, "these 7 spellings are the same
+ * customer" (found by dlsym, like strsim_join_*: the ABI version stays 1.7 and strsim_measure_supported does not describe these
+ * entry points).  The nnz edges (i, index[e]), e in [indptr[i], indptr[i + 1]), are read as UNDIRECTED: the upper-only CSR of a
+ * STRSIM_JOIN_UPPER self-join, a lower-only one and a two-sided one give the same answer; duplicate edges and self-loops are harmless.
+ *
+ * Output.  out_root[v] is the smallest row of v's component: canonical, the same run to run.  out_cluster[v] (may be NULL) is the
+ * number of roots below out_root[v]: the clusters are numbered 0 .. count - 1 in order of their first member.  *out_count (HOST
+ * memory) is the number of components; a row without an edge is a component of one.
+ *
+ * rows <= 2^32 - 1.  rows == 0 writes *out_count = 0 and touches no device memory; nnz == 0 gives the identity (one launch, no
+ * wait).  A NULL indptr or out_count, a NULL out_root with rows > 0, a NULL index with nnz > 0, too many rows: STRSIM_ERR_ARG; the
+ * arguments are checked first, the context last (a NULL ctx is STRSIM_ERR_ARG too): no argument error needs a device.  An
+ * index[e] >= rows is skipped by the kernel and counted; the call then returns STRSIM_ERR_ARG with "index out of range" (the labels
+ * of the remaining edges are written).  indptr is assumed non-decreasing from 0 to nnz; whatever it holds, no access leaves the
+ * caller's buffers (csrc/strsim_components.h has the argument).
+ *
+ * Device-resident: init, link (one lane per edge, hook-to-smaller with a compare-and-swap; no lane waits for another), compress,
+ * a scan of the root flags and the rank: seven launches and one 16-byte copy for every graph with nnz > 0, then the call's one
+ * wait for the stream (the count and the bad-index word come back together).  Scratch (20 bytes a row) the context cannot reserve
+ * is STRSIM_ERR_OOM.
+ */
+STRSIM_API int strsim_components_device(strsim_ctx_t *ctx, uint64_t rows, const uint64_t *indptr, const uint32_t *index, uint64_t nnz,
+                                        uint32_t *out_root, uint32_t *out_cluster, uint64_t *out_count);
+
+/* The same with HOST-RESIDENT buffers; synchronous. */
+STRSIM_API int strsim_components_host(strsim_ctx_t *ctx, uint64_t rows, const uint64_t *indptr, const uint32_t *index, uint64_t nnz,
+                                      uint32_t *out_root, uint32_t *out_cluster, uint64_t *out_count);
+
+/*
+ * The duplicate groups of one column: the STRSIM_JOIN_UPPER self-join of the column with itself at min_score, followed by
+ * strsim_components_device on its CSR.  The pairs live in a grow-only buffer of the context and never reach the host.  `measure`
+ * 0 .. 4 runs strsim_match_join_device, STRSIM_INDEL (8) and STRSIM_TOKEN_SORT_RATIO (14) run strsim_join_device; any other id is
+ * STRSIM_ERR_ARG.  The join is made with 4 * rows + 1024 slots and, when the hits do not fit, once more with exactly nnz.
+ * Components chain: a ~ b and b ~ c put a and c in one cluster even where a and c do not match each other.
+ *
+ * out_root, out_cluster (may be NULL) and *out_count (HOST memory) are those of strsim_components_device; *out_nnz (HOST memory,
+ * may be NULL) is the number of pairs of the self-join.  NaN and the range of min_score follow the join: above 1.0 nothing matches
+ * (the identity), -INFINITY or 0.0 gives one cluster, NaN is STRSIM_ERR_ARG.  rows <= 2^32 - 2; rows == 0 writes *out_count = 0.
+ * The arguments are checked first, the context last.  Waits: the join's, then the one of the components.
+ */
+STRSIM_API int strsim_cluster_device(strsim_ctx_t *ctx, int measure, const uint32_t *offsets, const uint8_t *values, uint64_t rows,
+                                     double min_score, uint32_t *out_root, uint32_t *out_cluster, uint64_t *out_count, uint64_t *out_nnz);
+
+/* The same with HOST-RESIDENT buffers; synchronous. */
+STRSIM_API int strsim_cluster_host(strsim_ctx_t *ctx, int measure, const uint32_t *offsets, const uint8_t *values, uint64_t rows,
+                                   double min_score, uint32_t *out_root, uint32_t *out_cluster, uint64_t *out_count, uint64_t *out_nnz);
+
 /* Row partition used to shard a column over `n` GPUs/ranks: the reference's split_offsets
  * (strsim.rs:21-39).  Writes n (offset,len) pairs into out_offset_len[2*n]. */
 STRSIM_API void strsim_split_offsets(uint64_t len, uint64_t n, uint64_t *out_offset_len);

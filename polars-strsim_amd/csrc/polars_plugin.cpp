@@ -155,6 +155,7 @@ void export_primitive(const char *format, const char *name, uint64_t n, void *da
 #include "plugin_extract.h"
 #include "plugin_cdist.h"
 #include "plugin_join.h"
+#include "plugin_cluster.h"
 #include "plugin_process.h"
 
 void run(int measure, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret, bool engine_parallel)
@@ -272,6 +273,9 @@ void _polars_plugin_strsim_coalesce_stats(uint64_t out[4]) { if (out) combiner()
 #define POLARS_PLUGIN_DEFINE_MATCH_JOIN(name, id)                                                             \
     POLARS_PLUGIN_EXPORT(match_join_##name, run_join(strsim_match_join_host, id, inputs, n_inputs, return_value), \
                          field_named_after_input0(input_fields, n_fields, return_value, fill_list_struct_schema))
+#define POLARS_PLUGIN_DEFINE_CLUSTER(name, id)                                        \
+    POLARS_PLUGIN_EXPORT(cluster_##name, run_cluster(id, inputs, n_inputs, return_value), \
+                         field_named_after_input0(input_fields, n_fields, return_value, [](ArrowSchema *s, const char *n) { fill_named_schema(s, "I", n); }))
 #define POLARS_PLUGIN_DEFINE_MATCH(name, id) \
     POLARS_PLUGIN_EXPORT(best_match_##name, run_best_match(id, inputs, n_inputs, return_value), STRUCT_FIELD(MATCH_STRUCT))
 
@@ -573,6 +577,13 @@ POLARS_PLUGIN_DEFINE_MATCH_JOIN(jaro, STRSIM_JARO)
 POLARS_PLUGIN_DEFINE_MATCH_JOIN(jaro_winkler, STRSIM_JARO_WINKLER)
 POLARS_PLUGIN_DEFINE_MATCH_JOIN(jaccard, STRSIM_JACCARD)
 POLARS_PLUGIN_DEFINE_MATCH_JOIN(sorensen_dice, STRSIM_SORENSEN_DICE)
+POLARS_PLUGIN_DEFINE_CLUSTER(ratio, STRSIM_INDEL)
+POLARS_PLUGIN_DEFINE_CLUSTER(token_sort_ratio, STRSIM_TOKEN_SORT_RATIO)
+POLARS_PLUGIN_DEFINE_CLUSTER(levenshtein, STRSIM_LEVENSHTEIN)
+POLARS_PLUGIN_DEFINE_CLUSTER(jaro, STRSIM_JARO)
+POLARS_PLUGIN_DEFINE_CLUSTER(jaro_winkler, STRSIM_JARO_WINKLER)
+POLARS_PLUGIN_DEFINE_CLUSTER(jaccard, STRSIM_JACCARD)
+POLARS_PLUGIN_DEFINE_CLUSTER(sorensen_dice, STRSIM_SORENSEN_DICE)
 POLARS_PLUGIN_EXPORT(default_process, run_default_process(inputs, n_inputs, return_value),
                      field_named_after_input0(input_fields, n_fields, return_value, [](ArrowSchema *s, const char *n) { fill_named_schema(s, "u", n); }))
 POLARS_PLUGIN_DEFINE_MATCH(levenshtein, STRSIM_LEVENSHTEIN)

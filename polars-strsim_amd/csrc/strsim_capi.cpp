@@ -30,6 +30,7 @@
 #include "strsim_cdist.h"
 #include "strsim_join.h"
 #include "strsim_match_join.h"
+#include "strsim_components.h"
 
 namespace strsim {
 
@@ -183,6 +184,11 @@ struct strsim_ctx {
     // buffers of its own, for the same reason; it reads extract_tab (the rank table, never rewritten) and scorer 14 normalises into
     // extract_off / extract_val, which no flow inside a join call uses
     DevBuf join_ws, join_scratch;
+    // strsim_components_device: parent[], the root flags and their scan, and the status words {count, indices out of range} with
+    // their pinned read-back; strsim_cluster_device: the CSR of its self-join, which never reaches the host -- buffers of their own,
+    // for the same reason (the join inside a cluster call uses every buffer above freely)
+    DevBuf components_ws, cluster_pairs;
+    uint64_t *components_host = nullptr;
 
     // ---- two-pass measures (two_pass: pairs_osa, distance_device_impl, partial_device_impl) ----
     DevBuf osa_list;                 // the work list of the wave kernel (one word per row)
@@ -498,6 +504,7 @@ void strsim_ctx_destroy(strsim_ctx_t *c)
             if (c->ev[s][i]) (void)hipEventDestroy(c->ev[s][i]);
     for (int i = 0; i < 2; ++i) if (c->ev_late[i]) (void)hipEventDestroy(c->ev_late[i]);
     if (c->match_counts_host) (void)hipHostFree(c->match_counts_host);
+    if (c->components_host) (void)hipHostFree(c->components_host);
     if (c->dist_status) (void)hipFree(c->dist_status);
     if (c->dist_status_host) (void)hipHostFree(c->dist_status_host);
     if (c->tok_status) (void)hipFree(c->tok_status);
@@ -2709,6 +2716,197 @@ int strsim_match_join_host(strsim_ctx_t *c, int measure, const uint32_t *q_off, 
 {
     return join_host(strsim_match_join_device, MATCH_JOIN_WORDS, "strsim_match_join_host", c, measure, Col{q_off, q_val, q_rows},
                      Col{c_off, c_val, c_rows}, min_score, flags, capacity, out_indptr, out_index, out_score, out_nnz);
+}
+
+} // extern "C"
+
+// ---- connected components of a CSR graph and the fused cluster call (strsim_components.h, strsim_components_kernels.h) ----
+
+static int components_check(const char *who, strsim_ctx_t *c, uint64_t rows, const uint64_t *indptr, const uint32_t *index, uint64_t nnz,
+                            const uint32_t *out_root, const uint64_t *out_count)
+{
+    if (rows > 0xFFFFFFFFull) { set_error("%s: %llu rows (at most 2^32 - 1)", who, (unsigned long long)rows); return STRSIM_ERR_ARG; }
+    if (!indptr) { set_error("%s: indptr is NULL", who); return STRSIM_ERR_ARG; }
+    if (nnz && !index) { set_error("%s: index is NULL with nnz=%llu", who, (unsigned long long)nnz); return STRSIM_ERR_ARG; }
+    if (rows && !out_root) { set_error("%s: out_root is NULL", who); return STRSIM_ERR_ARG; }
+    if (!out_count) { set_error("%s: out_count is NULL", who); return STRSIM_ERR_ARG; }
+    if (!c) { set_error("%s: ctx is NULL", who); return STRSIM_ERR_ARG; }
+    return STRSIM_OK;
+}
+
+// The labels of a device-resident CSR graph, rows >= 1, behind the check.  nnz == 0: one launch, no wait.  Otherwise
+// COMPONENTS_LAUNCHES launches and one copy whatever the graph holds, and the call's one wait: the count and the number of
+// indices out of range come back together.
+static int components_labels(strsim_ctx *c, const char *who, uint32_t rows, const uint64_t *indptr, const uint32_t *index, uint64_t nnz,
+                             uint32_t *out_root, uint32_t *out_cluster, uint64_t *out_count)
+{
+    hipStream_t st = c->stream;
+    if (nnz == 0u) {
+        HIP_TRY(launch_components_identity(rows, out_root, out_cluster, st));
+        c->enqueued_ops += 1u;
+        *out_count = rows;
+        return STRSIM_OK;
+    }
+    const size_t o_parent = 256, o_scan = o_parent + up256((size_t)rows * 4), o_sums = o_scan + up256((size_t)rows * 8),
+                 o_end = o_sums + up256((size_t)join_scan_blocks(rows) * 8);
+    int rc = c->components_ws.reserve(o_end);
+    if (rc) return rc;
+    if (!c->components_host) HIP_TRY(hipHostMalloc((void **)&c->components_host, 64, hipHostMallocDefault));
+    uint8_t *const b = c->components_ws.as<uint8_t>();
+    uint64_t *const status = (uint64_t *)b;
+    ComponentsArgs a{indptr, index, rows, nnz, (uint32_t *)(b + o_parent), (uint64_t *)(b + o_scan), (uint64_t *)(b + o_sums), status,
+                     out_root, out_cluster, st};
+    HIP_TRY(launch_components(a));
+    HIP_TRY(hipMemcpyAsync(c->components_host, status, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    c->enqueued_ops += COMPONENTS_LAUNCHES + 1u;
+    *out_count = c->components_host[0];
+    if (c->components_host[1]) {
+        set_error("%s: index out of range (%llu of %llu edges name a row >= rows=%u; they were skipped)", who,
+                  (unsigned long long)c->components_host[1], (unsigned long long)nnz, rows);
+        return STRSIM_ERR_ARG;
+    }
+    return STRSIM_OK;
+}
+
+// Which join flow a measure of cluster runs: 0 .. 4 strsim_match_join_device, 8 and 14 strsim_join_device; nullptr: refused.
+static JoinDeviceFn cluster_join(int measure)
+{
+    if (MATCH_JOIN_WORDS.accepts(measure)) return strsim_match_join_device;
+    if (JOIN_WORDS.accepts(measure)) return strsim_join_device;
+    return nullptr;
+}
+
+static int cluster_check(const char *who, strsim_ctx_t *c, int measure, const Col &col, double min_score, const uint32_t *out_root,
+                         const uint64_t *out_count)
+{
+    if (!cluster_join(measure)) {
+        set_error("%s: measure %d is not a measure of cluster (the reference measures 0 .. 4, STRSIM_INDEL = 8 or STRSIM_TOKEN_SORT_RATIO = 14)",
+                  who, measure);
+        return STRSIM_ERR_ARG;
+    }
+    if (min_score != min_score) { set_error("%s: min_score is NaN", who); return STRSIM_ERR_ARG; }
+    if (col.rows > 0xFFFFFFFEull) { set_error("%s: %llu rows (at most 2^32 - 2)", who, (unsigned long long)col.rows); return STRSIM_ERR_ARG; }
+    if (col.rows && (!col.off || !col.val)) { set_error("%s: NULL column buffer", who); return STRSIM_ERR_ARG; }
+    if (col.rows && !out_root) { set_error("%s: out_root is NULL", who); return STRSIM_ERR_ARG; }
+    if (!out_count) { set_error("%s: out_count is NULL", who); return STRSIM_ERR_ARG; }
+    if (!c) { set_error("%s: ctx is NULL", who); return STRSIM_ERR_ARG; }
+    return STRSIM_OK;
+}
+
+// The STRSIM_JOIN_UPPER self-join of a device-resident column, rows >= 1, into the context's cluster_pairs under the capacity
+// protocol (4 * rows + 1024 slots, or what the buffer already holds; when the hits do not fit, exactly nnz and one more call), then
+// the components of its CSR.
+static int cluster_labels(strsim_ctx *c, const char *who, int measure, const Col &col, double min_score, uint32_t *out_root,
+                          uint32_t *out_cluster, uint64_t *out_count, uint64_t *out_nnz)
+{
+    const JoinDeviceFn join = cluster_join(measure);
+    const size_t ptr_bytes = up256(((size_t)col.rows + 1) * sizeof(uint64_t));
+    uint64_t cap = 4u * col.rows + 1024u, nnz = 0;
+    if (c->cluster_pairs.cap > ptr_bytes + 256) { // the buffer only grows: what an earlier call left is the first capacity when it is more
+        const uint64_t have = (c->cluster_pairs.cap - ptr_bytes - 256) / (sizeof(uint32_t) + sizeof(double));
+        if (have > cap) cap = have;
+    }
+    uint64_t *d_ptr = nullptr;
+    uint32_t *d_idx = nullptr;
+    for (int call = 0;; ++call) {
+        const size_t idx_bytes = up256((size_t)cap * sizeof(uint32_t));
+        int rc = c->cluster_pairs.reserve(ptr_bytes + idx_bytes + (size_t)cap * sizeof(double));
+        if (rc) return rc;
+        uint8_t *const b = c->cluster_pairs.as<uint8_t>();
+        d_ptr = reinterpret_cast<uint64_t *>(b);
+        d_idx = reinterpret_cast<uint32_t *>(b + ptr_bytes);
+        rc = join(c, measure, col.off, col.val, col.rows, col.off, col.val, col.rows, min_score, STRSIM_JOIN_UPPER, cap, d_ptr, d_idx,
+                  reinterpret_cast<double *>(b + ptr_bytes + idx_bytes), &nnz);
+        if (rc) return rc;
+        if (nnz <= cap) break;
+        if (call) {
+            set_error("%s: nnz changed between two joins of the same column (%llu > %llu)", who, (unsigned long long)nnz, (unsigned long long)cap);
+            return STRSIM_ERR_INTERNAL;
+        }
+        cap = nnz;
+    }
+    if (out_nnz) *out_nnz = nnz;
+    return components_labels(c, who, (uint32_t)col.rows, d_ptr, d_idx, nnz, out_root, out_cluster, out_count);
+}
+
+// The labels of a *_host entry point back from stage[4]: root, then cluster at a 256-byte boundary behind it.
+static int labels_to_host(strsim_ctx *c, uint64_t rows, const uint8_t *d_out, uint32_t *out_root, uint32_t *out_cluster)
+{
+    HIP_TRY(hipMemcpyAsync(out_root, d_out, (size_t)rows * 4, hipMemcpyDeviceToHost, c->stream));
+    if (out_cluster) HIP_TRY(hipMemcpyAsync(out_cluster, d_out + up256((size_t)rows * 4), (size_t)rows * 4, hipMemcpyDeviceToHost, c->stream));
+    return strsim_ctx_synchronize(c);
+}
+
+extern "C" {
+
+int strsim_components_device(strsim_ctx_t *c, uint64_t rows, const uint64_t *indptr, const uint32_t *index, uint64_t nnz, uint32_t *out_root,
+                             uint32_t *out_cluster, uint64_t *out_count)
+{
+    int rc = components_check("strsim_components_device", c, rows, indptr, index, nnz, out_root, out_count);
+    if (rc) return rc;
+    *out_count = 0;
+    if (rows == 0) return STRSIM_OK;
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    return components_labels(c, "strsim_components_device", (uint32_t)rows, indptr, index, nnz, out_root, out_cluster, out_count);
+}
+
+int strsim_components_host(strsim_ctx_t *c, uint64_t rows, const uint64_t *indptr, const uint32_t *index, uint64_t nnz, uint32_t *out_root,
+                           uint32_t *out_cluster, uint64_t *out_count)
+{
+    int rc = components_check("strsim_components_host", c, rows, indptr, index, nnz, out_root, out_count);
+    if (rc) return rc;
+    *out_count = 0;
+    if (rows == 0) return STRSIM_OK;
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    const size_t ptr_bytes = ((size_t)rows + 1) * sizeof(uint64_t), idx_bytes = (size_t)nnz * sizeof(uint32_t), lab_bytes = up256((size_t)rows * 4);
+    rc = c->stage[0].reserve(ptr_bytes);
+    if (rc == STRSIM_OK) rc = c->stage[1].reserve(idx_bytes + 4);
+    if (rc == STRSIM_OK) rc = c->stage[4].reserve(2 * lab_bytes);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(c->stage[0].p, indptr, ptr_bytes, hipMemcpyHostToDevice, c->stream));
+    if (nnz) HIP_TRY(hipMemcpyAsync(c->stage[1].p, index, idx_bytes, hipMemcpyHostToDevice, c->stream));
+    uint8_t *const d_out = c->stage[4].as<uint8_t>();
+    rc = components_labels(c, "strsim_components_host", (uint32_t)rows, c->stage[0].as<uint64_t>(), c->stage[1].as<uint32_t>(), nnz,
+                           reinterpret_cast<uint32_t *>(d_out), out_cluster ? reinterpret_cast<uint32_t *>(d_out + lab_bytes) : nullptr, out_count);
+    if (rc) return rc;
+    return labels_to_host(c, rows, d_out, out_root, out_cluster);
+}
+
+int strsim_cluster_device(strsim_ctx_t *c, int measure, const uint32_t *offsets, const uint8_t *values, uint64_t rows, double min_score,
+                          uint32_t *out_root, uint32_t *out_cluster, uint64_t *out_count, uint64_t *out_nnz)
+{
+    const Col col{offsets, values, rows};
+    int rc = cluster_check("strsim_cluster_device", c, measure, col, min_score, out_root, out_count);
+    if (rc) return rc;
+    *out_count = 0;
+    if (out_nnz) *out_nnz = 0;
+    if (rows == 0) return STRSIM_OK;
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    return cluster_labels(c, "strsim_cluster_device", measure, col, min_score, out_root, out_cluster, out_count, out_nnz);
+}
+
+int strsim_cluster_host(strsim_ctx_t *c, int measure, const uint32_t *offsets, const uint8_t *values, uint64_t rows, double min_score,
+                        uint32_t *out_root, uint32_t *out_cluster, uint64_t *out_count, uint64_t *out_nnz)
+{
+    const Col col{offsets, values, rows};
+    int rc = cluster_check("strsim_cluster_host", c, measure, col, min_score, out_root, out_count);
+    if (rc) return rc;
+    *out_count = 0;
+    if (out_nnz) *out_nnz = 0;
+    if (rows == 0) return STRSIM_OK;
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    Staged s;
+    rc = ctx_stage(c, col, NO_COL, 2 * up256((size_t)rows * 4), &s);
+    if (rc) return rc;
+    rc = cluster_labels(c, "strsim_cluster_host", measure, s.a, min_score, reinterpret_cast<uint32_t *>(s.out),
+                        out_cluster ? reinterpret_cast<uint32_t *>(s.out + up256((size_t)rows * 4)) : nullptr, out_count, out_nnz);
+    if (rc) return rc;
+    return labels_to_host(c, rows, s.out, out_root, out_cluster);
 }
 
 } // extern "C"

@@ -279,5 +279,19 @@ hipError_t launch_join_sort_rows(const uint64_t *indptr, uint32_t nq, uint32_t n
 struct MatchJoinNeed;
 hipError_t launch_match_join_lane(int measure, bool fill, const JoinLaneArgs &a, const double *qtab, const MatchJoinNeed &need, double min_score);
 
+// Connected components of a CSR graph (strsim_components_kernels.h; the rules are in strsim_components.h).
+// launch_components_identity: the labels of a graph without edges, one launch.  launch_components: init, link, compress, the join's
+// three scan kernels over the root flags and the rank -- seven launches whatever the graph holds.  parent: rows words; scan: rows
+// 64-bit words; sums: join_scan_blocks(rows) words; status: {count, indices out of range}.
+hipError_t launch_components_identity(uint32_t rows, uint32_t *out_root, uint32_t *out_cluster, hipStream_t stream);
+struct ComponentsArgs {
+    const uint64_t *indptr; const uint32_t *index; uint32_t rows; uint64_t nnz;
+    uint32_t *parent; uint64_t *scan, *sums, *status;
+    uint32_t *out_root, *out_cluster;
+    hipStream_t stream;
+};
+constexpr uint32_t COMPONENTS_LAUNCHES = 7u;
+hipError_t launch_components(const ComponentsArgs &a);
+
 } // namespace strsim
 

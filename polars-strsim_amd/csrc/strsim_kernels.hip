@@ -76,6 +76,7 @@
 #include "strsim_cdist.h"
 #include "strsim_join.h"
 #include "strsim_match_join.h"
+#include "strsim_components.h"
 
 namespace strsim {
 
@@ -96,6 +97,7 @@ struct OutPtrs {
 #include "strsim_cdist_kernels.h"
 #include "strsim_join_kernels.h"
 #include "strsim_match_join_kernels.h"
+#include "strsim_components_kernels.h"
 
 #include "strsim_kernel_wide.h"
 #include "strsim_kernel_utf8.h"
@@ -673,6 +675,31 @@ hipError_t launch_match_join_lane(int measure, bool fill, const JoinLaneArgs &a,
     case JACCARD: launch_match_join_lane_m<JACCARD>(fill, a, qtab, need, min_score); break;
     default: launch_match_join_lane_m<SORENSEN_DICE>(fill, a, qtab, need, min_score); break;
     }
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// connected components (strsim_components_kernels.h)
+// ------------------------------------------------------------------------------------------------
+static unsigned components_grid(uint32_t rows) { return (unsigned)(((uint64_t)rows + COMPONENTS_BLOCK - 1u) / COMPONENTS_BLOCK); }
+
+hipError_t launch_components_identity(uint32_t rows, uint32_t *out_root, uint32_t *out_cluster, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_components_identity, dim3(components_grid(rows)), dim3(COMPONENTS_BLOCK), 0, stream, rows, out_root, out_cluster);
+    return hipGetLastError();
+}
+
+hipError_t launch_components(const ComponentsArgs &a)
+{
+    const dim3 grid(components_grid(a.rows)), block(COMPONENTS_BLOCK);
+    const unsigned nb = (unsigned)join_scan_blocks(a.rows);
+    hipLaunchKernelGGL(k_components_init, grid, block, 0, a.stream, a.rows, a.parent, a.status);
+    hipLaunchKernelGGL(k_components_link, dim3(components_link_grid(a.nnz)), block, 0, a.stream, a.indptr, a.index, a.rows, a.nnz, a.parent, a.status);
+    hipLaunchKernelGGL(k_components_compress, grid, block, 0, a.stream, a.rows, a.parent, a.out_root, a.scan);
+    hipLaunchKernelGGL(k_join_scan_sums, dim3(nb), dim3(JOIN_SCAN_BLOCK), 0, a.stream, a.scan, (uint64_t)a.rows, a.sums);
+    hipLaunchKernelGGL(k_join_scan_top, dim3(1), dim3(JOIN_SCAN_BLOCK), 0, a.stream, a.sums, (uint64_t)nb);
+    hipLaunchKernelGGL(k_join_scan_apply, dim3(nb), dim3(JOIN_SCAN_BLOCK), 0, a.stream, a.scan, (uint64_t)a.rows, a.sums);
+    hipLaunchKernelGGL(k_components_rank, grid, block, 0, a.stream, a.rows, a.out_root, a.scan, a.out_cluster, a.status);
     return hipGetLastError();
 }
 

@@ -387,3 +387,31 @@ def match_join(expr: IntoExpr, candidates: IntoExpr, measure: str = "jaro_winkle
         args=args,
         is_elementwise=False,
     )
+
+
+# (a statement of its own again)
+__all__ += ["cluster"]
+
+_CLUSTER_MEASURES = _MATCH_JOIN_MEASURES + _JOIN_SCORERS
+
+
+def cluster(expr: IntoExpr, measure: str = "jaro_winkler", min_score: float | None = None) -> pl.Expr:
+    """The duplicate groups of a column: rows that score at least min_score by `measure` (one of the five measures of this package,
+    "ratio" or "token_sort_ratio") are linked, and every row gets the row number of the first member of its group, as UInt32 --
+
+        df.with_columns(g=cluster("name", "jaro_winkler", 0.92)).group_by("g")
+
+    groups the spellings of one customer.  Groups are the connected components of the links, so they chain: a~b~c puts `a` and `c`
+    together even where they do not match each other.  A null row gives null and never joins anything.  min_score is required (None
+    would put every row in one group).  The whole column is clustered at once, whatever its chunks.  Not in the upstream
+    polars-strsim."""
+    if measure not in _CLUSTER_MEASURES:
+        raise ValueError(f"unknown measure {measure!r}; expected one of {_CLUSTER_MEASURES}")
+    if min_score is None:
+        raise ValueError("cluster: min_score is required (None would put every row in one group)")
+    return register_plugin_function(
+        plugin_path=_PLUGIN_DIR,
+        function_name="cluster_" + measure,
+        args=[parse_into_expr(expr, dtype=pl.Utf8), pl.lit(min_score, dtype=pl.Float64)],
+        is_elementwise=False,
+    )

@@ -423,6 +423,48 @@ def match_dedupe_pairs(measure, column, min_score, ctx=None, processor=None):
     return np.repeat(np.arange(len(column), dtype=np.int64), np.diff(indptr)), index, score
 
 
+CLUSTER_MEASURES = MEASURES + ("ratio", "token_sort_ratio")
+_CLUSTER_MEASURE = {**{m: m for m in MEASURES}, "ratio": "indel", "indel": "indel", "token_sort_ratio": "token_sort_ratio"}
+
+
+def components(indptr, index, rows=None, ctx=None):
+    """Connected components of a CSR graph, its edges read as undirected (the CSR of join(..., upper=True) as it is): (root int64
+    [rows], cluster int64 [rows], count).  root[v] is the smallest row of v's component, cluster[v] the number of roots below it --
+    the clusters are numbered 0 .. count - 1 in order of their first member -- and a row without an edge is a cluster of one."""
+    ctx = ctx or default_context()
+    root, cluster, count = ctx.components(np.asarray(indptr), np.asarray(index), rows)
+    return root.astype(np.int64), cluster.astype(np.int64), count
+
+
+def cluster(measure, column, min_score, ctx=None, processor=None):
+    """The duplicate groups of one column: the rows that score >= min_score by `measure` (CLUSTER_MEASURES; "indel" is an alias of
+    "ratio") are linked and the connected components of the links are the clusters -> (root int64 [n], cluster int64 [n], count).
+    root[r] is the position of the first member of r's cluster, cluster[r] numbers the clusters 0 .. count - 1 in order of their
+    first member.  Components chain: a ~ b and b ~ c put a and c together even where a and c do not match each other.  The pairs of
+    the self-join stay on the GPU.  A null row never joins anything: its root and cluster are -1 and it is not counted.
+    min_score=None is refused (it would put every row in one cluster).  processor="default_process" as in join()."""
+    if not isinstance(measure, str) or measure not in _CLUSTER_MEASURE:
+        raise ValueError(f"no cluster by measure {measure!r} (one of {CLUSTER_MEASURES})")
+    if min_score is None:
+        raise ValueError("cluster: min_score=None would put every row in one cluster; pass a score in [0, 1]")
+    if processor is not None:
+        processor_id(processor)
+    ctx = ctx or default_context()
+    column = list(column)
+    pos = np.flatnonzero(np.array([c is not None for c in column], dtype=bool))  # the nulls are dropped, never kept as ""
+    root = np.full(len(column), -1, dtype=np.int64)
+    label = np.full(len(column), -1, dtype=np.int64)
+    if not len(pos):
+        return root, label, 0
+    o, v = pack_strings([column[j] for j in pos])
+    if processor is not None:
+        o, v = ctx.default_process_host(o, v)
+    r, c, count = ctx.cluster(_CLUSTER_MEASURE[measure], o, v, min_score)
+    root[pos] = pos[np.asarray(r).astype(np.int64)]
+    label[pos] = np.asarray(c).astype(np.int64)
+    return root, label, count
+
+
 __all__ = ["default_process", "PROCESSORS", "best_match", "nearest", "Codec", "Context", "device_count", "pack_strings", "split_offsets", "similarity", "levenshtein", "jaro",
            "jaro_winkler", "jaccard", "sorensen_dice", "osa", "indel", "measure_supported", "distance", "levenshtein_distance", "osa_distance",
            "indel_distance", "INDEL_MEASURES", "partial_ratio", "partial_ratio_alignment", "PARTIAL_MEASURES",
@@ -430,4 +472,4 @@ __all__ = ["default_process", "PROCESSORS", "best_match", "nearest", "Codec", "C
            "token_ratio", "partial_token_sort_ratio", "partial_token_set_ratio", "partial_token_ratio", "wratio", "WEIGHTED_MEASURES",
            "DISTANCE_MEASURES", "DISTANCE_UNBOUNDED", "MEASURES", "EXTRA_MEASURES", "MEASURE_ID", "STATUS", "ShapeMismatch", "StrsimError",
            "extract", "EXTRACT_SCORERS", "cdist", "CDIST_MEASURES", "join", "dedupe_pairs", "JOIN_SCORERS",
-           "match_join", "match_dedupe_pairs", "MATCH_JOIN_MEASURES"]
+           "match_join", "match_dedupe_pairs", "MATCH_JOIN_MEASURES", "components", "cluster", "CLUSTER_MEASURES"]

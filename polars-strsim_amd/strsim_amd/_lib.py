@@ -173,6 +173,14 @@ def lib():
         f = getattr(L, name)
         f.restype = i32
         f.argtypes = [vp, i32, vp, vp, u64, vp, vp, u64, C.c_double, C.c_uint32, u64, vp, vp, vp, C.POINTER(u64)]
+    for name in ("strsim_components_device", "strsim_components_host"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, u64, vp, vp, u64, vp, vp, C.POINTER(u64)]
+    for name in ("strsim_cluster_device", "strsim_cluster_host"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, i32, vp, vp, u64, C.c_double, vp, vp, C.POINTER(u64), C.POINTER(u64)]
     L.strsim_measure_supported.restype = C.c_uint32
     L.strsim_measure_supported.argtypes = [i32, i32]
     L.strsim_pairs_device_all.restype = i32

@@ -473,6 +473,56 @@ class Context:
             cap = nnz.value  # the hits did not fit: nothing was written; once more with the exact size
         raise StrsimError(7, f"{entry}: nnz changed between two calls on the same columns ({nnz.value} > {cap})")
 
+    def components(self, indptr, index, rows=None):
+        """Connected components of a CSR graph (strsim_components_host for numpy arrays, strsim_components_device for torch tensors
+        on this context's device): the edges (i, index[e]), e in [indptr[i], indptr[i + 1]), read as undirected -> (root [rows],
+        cluster [rows], count).  root[v] is the smallest row of v's component, cluster[v] the number of roots below it (clusters are
+        numbered in order of their first member), count the number of components.  rows=None: len(indptr) - 1.  indptr is uint64 /
+        int64, index uint32 / int32.  numpy in: uint32 arrays out; device tensors in: int32 tensors out.  The call waits once."""
+        count = C.c_uint64(0)
+        if not isinstance(indptr, np.ndarray) and hasattr(indptr, "data_ptr"):
+            import torch
+            n = max(indptr.numel() - 1, 0) if rows is None else int(rows)
+            nnz = index.numel()
+            if indptr.numel() != n + 1 or indptr.dtype != torch.int64 or index.dtype != torch.int32:
+                raise ValueError(f"components: indptr must be an int64 tensor of {n + 1} words and index an int32 tensor")
+            root = torch.empty(n, dtype=torch.int32, device=indptr.device)
+            cluster = torch.empty(n, dtype=torch.int32, device=indptr.device)
+            check(lib().strsim_components_device(self._h, n, indptr.data_ptr(), index.data_ptr() if nnz else None, nnz,
+                                                 root.data_ptr() if n else None, cluster.data_ptr() if n else None, C.byref(count)))
+            return root, cluster, int(count.value)
+        ip = np.ascontiguousarray(indptr).astype(np.uint64, copy=False)
+        ix = np.ascontiguousarray(index).astype(np.uint32, copy=False)
+        n = max(ip.size - 1, 0) if rows is None else int(rows)
+        if ip.size != n + 1:
+            raise ValueError(f"components: indptr must hold rows + 1 = {n + 1} words, got {ip.size}")
+        root, cluster = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32)
+        check(lib().strsim_components_host(self._h, n, ip.ctypes.data, ix.ctypes.data if ix.size else None, ix.size,
+                                           root.ctypes.data if n else None, cluster.ctypes.data if n else None, C.byref(count)))
+        return root, cluster, int(count.value)
+
+    def cluster(self, measure, offsets, values, min_score, with_nnz=False):
+        """The duplicate groups of one column (strsim_cluster_host for numpy columns, strsim_cluster_device for torch tensors on this
+        context's device): the upper self-join of the column at min_score by `measure` (one of the five reference measures, "indel"
+        or "token_sort_ratio"), then the components of its hits -> (root, cluster, count) as components() returns them; the pairs
+        never reach the host.  with_nnz=True appends the number of pairs."""
+        count, nnz = C.c_uint64(0), C.c_uint64(0)
+        if not isinstance(offsets, np.ndarray) and hasattr(offsets, "data_ptr"):
+            import torch
+            n = max(offsets.numel() - 1, 0)
+            root = torch.empty(n, dtype=torch.int32, device=offsets.device)
+            cluster = torch.empty(n, dtype=torch.int32, device=offsets.device)
+            check(lib().strsim_cluster_device(self._h, measure_id(measure), offsets.data_ptr(), values.data_ptr(), n, float(min_score),
+                                              root.data_ptr() if n else None, cluster.data_ptr() if n else None, C.byref(count), C.byref(nnz)))
+        else:
+            o, v, n = _host_column(offsets, values)
+            n = max(n, 0)
+            root, cluster = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32)
+            check(lib().strsim_cluster_host(self._h, measure_id(measure), o.ctypes.data, v.ctypes.data, n, float(min_score),
+                                            root.ctypes.data if n else None, cluster.ctypes.data if n else None, C.byref(count), C.byref(nnz)))
+        out = (root, cluster, int(count.value))
+        return out + (int(nnz.value),) if with_nnz else out
+
 class Codec:
     """Lossless 16-bit transport codec for one measure's result column (include/strsim_amd.h: strsim_codec_*)."""
     EXC_CAP = 1 << 20
