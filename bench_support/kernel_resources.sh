@@ -16,8 +16,11 @@
 #                    a list) and the join kernels around the sweep
 #         cluster -- the kernels of strsim_components_device (strsim_cluster_device adds none: it runs the join's) and the join's
 #                    scan kernels they reuse
+#         qgram   -- the kernels of q-gram similarity (strsim_qgram.h), and below them the Indel / OSA / distance kernels whose headers
+#                    it includes (their figures must not move when strsim_qgram.h changes)
 ROOT=$(cd "$(dirname "$0")/.." && pwd); OUT=${TMPDIR:-/tmp}/strsim_co; mkdir -p $OUT
 case "$1" in
+    qgram) FILTER='k_qgram_|k_indel_|k_osa_|k_dist_' ;;
     wratio) FILTER='k_wratio_|k_take_|k_max_f64|k_token_|k_partial_|k_indel_|k_osa_|k_dist_' ;;
     token) FILTER='k_token_|k_partial_|k_indel_|k_osa_|k_dist_' ;;
     partial) FILTER='k_partial_|k_indel_|k_osa_|k_dist_' ;;

@@ -216,6 +216,16 @@ POLARS_PLUGIN_DECLARE(cluster_sorensen_dice)
  * belong to the array's release callback. */
 POLARS_PLUGIN_DECLARE(default_process)
 
+/* q-gram similarity (not in the reference; strsim_qgram_host of strsim_amd.h): Jaccard, Sorensen-Dice, overlap and cosine over the
+ * q-grams of the two strings.  Inputs 0 and 1 as for the similarities (shape rule, literal broadcast, nulls); input 2 is q, a
+ * length-1 non-null UInt32 series holding 1, 2 or 3 (required: without it the call fails with "q is missing: ..."); an optional
+ * input 3 is the set flag, a length-1 non-null UInt32 series holding 0 (multisets of grams, the default) or 1 (sets).  Output: one
+ * Float64 chunk named after input 0, null where either input is null.  These calls bypass the small-call combiner. */
+POLARS_PLUGIN_DECLARE(qgram_jaccard)
+POLARS_PLUGIN_DECLARE(qgram_sorensen_dice)
+POLARS_PLUGIN_DECLARE(qgram_overlap)
+POLARS_PLUGIN_DECLARE(qgram_cosine)
+
 /* ---- diagnostics of this implementation (not part of the polars-ffi contract; the engine never calls them) ----
  * The plugin's staging -- pinned host memory and its device mirrors, per pipeline set -- is leased per call from one process-wide
  * pool under POLARS_STRSIM_STAGING_BUDGET_MB (csrc/plugin_pack.h: StagingPool; reference counterpart: the per-call scratch of

@@ -308,6 +308,39 @@ STRSIM_API int strsim_distance_host(strsim_ctx_t *ctx, int measure,
                                     uint32_t max_distance, uint32_t *out, uint64_t out_rows);
 
 /*
+ * q-gram similarity (found by dlsym, like the distance calls: the ABI version stays 1.7, and no measure id is added).  Strings are
+ * sequences of Unicode scalar values; for q = 1, 2 or 3, G(s) is the multiset of the max(|s| - q + 1, 0) contiguous q-tuples of s.
+ * Multiset mode (flags = 0): na = |G(a)|, nb = |G(b)|, I = the sum over the grams of min(count in a, count in b).  Set mode
+ * (STRSIM_QGRAM_SET): na and nb are the numbers of distinct grams, I the number of grams present in both.  In this order:
+ * a == b bytewise (both empty included) is 1.0; na == 0 or nb == 0 is 0.0; otherwise, by `kind`,
+ *   STRSIM_QGRAM_JACCARD        I / (na + nb - I)
+ *   STRSIM_QGRAM_SORENSEN_DICE  (2.0 * I) / (na + nb)
+ *   STRSIM_QGRAM_OVERLAP        I / min(na, nb)
+ *   STRSIM_QGRAM_COSINE         I / sqrt(na * nb), the product formed in 64-bit integers
+ * each with correctly rounded f64 operations.  A NUL byte is a character like any other, and no gram holds padding.  At q = 1 in
+ * multiset mode the first two are STRSIM_JACCARD and STRSIM_SORENSEN_DICE of strsim_pairs_device, bit for bit.
+ *
+ * Shape rule, literal broadcast and out_rows as strsim_pairs_device; zero rows is a no-op.  A kind outside 0..3, q outside 1..3 or
+ * a flag bit other than STRSIM_QGRAM_SET is STRSIM_ERR_ARG; the arguments are checked first and the context last (a NULL ctx is
+ * STRSIM_ERR_ARG too): no argument error needs a device.  Rows where both strings are ASCII and at most 64 bytes are one pair per
+ * lane, every other row one pair per wave (any length; pairs of more than 2048 grams use a scratch buffer the context grows), and
+ * strsim_ctx_last_wave_rows counts the latter when the call returns.  Every row is complete in stream order; the call waits once
+ * for the stream after its first kernel (to size the second), so everything enqueued before it has completed when it returns.  It
+ * is not a pending call of strsim_ctx_synchronize and adds nothing to strsim_ctx_last_long_rows / _last_late_rows.  Its kernels
+ * read only the bytes the offsets describe.  The host variant stages the columns (strsim_pairs_host's copy path) and is synchronous.
+ */
+enum { STRSIM_QGRAM_JACCARD = 0, STRSIM_QGRAM_SORENSEN_DICE = 1, STRSIM_QGRAM_OVERLAP = 2, STRSIM_QGRAM_COSINE = 3 };
+#define STRSIM_QGRAM_SET 1u /* flags bit 0: sets of grams instead of multisets; every other bit must be 0 */
+STRSIM_API int strsim_qgram_device(strsim_ctx_t *ctx, int kind, uint32_t q, uint32_t flags,
+                                   const uint32_t *a_offsets, const uint8_t *a_values, uint64_t a_rows,
+                                   const uint32_t *b_offsets, const uint8_t *b_values, uint64_t b_rows,
+                                   double *out, uint64_t out_rows);
+STRSIM_API int strsim_qgram_host(strsim_ctx_t *ctx, int kind, uint32_t q, uint32_t flags,
+                                 const uint32_t *a_offsets, const uint8_t *a_values, uint64_t a_rows,
+                                 const uint32_t *b_offsets, const uint8_t *b_values, uint64_t b_rows,
+                                 double *out, uint64_t out_rows);
+
+/*
  * Partial ratio with its alignment (found by dlsym, like the distance calls: the ABI version stays 1.7).  out_score[i] is bit for
  * bit what strsim_pairs_device(STRSIM_PARTIAL_RATIO) returns for row i.  out_span is out_rows x 4 uint32, row-major: a_start, a_end,
  * b_start, b_end -- half open, in Unicode scalar values (not bytes).  The needle (the shorter string; a when the lengths are equal,

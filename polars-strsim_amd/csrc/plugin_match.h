@@ -235,13 +235,12 @@ struct Packed {
 strsim_ctx_t *leased_context(PipeLease &lease) { return lease.set->at(0).open(plugin_devices()[0]); }
 
 // ---- the two search families (best match, nearest): input 0 the queries, input 1 the candidates ----
-// max_distance from input 2 of the distance and nearest functions (STRSIM_DISTANCE_UNBOUNDED without one)
-uint32_t distance_cutoff(SeriesExport *inputs, size_t n_inputs)
+// The value of a length-1, non-null UInt32 series (Polars pickles keyword arguments; a literal series needs no parsing); `what`
+// names the argument in the messages.
+uint32_t uint32_literal(const SeriesExport &s, const std::string &what)
 {
-    if (n_inputs == 2) return STRSIM_DISTANCE_UNBOUNDED;
-    const SeriesExport &s = inputs[2];
     if (!s.field || !s.field->format || strcmp(s.field->format, "I") != 0)
-        fail(std::string("max_distance must be a UInt32 series, got Arrow format '") + (s.field && s.field->format ? s.field->format : "") + "'");
+        fail(what + " must be a UInt32 series, got Arrow format '" + (s.field && s.field->format ? s.field->format : "") + "'");
     uint64_t rows = 0;
     const ArrowArray *one = nullptr;
     for (size_t i = 0; i < s.len; ++i) {
@@ -250,11 +249,18 @@ uint32_t distance_cutoff(SeriesExport *inputs, size_t n_inputs)
         rows += (uint64_t)a->length;
         one = a;
     }
-    if (rows != 1) fail("max_distance must be a single value, got " + std::to_string(rows) + " rows");
+    if (rows != 1) fail(what + " must be a single value, got " + std::to_string(rows) + " rows");
     const uint8_t *valid = one->n_buffers > 0 ? static_cast<const uint8_t *>(one->buffers[0]) : nullptr;
-    if (one->null_count > 0 || (valid && !bit_at(valid, one->offset))) fail("max_distance must not be null");
-    if (one->n_buffers < 2 || !one->buffers[1]) fail("max_distance: the UInt32 series has no data buffer");
+    if (one->null_count > 0 || (valid && !bit_at(valid, one->offset))) fail(what + " must not be null");
+    if (one->n_buffers < 2 || !one->buffers[1]) fail(what + ": the UInt32 series has no data buffer");
     return static_cast<const uint32_t *>(one->buffers[1])[one->offset];
+}
+
+// max_distance from input 2 of the distance and nearest functions (STRSIM_DISTANCE_UNBOUNDED without one)
+uint32_t distance_cutoff(SeriesExport *inputs, size_t n_inputs)
+{
+    if (n_inputs == 2) return STRSIM_DISTANCE_UNBOUNDED;
+    return uint32_literal(inputs[2], "max_distance");
 }
 
 struct SearchInputs {

@@ -150,6 +150,7 @@ void export_primitive(const char *format, const char *name, uint64_t n, void *da
 }
 #include "plugin_match.h"
 #include "plugin_distance.h"
+#include "plugin_qgram.h"
 #include "plugin_partial.h"
 #include "plugin_nearest.h"
 #include "plugin_extract.h"
@@ -260,6 +261,8 @@ void _polars_plugin_strsim_coalesce_stats(uint64_t out[4]) { if (out) combiner()
 #define POLARS_PLUGIN_DEFINE_DISTANCE(name, id)                                                \
     POLARS_PLUGIN_EXPORT(name##_distance, run_distance(id, inputs, n_inputs, return_value), \
                          field_named_after_input0(input_fields, n_fields, return_value, [](ArrowSchema *s, const char *n) { fill_named_schema(s, "I", n); }))
+#define POLARS_PLUGIN_DEFINE_QGRAM(name, kind) \
+    POLARS_PLUGIN_EXPORT(qgram_##name, run_qgram(kind, inputs, n_inputs, return_value), field_entry(input_fields, n_fields, return_value))
 #define POLARS_PLUGIN_DEFINE_NEAREST(name, id) \
     POLARS_PLUGIN_EXPORT(nearest_##name, run_nearest(id, inputs, n_inputs, return_value), STRUCT_FIELD(NEAREST_STRUCT))
 #define POLARS_PLUGIN_DEFINE_EXTRACT(name, id) \
@@ -559,6 +562,10 @@ POLARS_PLUGIN_EXPORT(partial_ratio_alignment, run_partial_alignment(inputs, n_in
 POLARS_PLUGIN_DEFINE_DISTANCE(levenshtein, STRSIM_LEVENSHTEIN)
 POLARS_PLUGIN_DEFINE_DISTANCE(osa, STRSIM_OSA)
 POLARS_PLUGIN_DEFINE_DISTANCE(indel, STRSIM_INDEL)
+POLARS_PLUGIN_DEFINE_QGRAM(jaccard, STRSIM_QGRAM_JACCARD)
+POLARS_PLUGIN_DEFINE_QGRAM(sorensen_dice, STRSIM_QGRAM_SORENSEN_DICE)
+POLARS_PLUGIN_DEFINE_QGRAM(overlap, STRSIM_QGRAM_OVERLAP)
+POLARS_PLUGIN_DEFINE_QGRAM(cosine, STRSIM_QGRAM_COSINE)
 POLARS_PLUGIN_DEFINE_NEAREST(levenshtein, STRSIM_LEVENSHTEIN)
 POLARS_PLUGIN_DEFINE_NEAREST(osa, STRSIM_OSA)
 POLARS_PLUGIN_DEFINE_EXTRACT(ratio, STRSIM_INDEL)

@@ -21,6 +21,7 @@
 #include "strsim_osa.h"
 #include "strsim_distance.h"
 #include "strsim_indel.h"
+#include "strsim_qgram.h"
 #include "strsim_partial.h"
 #include "strsim_token.h"
 #include "strsim_wratio.h"
@@ -708,18 +709,20 @@ static int dist_report(strsim_ctx *c)
 static constexpr size_t OSA_SCRATCH_BUDGET = (size_t)1 << 30; // the wave kernel runs fewer waves rather than use more scratch
 
 // Which pair of kernels a call runs, and what they take beside the LaunchArgs.
-enum TwoPassKind { TP_OSA, TP_DIST, TP_INDEL, TP_PARTIAL };
+enum TwoPassKind { TP_OSA, TP_DIST, TP_INDEL, TP_PARTIAL, TP_QGRAM };
 struct TwoPassCall {
     TwoPassKind kind;
-    int measure;     // TP_DIST: STRSIM_LEVENSHTEIN or STRSIM_OSA
+    int measure;     // TP_DIST: STRSIM_LEVENSHTEIN or STRSIM_OSA; TP_QGRAM: the kind (STRSIM_QGRAM_*)
     uint32_t k;      // TP_DIST, TP_INDEL: the cutoff (DIST_UNBOUNDED: none)
     uint32_t *out32; // TP_DIST: the distances; TP_INDEL: the distances, or nullptr for the similarity in la.out
     uint32_t *span;  // TP_PARTIAL: the alignment, or nullptr for the score alone
+    uint32_t q = 0u;     // TP_QGRAM: 1..3
+    uint32_t flags = 0u; // TP_QGRAM: STRSIM_QGRAM_SET
 };
 static const char *const TWO_PASS_LANE[] = {"kernel launch (k_osa_lane)", "kernel launch (k_dist_lane)", "kernel launch (k_indel_lane)",
-                                            "kernel launch (k_partial_lane)"};
+                                            "kernel launch (k_partial_lane)", "kernel launch (k_qgram_lane)"};
 static const char *const TWO_PASS_WAVE[] = {"kernel launch (k_osa_wave)", "kernel launch (k_dist_wave)", "kernel launch (k_indel_wave)",
-                                            "kernel launch (k_partial_wave)"};
+                                            "kernel launch (k_partial_wave)", "kernel launch (k_qgram_wave)"};
 
 static hipError_t two_pass_lane(const TwoPassCall &t, const LaunchArgs &la, uint32_t *list)
 {
@@ -727,16 +730,22 @@ static hipError_t two_pass_lane(const TwoPassCall &t, const LaunchArgs &la, uint
     case TP_OSA: return launch_osa_lane(la, list);
     case TP_DIST: return launch_dist_lane(t.measure, la, t.k, t.out32, list);
     case TP_INDEL: return launch_indel_lane(la, t.k, t.out32, list);
+    case TP_QGRAM: return launch_qgram_lane(la, t.measure, t.q, (t.flags & STRSIM_QGRAM_SET) != 0u, list);
     default: return launch_partial_lane(la, t.span, list);
     }
 }
 
-static hipError_t two_pass_wave(const TwoPassCall &t, const LaunchArgs &la, const uint32_t *list, int grid, uint32_t *scratch, uint64_t words)
+// a bound of the grams of a pair on a q-gram call's work list: max_len / pad1[0] bound its shorter and its longer string (bytes)
+static uint64_t qgram_grams_bound(const DevStatus &st) { return (uint64_t)st.max_len + st.pad1[0]; }
+
+static hipError_t two_pass_wave(const TwoPassCall &t, const LaunchArgs &la, const DevStatus &st, const uint32_t *list, int grid, uint32_t *scratch,
+                                uint64_t words)
 {
     switch (t.kind) {
     case TP_OSA: return launch_osa_wave(la, list, grid, scratch, words);
     case TP_DIST: return launch_dist_wave(t.measure, la, t.k, t.out32, list, grid, scratch, words);
     case TP_INDEL: return launch_indel_wave(la, t.k, t.out32, list, grid, scratch, words);
+    case TP_QGRAM: return launch_qgram_wave(la, t.measure, t.q, (t.flags & STRSIM_QGRAM_SET) != 0u, qgram_grams_bound(st), list, grid, scratch, words);
     default: return launch_partial_wave(la, t.span, list, grid, scratch, words);
     }
 }
@@ -748,6 +757,10 @@ static uint64_t two_pass_slot_words(TwoPassKind kind, const DevStatus &st)
         // (partial_wave_words grows with both arguments: the larger of the two forms at the bounds covers every pair)
         const uint64_t w = std::max(partial_wave_words(64u, st.pad1[0]), partial_wave_words(std::max(st.max_len, 65u), st.pad1[0]));
         return w > PARTIAL_WAVE_LDS_WORDS ? (w + 1u) & ~(uint64_t)1 : 0u; // (64-bit words inside a slot)
+    }
+    if (kind == TP_QGRAM) { // the table of both strings' grams and the values of one string
+        const uint64_t grams = qgram_grams_bound(st);
+        return grams > QGRAM_WAVE_LDS_GRAMS ? qgram_wave_slot_words(grams, st.pad1[0]) : 0u;
     }
     if (st.max_len <= OSA_WAVE_LDS_CPS) return 0u; // (max_len bounds the pattern in scalar values: it is a byte length)
     return kind == TP_OSA ? osa_wave_slot_words(st.max_len) : kind == TP_DIST ? dist_wave_slot_words(st.max_len) : indel_wave_slot_words(st.max_len);
@@ -779,7 +792,7 @@ static int two_pass(strsim_ctx *c, const LaunchArgs &la, const TwoPassCall &t, i
         if (rc) return rc;
         scratch = c->osa_scratch.as<uint32_t>();
     }
-    e = two_pass_wave(t, la, list, grid, scratch, words);
+    e = two_pass_wave(t, la, st, list, grid, scratch, words);
     if (e != hipSuccess) return hip_fail(e, TWO_PASS_WAVE[t.kind]);
     c->enqueued_ops += 1u;
     return STRSIM_OK;
@@ -1784,6 +1797,58 @@ int strsim_distance_host(strsim_ctx_t *c, int measure, const uint32_t *a_off, co
     return elementwise_host(
         c, distance_check("strsim_distance_host", c, measure, a, b, out, out_rows), a, b, out_rows, out, out_rows * 4, nullptr, 0,
         [&](const Staged &s, uint8_t *d_out, uint8_t *) { return distance_device_impl(c, measure, s.a, s.b, max_distance, (uint32_t *)d_out, out_rows); },
+        nothing_to_settle);
+}
+
+} // extern "C"
+
+// ---- q-gram similarity (strsim_qgram.h) ----
+
+static int qgram_check(const char *who, strsim_ctx_t *c, int kind, uint32_t q, uint32_t flags, const Col &a, const Col &b, const double *out,
+                       uint64_t out_rows)
+{
+    if (kind < STRSIM_QGRAM_JACCARD || kind > STRSIM_QGRAM_COSINE) {
+        set_error("%s: unknown kind %d (STRSIM_QGRAM_JACCARD, _SORENSEN_DICE, _OVERLAP or _COSINE: 0..3)", who, kind);
+        return STRSIM_ERR_ARG;
+    }
+    if (q < 1u || q > QGRAM_MAX_Q) { set_error("%s: q=%u is outside 1..%u", who, q, QGRAM_MAX_Q); return STRSIM_ERR_ARG; }
+    if (flags & ~STRSIM_QGRAM_SET) {
+        set_error("%s: unknown flag bits 0x%x (STRSIM_QGRAM_SET is the only flag)", who, flags & ~STRSIM_QGRAM_SET);
+        return STRSIM_ERR_ARG;
+    }
+    return elementwise_check(who, c, a.rows, b.rows, out_rows, a.off && a.val && b.off && b.val && out);
+}
+
+// k_qgram_lane, then k_qgram_wave.  The size of the work list is what strsim_ctx_last_wave_rows reports (two_pass has waited for it).
+static int qgram_device_impl(strsim_ctx_t *c, int kind, uint32_t q, uint32_t flags, const Col &a, const Col &b, double *out, uint64_t n)
+{
+    int rc = dist_prepare(c, n);
+    if (rc) return rc;
+    const LaunchArgs la = two_pass_args(c, a, b, out, n, c->dist_status);
+    rc = two_pass(c, la, TwoPassCall{TP_QGRAM, kind, 0u, nullptr, nullptr, q, flags}, -1);
+    if (rc) return rc;
+    c->last_wave_rows = c->dist_status_host->wave_rows;
+    return STRSIM_OK;
+}
+
+extern "C" {
+
+int strsim_qgram_device(strsim_ctx_t *c, int kind, uint32_t q, uint32_t flags, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
+                        const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t out_rows)
+{
+    const Col a{a_off, a_val, a_rows}, b{b_off, b_val, b_rows};
+    int rc = qgram_check("strsim_qgram_device", c, kind, q, flags, a, b, out, out_rows);
+    if (rc || out_rows == 0) return rc;
+    return qgram_device_impl(c, kind, q, flags, a, b, out, out_rows);
+}
+
+int strsim_qgram_host(strsim_ctx_t *c, int kind, uint32_t q, uint32_t flags, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
+                      const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t out_rows)
+{
+    const Col a{a_off, a_val, a_rows}, b{b_off, b_val, b_rows};
+    return elementwise_host(
+        c, qgram_check("strsim_qgram_host", c, kind, q, flags, a, b, out, out_rows), a, b, out_rows, out, out_rows * 8, nullptr, 0,
+        [&](const Staged &s, uint8_t *d_out, uint8_t *) { return qgram_device_impl(c, kind, q, flags, s.a, s.b, (double *)d_out, out_rows); },
         nothing_to_settle);
 }
 

@@ -143,6 +143,14 @@ hipError_t launch_partial_lane(const LaunchArgs &a, uint32_t *span, uint32_t *wo
 hipError_t launch_partial_wave(const LaunchArgs &a, uint32_t *span, const uint32_t *worklist, int grid, uint32_t *scratch,
                                uint64_t slot_words);
 
+// q-gram similarity (strsim_qgram.h): the same two-kernel protocol.  kind: STRSIM_QGRAM_*, q: 1..3, set: the set mode.
+// k_qgram_lane leaves bounds of the work list's shorter and longer strings (bytes) in a.status->max_len and a.status->pad1[0];
+// grams: their sum, a bound of the grams of a listed pair, which picks the wave kernel's LDS table and lays out a scratch slot
+// (slot_words = qgram_wave_slot_words(grams, pad1[0]), for pairs of more than QGRAM_WAVE_LDS_GRAMS grams; nullptr without any).
+hipError_t launch_qgram_lane(const LaunchArgs &a, int kind, uint32_t q, bool set, uint32_t *worklist);
+hipError_t launch_qgram_wave(const LaunchArgs &a, int kind, uint32_t q, bool set, uint64_t grams, const uint32_t *worklist, int grid,
+                             uint32_t *scratch, uint64_t slot_words);
+
 // Token transforms (strsim_token.h), measure ids 14 and 16.  launch_token_bounds leaves a column's longest row and its first and
 // last offset in st (side 0 or 1; max_len zeroed first).  A form is a measuring pass (write = false: the bytes of row i into
 // out_off[i + 1], out_off[0] = 0, the rows the lane kernel cannot take onto `list`, counted in *count, zeroed first), then

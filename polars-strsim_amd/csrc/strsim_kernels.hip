@@ -27,6 +27,9 @@
 //                     outputs, a length prefilter and, in the wave tier, the block cutoff of Myers / Ukkonen.
 //   k_indel_lane / k_indel_wave  Indel (LCS) similarity and distance (measure 8, strsim_indel.h): one pair per lane for ASCII
 //                     strings of up to 128 bytes (1..4 mask words per wave), one pair per wave for the rest; in stream order.
+//   k_qgram_lane / k_qgram_wave  q-gram Jaccard, Dice, overlap and cosine (strsim_qgram.h; q = 1..3, multiset or set): one pair per
+//                     lane for ASCII strings of up to 64 bytes (gram masks from shifted match masks), one pair per wave through a
+//                     hash table of the grams of both strings for the rest; in stream order.
 //   k_partial_lane / k_partial_wave  partial ratio and its alignment (measure 10, strsim_partial.h): the best window of the longer
 //                     string against the shorter one, match masks built once per pair; ASCII strings of up to 32 bytes per lane,
 //                     the rest one pair per wave; in stream order.
@@ -68,6 +71,7 @@
 #include "strsim_distance.h"
 #include "strsim_indel.h"
 #include "strsim_partial.h"
+#include "strsim_qgram.h"
 #include "strsim_token.h"
 #include "strsim_wratio.h"
 #include "strsim_process.h"
@@ -761,6 +765,43 @@ hipError_t launch_indel_wave(const LaunchArgs &a, uint32_t k, uint32_t *out32, c
 {
     hipLaunchKernelGGL(k_indel_wave, dim3((unsigned)grid), dim3(64), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB, a.rowsB, k,
                        a.out, out32, worklist, a.status, scratch, slot_words);
+    return hipGetLastError();
+}
+
+// f(std::integral_constant<int, Q>, std::bool_constant<SET>): the q (1..3) and the mode of a q-gram call
+template <class F>
+static void with_qgram(uint32_t q, bool set, F f)
+{
+    auto mode = [&](auto Q) {
+        if (set) f(Q, std::true_type{});
+        else f(Q, std::false_type{});
+    };
+    if (q == 1u) mode(std::integral_constant<int, 1>{});
+    else if (q == 2u) mode(std::integral_constant<int, 2>{});
+    else mode(std::integral_constant<int, 3>{});
+}
+
+hipError_t launch_qgram_lane(const LaunchArgs &a, int kind, uint32_t q, bool set, uint32_t *worklist)
+{
+    with_qgram(q, set, [&](auto Q, auto SET) {
+        hipLaunchKernelGGL((k_qgram_lane<decltype(Q)::value, decltype(SET)::value>), lane_grid(a), dim3(256), 0, a.stream, a.offA, a.valA, a.rowsA,
+                           a.offB, a.valB, a.rowsB, a.n, kind, a.out, worklist, a.status);
+    });
+    return hipGetLastError();
+}
+
+hipError_t launch_qgram_wave(const LaunchArgs &a, int kind, uint32_t q, bool set, uint64_t grams, const uint32_t *worklist, int grid,
+                             uint32_t *scratch, uint64_t slot_words)
+{
+    const uint64_t slots = qgram_table_slots(grams); // (the layout of a scratch slot: qgram_wave_slot_words)
+    with_qgram(q, set, [&](auto Q, auto SET) {
+        if (grams <= QGRAM_WAVE_SMALL_GRAMS)
+            hipLaunchKernelGGL((k_qgram_wave<QGRAM_WAVE_SMALL_GRAMS, decltype(Q)::value, decltype(SET)::value>), dim3((unsigned)grid), dim3(64), 0,
+                               a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB, a.rowsB, kind, a.out, worklist, a.status, scratch, slot_words, slots);
+        else
+            hipLaunchKernelGGL((k_qgram_wave<QGRAM_WAVE_LDS_GRAMS, decltype(Q)::value, decltype(SET)::value>), dim3((unsigned)grid), dim3(64), 0,
+                               a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB, a.rowsB, kind, a.out, worklist, a.status, scratch, slot_words, slots);
+    });
     return hipGetLastError();
 }
 

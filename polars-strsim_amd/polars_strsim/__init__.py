@@ -415,3 +415,50 @@ def cluster(expr: IntoExpr, measure: str = "jaro_winkler", min_score: float | No
         args=[parse_into_expr(expr, dtype=pl.Utf8), pl.lit(min_score, dtype=pl.Float64)],
         is_elementwise=False,
     )
+
+
+# (a statement of its own again)
+__all__ += ["qgram_jaccard", "qgram_sorensen_dice", "qgram_overlap", "qgram_cosine"]
+
+_QGRAM_KINDS = ("jaccard", "sorensen_dice", "overlap", "cosine")
+
+
+def _qgram(kind: str, expr: IntoExpr, other: IntoExpr, q: int, multiset: bool) -> pl.Expr:
+    if kind not in _QGRAM_KINDS:
+        raise ValueError(f"unknown q-gram kind {kind!r}; expected one of {_QGRAM_KINDS}")
+    if isinstance(q, bool) or not isinstance(q, int) or not 1 <= q <= 3:
+        raise ValueError(f"q={q!r} is outside 1 .. 3")
+    return register_plugin_function(
+        plugin_path=_PLUGIN_DIR,
+        function_name="qgram_" + kind,
+        args=[parse_into_expr(expr), other, pl.lit(q, dtype=pl.UInt32), pl.lit(0 if multiset else 1, dtype=pl.UInt32)],
+        is_elementwise=True,
+    )
+
+
+def qgram_jaccard(expr: IntoExpr, other: IntoExpr, q: int = 2, multiset: bool = True) -> pl.Expr:
+    """Jaccard similarity over q-grams (q consecutive characters, q = 1, 2 or 3): I / (na + nb - I), with na and nb the grams of
+    the two strings and I those they share.  multiset=True counts a repeated gram as often as it occurs (I is the sum of the
+    smaller counts), False compares the sets of distinct grams.  Equal strings score 1.0, also when they are shorter than q;
+    otherwise a string without a gram scores 0.0.  `jaccard` is this at q = 1: there "abc" and "cba" score 1.0, here, at q = 2,
+    0.0.  Not in the upstream polars-strsim."""
+    return _qgram("jaccard", expr, other, q, multiset)
+
+
+def qgram_sorensen_dice(expr: IntoExpr, other: IntoExpr, q: int = 2, multiset: bool = True) -> pl.Expr:
+    """Sorensen-Dice similarity over q-grams: 2 I / (na + nb); q, multiset and the edge cases as in `qgram_jaccard`.  At q = 2 this
+    is the bigram Dice coefficient of the Rust `strsim` crate, without its removal of whitespace; `sorensen_dice` is this at q = 1.
+    Not in the upstream polars-strsim."""
+    return _qgram("sorensen_dice", expr, other, q, multiset)
+
+
+def qgram_overlap(expr: IntoExpr, other: IntoExpr, q: int = 2, multiset: bool = True) -> pl.Expr:
+    """Overlap coefficient over q-grams: I / min(na, nb) -- 1.0 when the grams of one string are all found in the other; q,
+    multiset and the edge cases as in `qgram_jaccard`.  Not in the upstream polars-strsim."""
+    return _qgram("overlap", expr, other, q, multiset)
+
+
+def qgram_cosine(expr: IntoExpr, other: IntoExpr, q: int = 2, multiset: bool = True) -> pl.Expr:
+    """Cosine (Ochiai) coefficient over q-grams: I / sqrt(na nb); q, multiset and the edge cases as in `qgram_jaccard`.  Not in the
+    upstream polars-strsim."""
+    return _qgram("cosine", expr, other, q, multiset)

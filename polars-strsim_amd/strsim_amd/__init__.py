@@ -8,7 +8,7 @@ validity mask), as in README.md:69-70.
 """
 import numpy as np
 
-from ._lib import PROCESSORS, DISTANCE_MEASURES, DISTANCE_UNBOUNDED, ENTRY_POINT_ID, EXTRA_MEASURES, INDEL_MEASURES, MEASURES, MEASURE_ID, PARTIAL_MEASURES, TOKEN_MEASURES, WEIGHTED_MEASURES, LIB_PATH, STATUS, ShapeMismatch, StrsimError, lib, processor_id
+from ._lib import PROCESSORS, QGRAM_KINDS, QGRAM_MAX_Q, qgram_args, DISTANCE_MEASURES, DISTANCE_UNBOUNDED, ENTRY_POINT_ID, EXTRA_MEASURES, INDEL_MEASURES, MEASURES, MEASURE_ID, PARTIAL_MEASURES, TOKEN_MEASURES, WEIGHTED_MEASURES, LIB_PATH, STATUS, ShapeMismatch, StrsimError, lib, processor_id
 from .context import Codec, Context, device_count, pack_strings, split_offsets
 
 _default_ctx = None
@@ -226,6 +226,24 @@ def distance(measure, a, b, max_distance=None, ctx=None):
     bo, bv = pack_strings(B)
     out = ctx.distance_host(measure, ao, av, bo, bv, max_distance)
     return np.ma.MaskedArray(out, mask=_null_mask(out.size, va, vb))
+
+
+def qgram(kind, a, b, q=2, multiset=True, ctx=None):
+    """q-gram similarity of two columns / a column and a literal -> f64 numpy array, NaN where either input is null.  kind is one
+    of QGRAM_KINDS, over the grams (q consecutive characters, q = 1, 2 or 3) of the two strings: with I the grams in common and
+    na, nb the grams of each, "jaccard" is I / (na + nb - I), "sorensen_dice" 2 I / (na + nb), "overlap" I / min(na, nb) and
+    "cosine" I / sqrt(na nb).  multiset=True counts a repeated gram as often as it occurs (I = sum of min(count_a, count_b)),
+    False compares the sets of distinct grams.  Equal strings score 1.0, also when they are shorter than q; otherwise a string
+    without a gram scores 0.0.  At q = 1 the first two are jaccard() and sorensen_dice()."""
+    qgram_args(kind, q, multiset)
+    ctx = ctx or default_context()
+    A, va = _as_column(a)
+    B, vb = _as_column(b)
+    ao, av = pack_strings(A)
+    bo, bv = pack_strings(B)
+    out = ctx.qgram_host(kind, ao, av, bo, bv, q, multiset)
+    out[_null_mask(out.size, va, vb)] = np.nan
+    return out
 
 
 def levenshtein_distance(a, b, max_distance=None, ctx=None):
@@ -472,4 +490,5 @@ __all__ = ["default_process", "PROCESSORS", "best_match", "nearest", "Codec", "C
            "token_ratio", "partial_token_sort_ratio", "partial_token_set_ratio", "partial_token_ratio", "wratio", "WEIGHTED_MEASURES",
            "DISTANCE_MEASURES", "DISTANCE_UNBOUNDED", "MEASURES", "EXTRA_MEASURES", "MEASURE_ID", "STATUS", "ShapeMismatch", "StrsimError",
            "extract", "EXTRACT_SCORERS", "cdist", "CDIST_MEASURES", "join", "dedupe_pairs", "JOIN_SCORERS",
-           "match_join", "match_dedupe_pairs", "MATCH_JOIN_MEASURES", "components", "cluster", "CLUSTER_MEASURES"]
+           "match_join", "match_dedupe_pairs", "MATCH_JOIN_MEASURES", "components", "cluster", "CLUSTER_MEASURES",
+           "qgram", "QGRAM_KINDS", "QGRAM_MAX_Q"]

@@ -52,6 +52,20 @@ def processor_id(processor):
 DISTANCE_MEASURES = ("levenshtein", "osa")
 DISTANCE_UNBOUNDED = 0xFFFFFFFF
 JOIN_UPPER = 1  # STRSIM_JOIN_UPPER: only pairs with j > i
+# The kinds of the q-gram calls (strsim_qgram_device / _host) in the order of their ids, STRSIM_QGRAM_JACCARD = 0 .. _COSINE = 3.  They
+# are not measures: q (1 .. QGRAM_MAX_Q) and the mode (STRSIM_QGRAM_SET = 1: sets of grams instead of multisets) come with the call.
+QGRAM_KINDS = ("jaccard", "sorensen_dice", "overlap", "cosine")
+QGRAM_MAX_Q = 3
+QGRAM_SET = 1
+
+
+def qgram_args(kind, q, multiset=True):
+    """(kind id, q, flags) of a q-gram call; ValueError for a kind that is not one of QGRAM_KINDS or a q outside 1 .. QGRAM_MAX_Q."""
+    if not isinstance(kind, str) or kind not in QGRAM_KINDS:
+        raise ValueError(f"unknown q-gram kind {kind!r} (one of {QGRAM_KINDS})")
+    if isinstance(q, bool) or not isinstance(q, int) or not 1 <= q <= QGRAM_MAX_Q:
+        raise ValueError(f"q={q!r} is outside 1 .. {QGRAM_MAX_Q}")
+    return QGRAM_KINDS.index(kind), q, 0 if multiset else QGRAM_SET
 
 STATUS = {0: "OK", 1: "ERR_SHAPE", 2: "ERR_ARG", 3: "ERR_NO_DEVICE", 4: "ERR_HIP", 5: "ERR_OOM", 6: "ERR_DTYPE",
           7: "ERR_INTERNAL", 8: "ERR_EARLIER_CALL"}
@@ -131,6 +145,10 @@ def lib():
         f = getattr(L, name)
         f.restype = i32
         f.argtypes = [vp, i32, vp, vp, u64, vp, vp, u64, C.c_uint32, vp, u64]
+    for name in ("strsim_qgram_device", "strsim_qgram_host"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, i32, C.c_uint32, C.c_uint32, vp, vp, u64, vp, vp, u64, vp, u64]
     for name in ("strsim_partial_alignment_device", "strsim_partial_alignment_host"):
         f = getattr(L, name)
         f.restype = i32

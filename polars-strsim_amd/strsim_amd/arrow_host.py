@@ -108,7 +108,8 @@ def call_plugin(name, a, b, layout="vu", names=("a", "b"), parallel=False, _prob
     """Evaluate plugin expression `name` over two columns (lists / pyarrow arrays / a single literal).
     Returns a pyarrow ChunkedArray of float64 (or of `out_type`: the best_match_* functions return a struct).  `layout` picks
     the Arrow string layout sent to the plugin.  `extra`: further inputs after the two columns, pyarrow arrays exported as they
-    are (the *_distance functions take max_distance as a one-row UInt32 array)."""
+    are (the *_distance functions take max_distance as a one-row UInt32 array; the qgram_* functions take q and, optionally, the set
+    flag the same way)."""
     out_type = pa.float64() if out_type is None else out_type
     L = _load()
     fn = getattr(L, "_polars_plugin_" + name)

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import DISTANCE_UNBOUNDED, JOIN_UPPER, StrsimError, check, lib, measure_id, processor_id
+from ._lib import DISTANCE_UNBOUNDED, JOIN_UPPER, StrsimError, check, lib, measure_id, processor_id, qgram_args
 
 
 def split_offsets(length, n):
@@ -205,6 +205,22 @@ class Context:
                                            out.data_ptr(), out.numel()))
         return out
 
+    def qgram_device(self, kind, a_offsets, a_values, b_offsets, b_values, q=2, multiset=True, out=None):
+        """q-gram similarity (strsim_qgram_device) of device tensors laid out as for pairs_device -> f64 tensor.  kind: one of
+        QGRAM_KINDS; q: 1, 2 or 3; multiset=False compares the sets of grams.  Complete in stream order; last_wave_rows counts the
+        rows that took the one-pair-per-wave tier."""
+        import torch
+        kid, q, flags = qgram_args(kind, q, multiset)
+        ra, rb = a_offsets.numel() - 1, b_offsets.numel() - 1
+        n = rb if ra == 1 else ra
+        _check_device_column(a_offsets, a_values)
+        _check_device_column(b_offsets, b_values)
+        if out is None:
+            out = torch.empty(n if (ra == rb or ra == 1 or rb == 1) else 0, dtype=torch.float64, device=a_offsets.device)
+        check(lib().strsim_qgram_device(self._h, kid, q, flags, a_offsets.data_ptr(), a_values.data_ptr(), ra,
+                                        b_offsets.data_ptr(), b_values.data_ptr(), rb, out.data_ptr(), out.numel()))
+        return out
+
     def partial_alignment_device(self, a_offsets, a_values, b_offsets, b_values, score=None, span=None):
         """Partial ratio with its alignment (strsim_partial_alignment_device) of device tensors laid out as for pairs_device ->
         (score f64 [n], span int32 [n, 4] holding uint32 a_start, a_end, b_start, b_end in characters).  Complete in stream order."""
@@ -327,6 +343,18 @@ class Context:
         out = np.empty(n, dtype=np.uint32)
         check(lib().strsim_distance_host(self._h, measure_id(measure), ao.ctypes.data, av.ctypes.data, ra,
                                          bo.ctypes.data, bv.ctypes.data, rb, _max_distance(max_distance), out.ctypes.data, n))
+        return out
+
+    def qgram_host(self, kind, a_offsets, a_values, b_offsets, b_values, q=2, multiset=True):
+        """Synchronous q-gram similarity (strsim_qgram_host): numpy uint32 offsets + uint8 values in, numpy f64 out.  kind: one of
+        QGRAM_KINDS; q: 1, 2 or 3; multiset=False compares the sets of grams."""
+        kid, q, flags = qgram_args(kind, q, multiset)
+        ao, av, ra = _host_column(a_offsets, a_values)
+        bo, bv, rb = _host_column(b_offsets, b_values)
+        n = _rows_out(ra, rb)
+        out = np.empty(n, dtype=np.float64)
+        check(lib().strsim_qgram_host(self._h, kid, q, flags, ao.ctypes.data, av.ctypes.data, ra, bo.ctypes.data, bv.ctypes.data, rb,
+                                      out.ctypes.data, n))
         return out
 
     def partial_alignment_host(self, a_offsets, a_values, b_offsets, b_values):
