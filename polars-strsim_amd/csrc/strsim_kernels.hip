@@ -63,6 +63,7 @@
 #include "strsim_bounds.h"
 #include "strsim_lane_core.h"
 #include "strsim_lane_lut.h"
+#include "strsim_lane_ptab.h"
 #include "strsim_lane_wide.h"
 #include "strsim_lane_sym.h"
 #include "strsim_kernels.h"

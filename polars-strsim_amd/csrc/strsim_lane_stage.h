@@ -48,6 +48,12 @@
 #ifndef STRSIM_STAGE_LUT
 #define STRSIM_STAGE_LUT 0x26 // bit m set: measure m (bit 5: the five-output pass) takes its match masks from per-lane LDS tables
 #endif                       //   (strsim_lane_lut.h) instead of bit fills.  Default: Jaro, Jaro-Winkler, the five-output pass.
+#ifndef STRSIM_STAGE_PTAB_MIN
+// Levenshtein, five-plane rounds of the short-row geometry: a round whose longest text runs at least this many columns takes its
+// match masks from per-lane register tables (strsim_lane_ptab.h: 23 instructions per four columns instead of 40, 36 to build
+// the tables), a shorter one keeps the bit fills.  33 = never (the table core is not instantiated).
+#define STRSIM_STAGE_PTAB_MIN 12
+#endif
 #ifndef STRSIM_JARO_KEEP_EQ_FILLS
 #define STRSIM_JARO_KEEP_EQ_FILLS 1 // the bit-fill form of Jaro's cores (the long-row geometry) keeps the first pass's masks for the zip pass too
 #endif
@@ -208,7 +214,7 @@ __device__ __forceinline__ uint32_t scan32_inclusive(uint32_t x)
 }
 
 // Levenshtein result as an index into the table of integer quotients (dist * QTAB_N + den); 0xFFFF is never produced
-template <int NP, bool USE_LUT> // match masks from bit fills / from the tables
+template <int NP, bool USE_LUT, bool PTAB = false> // match masks from bit fills / from the LDS tables; PTAB: register tables in long rounds
 __device__ __forceinline__ uint32_t stage_lev_code(const EqLut &lut, const uint32_t (&wa)[8], uint32_t la, const uint32_t (&wb)[8],
                                                    uint32_t lb, uint32_t tmin, uint32_t tmax, uint32_t stripped = 0u)
 {
@@ -218,7 +224,14 @@ __device__ __forceinline__ uint32_t stage_lev_code(const EqLut &lut, const uint3
     if (USE_LUT) lut_build<NP>(t, P, 0xFFFFFFFFu);
     const bool live = la != 0u && lb != 0u;
     const uint32_t la1 = live ? la : 1u, lb1 = live ? lb : 1u;
-    const uint32_t dist = USE_LUT ? lev_myers32_lut<NP>(t, wa, la1, tmin, tmax, P, lb1) : lev_myers32_snap<NP>(wa, la1, tmin, tmax, P, lb1);
+    uint32_t dist;
+    if constexpr (PTAB && NP == 5 && !USE_LUT && STRSIM_STAGE_PTAB_MIN <= 32) {
+        // (tmax is wave-uniform: one scalar branch per round)
+        if (tmax >= (uint32_t)STRSIM_STAGE_PTAB_MIN) dist = lev_myers32_ptab<NP>(wa, la1, tmin, tmax, P, lb1);
+        else dist = lev_myers32_snap<NP>(wa, la1, tmin, tmax, P, lb1);
+    } else {
+        dist = USE_LUT ? lev_myers32_lut<NP>(t, wa, la1, tmin, tmax, P, lb1) : lev_myers32_snap<NP>(wa, la1, tmin, tmax, P, lb1);
+    }
     uint32_t code = dist * (uint32_t)QTAB_N + (la1 > lb1 ? la1 : lb1);
     // both empty: 1.0 = 1 - 0/1; one side empty: 0.0 = 1 - 1/1   (strsim.rs:128, :160)
     if (!live) code = (la == 0u && lb == 0u) ? 1u : (uint32_t)QTAB_N + 1u;
@@ -321,7 +334,7 @@ __device__ __forceinline__ double stage_epilogue(uint32_t pk, double qa, double 
 }
 
 // `last`: the round's last lane that holds a row of this kernel (uniform)
-template <int MEASURE, bool LUT>
+template <int MEASURE, bool LUT, bool PTAB = false>
 __device__ __forceinline__ void stage_compute(const EqLut &lut, const uint32_t (&wt)[8], const uint32_t (&wp)[8], uint32_t meta,
                                               uint32_t last, uint16_t *s_code, uint32_t *s_word, double *s_val)
 {
@@ -350,7 +363,7 @@ __device__ __forceinline__ void stage_compute(const EqLut &lut, const uint32_t (
     if (MEASURE == LEVENSHTEIN) {
         uint32_t code;
         if (wide) code = stage_lev_code<7, LUT>(lut, wt, la, wp, lb, tmin, tmax, stripped);
-        else code = stage_lev_code<5, LUT>(lut, wt, la, wp, lb, tmin, tmax, stripped);
+        else code = stage_lev_code<5, LUT, PTAB>(lut, wt, la, wp, lb, tmin, tmax, stripped);
         if (fast) STRSIM_CHECK_INDEX(K_STAGE, 42, ~0ull, idx, STAGE_ROWS);
         if (fast) s_code[idx] = (uint16_t)code;
     } else if (MEASURE == ALL_MEASURES) {
@@ -785,7 +798,7 @@ lane_stage_body(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ v
     #endif
                 STAGE_STAMP(7);
                 __builtin_amdgcn_s_setprio(0);
-                stage_compute<MEASURE, LUT>(lut, wt, wp, lane < in_round ? d.y : STAGE_DEAD, in_round - 1u, s_code, s_word, s_val);
+                stage_compute<MEASURE, LUT, LEV && !LUT && !LONG>(lut, wt, wp, lane < in_round ? d.y : STAGE_DEAD, in_round - 1u, s_code, s_word, s_val);
                 STAGE_STAMP(8);
             }
         }
