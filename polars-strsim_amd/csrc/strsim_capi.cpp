@@ -2585,7 +2585,7 @@ static int join_pairs(strsim_ctx *c, const char *who, const Col &q, const Col &c
     const bool slow = p.q_slow || p.c_slow;
     const uint32_t ns = fast ? splits : 0u; // lists of the sweep; list ns is the fallback's
     uint32_t *const fb = cnt + (size_t)ns * nq;
-    JoinLaneArgs la{p.qw, p.qm, qperm, qstart, nq, sw, sm, si, cstart, splits, nullptr, 0u, upper, cnt, // (tab, rlimit: sweep's to set)
+    JoinLaneArgs la{p.qw, p.qm, qperm, qstart, nq, sw, sm, si, cstart, splits, upper, cnt,
                     (uint32_t *)(p.tail + o_map), map_words, map_shift, out_indptr, out_index, out_score, st};
     JoinSlowArgs sa{c->join_scratch.as<double>(), nullptr, 0u, p.qm, nq, nc, cutoff, upper, fb, cur, out_indptr, out_index, out_score, st};
     const uint64_t calls = fallback_calls(nq, nc);
@@ -2734,11 +2734,7 @@ int strsim_join_device(strsim_ctx_t *c, int scorer, const uint32_t *q_off, const
             c->extract_tab_ready = true;
             return STRSIM_OK;
         },
-        [&](bool fill, JoinLaneArgs &a) {
-            a.tab = c->extract_tab.as<ExtractTable>();
-            a.rlimit = rlimit;
-            return launch_join_lane(fill, a);
-        },
+        [&](bool fill, const JoinLaneArgs &a) { return launch_join_lane(fill, a, c->extract_tab.as<ExtractTable>(), rlimit); },
         STRSIM_INDEL);
 }
 
@@ -2772,7 +2768,7 @@ int strsim_match_join_device(strsim_ctx_t *c, int measure, const uint32_t *q_off
     return join_pairs(
         c, "strsim_match_join_device", q, cnd, min_score, flags, capacity, out_indptr, out_index, out_score, out_nnz, !some,
         []() -> int { return STRSIM_OK; }, // (the quotient table is the context's, on the device since the context was made)
-        [&](bool fill, JoinLaneArgs &a) { return launch_match_join_lane(measure, fill, a, c->qtab, need, min_score); }, measure);
+        [&](bool fill, const JoinLaneArgs &a) { return launch_match_join_lane(measure, fill, a, c->qtab, need, min_score); }, measure);
 }
 
 int strsim_match_join_host(strsim_ctx_t *c, int measure, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows, const uint32_t *c_off,

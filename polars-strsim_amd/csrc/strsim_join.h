@@ -2,10 +2,11 @@
 // candidate index (strsim_join_device; record linkage and deduplication: "which pairs score at least 0.85").
 // score = indel(q, c) of strsim_indel.h, bit for bit the pairwise call's; STRSIM_JOIN_UPPER keeps only j > i (a self-join).
 //
-// This header holds what the host shares with the kernels (tests/cpu_harness/join_harness.cpp compiles it with g++): the skip and
-// hit rules of a wave's sweep, the slice a split takes of a length bucket, the split rule, the layout of the per-(list, query)
-// counts and their prefix, the 64-bit scan's partition and the comparators of the row sort.  The kernels are in
-// strsim_join_kernels.h.
+// This header holds what the host shares with the kernels (tests/cpu_harness/join_sweep_host.h and join_harness.cpp compile it with
+// g++): the skip and hit rules of a wave's sweep and the rule object that carries them into the sweep's one body (JoinRankRule),
+// the slice a split takes of a length bucket, the split rule, the layout of the per-(list, query) counts and their prefix, the hit
+// map, the 64-bit scan's partition and the comparators of the row sort.  The kernels are in strsim_join_kernels.h; the body of the
+// sweep there (join_lane_start / _slice / _end) is also strsim_match_join.h's, under a rule object of its own.
 //
 // Two sweeps, no lists.  The queries and candidates of the lane class (at most 32 ASCII bytes) are put in length order once per
 // call (k_match_pack, k_nearest_hist / _scan / _scatter) and swept twice by k_join_lane over the rank table of strsim_extract.h,
@@ -53,6 +54,18 @@ STRSIM_HD bool join_needs(const uint16_t *rank, uint32_t lq, uint32_t lc, uint32
 
 // Whether pair (i, j) of rank r is reported.
 STRSIM_HD bool join_hit(uint32_t r, uint32_t rlimit, bool upper, uint32_t i, uint32_t j) { return r < rlimit && (!upper || j > i); }
+
+// What a pair yields in this join's sweep and what becomes of it (the rule object of join_lane_slice in strsim_join_kernels.h and of
+// its host transcript, as NearestRules / ExtractRules are search_sweep_lane's): its rank, looked up in the lane's row of the rank
+// table at the candidate length in hand; the f64 score is formed only for a hit that is stored.
+struct JoinRankRule {
+    const uint16_t *row; // rank[lq + lc]: indexed by the distance
+    uint32_t rlimit;
+    const uint16_t *rep;
+    STRSIM_HD uint32_t value(uint32_t d) const { return row[d]; } // d <= lq + lc: inside the row
+    STRSIM_HD bool hit(uint32_t r, bool upper, uint32_t i, uint32_t j) const { return join_hit(r, rlimit, upper, i, j); }
+    STRSIM_HD double score(uint32_t r) const { return extract_rank_score(rep, r); }
+};
 
 // Split `split` of `splits` takes [x0, x1) of the length bucket [c0, c0 + n) of the length-ordered candidates.
 STRSIM_HD void join_slice(uint32_t c0, uint32_t n, uint32_t split, uint32_t splits, uint32_t &x0, uint32_t &x1)

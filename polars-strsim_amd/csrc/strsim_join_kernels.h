@@ -2,14 +2,18 @@
 // Included by strsim_kernels.hip inside namespace strsim, after strsim_cdist_kernels.h: the strings are packed by k_match_pack and
 // put in length order by k_nearest_hist / _scan / _scatter, once per call; both sweeps read that one order.
 //
-//   k_join_lane<FILL>   ONE QUERY PER LANE in length order, its bit-planes in registers (match_lane_query), the candidate
-//                       wave-uniform text through scalar loads, the rank table of strsim_extract.h in LDS.  blockIdx.y takes its
-//                       slice of every length bucket; the lengths of the wave's window are visited nearest-first, a length no live
-//                       lane needs is skipped and the wave stops after a step none of whose lengths was needed (strsim_join.h).
-//                       FILL = false counts a lane's hits in a register and stores one count per (split, query), and marks in the
-//                       wave's hit map which candidates had a hit at all; FILL = true computes those candidates only and stores
-//                       (j, score) into the lane's own segment, the cursor compared with the segment's end before every store.
-//                       No atomics; the f64 score is formed only on a hit (extract_rank_score).
+//   join_lane_start / join_lane_slice / join_lane_end   THE ONE BODY of a join's lane sweep, shared by k_join_lane and
+//                       k_match_join_lane (strsim_match_join_kernels.h).  ONE QUERY PER LANE in length order, its bit-planes in
+//                       registers (match_lane_query), the candidate wave-uniform text through scalar loads; blockIdx.y takes its
+//                       slice of every length bucket.  FILL = false counts a lane's hits in a register and stores one count per
+//                       (split, query), and marks in the wave's hit map which candidates had a hit at all; FILL = true computes those
+//                       candidates only and stores (j, score) into the lane's own segment, the cursor compared with the segment's
+//                       end before every store.  No atomics.  What a pair yields, whether it is a hit and the score that is stored
+//                       come from the caller: a rule object (JoinRankRule, MatchJoinRule) with the kernel's own scoring call.
+//   k_join_lane<FILL>   adds the rank table of strsim_extract.h in LDS and the visiting order: the lengths of the wave's window
+//                       nearest-first, a length no live lane needs is skipped and the wave stops after a step none of whose lengths
+//                       was needed (strsim_join.h).  A pair yields its rank; the f64 score is formed only on a hit that is stored
+//                       (extract_rank_score).
 //   k_join_totals       one thread per query: its counts into their exclusive prefix (join_row_prefix), the total to indptr[i + 1].
 //   k_join_scan_sums / _top / _apply   the 64-bit inclusive scan of the totals in place: indptr.
 //   k_join_slow<SIDE, FILL>  fallback.  SIDE 0: a slow QUERY's column of nc pairwise scores -> that row's hits; SIDE 1: a slow
@@ -23,9 +27,110 @@
 // Every loop is bounded by the kernel's arguments, no kernel waits on another workgroup, and every store is a plain vector store.
 #pragma once
 
-// Grid: (ceil(nq / MATCH_BLOCK), splits); the arguments of k_extract_lane, then: upper (STRSIM_JOIN_UPPER), cnt: (splits + 1) x nq
-// words -- the counts (written by FILL = false), their prefix (read by FILL = true) --, the hit map (ceil(nq / 64) waves x map_words
-// words, written by FILL = false, read by FILL = true; join_map_words / join_map_shift), indptr (FILL: nq + 1) and the outputs.
+// The arguments both lane sweeps take, as the pieces below read them.  Grid: (ceil(nq / MATCH_BLOCK), splits); the queries and the
+// length-ordered candidates of k_extract_lane, then: upper (STRSIM_JOIN_UPPER), cnt: (splits + 1) x nq words -- the counts (written
+// by FILL = false), their prefix (read by FILL = true) --, the hit map (ceil(nq / 64) waves x map_words words, written by
+// FILL = false, read by FILL = true; join_map_words / join_map_shift), indptr (FILL: nq + 1) and the outputs.
+struct JoinSweep {
+    const uint32_t *qwords, *qmeta, *qperm, *qstart; uint32_t nq;
+    const uint32_t *sw, *sm, *sidx, *cstart;
+    bool upper;
+    uint32_t *cnt, *map; uint64_t map_words; uint32_t map_shift;
+    const uint64_t *indptr; uint32_t *out_index; double *out_score;
+};
+
+// A lane of the sweep: its query, the wave's hit map and, between the slices, its count (FILL = false) or its cursor (FILL = true).
+struct JoinLane {
+    uint32_t split, splits;
+    uint32_t i, lq;
+    bool have, live;
+    LaneQuery q;
+    uint32_t *wmap; // the wave's hit map (strsim_join.h)
+    bool lane0;
+    uint32_t count;
+    uint64_t cur, end; // FILL: the lane's segment (empty unless live)
+};
+
+template <bool FILL>
+__device__ __forceinline__ void join_lane_start(const JoinSweep &s, JoinLane &L)
+{
+    // the last positions of the length order first: the longest queries have the widest windows and the longest candidates
+    const uint32_t p = (gridDim.x - 1u - blockIdx.x) * MATCH_BLOCK + threadIdx.x;
+    L.split = blockIdx.y, L.splits = gridDim.y;
+    L.have = p < s.nq;
+    L.i = L.have ? s.qperm[p] : 0u;
+    L.live = L.have && p < s.qstart[NEAREST_SLOW_BUCKET];
+    const uint32_t qm = L.live ? s.qmeta[L.i] : 0u;
+    L.lq = qm & 63u;
+    L.q = match_lane_query(s.qwords, L.i, L.live, qm);
+    L.wmap = s.map + (size_t)(p >> 6) * s.map_words;
+    L.lane0 = (threadIdx.x & 63u) == 0u;
+    L.count = 0u;
+    L.cur = 0u, L.end = 0u;
+    if (FILL && L.live) {
+        const uint64_t base = s.indptr[L.i];
+        L.cur = base + s.cnt[(size_t)L.split * s.nq + L.i];
+        L.end = base + s.cnt[(size_t)(L.split + 1u) * s.nq + L.i]; // (list `splits` is the fallback's: the row always exists)
+    }
+}
+
+// One slice: the candidates of length lc that this split takes.  `need` is the lane's own (of (lq, lc) alone: out of the candidate
+// loop); the caller has seen that some lane of the wave needs the length.  R.core<NP>(wt, lc, P, w0, lq) is the kernel's scoring call
+// on this lane's planes and the candidate text wt, R.value(c) what the pair yields, R.hit(v, upper, i, j) whether it is reported,
+// R.score(v) the f64 that is stored.
+template <bool FILL, class Rule>
+__device__ __forceinline__ void join_lane_slice(const JoinSweep &s, JoinLane &L, uint32_t lc, bool need, const Rule &R)
+{
+    const uint32_t c0 = s.cstart[lc], n = s.cstart[lc + 1u] - c0;
+    uint32_t x0, x1;
+    join_slice(c0, n, L.split, L.splits, x0, x1);
+    const uint32_t k = join_map_slice(lc, L.split, L.splits);
+    uint64_t at = ~0ull; // the word of the hit map in hand (uniform), its bits
+    uint32_t bits = 0u;
+    for (uint32_t x = x0; x < x1; ++x) { // (uniform: scalar loads)
+        const uint64_t w = join_map_word(x, s.map_shift, k);
+        if (w != at) {
+            if (!FILL && at != ~0ull && L.lane0) L.wmap[at] = bits;
+            at = w;
+            bits = FILL ? wave_uniform(L.wmap[w]) : 0u;
+        }
+        const uint32_t bit = join_map_bit(x, s.map_shift);
+        if (FILL && !(bits & bit)) continue; // no lane of the wave had a hit in this group
+        const uint32_t cm = s.sm[x], j = s.sidx[x];
+        uint32_t wt[8];
+#pragma unroll
+        for (int w = 0; w < 8; ++w) wt[w] = s.sw[(size_t)x * 8u + w];
+        decltype(R.template core<5>(wt, lc, L.q.P5, L.q.w0, L.lq)) c;
+        if (match_five_planes(L.q.wcls | ((cm >> 8) & 15u))) c = R.template core<5>(wt, lc, L.q.P5, L.q.w0, L.lq);
+        else c = R.template core<7>(wt, lc, L.q.P, L.q.w0, L.lq);
+        const auto v = R.value(c);
+        const bool hit = need && R.hit(v, s.upper, L.i, j);
+        if (FILL) {
+            if (hit) join_store(L.cur, L.end, j, R.score(v), s.out_index, s.out_score);
+        } else {
+            L.count += hit ? 1u : 0u;
+            if (__ballot(hit) != 0ull) bits |= bit;
+        }
+    }
+    if (!FILL && at != ~0ull && L.lane0) L.wmap[at] = bits;
+}
+
+template <bool FILL>
+__device__ __forceinline__ void join_lane_end(const JoinSweep &s, const JoinLane &L)
+{
+    if (!FILL && L.have) s.cnt[(size_t)L.split * s.nq + L.i] = L.count; // (0 for a slow query: its hits are the fallback's)
+}
+
+// JoinRankRule with the rank join's scoring call: the Indel distance of the pair.
+struct JoinRankSweep : JoinRankRule {
+    template <int NP>
+    __device__ __forceinline__ uint32_t core(const uint32_t (&wt)[8], uint32_t lc, const uint32_t (&P)[NP], uint32_t, uint32_t lq) const
+    {
+        return extract_indel_uniform_text<NP>(wt, lc, P, lq);
+    }
+};
+
+// The sweep of JoinSweep's arguments over the rank table `tab` under the integer cutoff rlimit >= 1.
 template <bool FILL>
 __global__ __launch_bounds__(MATCH_BLOCK) void k_join_lane(const uint32_t *__restrict__ qwords, const uint32_t *__restrict__ qmeta,
                                                            const uint32_t *__restrict__ qperm, const uint32_t *__restrict__ qstart,
@@ -44,29 +149,12 @@ __global__ __launch_bounds__(MATCH_BLOCK) void k_join_lane(const uint32_t *__res
     __syncthreads();
     const uint16_t *const s_rank = reinterpret_cast<const uint16_t *>(s_words);
 
-    // the last positions of the length order first: the longest queries have the widest windows and the longest candidates
-    const uint32_t p = (gridDim.x - 1u - blockIdx.x) * MATCH_BLOCK + threadIdx.x;
-    const uint32_t split = blockIdx.y, splits = gridDim.y;
-    const bool upper = upper_flag != 0u;
-    const bool have = p < nq;
-    const uint32_t i = have ? qperm[p] : 0u;
-    const bool live = have && p < qstart[NEAREST_SLOW_BUCKET];
-    const uint32_t qm = live ? qmeta[i] : 0u;
-    const uint32_t lq = qm & 63u;
-    const LaneQuery q = match_lane_query(qwords, i, live, qm);
-
-    uint32_t *const wmap = map + (size_t)(p >> 6) * map_words; // the wave's hit map (strsim_join.h)
-    const bool lane0 = (threadIdx.x & 63u) == 0u;
-    uint32_t count = 0u;
-    uint64_t cur = 0u, end = 0u; // FILL: the lane's segment (empty unless live)
-    if (FILL && live) {
-        const uint64_t base = indptr[i];
-        cur = base + cnt[(size_t)split * nq + i];
-        end = base + cnt[(size_t)(split + 1u) * nq + i]; // (list `splits` is the fallback's: the row always exists)
-    }
-
-    if (__ballot(live) != 0ull) {
-        const uint32_t lmin = nearest_wave_min(live ? lq : 0xFFFFFFFFu), lmax = nearest_wave_max(live ? lq : 0u);
+    const JoinSweep s{qwords, qmeta, qperm, qstart, nq, sw, sm, sidx, cstart, upper_flag != 0u, cnt, map, map_words, map_shift, indptr,
+                      out_index, out_score};
+    JoinLane L;
+    join_lane_start<FILL>(s, L);
+    if (__ballot(L.live) != 0ull) {
+        const uint32_t lmin = nearest_wave_min(L.live ? L.lq : 0xFFFFFFFFu), lmax = nearest_wave_max(L.live ? L.lq : 0u);
         uint32_t lo, hi;
         extract_window(s_rank, lmin, lmax, rlimit, lo, hi);
         const uint32_t steps = nearest_steps(lmin, lmax, lo, hi);
@@ -75,47 +163,16 @@ __global__ __launch_bounds__(MATCH_BLOCK) void k_join_lane(const uint32_t *__res
             if (!nearest_step_range(lmin, lmax, lo, hi, g, first, last, stride)) continue;
             bool needed = false; // (uniform) some live lane needs a length of this step
             for (uint32_t lc = first; lc <= last; lc += stride) {
-                const bool need = live && join_needs(s_rank, lq, lc, rlimit); // of (lq, lc) alone: out of the candidate loop
+                const bool need = L.live && join_needs(s_rank, L.lq, lc, rlimit);
                 if (__ballot(need) == 0ull) continue;
                 needed = true;
-                const uint16_t *const row = s_rank + (lq + lc) * EXTRACT_TAB_W;
-                const uint32_t c0 = cstart[lc], n = cstart[lc + 1u] - c0;
-                uint32_t x0, x1;
-                join_slice(c0, n, split, splits, x0, x1);
-                const uint32_t k = join_map_slice(lc, split, splits);
-                uint64_t at = ~0ull; // the word of the hit map in hand (uniform), its bits
-                uint32_t bits = 0u;
-                for (uint32_t x = x0; x < x1; ++x) { // (uniform: scalar loads)
-                    const uint64_t w = join_map_word(x, map_shift, k);
-                    if (w != at) {
-                        if (!FILL && at != ~0ull && lane0) wmap[at] = bits;
-                        at = w;
-                        bits = FILL ? wave_uniform(wmap[w]) : 0u;
-                    }
-                    const uint32_t bit = join_map_bit(x, map_shift);
-                    if (FILL && !(bits & bit)) continue; // no lane of the wave had a hit in this group
-                    const uint32_t cm = sm[x], j = sidx[x];
-                    uint32_t wt[8];
-#pragma unroll
-                    for (int w = 0; w < 8; ++w) wt[w] = sw[(size_t)x * 8u + w];
-                    uint32_t d;
-                    if (match_five_planes(q.wcls | ((cm >> 8) & 15u))) d = extract_indel_uniform_text<5>(wt, lc, q.P5, lq);
-                    else d = extract_indel_uniform_text<7>(wt, lc, q.P, lq);
-                    const uint32_t r = row[d]; // d <= lq + lc: inside the row
-                    const bool hit = need && join_hit(r, rlimit, upper, i, j);
-                    if (FILL) {
-                        if (hit) join_store(cur, end, j, extract_rank_score(tab->rep, r), out_index, out_score);
-                    } else {
-                        count += hit ? 1u : 0u;
-                        if (__ballot(hit) != 0ull) bits |= bit;
-                    }
-                }
-                if (!FILL && at != ~0ull && lane0) wmap[at] = bits;
+                const JoinRankSweep R{{s_rank + (L.lq + lc) * EXTRACT_TAB_W, rlimit, tab->rep}};
+                join_lane_slice<FILL>(s, L, lc, need, R);
             }
             if (!needed) break;
         }
     }
-    if (!FILL && have) cnt[(size_t)split * nq + i] = count; // (0 for a slow query: its hits are the fallback's)
+    join_lane_end<FILL>(s, L);
 }
 
 // One thread per query: cnt[l * nq + i], l < lists, into their exclusive prefix; indptr[i + 1] = the row's total, indptr[0] = 0.

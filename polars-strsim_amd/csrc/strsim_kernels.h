@@ -250,25 +250,26 @@ hipError_t launch_cdist_put_col(const double *scores, const uint32_t *clist, uin
                                 double *out, uint64_t ld, hipStream_t stream);
 hipError_t launch_cdist_cutoff(double *out, const uint32_t *qlist, uint32_t nb, uint32_t nc, uint64_t ld, double cutoff, hipStream_t stream);
 
-// Threshold join (strsim_join_kernels.h; the rules are in strsim_join.h).  Both sides packed by launch_match_pack and put in length
-// order by launch_nearest_order, once per call.  launch_join_lane(false) stores the hits of (split, query i) at cnt[split * nq + i];
-// launch_join_indptr turns the `lists` counts of every query (the splits, then the fallback's list) into their prefix in place and
-// the totals into indptr (nq + 1 words; sums: join_scan_blocks(nq) words); launch_join_lane(true) stores every hit inside the segment
-// the counts gave it.  launch_join_slow: nb columns of pairwise scores of slow queries (side 0: nc scores each) or slow candidates
-// (side 1: nq scores each) counted into / stored in the fallback's list fb (nq words; cur: nq cursors, zeroed before the fill).
-// launch_join_sort_rows: every row by candidate index.
+// Threshold join (strsim_join_kernels.h; the rules are in strsim_join.h).  Both sides packed by launch_match_pack and put in
+// length order by launch_nearest_order, once per call.  JoinLaneArgs: what every join's lane sweep takes; what one sweep adds
+// (here the rank table and rlimit >= 1) is its launcher's own argument.  launch_join_lane(false) stores the hits of (split, query
+// i) at cnt[split * nq + i]; launch_join_indptr turns the `lists` counts of every query (the splits, then the fallback's list) into
+// their prefix in place and the totals into indptr (nq + 1 words; sums: join_scan_blocks(nq) words); launch_join_lane(true) stores
+// every hit inside the segment the counts gave it.  launch_join_slow: nb columns of pairwise scores of slow queries (side 0: nc
+// scores each) or slow candidates (side 1: nq scores each) counted into / stored in the fallback's list fb (nq words; cur: nq
+// cursors, zeroed before the fill).  launch_join_sort_rows: every row by candidate index.
 struct JoinLaneArgs {
     const uint32_t *qwords, *qmeta, *qperm, *qstart; uint32_t nq;
     const uint32_t *swords, *smeta, *sidx, *cstart;
     uint32_t splits;
-    const ExtractTable *tab; uint32_t rlimit, upper;
+    uint32_t upper;
     uint32_t *cnt;
     uint32_t *map; uint64_t map_words; uint32_t map_shift; // the hit map: ceil(nq / 64) x map_words words
     const uint64_t *indptr;
     uint32_t *out_index; double *out_score;
     hipStream_t stream;
 };
-hipError_t launch_join_lane(bool fill, const JoinLaneArgs &a);
+hipError_t launch_join_lane(bool fill, const JoinLaneArgs &a, const ExtractTable *tab, uint32_t rlimit);
 hipError_t launch_join_indptr(uint32_t *cnt, uint32_t nq, uint32_t lists, uint64_t *indptr, uint64_t *sums, hipStream_t stream);
 struct JoinSlowArgs {
     const double *scores; const uint32_t *list; uint32_t nb;
@@ -282,8 +283,8 @@ hipError_t launch_join_slow(int side, bool fill, const JoinSlowArgs &a);
 hipError_t launch_join_sort_rows(const uint64_t *indptr, uint32_t nq, uint32_t nc, uint32_t *index, double *score, hipStream_t stream);
 
 // Threshold join by a reference measure 0 .. 4 (strsim_match_join_kernels.h; the rule is in strsim_match_join.h): the sweep that
-// stands where launch_join_lane stands, everything around it is the join's.  Of `a`, tab and rlimit are not read; qtab: the quotient
-// table (measures 0 .. 2), need: the lengths a query of each length visits, passed by value.
+// stands where launch_join_lane stands, everything around it is the join's.  qtab: the quotient table (measures 0 .. 2), need: the
+// lengths a query of each length visits, passed by value.
 struct MatchJoinNeed;
 hipError_t launch_match_join_lane(int measure, bool fill, const JoinLaneArgs &a, const double *qtab, const MatchJoinNeed &need, double min_score);
 

@@ -600,25 +600,37 @@ hipError_t launch_cdist_cutoff(double *out, const uint32_t *qlist, uint32_t nb, 
 // ------------------------------------------------------------------------------------------------
 // threshold join (strsim_join_kernels.h)
 // ------------------------------------------------------------------------------------------------
-hipError_t launch_join_lane(bool fill, const JoinLaneArgs &a)
+// f(std::bool_constant<FILL>): the count (false) or the fill (true) form of a join kernel
+template <class F>
+static void with_fill(bool fill, F f)
 {
-    const dim3 grid(match_grid(a.nq), a.splits);
-    if (fill)
-        hipLaunchKernelGGL(k_join_lane<true>, grid, dim3(MATCH_BLOCK), 0, a.stream, a.qwords, a.qmeta, a.qperm, a.qstart, a.nq, a.swords, a.smeta,
-                           a.sidx, a.cstart, a.tab, a.rlimit, a.upper, a.cnt, a.map, a.map_words, a.map_shift, a.indptr, a.out_index, a.out_score);
-    else
-        hipLaunchKernelGGL(k_join_lane<false>, grid, dim3(MATCH_BLOCK), 0, a.stream, a.qwords, a.qmeta, a.qperm, a.qstart, a.nq, a.swords, a.smeta,
-                           a.sidx, a.cstart, a.tab, a.rlimit, a.upper, a.cnt, a.map, a.map_words, a.map_shift, a.indptr, a.out_index, a.out_score);
+    if (fill) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+hipError_t launch_join_lane(bool fill, const JoinLaneArgs &a, const ExtractTable *tab, uint32_t rlimit)
+{
+    with_fill(fill, [&](auto FILL) {
+        hipLaunchKernelGGL(k_join_lane<decltype(FILL)::value>, dim3(match_grid(a.nq), a.splits), dim3(MATCH_BLOCK), 0, a.stream, a.qwords, a.qmeta,
+                           a.qperm, a.qstart, a.nq, a.swords, a.smeta, a.sidx, a.cstart, tab, rlimit, a.upper, a.cnt, a.map, a.map_words, a.map_shift,
+                           a.indptr, a.out_index, a.out_score);
+    });
     return hipGetLastError();
+}
+
+// The 64-bit inclusive scan of v[0 .. n) in place (sums: join_scan_blocks(n) words): three launches.
+static void launch_join_scan(uint64_t *v, uint64_t n, uint64_t *sums, hipStream_t stream)
+{
+    const unsigned nb = (unsigned)join_scan_blocks(n);
+    hipLaunchKernelGGL(k_join_scan_sums, dim3(nb), dim3(JOIN_SCAN_BLOCK), 0, stream, v, n, sums);
+    hipLaunchKernelGGL(k_join_scan_top, dim3(1), dim3(JOIN_SCAN_BLOCK), 0, stream, sums, (uint64_t)nb);
+    hipLaunchKernelGGL(k_join_scan_apply, dim3(nb), dim3(JOIN_SCAN_BLOCK), 0, stream, v, n, sums);
 }
 
 hipError_t launch_join_indptr(uint32_t *cnt, uint32_t nq, uint32_t lists, uint64_t *indptr, uint64_t *sums, hipStream_t stream)
 {
-    const unsigned nb = (unsigned)join_scan_blocks(nq);
     hipLaunchKernelGGL(k_join_totals, dim3(match_grid(nq)), dim3(MATCH_BLOCK), 0, stream, cnt, nq, lists, indptr);
-    hipLaunchKernelGGL(k_join_scan_sums, dim3(nb), dim3(JOIN_SCAN_BLOCK), 0, stream, indptr + 1, (uint64_t)nq, sums);
-    hipLaunchKernelGGL(k_join_scan_top, dim3(1), dim3(JOIN_SCAN_BLOCK), 0, stream, sums, (uint64_t)nb);
-    hipLaunchKernelGGL(k_join_scan_apply, dim3(nb), dim3(JOIN_SCAN_BLOCK), 0, stream, indptr + 1, (uint64_t)nq, sums);
+    launch_join_scan(indptr + 1, nq, sums, stream);
     return hipGetLastError();
 }
 
@@ -626,13 +638,10 @@ template <int SIDE>
 static void launch_join_slow_side(bool fill, const JoinSlowArgs &a)
 {
     const uint32_t rows = SIDE == 0 ? a.nc : a.nq;
-    const dim3 grid(match_grid(rows), a.nb);
-    if (fill)
-        hipLaunchKernelGGL((k_join_slow<SIDE, true>), grid, dim3(MATCH_BLOCK), 0, a.stream, a.scores, a.list, a.qmeta, rows, a.cutoff, a.upper, a.fb,
-                           a.cur, a.indptr, a.out_index, a.out_score);
-    else
-        hipLaunchKernelGGL((k_join_slow<SIDE, false>), grid, dim3(MATCH_BLOCK), 0, a.stream, a.scores, a.list, a.qmeta, rows, a.cutoff, a.upper, a.fb,
-                           a.cur, a.indptr, a.out_index, a.out_score);
+    with_fill(fill, [&](auto FILL) {
+        hipLaunchKernelGGL((k_join_slow<SIDE, decltype(FILL)::value>), dim3(match_grid(rows), a.nb), dim3(MATCH_BLOCK), 0, a.stream, a.scores, a.list,
+                           a.qmeta, rows, a.cutoff, a.upper, a.fb, a.cur, a.indptr, a.out_index, a.out_score);
+    });
 }
 
 hipError_t launch_join_slow(int side, bool fill, const JoinSlowArgs &a)
@@ -660,15 +669,11 @@ hipError_t launch_join_sort_rows(const uint64_t *indptr, uint32_t nq, uint32_t n
 template <int M>
 static void launch_match_join_lane_m(bool fill, const JoinLaneArgs &a, const double *qtab, const MatchJoinNeed &need, double min_score)
 {
-    const dim3 grid(match_grid(a.nq), a.splits);
-    if (fill)
-        hipLaunchKernelGGL((k_match_join_lane<M, true>), grid, dim3(MATCH_BLOCK), 0, a.stream, a.qwords, a.qmeta, a.qperm, a.qstart, a.nq, a.swords,
-                           a.smeta, a.sidx, a.cstart, qtab, need, min_score, a.upper, a.cnt, a.map, a.map_words, a.map_shift, a.indptr, a.out_index,
-                           a.out_score);
-    else
-        hipLaunchKernelGGL((k_match_join_lane<M, false>), grid, dim3(MATCH_BLOCK), 0, a.stream, a.qwords, a.qmeta, a.qperm, a.qstart, a.nq, a.swords,
-                           a.smeta, a.sidx, a.cstart, qtab, need, min_score, a.upper, a.cnt, a.map, a.map_words, a.map_shift, a.indptr, a.out_index,
-                           a.out_score);
+    with_fill(fill, [&](auto FILL) {
+        hipLaunchKernelGGL((k_match_join_lane<M, decltype(FILL)::value>), dim3(match_grid(a.nq), a.splits), dim3(MATCH_BLOCK), 0, a.stream, a.qwords,
+                           a.qmeta, a.qperm, a.qstart, a.nq, a.swords, a.smeta, a.sidx, a.cstart, qtab, need, min_score, a.upper, a.cnt, a.map,
+                           a.map_words, a.map_shift, a.indptr, a.out_index, a.out_score);
+    });
 }
 
 hipError_t launch_match_join_lane(int measure, bool fill, const JoinLaneArgs &a, const double *qtab, const MatchJoinNeed &need, double min_score)
@@ -697,13 +702,10 @@ hipError_t launch_components_identity(uint32_t rows, uint32_t *out_root, uint32_
 hipError_t launch_components(const ComponentsArgs &a)
 {
     const dim3 grid(components_grid(a.rows)), block(COMPONENTS_BLOCK);
-    const unsigned nb = (unsigned)join_scan_blocks(a.rows);
     hipLaunchKernelGGL(k_components_init, grid, block, 0, a.stream, a.rows, a.parent, a.status);
     hipLaunchKernelGGL(k_components_link, dim3(components_link_grid(a.nnz)), block, 0, a.stream, a.indptr, a.index, a.rows, a.nnz, a.parent, a.status);
     hipLaunchKernelGGL(k_components_compress, grid, block, 0, a.stream, a.rows, a.parent, a.out_root, a.scan);
-    hipLaunchKernelGGL(k_join_scan_sums, dim3(nb), dim3(JOIN_SCAN_BLOCK), 0, a.stream, a.scan, (uint64_t)a.rows, a.sums);
-    hipLaunchKernelGGL(k_join_scan_top, dim3(1), dim3(JOIN_SCAN_BLOCK), 0, a.stream, a.sums, (uint64_t)nb);
-    hipLaunchKernelGGL(k_join_scan_apply, dim3(nb), dim3(JOIN_SCAN_BLOCK), 0, a.stream, a.scan, (uint64_t)a.rows, a.sums);
+    launch_join_scan(a.scan, a.rows, a.sums, a.stream);
     hipLaunchKernelGGL(k_components_rank, grid, block, 0, a.stream, a.rows, a.out_root, a.scan, a.out_cluster, a.status);
     return hipGetLastError();
 }

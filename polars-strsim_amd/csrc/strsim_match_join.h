@@ -4,8 +4,9 @@
 //
 // The protocol is strsim_join.h's, unchanged: the length order, two sweeps (count, fill) with the hit map between them, the
 // per-(split, query) counts and their prefix, the 64-bit scan, the fallback for strings outside the lane class and the row sort.
-// This header holds what differs and what the host shares with the kernel (tests/cpu_harness/match_join_harness.cpp compiles it
-// with g++): the pruning rule.
+// The sweep's body is the join's too (join_lane_start / _slice / _end of strsim_join_kernels.h).  This header holds what differs
+// and what the host shares with the kernel (tests/cpu_harness/match_join_harness.cpp compiles it with g++): the pruning rule, and
+// the rule object that tells that body what a pair yields here (MatchJoinRule).
 //
 // Pruning (exact).  The scores are f64 values without a rank table, so the bound of a length pair is the measure's OWN epilogue at
 // the best integers the lengths allow -- the same function the kernels end in, never a separately rounded expression:
@@ -67,5 +68,14 @@ inline bool match_join_need_mask(int measure, double min_score, MatchJoinNeed &n
 
 // Whether pair (i, j) of score v is reported.
 STRSIM_HD bool match_join_hit(double v, double min_score, bool upper, uint32_t i, uint32_t j) { return v >= min_score && (!upper || j > i); }
+
+// The rule object of the shared sweep (join_lane_slice, where JoinRankRule stands for the rank join): a pair yields its f64 score,
+// which is what is stored.
+struct MatchJoinRule {
+    double min_score;
+    STRSIM_HD double value(double v) const { return v; }
+    STRSIM_HD bool hit(double v, bool upper, uint32_t i, uint32_t j) const { return match_join_hit(v, min_score, upper, i, j); }
+    STRSIM_HD double score(double v) const { return v; }
+};
 
 } // namespace strsim

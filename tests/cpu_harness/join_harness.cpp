@@ -1,11 +1,9 @@
 // join_harness.cpp -- host build of the rules strsim_join.h shares with the join kernels (strsim_join_kernels.h), for
 // tests/test_join_cpu.py: g++ compiles the same header.
-//   join_replay      a wave's count sweep, the counts -> prefix -> 64-bit scan, and its fill sweep (k_join_lane<false / true>, every
-//                    split in turn, a ballot written as a loop over the lanes) over a random (d, s) matrix against brute force:
-//                    every hit found exactly once with its own score, the fill positions exactly the counted segments, nothing
-//                    written outside a segment (guard words around the outputs, and one deliberately undersized segment), then the
-//                    row sort; the count sweep marks the hit map and the fill sweep computes the marked candidates only (every word of
-//                    the map has one writer); reports how many candidates the count sweep visited.
+//   join_replay      join_replay_host of join_sweep_host.h (a wave's count sweep, the counts -> prefix -> 64-bit scan, its fill sweep
+//                    and the row sort against brute force, with every check of the protocol) under k_join_lane's own part: the
+//                    window, the nearest-first steps and the stop rule over the rank table, a pair yielding the rank of a random
+//                    (d, s); reports how many candidates the count sweep visited.
 //   join_sort_check  the comparator network of k_join_sort_rows over n distinct keys against std::sort, guard words around the row.
 //   join_scan_check  the three passes of the 64-bit scan as the kernels partition them, against a serial prefix sum.
 // Built as a shared library; with -DJOIN_HARNESS_MAIN it is a stand-alone program that runs the whole sweep of cases (the form
@@ -20,7 +18,7 @@
 #include <numeric>
 #include <vector>
 
-#include "strsim_join.h"
+#include "join_sweep_host.h"
 
 using namespace strsim;
 
@@ -34,82 +32,23 @@ static const ExtractTable &table()
     return *t;
 }
 
-struct Rng {
-    uint64_t s;
-    uint32_t next() { s = s * 6364136223846793005ull + 1442695040888963407ull; return (uint32_t)(s >> 33); }
-    uint32_t below(uint32_t n) { return n ? next() % n : 0u; }
-};
+// What k_join_lane adds to the shared sweep, over given Indel distances dist[i * nc + j].
+struct RankCase {
+    const std::vector<uint32_t> &qlen, &clen;
+    const uint32_t *dist;
+    uint32_t rlimit;
+    double cutoff;
+    bool nothing;
 
-static const uint32_t GUARD_I = 0xDEADBEEFu;
-static const uint64_t GUARD_S = 0x7FF8DEADBEEF0001ull; // a NaN payload no score has
-static const size_t EDGE = 8;
+    double expected(uint32_t i, uint32_t j) const { return epilogue_indel(dist[(size_t)i * clen.size() + j], qlen[i] + clen[j], 0u); }
 
-static double guard_score() { double g; memcpy(&g, &GUARD_S, 8); return g; }
-static bool is_guard(double v) { uint64_t b; memcpy(&b, &v, 8); return b == GUARD_S; }
-
-// The 64-bit inclusive scan of v[0 .. n) as k_join_scan_sums / _top / _apply partition it.
-static void scan_as_kernels(std::vector<uint64_t> &v)
-{
-    const uint64_t n = v.size(), nb = join_scan_blocks(n);
-    std::vector<uint64_t> sums(nb ? nb : 1, 0);
-    for (uint64_t b = 0; b < nb; ++b)
-        for (uint32_t t = 0; t < JOIN_SCAN_BLOCK; ++t) {
-            uint64_t first, last;
-            join_scan_range(b, t, n, first, last);
-            sums[b] += join_scan_sum(v.data(), first, last);
-        }
-    { // the top pass: thread t's base is the sum of the chunks of the threads before it
-        uint64_t base = 0;
-        for (uint32_t t = 0; t < JOIN_SCAN_BLOCK; ++t) {
-            uint64_t first, last;
-            join_scan_top_range(t, nb, first, last);
-            for (uint64_t x = first; x < last; ++x) { const uint64_t s = sums[x]; sums[x] = base; base += s; }
-        }
-    }
-    for (uint64_t b = 0; b < nb; ++b) {
-        uint64_t base = 0;
-        for (uint32_t t = 0; t < JOIN_SCAN_BLOCK; ++t) {
-            uint64_t first, last;
-            join_scan_range(b, t, n, first, last);
-            const uint64_t mine = join_scan_sum(v.data(), first, last);
-            join_scan_write(v.data(), first, last, sums[b] + base);
-            base += mine;
-        }
-    }
-}
-
-// The network of k_join_sort_rows over a row of n pairs: every comparator of every step, in any order inside a step.
-static void sort_as_kernels(uint32_t *index, double *score, uint64_t n)
-{
-    const uint64_t P = join_sort_pow2(n);
-    for (uint64_t k = 2; k <= P; k <<= 1)
-        for (uint64_t h = k >> 1; h > 0; h >>= 1)
-            for (uint64_t t = P / 2; t-- > 0;) { // (descending: the order inside a step must not matter)
-                uint64_t a, b;
-                join_sort_pair(t, k, h, a, b);
-                if (b < n) join_sort_cmpx(index, score, a, b);
-            }
-}
-
-// One sweep of a wave, every split in turn: on_hit(split, i, j, r) for every pair the sweep reports.  fill = false marks the
-// wave's hit map, fill = true computes only the candidates marked there (k_join_lane's candidate loop).  Returns the candidates
-// computed.
-template <class OnHit>
-static uint64_t sweep(const std::vector<uint32_t> &qlen, const std::vector<uint32_t> &order, const uint32_t *cstart, const uint32_t *dist,
-                      uint32_t nc, uint32_t rlimit, bool upper, uint32_t splits, bool fill, uint32_t shift, std::vector<uint32_t> &map,
-                      std::vector<uint8_t> &map_writes, OnHit on_hit)
-{
-    const uint16_t *const rank = table().rank;
-    const uint32_t nq = (uint32_t)qlen.size();
-    uint64_t visited = 0;
-    uint32_t lmin = 0xFFFFFFFFu, lmax = 0u;
-    for (uint32_t i = 0; i < nq; ++i) { lmin = std::min(lmin, qlen[i]); lmax = std::max(lmax, qlen[i]); }
-    auto flush = [&](uint64_t at, uint32_t bits) { // one writer per word, and inside the wave's map
-        if (fill || at == ~0ull) return;
-        map.at(at) = bits;
-        ++map_writes.at(at);
-    };
-    for (uint32_t split = 0; split < splits; ++split) {
+    // k_join_lane's loop over the lengths: the wave's window nearest-first, a length no lane needs skipped, the stop after a step
+    // none of whose lengths was needed
+    void lengths(JoinWave &W, bool fill, uint32_t split) const
+    {
+        const uint16_t *const rank = table().rank;
+        uint32_t lmin = 0xFFFFFFFFu, lmax = 0u;
+        for (uint32_t i = 0; i < W.nq; ++i) { lmin = std::min(lmin, qlen[i]); lmax = std::max(lmax, qlen[i]); }
         uint32_t lo, hi;
         extract_window(rank, lmin, lmax, rlimit, lo, hi);
         const uint32_t steps = nearest_steps(lmin, lmax, lo, hi);
@@ -118,41 +57,21 @@ static uint64_t sweep(const std::vector<uint32_t> &qlen, const std::vector<uint3
             if (!nearest_step_range(lmin, lmax, lo, hi, g, first, last, stride)) continue;
             bool needed = false;
             for (uint32_t lc = first; lc <= last; lc += stride) {
-                std::vector<uint8_t> need(nq);
+                std::vector<uint8_t> need(W.nq);
                 bool any = false;
-                for (uint32_t i = 0; i < nq; ++i) any |= (need[i] = join_needs(rank, qlen[i], lc, rlimit));
+                for (uint32_t i = 0; i < W.nq; ++i) any |= (need[i] = join_needs(rank, qlen[i], lc, rlimit));
                 if (!any) continue;
                 needed = true;
-                uint32_t x0, x1;
-                join_slice(cstart[lc], cstart[lc + 1] - cstart[lc], split, splits, x0, x1);
-                const uint32_t k = join_map_slice(lc, split, splits);
-                uint64_t at = ~0ull;
-                uint32_t bits = 0;
-                for (uint32_t x = x0; x < x1; ++x) {
-                    const uint64_t w = join_map_word(x, shift, k);
-                    if (w != at) {
-                        flush(at, bits);
-                        at = w;
-                        bits = fill ? map.at(w) : 0u;
-                    }
-                    const uint32_t bit = join_map_bit(x, shift);
-                    if (fill && !(bits & bit)) continue;
-                    const uint32_t j = order[x];
-                    ++visited;
-                    bool any_hit = false;
-                    for (uint32_t i = 0; i < nq; ++i) {
-                        const uint32_t r = extract_rank(rank, dist[(size_t)i * nc + j], qlen[i] + lc);
-                        if (need[i] && join_hit(r, rlimit, upper, i, j)) { on_hit(split, i, j, r); any_hit = true; }
-                    }
-                    if (!fill && any_hit) bits |= bit;
-                }
-                flush(at, bits);
+                join_slice_host(
+                    W, fill, split, lc, [&](uint32_t i) { return need[i] != 0; },
+                    [&](uint32_t i) { return JoinRankRule{rank + (qlen[i] + lc) * EXTRACT_TAB_W, rlimit, table().rep}; },
+                    [&](uint32_t i, uint32_t j) { return dist[(size_t)i * W.nc + j]; });
             }
             if (!needed) break;
         }
     }
-    return visited;
-}
+    int after(const JoinWave &, bool) const { return 0; }
+};
 
 // nq <= 64 queries and nc candidates of random lengths 0 .. maxlen with random Indel distances; stats[0] = candidates visited by
 // one sweep (out of nc), stats[1] = hits.  0, or the number of the first check that failed.
@@ -170,90 +89,9 @@ extern "C" int join_replay(uint64_t seed, uint32_t nq, uint32_t nc, uint32_t max
             dist[(size_t)i * nc + j] = qlen[i] + clen[j] - 2 * lcs;
         }
     const uint32_t rlimit = extract_rank_limit(table(), cutoff);
-    stats[0] = stats[1] = 0;
-    // brute force
-    std::vector<std::vector<uint32_t>> want(nq);
-    for (uint32_t i = 0; i < nq; ++i)
-        for (uint32_t j = 0; j < nc; ++j)
-            if (epilogue_indel(dist[(size_t)i * nc + j], qlen[i] + clen[j], 0u) >= cutoff && (!upper || j > i)) want[i].push_back(j);
-    if (rlimit == 0u || nq == 0u) { // (the library launches no sweep)
-        for (auto &w : want) if (!w.empty()) return 1;
-        return 0;
-    }
-    // the length order: any order inside a length (here, descending index)
-    std::vector<uint32_t> order(nc);
-    std::iota(order.begin(), order.end(), 0u);
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return clen[a] != clen[b] ? clen[a] < clen[b] : a > b; });
-    uint32_t cstart[NEAREST_BUCKETS + 1] = {};
-    for (uint32_t j = 0; j < nc; ++j) ++cstart[clen[j] + 1];
-    for (uint32_t b = 0; b < NEAREST_BUCKETS; ++b) cstart[b + 1] += cstart[b];
-
-    // count
-    const uint32_t lists = splits + 1;
-    std::vector<uint32_t> cnt((size_t)lists * nq, 0);
+    RankCase C{qlen, clen, dist.data(), rlimit, cutoff, rlimit == 0u};
     const uint32_t shift = (uint32_t)(seed % 3u); // groups of 1, 2 and 4 positions
-    std::vector<uint32_t> map(join_map_words(nc, splits, shift), 0xA5A5A5A5u);
-    std::vector<uint8_t> map_writes(map.size(), 0);
-    stats[0] = sweep(qlen, order, cstart, dist.data(), nc, rlimit, upper != 0, splits, false, shift, map, map_writes, [&](uint32_t s, uint32_t i, uint32_t, uint32_t) { ++cnt[(size_t)s * nq + i]; });
-    const std::vector<uint32_t> raw = cnt;
-    std::vector<uint64_t> indptr(nq + 1, 0), tot(nq);
-    for (uint32_t i = 0; i < nq; ++i) tot[i] = join_row_prefix(cnt.data(), nq, i, lists);
-    scan_as_kernels(tot);
-    for (uint32_t i = 0; i < nq; ++i) indptr[i + 1] = tot[i];
-    const uint64_t nnz = indptr[nq];
-    stats[1] = nnz;
-    for (uint32_t i = 0; i < nq; ++i)
-        if (indptr[i + 1] - indptr[i] != want[i].size()) return 2;
-
-    // fill, guard words around the outputs
-    std::vector<uint32_t> oi(nnz + 2 * EDGE, GUARD_I);
-    std::vector<double> os(nnz + 2 * EDGE, guard_score());
-    std::vector<uint8_t> writes(nnz + 2 * EDGE, 0);
-    uint32_t *const out_index = oi.data() + EDGE;
-    double *const out_score = os.data() + EDGE;
-    std::vector<uint64_t> cur((size_t)splits * nq), end((size_t)splits * nq);
-    int64_t short_at = -1; // the undersized segment: its last slot is taken away
-    for (uint32_t s = 0; s < splits; ++s)
-        for (uint32_t i = 0; i < nq; ++i) {
-            cur[(size_t)s * nq + i] = indptr[i] + cnt[(size_t)s * nq + i];
-            end[(size_t)s * nq + i] = indptr[i] + cnt[(size_t)(s + 1) * nq + i];
-            if (end[(size_t)s * nq + i] - cur[(size_t)s * nq + i] != raw[(size_t)s * nq + i]) return 3;
-            if (undersize && short_at < 0 && raw[(size_t)s * nq + i]) { short_at = (int64_t)--end[(size_t)s * nq + i]; }
-        }
-    int bad = 0;
-    uint32_t refused = 0;
-    for (uint8_t n : map_writes)
-        if (n > 1) return 12; // every word of the hit map has one writer
-    const uint64_t again = sweep(qlen, order, cstart, dist.data(), nc, rlimit, upper != 0, splits, true, shift, map, map_writes, [&](uint32_t s, uint32_t i, uint32_t j, uint32_t r) {
-        uint64_t &c = cur[(size_t)s * nq + i];
-        const uint64_t at = c;
-        if (join_store(c, end[(size_t)s * nq + i], j, extract_rank_score(table().rep, r), out_index, out_score)) {
-            if (at < indptr[i] || at >= indptr[i + 1]) bad = 4;
-            if (++writes[EDGE + at] > 1) bad = 5;
-        } else ++refused;
-    });
-    if (bad) return bad;
-    if (again > stats[0] || again > (nnz << shift)) return 6; // the fill computes marked candidates only: at most 2^shift per hit
-    if (refused != (short_at >= 0 ? 1u : 0u)) return 7;
-    for (size_t x = 0; x < oi.size(); ++x) {
-        const bool inside = x >= EDGE && x < EDGE + nnz && (int64_t)(x - EDGE) != short_at;
-        if (inside ? writes[x] != 1 : (writes[x] || oi[x] != GUARD_I || !is_guard(os[x]))) return 8;
-    }
-    if (short_at >= 0) return 0; // (the row with the hole is not a result)
-    // every hit exactly once, with its own score; then the row sort
-    for (uint32_t i = 0; i < nq; ++i) {
-        const uint64_t r0 = indptr[i], n = indptr[i + 1] - r0;
-        sort_as_kernels(out_index + r0, out_score + r0, n);
-        for (uint64_t x = 0; x < n; ++x) {
-            const uint32_t j = out_index[r0 + x];
-            if (j != want[i][x]) return 9;
-            const double e = epilogue_indel(dist[(size_t)i * nc + j], qlen[i] + clen[j], 0u);
-            if (memcmp(&e, &out_score[r0 + x], 8)) return 10;
-        }
-    }
-    for (size_t x = 0; x < EDGE; ++x)
-        if (oi[x] != GUARD_I || oi[EDGE + nnz + x] != GUARD_I || !is_guard(os[x]) || !is_guard(os[EDGE + nnz + x])) return 11;
-    return 0;
+    return join_replay_host(C, nq, clen, upper != 0, splits, undersize, shift, stats);
 }
 
 // A row of n distinct keys in random order, each with a score of its own, guard words around it.
