@@ -2,12 +2,13 @@
 # Registers / LDS / scratch of the kernels in csrc/strsim_kernels.hip (device-only compile, then the code object's metadata).
 #   bash bench_support/kernel_resources.sh [name-filter-regex | group] [EXTRA flags]
 # groups: nearest -- the kernels of strsim_nearest_device (its own and the best-match kernels it reuses)
-#         partial -- the kernels of the partial ratio (strsim_partial.h), and below them the OSA / distance / Indel kernels whose
-#                    headers it includes (their figures must not move when strsim_partial.h changes)
-#         token   -- the kernels of the token ratios (strsim_token.h), and below them the OSA / distance / Indel / partial kernels
+#         partial -- the kernels of the partial ratio (strsim_partial.h), and below them the edit-distance kernels (k_dist_*: the
+#                    distances and the OSA similarity) and the Indel kernels whose headers it includes (their figures must not move
+#                    when strsim_partial.h changes)
+#         token   -- the kernels of the token ratios (strsim_token.h), and below them the edit-distance / Indel / partial kernels
 #                    whose headers it includes (their figures must not move when strsim_token.h changes)
 #         wratio  -- the kernels of WRatio and the token compositions (strsim_wratio.h), and below them the token / partial / Indel /
-#                    OSA / distance kernels whose headers it includes (their figures must not move when strsim_wratio.h changes)
+#                    edit-distance kernels whose headers it includes (their figures must not move when strsim_wratio.h changes)
 #         extract -- the kernel of strsim_extract_device and the nearest / best-match kernels it reuses
 #         cdist   -- the kernels of strsim_cdist_device and the best-match kernels beside them (k_match_lane: the same sweep with a list)
 #         join    -- the kernels of strsim_join_device, the pack and length-order kernels it reuses and k_extract_lane beside them (the
@@ -16,14 +17,14 @@
 #                    a list) and the join kernels around the sweep
 #         cluster -- the kernels of strsim_components_device (strsim_cluster_device adds none: it runs the join's) and the join's
 #                    scan kernels they reuse
-#         qgram   -- the kernels of q-gram similarity (strsim_qgram.h), and below them the Indel / OSA / distance kernels whose headers
+#         qgram   -- the kernels of q-gram similarity (strsim_qgram.h), and below them the Indel / edit-distance kernels whose headers
 #                    it includes (their figures must not move when strsim_qgram.h changes)
 ROOT=$(cd "$(dirname "$0")/.." && pwd); OUT=${TMPDIR:-/tmp}/strsim_co; mkdir -p $OUT
 case "$1" in
-    qgram) FILTER='k_qgram_|k_indel_|k_osa_|k_dist_' ;;
-    wratio) FILTER='k_wratio_|k_take_|k_max_f64|k_token_|k_partial_|k_indel_|k_osa_|k_dist_' ;;
-    token) FILTER='k_token_|k_partial_|k_indel_|k_osa_|k_dist_' ;;
-    partial) FILTER='k_partial_|k_indel_|k_osa_|k_dist_' ;;
+    qgram) FILTER='k_qgram_|k_indel_|k_dist_' ;;
+    wratio) FILTER='k_wratio_|k_take_|k_max_f64|k_token_|k_partial_|k_indel_|k_dist_' ;;
+    token) FILTER='k_token_|k_partial_|k_indel_|k_dist_' ;;
+    partial) FILTER='k_partial_|k_indel_|k_dist_' ;;
     extract) FILTER='k_extract_|k_nearest_hist|k_nearest_scan|k_nearest_scatter|k_match_pack|k_match_clear|k_match_fold|k_match_merge' ;;
     cdist) FILTER='k_cdist_|k_match_pack|k_match_lane' ;;
     join) FILTER='k_join_|k_extract_|k_nearest_hist|k_nearest_scan|k_nearest_scatter|k_match_pack' ;;

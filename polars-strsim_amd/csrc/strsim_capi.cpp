@@ -709,25 +709,24 @@ static int dist_report(strsim_ctx *c)
 static constexpr size_t OSA_SCRATCH_BUDGET = (size_t)1 << 30; // the wave kernel runs fewer waves rather than use more scratch
 
 // Which pair of kernels a call runs, and what they take beside the LaunchArgs.
-enum TwoPassKind { TP_OSA, TP_DIST, TP_INDEL, TP_PARTIAL, TP_QGRAM };
+enum TwoPassKind { TP_DIST, TP_INDEL, TP_PARTIAL, TP_QGRAM };
 struct TwoPassCall {
     TwoPassKind kind;
     int measure;     // TP_DIST: STRSIM_LEVENSHTEIN or STRSIM_OSA; TP_QGRAM: the kind (STRSIM_QGRAM_*)
     uint32_t k;      // TP_DIST, TP_INDEL: the cutoff (DIST_UNBOUNDED: none)
-    uint32_t *out32; // TP_DIST: the distances; TP_INDEL: the distances, or nullptr for the similarity in la.out
+    uint32_t *out32; // TP_DIST, TP_INDEL: the distances, or nullptr for the similarity in la.out (TP_DIST: of STRSIM_OSA)
     uint32_t *span;  // TP_PARTIAL: the alignment, or nullptr for the score alone
     uint32_t q = 0u;     // TP_QGRAM: 1..3
     uint32_t flags = 0u; // TP_QGRAM: STRSIM_QGRAM_SET
 };
-static const char *const TWO_PASS_LANE[] = {"kernel launch (k_osa_lane)", "kernel launch (k_dist_lane)", "kernel launch (k_indel_lane)",
+static const char *const TWO_PASS_LANE[] = {"kernel launch (k_dist_lane)", "kernel launch (k_indel_lane)",
                                             "kernel launch (k_partial_lane)", "kernel launch (k_qgram_lane)"};
-static const char *const TWO_PASS_WAVE[] = {"kernel launch (k_osa_wave)", "kernel launch (k_dist_wave)", "kernel launch (k_indel_wave)",
+static const char *const TWO_PASS_WAVE[] = {"kernel launch (k_dist_wave)", "kernel launch (k_indel_wave)",
                                             "kernel launch (k_partial_wave)", "kernel launch (k_qgram_wave)"};
 
 static hipError_t two_pass_lane(const TwoPassCall &t, const LaunchArgs &la, uint32_t *list)
 {
     switch (t.kind) {
-    case TP_OSA: return launch_osa_lane(la, list);
     case TP_DIST: return launch_dist_lane(t.measure, la, t.k, t.out32, list);
     case TP_INDEL: return launch_indel_lane(la, t.k, t.out32, list);
     case TP_QGRAM: return launch_qgram_lane(la, t.measure, t.q, (t.flags & STRSIM_QGRAM_SET) != 0u, list);
@@ -742,7 +741,6 @@ static hipError_t two_pass_wave(const TwoPassCall &t, const LaunchArgs &la, cons
                                 uint64_t words)
 {
     switch (t.kind) {
-    case TP_OSA: return launch_osa_wave(la, list, grid, scratch, words);
     case TP_DIST: return launch_dist_wave(t.measure, la, t.k, t.out32, list, grid, scratch, words);
     case TP_INDEL: return launch_indel_wave(la, t.k, t.out32, list, grid, scratch, words);
     case TP_QGRAM: return launch_qgram_wave(la, t.measure, t.q, (t.flags & STRSIM_QGRAM_SET) != 0u, qgram_grams_bound(st), list, grid, scratch, words);
@@ -763,7 +761,7 @@ static uint64_t two_pass_slot_words(TwoPassKind kind, const DevStatus &st)
         return grams > QGRAM_WAVE_LDS_GRAMS ? qgram_wave_slot_words(grams, st.pad1[0]) : 0u;
     }
     if (st.max_len <= OSA_WAVE_LDS_CPS) return 0u; // (max_len bounds the pattern in scalar values: it is a byte length)
-    return kind == TP_OSA ? osa_wave_slot_words(st.max_len) : kind == TP_DIST ? dist_wave_slot_words(st.max_len) : indel_wave_slot_words(st.max_len);
+    return kind == TP_DIST ? dist_wave_slot_words(st.max_len) : indel_wave_slot_words(st.max_len);
 }
 
 // The shared flow.  la.status is the device status block the lane kernel counts into.  slot >= 0: a pairwise call, whose status
@@ -823,7 +821,7 @@ static int pairs_osa(strsim_ctx *c, int slot, int measure, const PairCols &p, do
     if (rc) return rc;
     slot_begin(c, slot);
     const LaunchArgs la = two_pass_args(c, p.a, p.b, out, p.n, c->status + slot);
-    const TwoPassKind kind = measure == STRSIM_PARTIAL_RATIO ? TP_PARTIAL : measure == STRSIM_INDEL ? TP_INDEL : TP_OSA;
+    const TwoPassKind kind = measure == STRSIM_PARTIAL_RATIO ? TP_PARTIAL : measure == STRSIM_INDEL ? TP_INDEL : TP_DIST;
     rc = two_pass(c, la, TwoPassCall{kind, measure, DIST_UNBOUNDED, nullptr, nullptr}, slot);
     if (rc) return rc;
     slot_commit(c, slot, la, measure, false, false, nullptr);

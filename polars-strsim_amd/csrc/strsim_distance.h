@@ -1,20 +1,27 @@
-// strsim_distance.h -- bounded edit distances as integers: Levenshtein (measure 0) and optimal string alignment (measure 6),
-// for strsim_distance_device / _host.
+// strsim_distance.h -- the edit-distance kernels: Levenshtein (measure 0) and optimal string alignment (measure 6) as bounded
+// integers, for strsim_distance_device / _host, and the OSA similarity of strsim_pairs_device (section 11).
 //
 // d is the edit distance over Unicode scalar values (Levenshtein: insert, delete, substitute; OSA: plus the restricted swap of two
 // adjacent characters of strsim_osa.h).  With a cutoff k (max_distance != STRSIM_DISTANCE_UNBOUNDED) a row's output is d when
-// d <= k and k + 1 otherwise (rapidfuzz's score_cutoff convention).
+// d <= k and k + 1 otherwise (rapidfuzz's score_cutoff convention).  The similarity is epilogue_osa of the unbounded d.
 //
 // Two tiers, both finished in stream order:
-//   k_dist_lane<TR, LIT>  one pair per lane, both strings ASCII and <= 64 bytes: the lane class, bit-planes and text walk of
-//                         k_osa_lane; TR = 1 adds the transposition term (OSA), TR = 0 is Myers' step.  A pair whose lengths
-//                         differ by more than k is k + 1 without the DP.  Every other row goes to a work list.
-//   k_dist_wave<TR>       one pair per wave for the work list: any UTF-8, any length, the decode and pattern storage of k_osa_wave
-//                         and its word step (osa_word_step).
+//   k_dist_lane<TR, LIT, OUT>  one pair per lane, both strings ASCII and <= 64 bytes; the pattern in seven bit-planes of 32 or 64
+//                         bits (eq_mask of strsim_lane_core.h), the text walked byte by byte from registers.  TR = 1 adds the
+//                         transposition term (OSA), TR = 0 is Myers' step.  A pair whose lengths differ by more than k is k + 1
+//                         without the DP.  Every other row is appended to a work list (worklist_append of strsim_wave_util.h).
+//   k_dist_wave<TR, OUT>  one pair per wave for the work list: any UTF-8, any length.  Both strings are decoded to scalar values;
+//                         the shorter (in scalar values) is the pattern, held in LDS up to OSA_WAVE_LDS_CPS values and in the
+//                         context's scratch above that (wave_stage of strsim_wave_util.h).  The match words of a text character
+//                         are built 64 pattern values at a time by a compare and a ballot; the words are then advanced one after
+//                         the other with the four carries between them (osa_word_step).
 //                         With a cutoff only the words 0..y of a column are advanced (the block cutoff of Myers 1999, section 4,
 //                         as in edlib), y being the last word that may still hold a cell <= k (dist_column below).
+// OUT = uint32_t is the distance.  OUT = double is the similarity, instantiated for TR = 1 alone: k is DIST_UNBOUNDED at compile
+// time, so the length cut, the clamp and the block cutoff's bookkeeping are compiled out.
 #pragma once
 #include <stdint.h>
+#include <type_traits>
 
 #include "strsim_osa.h"
 
@@ -24,6 +31,14 @@ constexpr uint32_t DIST_UNBOUNDED = 0xFFFFFFFFu; // = STRSIM_DISTANCE_UNBOUNDED
 
 // the output of a row: d, or k + 1 when d > k (never taken for k = DIST_UNBOUNDED: d < 2^32)
 STRSIM_HD uint32_t dist_clamp(uint64_t d, uint32_t k) { return d > (uint64_t)k ? k + 1u : (uint32_t)d; }
+
+// what both tiers write for a pair of la and lb scalar values: the clamped distance, or as a double the similarity (k: none)
+template <typename OUT>
+STRSIM_HD OUT dist_result(uint64_t d, uint64_t la, uint64_t lb, uint32_t k)
+{
+    if constexpr (std::is_same<OUT, double>::value) return epilogue_osa(d, la, lb);
+    else return dist_clamp(d, k);
+}
 
 // Length prefilter of both tiers: d >= | |a| - |b| |, so a pair whose lengths (in scalar values) differ by more than k is k + 1
 // without the DP.
@@ -53,7 +68,9 @@ STRSIM_HD void lev_step(T Eq, T &VP, T &VN)
     VN = D0 & X;
 }
 
-// Edit distance of an ASCII pattern against the text in wt: osa_lane_core with the step chosen by TR.
+// Edit distance of an ASCII pattern (lp <= 32 for T = uint32_t, <= 64 for uint64_t; planes from build_planes<7>) against the
+// text in wt (lt <= 64 bytes), the step chosen by TR.  Columns tmax and beyond are not run (lane-uniform, >= lt); columns
+// lt .. tmax-1 leave the state alone.
 template <typename T, bool TR>
 STRSIM_HD uint32_t dist_lane_core(const uint32_t (&wt)[16], uint32_t lt, uint32_t tmax, const uint32_t (&Plo)[7],
                                   const uint32_t (&Phi)[7], uint32_t lp)
@@ -79,8 +96,24 @@ STRSIM_HD uint32_t dist_lane_core(const uint32_t (&wt)[16], uint32_t lt, uint32_
 struct DistWord {
     uint64_t VP, VN, D0p, EQp, score;
 };
+// The same without the score, for the similarity (never a cutoff): 32 bytes a word, which keeps the 16-byte halves of every word
+// aligned -- in an array of DistWord those of every second word are not, and the wave kernel's loads and stores of them are slow.
+struct DistWordFree {
+    uint64_t VP, VN, D0p, EQp;
+};
+template <typename Word>
+constexpr bool dist_scored = std::is_same<Word, DistWord>::value;
+
+// word w before the first column
+template <typename Word>
+STRSIM_HD Word dist_word_start(uint32_t w)
+{
+    if constexpr (dist_scored<Word>) return Word{~0ull, 0ull, 0ull, 0ull, 64ull * (w + 1u)};
+    else return Word{~0ull, 0ull, 0ull, 0ull};
+}
 
 // k_dist_wave scratch of one wave for patterns of up to m scalar values: the values (padded to whole words) and a DistWord per word
+// (which holds the similarity's DistWordFree words as well)
 STRSIM_HD uint64_t dist_wave_slot_words(uint64_t m)
 {
     const uint64_t words = (m + 63u) / 64u;
@@ -103,30 +136,37 @@ STRSIM_HD int dist_first_y(uint32_t W, uint64_t m, uint64_t k, bool bounded)
 //   - afterwards, while word y's bottom score is >= k + 64, every cell of it is > k (neighbouring rows differ by at most 1) and
 //     y drops by one.
 // Words beyond y keep stale state; computed cells are never below the true ones, and equal them wherever the true value is <= k.
-template <bool TR, typename EqFn>
-STRSIM_HD void dist_column(DistWord *st, int &y, uint32_t W, uint64_t k, uint64_t c, bool bounded, EqFn &&eq)
+// Words without a score (DistWordFree: never bounded, y = W - 1 throughout) leave the scores and the moves of y out of the code.
+template <bool TR, typename Word, typename EqFn>
+STRSIM_HD void dist_column(Word *st, int &y, uint32_t W, uint64_t k, uint64_t c, bool bounded, EqFn &&eq)
 {
-    if (bounded && y + 1 < (int)W) {
-        const uint64_t above = y < 0 ? c : st[y].score;
-        if (above <= k) {
-            ++y;
-            DistWord &n = st[y];
-            n.VP = ~0ull; n.VN = 0ull; n.D0p = 0ull; n.EQp = 0ull;
-            n.score = above + 64u;
+    constexpr bool SCORED = dist_scored<Word>;
+    if constexpr (SCORED) {
+        if (bounded && y + 1 < (int)W) {
+            const uint64_t above = y < 0 ? c : st[y].score;
+            if (above <= k) {
+                ++y;
+                DistWord &n = st[y];
+                n.VP = ~0ull; n.VN = 0ull; n.D0p = 0ull; n.EQp = 0ull;
+                n.score = above + 64u;
+            }
         }
     }
     uint64_t add_c = 0ull, hp_c = 1ull, hn_c = 0ull, tr_c = 0ull;
     for (int w = 0; w <= y; ++w) {
-        DistWord &s = st[w];
+        Word &s = st[w];
         osa_word_step<TR>(eq((uint32_t)w), s.VP, s.VN, s.D0p, s.EQp, add_c, hp_c, hn_c, tr_c);
-        s.score = s.score + hp_c - hn_c;
+        if constexpr (SCORED) s.score = s.score + hp_c - hn_c;
     }
-    if (bounded)
-        while (y >= 0 && st[y].score >= k + 64u) --y;
+    if constexpr (SCORED) {
+        if (bounded)
+            while (y >= 0 && st[y].score >= k + 64u) --y;
+    }
 }
 
 // The result once the columns are done: d from the last column when every word is active, else > k.
-STRSIM_HD uint64_t dist_final(const DistWord *st, int y, uint32_t W, uint64_t m, uint64_t nt, uint64_t k)
+template <typename Word>
+STRSIM_HD uint64_t dist_final(const Word *st, int y, uint32_t W, uint64_t m, uint64_t nt, uint64_t k)
 {
     if (y != (int)W - 1) return k + 1u;
     uint64_t up = 0u, dn = 0u;
@@ -144,92 +184,88 @@ STRSIM_HD uint64_t dist_final(const DistWord *st, int y, uint32_t W, uint64_t m,
 // device side
 // ------------------------------------------------------------------------------------------------
 
-// One pair per lane (k_osa_lane's classes and text walk).  TR: 1 = OSA, 0 = Levenshtein.  LIT as k_osa_lane.  A row whose
-// lengths differ by more than k is k + 1 without the DP, and a wave of such rows runs no columns.  Rows this kernel cannot take
-// are appended to `worklist` (worklist_append of strsim_wave_util.h); the status block is zeroed before the launch.
-template <bool TR, int LIT>
+// One pair per lane.  TR: 1 = OSA, 0 = Levenshtein.  LIT: 0 = row against row, 1 = a is a literal (rowsA == 1), 2 = b is
+// (lane_pick of strsim_wave_util.h: a literal is the text).  OUT: uint32_t = the distance under the cutoff kcut, a row whose
+// lengths differ by more than it is kcut + 1 without the DP, and a wave of such rows runs no columns; double = the similarity
+// (kcut is not looked at).  Rows this kernel cannot take are appended to `worklist`; st->wave_rows counts them and st->max_len
+// bounds their patterns (min of the two byte lengths).  The status block is zeroed before the launch.
+template <bool TR, int LIT, typename OUT>
 __global__ __launch_bounds__(256) void k_dist_lane(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ valA,
                                                    const uint32_t *__restrict__ offB, const uint8_t *__restrict__ valB, uint64_t n,
-                                                   uint32_t k, uint32_t *__restrict__ out, uint32_t *__restrict__ worklist,
-                                                   DevStatus *st)
+                                                   uint32_t kcut, OUT *__restrict__ out, uint32_t *__restrict__ worklist, DevStatus *st)
 {
-    const uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = row < n;
-    const uint64_t ia = (LIT == 1 || !live) ? 0 : row, ib = (LIT == 2 || !live) ? 0 : row;
-    const uint32_t a0 = offA[ia], la = offA[ia + 1] - a0;
-    const uint32_t b0 = offB[ib], lb = offB[ib + 1] - b0;
-    const bool fits = live && dist_lane_fits(la, lb);
-    const bool a_is_pat = LIT == 1 ? false : (LIT == 2 ? true : la >= lb);
-    const uint8_t *pv = a_is_pat ? valA : valB, *tv = a_is_pat ? valB : valA;
-    const uint32_t po = a_is_pat ? a0 : b0, to = a_is_pat ? b0 : a0;
-    const uint32_t lp = a_is_pat ? la : lb, lt = a_is_pat ? lb : la;
+    constexpr bool SIM = std::is_same<OUT, double>::value;
+    const uint32_t k = SIM ? DIST_UNBOUNDED : kcut;
+    const LaneRow r = lane_row(offA, offB, n, LIT == 1, LIT == 2);
+    const uint64_t row = r.row;
+    const uint32_t la = r.la, lb = r.lb;
+    const bool fits = r.live && dist_lane_fits(la, lb);
+    const LanePick p = lane_pick<LIT>(valA, valB, r);
+    const uint32_t lp = p.lp, lt = p.lt;
     uint32_t wp[16] = {}, wt[16] = {};
     bool ascii = false;
     if (fits) {
-        osa_load64(pv, po, lp, wp);
-        osa_load64(tv, to, lt, wt);
+        osa_load64(p.pv, p.po, lp, wp);
+        osa_load64(p.tv, p.to, lt, wt);
         ascii = (osa_high_bits(wp) | osa_high_bits(wt)) == 0u;
     }
-    const uint32_t cls = dist_lane_row(live, la, lb, ascii, k);
-    worklist_append<false>(cls == DIST_ROW_WAVE, row, la, lb, worklist, st);
-    if (cls == DIST_ROW_CUT) out[row] = k + 1u;
+    const uint32_t cls = dist_lane_row(r.live, la, lb, ascii, k);
+    worklist_append<false>(cls == DIST_ROW_WAVE, row, la, lb, worklist, st); // rows for k_dist_wave
+    if constexpr (!SIM)
+        if (cls == DIST_ROW_CUT) out[row] = k + 1u;
     const bool run = cls == DIST_ROW_RUN;
     if (__ballot(run) == 0ull) return;
     const uint32_t tmax = osa_wave_max(run ? lt : 0u);
     const uint32_t pmax = osa_wave_max(run ? lp : 0u);
     uint32_t Plo[7], Phi[7];
     osa_planes(wp, Plo, Phi, pmax > 32u);
+    // (a row the cutoff decided has its text loaded and runs no column; without a cutoff there is none, and a literal's length stays
+    // a uniform value)
+    const uint32_t cols = (SIM || run) ? lt : 0u;
     uint32_t d;
-    if (pmax <= 32u) d = dist_lane_core<uint32_t, TR>(wt, run ? lt : 0u, tmax, Plo, Phi, lp);
-    else d = dist_lane_core<uint64_t, TR>(wt, run ? lt : 0u, tmax, Plo, Phi, lp);
-    if (run) out[row] = dist_clamp(d, k);
+    if (pmax <= 32u) d = dist_lane_core<uint32_t, TR>(wt, cols, tmax, Plo, Phi, lp);
+    else d = dist_lane_core<uint64_t, TR>(wt, cols, tmax, Plo, Phi, lp);
+    if (run) out[row] = dist_result<OUT>(d, la, lb, k);
 }
 
-// One pair per wave (blockDim.x = 64) for the rows k_dist_lane put on the work list.  scratch: gridDim.x slots of slot_words
-// words for patterns of more than OSA_WAVE_LDS_CPS values (nullptr when the call has none).
-template <bool TR>
+// One pair per wave (blockDim.x = 64) for the rows k_dist_lane put on the work list (st->wave_rows of them).  scratch: gridDim.x
+// slots of slot_words words for patterns of more than OSA_WAVE_LDS_CPS values (nullptr when the call has none).  OUT as k_dist_lane.
+template <bool TR, typename OUT>
 __global__ __launch_bounds__(64) void k_dist_wave(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ valA, uint64_t rowsA,
                                                   const uint32_t *__restrict__ offB, const uint8_t *__restrict__ valB, uint64_t rowsB,
-                                                  uint32_t k, uint32_t *__restrict__ out, const uint32_t *__restrict__ worklist,
+                                                  uint32_t kcut, OUT *__restrict__ out, const uint32_t *__restrict__ worklist,
                                                   const DevStatus *st, uint32_t *scratch, uint64_t slot_words)
 {
+    constexpr bool SIM = std::is_same<OUT, double>::value;
+    const uint32_t k = SIM ? DIST_UNBOUNDED : kcut;
     __shared__ uint32_t s_pat[OSA_WAVE_LDS_CPS];
-    __shared__ DistWord s_state[OSA_WAVE_LDS_CPS / 64u];
+    using Word = std::conditional_t<SIM, DistWordFree, DistWord>;
+    __shared__ Word s_state[OSA_WAVE_LDS_CPS / 64u];
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t count = st->wave_rows;
     for (uint32_t r = blockIdx.x; r < count; r += gridDim.x) {
-        const auto [row, pa, pb, na, nb, ca, cb] = wave_pair(offA, valA, rowsA, offB, valB, rowsB, worklist[r]);
-        const bool a_is_pat = ca <= cb;
-        const uint8_t *pp = a_is_pat ? pa : pb, *tp = a_is_pat ? pb : pa;
-        const uint32_t pbytes = a_is_pat ? na : nb, tbytes = a_is_pat ? nb : na;
-        const uint32_t m = a_is_pat ? ca : cb, nt = a_is_pat ? cb : ca;
+        const WavePair p = wave_pair(offA, valA, rowsA, offB, valB, rowsB, worklist[r]);
+        const WaveStage<Word> s = wave_stage(p, s_pat, s_state, OSA_WAVE_LDS_CPS, scratch, slot_words);
+        const uint32_t m = s.m, nt = s.nt, W = s.W;
         uint64_t d = nt;
-        if (dist_length_cut(m, nt, k)) {
+        if (!SIM && dist_length_cut(m, nt, k)) {
             d = (uint64_t)k + 1u;
         } else if (m != 0u) {
-            const uint32_t W = (m + 63u) / 64u;
-            const bool bounded = k < nt; // (d <= nt: a larger k cuts nothing)
-            uint32_t *pat = s_pat;
-            DistWord *state = s_state;
-            if (m > OSA_WAVE_LDS_CPS) {
-                pat = scratch + (uint64_t)blockIdx.x * slot_words;
-                state = reinterpret_cast<DistWord *>(pat + (uint64_t)W * 64u);
-            }
-            wave_decode(pp, pbytes, pat, lane);
-            for (uint32_t i = m + lane; i < W * 64u; i += 64u) pat[i] = 0xFFFFFFFFu;
+            const bool bounded = !SIM && k < nt; // (d <= nt: a larger k cuts nothing)
+            wave_pattern(s.pp, s.pbytes, m, W, s.pat, lane);
             int y = dist_first_y(W, m, k, bounded);
-            for (uint32_t w = lane; w < W; w += 64u) state[w] = DistWord{~0ull, 0ull, 0ull, 0ull, 64ull * (w + 1u)};
+            for (uint32_t w = lane; w < W; w += 64u) s.state[w] = dist_word_start<Word>(w);
             __syncthreads();
             uint64_t c = 0u;
-            const bool done = wave_each_char(tp, tbytes, lane, [&](uint32_t ch) {
-                dist_column<TR>(state, y, W, k, c, bounded, [&](uint32_t w) { return (uint64_t)__ballot(pat[64u * w + lane] == ch); });
+            const bool done = wave_each_char(s.tp, s.tbytes, lane, [&](uint32_t ch) {
+                dist_column<TR>(s.state, y, W, k, c, bounded, [&](uint32_t w) { return (uint64_t)__ballot(s.pat[64u * w + lane] == ch); });
                 ++c;
-                return !(y < 0 && c > k); // false: no cell of this column is <= k (row 0 holds c), the pair is decided
+                return SIM || !(y < 0 && c > k); // false: no cell of this column is <= k (row 0 holds c), the pair is decided
             });
-            d = done ? dist_final(state, y, W, m, nt, k) : (uint64_t)k + 1u;
+            d = done ? dist_final(s.state, y, W, m, nt, k) : (uint64_t)k + 1u;
             __syncthreads(); // (the next row overwrites pat / state)
         }
-        if (lane == 0u) out[row] = dist_clamp(d, k);
+        if (lane == 0u) out[p.row] = dist_result<OUT>(d, p.ca, p.cb, k);
     }
 }
 #endif // __HIPCC__ && !STRSIM_OSA_NO_KERNELS

@@ -188,7 +188,7 @@ __device__ __forceinline__ uint32_t indel_lane_run(const uint8_t *__restrict__ p
     return indel_lane_lcs<W>(V, lp);
 }
 
-// One pair per lane.  LIT as k_osa_lane: 0 = row against row (the longer string is the pattern), 1 = a is a literal, 2 = b is (the
+// One pair per lane.  LIT as k_dist_lane: 0 = row against row (the longer string is the pattern), 1 = a is a literal, 2 = b is (the
 // literal is the text, read through a wave-uniform address; the row is the pattern).  k: the distance cutoff (DIST_UNBOUNDED for
 // the similarity); a pair of ASCII strings whose lengths differ by more than k is k + 1 without any column.  Rows this kernel
 // cannot take are appended to `worklist` (worklist_append of strsim_wave_util.h); the status block is zeroed before the launch.
@@ -199,23 +199,21 @@ __global__ __launch_bounds__(256) void k_indel_lane(const uint32_t *__restrict__
                                                     uint32_t *__restrict__ worklist, DevStatus *st)
 {
     constexpr bool UNI = LIT != 0;
-    const uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = row < n;
-    const uint64_t ia = (LIT == 1 || !live) ? 0 : row, ib = (LIT == 2 || !live) ? 0 : row;
-    const uint32_t a0 = offA[ia], la = offA[ia + 1] - a0;
-    const uint32_t b0 = offB[ib], lb = offB[ib + 1] - b0;
-    const bool fits = live && la <= INDEL_LANE_MAX_BYTES && lb <= INDEL_LANE_MAX_BYTES;
-    const bool a_is_pat = LIT == 1 ? false : (LIT == 2 ? true : la >= lb);
-    const uint8_t *pv = a_is_pat ? valA : valB, *tv = a_is_pat ? valB : valA;
-    const uint32_t po = a_is_pat ? a0 : b0;
+    const LaneRow r = lane_row(offA, offB, n, LIT == 1, LIT == 2);
+    const uint64_t row = r.row;
+    const uint32_t la = r.la, lb = r.lb;
+    const bool live = r.live, fits = live && la <= INDEL_LANE_MAX_BYTES && lb <= INDEL_LANE_MAX_BYTES;
+    const LanePick p = lane_pick<LIT>(valA, valB, r);
+    const uint8_t *pv = p.pv, *tv = p.tv;
+    const uint32_t po = p.po;
     // a lane that does not fit loads nothing and runs no column
-    const uint32_t lp = fits ? (a_is_pat ? la : lb) : 0u, lt = fits ? (a_is_pat ? lb : la) : 0u;
+    const uint32_t lp = fits ? p.lp : 0u, lt = fits ? p.lt : 0u;
     const bool cut = dist_length_cut(la, lb, k); // (holds for an ASCII row: bytes are scalar values)
     const uint32_t lt_run = cut ? 0u : lt;
     // The text as it is loaded: a literal by every lane alike (whether or not the lane's row fits), a row's by its lane.
-    uint32_t to = a_is_pat ? b0 : a0, nt = lt;
+    uint32_t to = p.to, nt = lt;
     if constexpr (UNI) {
-        const uint32_t llit = wave_uniform(a_is_pat ? lb : la);
+        const uint32_t llit = wave_uniform(p.lt);
         to = wave_uniform(to);
         nt = llit <= INDEL_LANE_MAX_BYTES ? llit : 0u;
     }
@@ -276,25 +274,16 @@ __global__ __launch_bounds__(64) void k_indel_wave(const uint32_t *__restrict__ 
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t count = st->wave_rows;
     for (uint32_t r = blockIdx.x; r < count; r += gridDim.x) {
-        const auto [row, pa, pb, na, nb, ca, cb] = wave_pair(offA, valA, rowsA, offB, valB, rowsB, worklist[r]);
-        const bool a_is_pat = ca <= cb;
-        const uint8_t *pp = a_is_pat ? pa : pb, *tp = a_is_pat ? pb : pa;
-        const uint32_t pbytes = a_is_pat ? na : nb, tbytes = a_is_pat ? nb : na;
-        const uint32_t m = a_is_pat ? ca : cb;
+        const WavePair p = wave_pair(offA, valA, rowsA, offB, valB, rowsB, worklist[r]);
+        const WaveStage<uint64_t> s = wave_stage(p, s_pat, s_state, OSA_WAVE_LDS_CPS, scratch, slot_words);
+        const uint32_t row = p.row, ca = p.ca, cb = p.cb, m = s.m, W = s.W, tbytes = s.tbytes;
+        const uint8_t *tp = s.tp;
+        uint32_t *const pat = s.pat;
+        uint64_t *const state = s.state;
         const bool cut = dist_length_cut(ca, cb, k);
         uint32_t l = 0u;
         if (!cut && m != 0u) {
-            const uint32_t W = (m + 63u) / 64u;
-            const uint32_t Wpad = W == 3u ? 4u : W; // (the register form has 1, 2 or 4 words)
-            uint32_t *pat = s_pat;
-            uint64_t *state = s_state;
-            if (m > OSA_WAVE_LDS_CPS) {
-                pat = scratch + (uint64_t)blockIdx.x * slot_words;
-                state = reinterpret_cast<uint64_t *>(pat + (uint64_t)W * 64u);
-            }
-            // the pattern's values; those past m never match (no scalar value is 0xFFFFFFFF)
-            wave_decode(pp, pbytes, pat, lane);
-            for (uint32_t i = m + lane; i < Wpad * 64u; i += 64u) pat[i] = 0xFFFFFFFFu;
+            wave_pattern(s.pp, s.pbytes, m, W == 3u ? 4u : W, pat, lane); // (the register form has 1, 2 or 4 words)
             for (uint32_t w = lane; w < W; w += 64u) state[w] = ~0ull;
             __syncthreads();
             if (W == 1u) l = indel_wave_reg<1>(pat, m, tp, tbytes, lane);

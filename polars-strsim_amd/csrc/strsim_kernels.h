@@ -117,17 +117,14 @@ hipError_t launch_match_fold_rows(uint32_t k, const double *scores, const uint32
 hipError_t launch_match_merge(uint32_t k, const double *pscore, const uint32_t *pidx, uint32_t nl, uint32_t nq, uint32_t *out_index,
                               double *out_score, hipStream_t stream);
 
-// Optimal string alignment (strsim_osa.h), measure id 6.  k_osa_lane over all a.n rows: the rows it cannot take go to `worklist`
-// (a.n words), counted in a.status->wave_rows, with a.status->max_len a bound of their pattern lengths; the caller zeroes the
-// status block first.  k_osa_wave then finishes the work list on `grid` waves, each with slot_words words of `scratch` (patterns
-// longer than OSA_WAVE_LDS_CPS scalar values; nullptr when there are none).
-hipError_t launch_osa_lane(const LaunchArgs &a, uint32_t *worklist);
-hipError_t launch_osa_wave(const LaunchArgs &a, const uint32_t *worklist, int grid, uint32_t *scratch, uint64_t slot_words);
-
-// Bounded edit distances (strsim_distance.h): measure 0 (Levenshtein) or 6 (OSA), uint32 outputs (a.out is not used).  The same
-// two-kernel protocol as the OSA launches above: k_dist_lane over all a.n rows, then k_dist_wave over its work list.
-hipError_t launch_dist_lane(int measure, const LaunchArgs &a, uint32_t k, uint32_t *out, uint32_t *worklist);
-hipError_t launch_dist_wave(int measure, const LaunchArgs &a, uint32_t k, uint32_t *out, const uint32_t *worklist, int grid,
+// Edit distances (strsim_distance.h): measure 0 (Levenshtein) or 6 (OSA).  k_dist_lane over all a.n rows: the rows it cannot take
+// go to `worklist` (a.n words), counted in a.status->wave_rows, with a.status->max_len a bound of their pattern lengths; the caller
+// zeroes the status block first.  k_dist_wave then finishes the work list on `grid` waves, each with slot_words words of `scratch`
+// (patterns longer than OSA_WAVE_LDS_CPS scalar values; nullptr when there are none).  out32 != nullptr: the uint32 distance
+// clamped by k into out32 (a.out is not used); out32 == nullptr, measure 6 alone: the f64 OSA similarity into a.out
+// (k = DIST_UNBOUNDED).
+hipError_t launch_dist_lane(int measure, const LaunchArgs &a, uint32_t k, uint32_t *out32, uint32_t *worklist);
+hipError_t launch_dist_wave(int measure, const LaunchArgs &a, uint32_t k, uint32_t *out32, const uint32_t *worklist, int grid,
                             uint32_t *scratch, uint64_t slot_words);
 
 // Indel similarity / distance (strsim_indel.h), measure id 8: the same two-kernel protocol.  out32 == nullptr: the f64 similarity

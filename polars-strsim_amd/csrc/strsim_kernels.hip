@@ -21,10 +21,10 @@
 //                     lane, DPP hand-off), match masks from a per-lane LDS table, texts in a global arena; on bytes
 //                     (ASCII) or on 16-bit scalar values (the reference works on `char`s, strsim.rs:133,189,297).
 //                     Other measures: one pair per wave, scalar values in LDS, ballot matching / histograms.
-//   k_osa_lane / k_osa_wave  optimal string alignment (measure 6, strsim_osa.h): one pair per lane for ASCII strings of up
-//                     to 64 bytes, one pair per wave for the rest; both in stream order, no second pass.
-//   k_dist_lane / k_dist_wave  bounded integer edit distances (Levenshtein, OSA; strsim_distance.h): the same two tiers, uint32
-//                     outputs, a length prefilter and, in the wave tier, the block cutoff of Myers / Ukkonen.
+//   k_dist_lane / k_dist_wave  the edit distances over scalar values (strsim_distance.h): one pair per lane for ASCII strings of up
+//                     to 64 bytes, one pair per wave for the rest; both in stream order, no second pass.  As uint32: the bounded
+//                     Levenshtein and OSA distances, with a length prefilter and, in the wave tier, the block cutoff of Myers /
+//                     Ukkonen.  As double: the optimal string alignment similarity (measure 6, strsim_osa.h), never a cutoff.
 //   k_indel_lane / k_indel_wave  Indel (LCS) similarity and distance (measure 8, strsim_indel.h): one pair per lane for ASCII
 //                     strings of up to 128 bytes (1..4 mask words per wave), one pair per wave for the rest; in stream order.
 //   k_qgram_lane / k_qgram_wave  q-gram Jaccard, Dice, overlap and cosine (strsim_qgram.h; q = 1..3, multiset or set): one pair per
@@ -710,47 +710,38 @@ hipError_t launch_components(const ComponentsArgs &a)
     return hipGetLastError();
 }
 
-hipError_t launch_osa_lane(const LaunchArgs &a, uint32_t *worklist)
+// OUT = uint32_t: the distance into out32; OUT = double (OSA alone): the similarity into a.out
+template <bool TR, typename OUT>
+static void launch_dist_lane_as(const LaunchArgs &a, uint32_t k, OUT *out, uint32_t *worklist)
 {
     with_literal(a, [&](auto LIT) {
-        hipLaunchKernelGGL(k_osa_lane<decltype(LIT)::value>, lane_grid(a), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, a.out,
-                           worklist, a.status);
-    });
-    return hipGetLastError();
-}
-
-hipError_t launch_osa_wave(const LaunchArgs &a, const uint32_t *worklist, int grid, uint32_t *scratch, uint64_t slot_words)
-{
-    hipLaunchKernelGGL(k_osa_wave, dim3((unsigned)grid), dim3(64), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB, a.rowsB,
-                       a.out, worklist, a.status, scratch, slot_words);
-    return hipGetLastError();
-}
-
-template <bool TR>
-static void launch_dist_lane_tr(const LaunchArgs &a, uint32_t k, uint32_t *out, uint32_t *worklist)
-{
-    with_literal(a, [&](auto LIT) {
-        hipLaunchKernelGGL((k_dist_lane<TR, decltype(LIT)::value>), lane_grid(a), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, k,
-                           out, worklist, a.status);
+        hipLaunchKernelGGL((k_dist_lane<TR, decltype(LIT)::value, OUT>), lane_grid(a), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n,
+                           k, out, worklist, a.status);
     });
 }
 
-hipError_t launch_dist_lane(int measure, const LaunchArgs &a, uint32_t k, uint32_t *out, uint32_t *worklist)
+template <bool TR, typename OUT>
+static void launch_dist_wave_as(const LaunchArgs &a, uint32_t k, OUT *out, const uint32_t *worklist, int grid, uint32_t *scratch,
+                                uint64_t slot_words)
 {
-    if (measure == OSA) launch_dist_lane_tr<true>(a, k, out, worklist);
-    else launch_dist_lane_tr<false>(a, k, out, worklist);
+    hipLaunchKernelGGL((k_dist_wave<TR, OUT>), dim3((unsigned)grid), dim3(64), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB, a.rowsB,
+                       k, out, worklist, a.status, scratch, slot_words);
+}
+
+hipError_t launch_dist_lane(int measure, const LaunchArgs &a, uint32_t k, uint32_t *out32, uint32_t *worklist)
+{
+    if (measure != OSA) launch_dist_lane_as<false>(a, k, out32, worklist);
+    else if (out32) launch_dist_lane_as<true>(a, k, out32, worklist);
+    else launch_dist_lane_as<true>(a, k, a.out, worklist);
     return hipGetLastError();
 }
 
-hipError_t launch_dist_wave(int measure, const LaunchArgs &a, uint32_t k, uint32_t *out, const uint32_t *worklist, int grid,
+hipError_t launch_dist_wave(int measure, const LaunchArgs &a, uint32_t k, uint32_t *out32, const uint32_t *worklist, int grid,
                             uint32_t *scratch, uint64_t slot_words)
 {
-    if (measure == OSA)
-        hipLaunchKernelGGL(k_dist_wave<true>, dim3((unsigned)grid), dim3(64), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB,
-                           a.rowsB, k, out, worklist, a.status, scratch, slot_words);
-    else
-        hipLaunchKernelGGL(k_dist_wave<false>, dim3((unsigned)grid), dim3(64), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB,
-                           a.rowsB, k, out, worklist, a.status, scratch, slot_words);
+    if (measure != OSA) launch_dist_wave_as<false>(a, k, out32, worklist, grid, scratch, slot_words);
+    else if (out32) launch_dist_wave_as<true>(a, k, out32, worklist, grid, scratch, slot_words);
+    else launch_dist_wave_as<true>(a, k, a.out, worklist, grid, scratch, slot_words);
     return hipGetLastError();
 }
 

@@ -259,11 +259,7 @@ __global__ __launch_bounds__(256) void k_partial_lane(const uint32_t *__restrict
                                                       uint32_t *__restrict__ worklist, DevStatus *st)
 {
     __shared__ uint32_t s_eq[PARTIAL_LANE_MAX_BYTES * 256u]; // [column][thread]
-    const uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = row < nrows;
-    const uint64_t ia = (LIT == 1 || !live) ? 0 : row, ib = (LIT == 2 || !live) ? 0 : row;
-    const uint32_t a0 = offA[ia], la = offA[ia + 1] - a0;
-    const uint32_t b0 = offB[ib], lb = offB[ib + 1] - b0;
+    const auto [row, live, a0, la, b0, lb] = lane_row(offA, offB, nrows, LIT == 1, LIT == 2);
     const bool fits = live && la <= PARTIAL_LANE_MAX_BYTES && lb <= PARTIAL_LANE_MAX_BYTES;
     const bool a_needle = la <= lb;
     // a lane that does not fit loads nothing and runs no column
@@ -361,8 +357,7 @@ __device__ __forceinline__ PartialWin partial_wave_pair(const uint8_t *__restric
         uint32_t *hay = mem, *pat = mem + n;
         uint64_t *V = reinterpret_cast<uint64_t *>(mem + ((n + 64u * W + 1u) & ~1u));
         wave_decode(tp, tbytes, hay, lane);
-        wave_decode(pp, pbytes, pat, lane);
-        for (uint32_t i = m + lane; i < W * 64u; i += 64u) pat[i] = 0xFFFFFFFFu;
+        wave_pattern(pp, pbytes, m, W, pat, lane);
         __syncthreads();
         // (every lane stores the same V words and reads back its own store)
         best = partial_words_windows(

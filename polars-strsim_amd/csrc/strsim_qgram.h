@@ -213,11 +213,7 @@ __global__ __launch_bounds__(256) void k_qgram_lane(const uint32_t *__restrict__
                                                     uint64_t n, int kind, double *__restrict__ out, uint32_t *__restrict__ worklist,
                                                     DevStatus *st)
 {
-    const uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = row < n;
-    const uint64_t ia = (rowsA == 1 || !live) ? 0 : row, ib = (rowsB == 1 || !live) ? 0 : row;
-    const uint32_t a0 = offA[ia], la = offA[ia + 1] - a0;
-    const uint32_t b0 = offB[ib], lb = offB[ib + 1] - b0;
+    const auto [row, live, a0, la, b0, lb] = lane_row(offA, offB, n, rowsA == 1, rowsB == 1);
     const bool fits = live && la <= QGRAM_LANE_MAX_BYTES && lb <= QGRAM_LANE_MAX_BYTES;
     // a lane that does not fit loads nothing and has no gram
     const uint32_t lar = fits ? la : 0u, lbr = fits ? lb : 0u;

@@ -1,9 +1,11 @@
 // strsim_wave_util.h -- what the two-pass measures' kernels share on the device (strsim_osa.h, strsim_distance.h, strsim_indel.h,
 // strsim_partial.h, strsim_token.h, strsim_wratio.h): a lane kernel takes the rows it can and appends the others to a work list, a
 // wave kernel then takes one listed pair per wave.
+//   lane_row, lane_pick                             the lane kernel's row (offsets, lengths) and its choice of pattern and text
 //   wave_append, worklist_append                    the lane kernel's append of a row to the list (one atomic a wave)
 //   osa_is_start, osa_decode_at, osa_count_chars    UTF-8 by the wave, 64 bytes at a time
 //   wave_pair, wave_decode, wave_each_char          the wave kernel's pair, its pattern as scalar values, its text column by column
+//   wave_stage, wave_pattern                        the wave kernel's pattern and text, where pattern and state live, the padded decode
 // None of them holds a barrier: a kernel that stores through wave_decode and reads another lane's value puts its own
 // __syncthreads() between the two.  (DevStatus: strsim_kernels.h, included before this header.)
 #pragma once
@@ -25,6 +27,50 @@ __device__ __forceinline__ uint32_t osa_wave_max(uint32_t v)
 }
 
 // ---- the lane kernel's side ----
+
+// The row of a lane (blockDim.x rows a block): whether it is one of the call's n, and where its two strings start and how many bytes
+// they have.  lit_a / lit_b: that side is a literal, row 0 for every lane (constants in the LIT kernels); a lane past the end reads
+// row 0 of both sides.
+struct LaneRow {
+    uint64_t row;
+    bool live;
+    uint32_t a0, la, b0, lb;
+};
+__device__ __forceinline__ LaneRow lane_row(const uint32_t *__restrict__ offA, const uint32_t *__restrict__ offB, uint64_t n, bool lit_a,
+                                            bool lit_b)
+{
+    LaneRow r;
+    r.row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    r.live = r.row < n;
+    const uint64_t ia = (lit_a || !r.live) ? 0 : r.row, ib = (lit_b || !r.live) ? 0 : r.row;
+    r.a0 = offA[ia];
+    r.la = offA[ia + 1] - r.a0;
+    r.b0 = offB[ib];
+    r.lb = offB[ib + 1] - r.b0;
+    return r;
+}
+
+// Pattern and text of a lane's row.  LIT: 0 = row against row, the longer string is the pattern and the shorter one the text (fewer
+// columns); 1 = a is a literal, 2 = b is: the literal is the text -- the same bytes in every lane, read through a wave-uniform
+// address -- and the row string the pattern.  pv / tv: the value columns, po / to: the offsets, lp / lt: the byte lengths.
+struct LanePick {
+    bool a_is_pat;
+    const uint8_t *pv, *tv;
+    uint32_t po, to, lp, lt;
+};
+template <int LIT>
+__device__ __forceinline__ LanePick lane_pick(const uint8_t *__restrict__ valA, const uint8_t *__restrict__ valB, const LaneRow &r)
+{
+    LanePick p;
+    p.a_is_pat = LIT == 1 ? false : (LIT == 2 ? true : r.la >= r.lb);
+    p.pv = p.a_is_pat ? valA : valB;
+    p.tv = p.a_is_pat ? valB : valA;
+    p.po = p.a_is_pat ? r.a0 : r.b0;
+    p.to = p.a_is_pat ? r.b0 : r.a0;
+    p.lp = p.a_is_pat ? r.la : r.lb;
+    p.lt = p.a_is_pat ? r.lb : r.la;
+    return p;
+}
 
 // Wave-aggregated append of the lanes with `take` to a work list: the first of them adds their number to *count, each stores its
 // row at its rank behind that base.  Returns where the lane's row went (0 in a wave without any).
@@ -128,6 +174,49 @@ __device__ __forceinline__ void wave_decode(const uint8_t *__restrict__ p, uint3
         if (s) dst[pos + (uint32_t)__popcll(sm & ((1ull << lane) - 1ull))] = osa_decode_at(p, base + lane, bytes);
         pos += (uint32_t)__popcll(sm);
     }
+}
+
+// Pattern and text of a wave kernel's pair -- the string with fewer scalar values is the pattern (m values, W words of 64), the
+// other the text (nt values) -- and where the pattern's values and the State words behind them live: s_pat / s_state (LDS) for
+// patterns of up to lds_cps values, else the wave's slot of `scratch` (slot_words words a wave, the state behind W whole words of
+// values).  Nothing is loaded or stored here.
+template <typename State>
+struct WaveStage {
+    uint32_t m, nt, W;
+    const uint8_t *pp, *tp;
+    uint32_t pbytes, tbytes;
+    uint32_t *pat;
+    State *state;
+};
+template <typename State>
+__device__ __forceinline__ WaveStage<State> wave_stage(const WavePair &p, uint32_t *s_pat, State *s_state, uint32_t lds_cps,
+                                                       uint32_t *scratch, uint64_t slot_words)
+{
+    const bool a_is_pat = p.ca <= p.cb;
+    WaveStage<State> s;
+    s.pp = a_is_pat ? p.pa : p.pb;
+    s.tp = a_is_pat ? p.pb : p.pa;
+    s.pbytes = a_is_pat ? p.na : p.nb;
+    s.tbytes = a_is_pat ? p.nb : p.na;
+    s.m = a_is_pat ? p.ca : p.cb;
+    s.nt = a_is_pat ? p.cb : p.ca;
+    s.W = (s.m + 63u) / 64u;
+    s.pat = s_pat;
+    s.state = s_state;
+    if (s.m > lds_cps) {
+        s.pat = scratch + (uint64_t)blockIdx.x * slot_words;
+        s.state = reinterpret_cast<State *>(s.pat + (uint64_t)s.W * 64u);
+    }
+    return s;
+}
+
+// The pattern's m scalar values into pat, padded to `words` whole words of 64 with values that never match (no scalar value is
+// 0xFFFFFFFF).  The barrier before another lane's value is read is the kernel's.
+__device__ __forceinline__ void wave_pattern(const uint8_t *__restrict__ pp, uint32_t pbytes, uint32_t m, uint32_t words, uint32_t *pat,
+                                             uint32_t lane)
+{
+    wave_decode(pp, pbytes, pat, lane);
+    for (uint32_t i = m + lane; i < words * 64u; i += 64u) pat[i] = 0xFFFFFFFFu;
 }
 
 // f(ch) once per scalar value of p[0, bytes), in order, ch wave-uniform: 64 bytes are decoded at a time, one by each lane, and the

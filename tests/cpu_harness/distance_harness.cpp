@@ -49,7 +49,7 @@ static uint64_t block_run(const uint32_t *pat, uint32_t m, const uint32_t *txt, 
     for (uint32_t i = 0; i < m; ++i) P[i] = pat[i];
     std::vector<DistWord> st(W);
     int y = dist_first_y(W, m, k, bounded);
-    for (uint32_t w = 0; w < W; ++w) st[w] = DistWord{~0ull, 0ull, 0ull, 0ull, 64ull * (w + 1u)};
+    for (uint32_t w = 0; w < W; ++w) st[w] = dist_word_start<DistWord>(w);
     uint64_t c = 0;
     for (uint32_t j = 0; j < nt; ++j) {
         const uint32_t ch = txt[j];

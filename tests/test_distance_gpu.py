@@ -198,6 +198,85 @@ def test_dist_gpu_matches_the_similarities(S, ctx):
         assert np.array_equal(want.view(np.uint64), sim.view(np.uint64)), m
 
 
+def _osa_tier_frame():
+    """A few hundred pairs on every path of k_dist_lane / k_dist_wave: ASCII patterns (the longer string of a lane pair) of 0, 1,
+    31..33 and 63, 64 bytes, 65-byte pairs (the first wave rows), short non-ASCII pairs, wave patterns (the string with fewer
+    scalar values) of 64, 65 and 128 values, 2048 and 2049 values (the last pattern in LDS, the first in scratch), and swaps of two
+    neighbours across byte 31/32 of a lane pair and across value 63/64 of a wave pair."""
+    rng = random.Random(21)
+    abc = "abcdefghijklmnopqrstuvwxyz"
+    A, B = [], []
+    for n in (0, 1, 31, 32, 33, 63, 64):
+        for _ in range(12):
+            a = "".join(rng.choice(abc) for _ in range(n))
+            A += [a, a, a, a[: n // 2]]
+            B += [_edits(rng, a, abc, rng.randint(0, 4))[:n], "".join(rng.choice(abc) for _ in range(rng.randint(0, n))), "", a]
+    for _ in range(20):
+        a = "".join(rng.choice(abc) for _ in range(65))
+        A += [a, a[:40]]
+        B += [(_edits(rng, a, abc, 5) + "xx")[:65], a]
+    for _ in range(30):
+        a = gen.rand_string(rng, gen.MIXED, 0, 20)
+        A += [a, a]
+        B += [_edits(rng, a, "é日😀ab", 3), gen.rand_string(rng, gen.MIXED, 0, 20)]
+    for n in (64, 65, 128):
+        for alphabet in (abc, "аб日😀éxyz"):
+            for _ in range(4):
+                a = "".join(rng.choice(alphabet) for _ in range(n))
+                A += [a, a + "tail of the text"]
+                B += [_edits(rng, a, alphabet, 6) + "longer", _edits(rng, a, alphabet, 3)[:n]]
+    for n in (2048, 2049):
+        a = "".join(rng.choice(abc) for _ in range(n))
+        A.append(a)
+        B.append(_edits(rng, a, abc, 40) + "z" * 50)
+    for at, n in ((31, 40), (31, 64), (63, 70), (63, 200)):
+        a = list("".join(rng.choice(abc) for _ in range(n)))
+        a[at], a[at + 1] = "Q", "R"
+        b = a[:]
+        b[at], b[at + 1] = "R", "Q"
+        A += ["".join(a), "".join(b)]
+        B += ["".join(b), "".join(a) + ("é" if n > 64 else "")]
+    assert 300 <= len(A) == len(B) <= 900
+    return A, B
+
+
+@pytest.fixture(scope="module")
+def osa_tier_frame():
+    return _osa_tier_frame()
+
+
+@pytest.mark.parametrize("shape", ("rows", "literal a", "literal b"))
+def test_dist_gpu_osa_similarity_is_the_epilogue_of_the_distance(S, ctx, osa_tier_frame, shape):
+    """The OSA similarity and the OSA distance are two instantiations of one kernel pair: on the device, the similarity is bit for
+    bit 1 - d / max(|a|, |b|) of the unbounded distance (1.0 for two empty strings), row against row and with a literal on either
+    side."""
+    import torch
+    A, B = osa_tier_frame
+    dev = torch.device("cuda", 0)
+
+    def column(X):
+        o, v = S.pack_strings(X)
+        return [torch.from_numpy(o.view(np.int32)).to(dev), torch.from_numpy(v if v.size else np.zeros(1, np.uint8)).to(dev)]
+
+    lits = ("", "a" * 31 + "QR" + "b" * 7, "héllo wörld", "x" * 70)
+    cases = [(A, B)] if shape == "rows" else [([lit], B) if shape == "literal a" else (A, [lit]) for lit in lits]
+    for X, Y in cases:
+        cols = column(X) + column(Y)
+        torch.cuda.synchronize()  # (the uploads ran on torch's stream, the calls run on the context's)
+        d = ctx.distance_device("osa", *cols, None)
+        sim = ctx.pairs_device("osa", *cols)
+        ctx.synchronize()
+        d = d.cpu().numpy().view(np.uint32).astype(np.float64)
+        n = max(len(X), len(Y))
+        la = np.array([len(s) for s in X], dtype=np.float64) * np.ones(n)
+        lb = np.array([len(s) for s in Y], dtype=np.float64) * np.ones(n)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            want = 1.0 - d / np.maximum(la, lb)
+        want[(la == 0) & (lb == 0)] = 1.0
+        bad = np.flatnonzero(want.view(np.uint64) != sim.cpu().numpy().view(np.uint64))
+        assert bad.size == 0, (shape, X[0][:20] if len(X) == 1 else Y[0][:20], bad[:5].tolist())
+
+
 def test_dist_gpu_python_wrappers_mask_nulls(S):
     got = S.levenshtein_distance(["kitten", None, "abcd"], ["sitting", "x", "acbd"])
     assert isinstance(got, np.ma.MaskedArray) and got.dtype == np.uint32

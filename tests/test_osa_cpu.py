@@ -133,7 +133,7 @@ def _words_distance(lane, p, t):
     return int(lane.osa_words_distance(x.ctypes.data, len(p), y.ctypes.data, len(t)))
 
 
-# pattern lengths around the 64-row words of k_osa_wave's state: one word, the last row of a word, the first of the next, three and
+# pattern lengths around the 64-row words of k_dist_wave's state: one word, the last row of a word, the first of the next, three and
 # four words
 WORDS_PATTERN_LENGTHS = (1, 63, 64, 65, 127, 128, 129, 200)
 WORDS_ALPHABETS = ("ab\U0001F600", "abc\U00010348")  # three or four scalar values (one above 0xFFFF): matches and swaps are dense

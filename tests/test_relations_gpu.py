@@ -79,7 +79,7 @@ def check_tiers(be):
             cap = DIST_CAP[m] if entry == "dist" else PAIR_CAP[m]
             beyond, total = sum(not (lane_string(a, cap) and lane_string(b, cap)) for a, b in zip(A, B)), len(A)
             if entry == "sim" and m not in RC.CLASSIC:
-                counter = e["wave"]  # (k_osa_lane / k_indel_lane / k_partial_lane count exactly the rows they leave)
+                counter = e["wave"]  # (k_dist_lane / k_indel_lane / k_partial_lane count exactly the rows they leave)
         what = (role, entry, m, beyond, total, counter, e["wave"], e["late"], e["long"])
         if role in ("base", "edge"):
             assert beyond == 0, what
