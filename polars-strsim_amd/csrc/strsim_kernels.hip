@@ -181,8 +181,14 @@ static void launch_lane_t(const LaunchArgs &a)
             constexpr bool T = decltype(tables)::value, L = decltype(long_rows)::value;
             const uint64_t res = (uint64_t)a.stage_grid * (uint64_t)stage_waves_per_eu<M, T, L>() / (uint64_t)STRSIM_STAGE_WAVES_PER_EU;
             const uint64_t gs = stage_launch_size(nsb, res, (uint64_t)a.stage_grid / (uint64_t)STRSIM_STAGE_WAVES_PER_EU);
-            hipLaunchKernelGGL((k_lane_stage<M, T, L>), dim3((unsigned)gs), dim3(STAGE_BLOCK), 0, a.stream, a.offA, a.valA, a.rowsA,
-                               a.offB, a.valB, a.rowsB, op, a.n, a.slowmask, a.status, a.qtab, a.sched, a.publish_host, a.publish_ticket);
+            // (neither side a literal: the instantiation that has no literal code in it, where the measure has one)
+            constexpr bool C = stage_has_cols_only<M, T, L>();
+            if (C && a.rowsA != 1 && a.rowsB != 1)
+                hipLaunchKernelGGL((k_lane_stage<M, T, L, C>), dim3((unsigned)gs), dim3(STAGE_BLOCK), 0, a.stream, a.offA, a.valA, a.rowsA,
+                                   a.offB, a.valB, a.rowsB, op, a.n, a.slowmask, a.status, a.qtab, a.sched, a.publish_host, a.publish_ticket);
+            else
+                hipLaunchKernelGGL((k_lane_stage<M, T, L>), dim3((unsigned)gs), dim3(STAGE_BLOCK), 0, a.stream, a.offA, a.valA, a.rowsA,
+                                   a.offB, a.valB, a.rowsB, op, a.n, a.slowmask, a.status, a.qtab, a.sched, a.publish_host, a.publish_ticket);
         };
 #if defined(STRSIM_LAB) && defined(STRSIM_STAGE_PC)
         if (((STRSIM_STAGE_PC >> M) & 1) != 0 && a.rowsA != 1 && a.rowsB != 1 && !a.long_rows) {

@@ -73,6 +73,28 @@
 #define STRSIM_STAGE_RANGE_MIN_BLOCKS 2 // ... and at least this many blocks (1: a 3 M-row call 132 us instead of 102, cfg2 +2 %: the counter is one contended address)
 #endif
 
+// Three separable changes to the per-block skeleton (LAB 3.1c; each measured alone against the previous commit, whose ISA all three
+// switched off give back instruction for instruction):
+#ifndef STRSIM_STAGE_CUT_CARRY
+// 1: the block cut without its chain of LDS round trips -- a block that starts where the previous one ended (same range) takes its
+// base offsets from that block's end offsets, which are in SGPRs, and the end offsets come from the lane of the fit test that has
+// already loaded them (v_readlane), so the cut waits for LDS once instead of five times.  Closed experiment, cfg2, G pairs/s by the
+// medians: box A 75.45 against the parent's 75.20, box B 74.51 against 74.74, both inside the parent's spread.  0: every block reads s_off[side][0] and s_off[side][rows].
+#define STRSIM_STAGE_CUT_CARRY 0
+#endif
+#ifndef STRSIM_STAGE_CUT_UNDER_STORE
+// 1: the store phase in two parts around the cut (Levenshtein's short-row geometry) -- the staged codes leave LDS and the
+// quotient-table loads are issued, then the cut (LDS and scalar work only) runs under their L2 round trip, then the wait, the
+// arithmetic and the stores.  Closed experiment: +0.5 % on one box (every run above every parent run, by 0.01 %), nothing on the
+// other; costs 8 VGPRs.  0: the store phase in one piece.
+#define STRSIM_STAGE_CUT_UNDER_STORE 0
+#endif
+#ifndef STRSIM_STAGE_COLS_ONLY
+// Bit m set: measure m's short-row instantiation without tables exists a second time for calls where neither side is a literal (the
+// launcher knows): no literal windows, no selects on them, no uniform branches.  Default: Levenshtein (cfg2 +2 %, LAB 3.1c).
+#define STRSIM_STAGE_COLS_ONLY 0x01
+#endif
+
 #if defined(STRSIM_LAB) && defined(STRSIM_STAGE_STAMPS)
 // lab build only (make EXTRA="-DSTRSIM_LAB -DSTRSIM_STAGE_STAMPS"; never in the product library): per-wave cycle sums of the phases of k_lane_stage, read back with
 // strsim_debug_stage_stamps().  [0] block cut + bytes DMA issue [1] store [2] sortA [3] barrier [4] sortB [5] DMA wait +
@@ -98,6 +120,14 @@ constexpr int STAGE_RPW = STAGE_NR / STAGE_WAVES;     // rounds per wave and blo
 // Jaro 41 -> 45.6 G pairs/s on cfg2's lengths.  Levenshtein, Jaccard and Dice are issue-bound at 5 workgroups per CU and
 // latency-bound at 4: 28 % fewer vector instructions bought nothing there.
 template <int MEASURE> constexpr bool stage_uses_lut() { return ((STRSIM_STAGE_LUT >> MEASURE) & 1) != 0; } // (5: five outputs)
+// Which instantiations carry the cut's offsets in registers (STRSIM_STAGE_CUT_CARRY: all of them, the other measures'
+// lines of bench_support/kernel_resources.sh do not move) / cut under the store's loads (STRSIM_STAGE_CUT_UNDER_STORE: Levenshtein's short-row
+// geometry.  The store phase's registers stay live across the cut: Jaro's three table values per row and the five-output pass's four
+// turned into spills -- k_lane_stage_all 0 -> 12, k_lane_stage<1, true> 4 -> 10, <2, true> 6 -> 11 -- and Jaccard and Dice load nothing).
+template <int MEASURE, bool TABLES, bool LONG> constexpr bool stage_cut_carry() { return STRSIM_STAGE_CUT_CARRY != 0; }
+template <int MEASURE, bool TABLES, bool LONG> constexpr bool stage_cut_under_store() { return STRSIM_STAGE_CUT_UNDER_STORE != 0 && MEASURE == LEVENSHTEIN && !TABLES && !LONG; }
+// Which instantiations have a twin for column x column calls (STRSIM_STAGE_COLS_ONLY).
+template <int MEASURE, bool TABLES, bool LONG> constexpr bool stage_has_cols_only() { return !TABLES && !LONG && MEASURE < 5 && ((STRSIM_STAGE_COLS_ONLY >> MEASURE) & 1) != 0; }
 
 // staged bytes per column: Levenshtein keeps 16 bits per row for the store phase, the other measures 32 (64: five outputs)
 // LONG: the geometry for frames of long strings (the launcher takes it when the context's last call left more than 1/16 of its
@@ -382,7 +412,8 @@ __device__ __forceinline__ void stage_compute(const EqLut &lut, const uint32_t (
     }
 }
 
-template <int MEASURE, bool LUT, bool LONG = false>
+// COLS: neither side is a literal (rowsA != 1 && rowsB != 1, the launcher's promise)
+template <int MEASURE, bool LUT, bool LONG = false, bool COLS = false>
 __device__ __forceinline__ void
 lane_stage_body(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ valA, uint64_t rowsA,
              const uint32_t *__restrict__ offB, const uint8_t *__restrict__ valB, uint64_t rowsB, OutPtrs outs,
@@ -395,6 +426,7 @@ lane_stage_body(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ v
     constexpr int STAGE_CAP = StageGeom<LUT, LONG>::CAP, STAGE_COL = StageGeom<LUT, LONG>::COL;
     constexpr int STAGE_DMA_ITERS = StageGeom<LUT, LONG>::DMA_ITERS;
     constexpr uint32_t COLB = STAGE_COL, LIT = 2u * STAGE_COL; // s_bytes: column a | column b | the literals' windows
+    constexpr bool CARRY = stage_cut_carry<MEASURE, LUT, LONG>(), UNDER = stage_cut_under_store<MEASURE, LUT, LONG>();
     // Match-mask tables (strsim_lane_lut.h), for the measures that use them: per wave 3 KB at a 4 KB boundary -- entry e of
     // lane l at e * 256 + l * 4, and the boundary makes (table base >> 8) | e the address byte.
     // The 1 KB behind each wave's tables holds 128 of the block's row descriptors (without tables: an array of their own).
@@ -436,7 +468,7 @@ lane_stage_body(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ v
 #if STRSIM_BOUNDS_ON
     const uint32_t firstA = load_invariant(offA), firstB = load_invariant(offB); // (lab: where the columns' bytes begin)
 #endif
-    const bool bcastA = rowsA == 1, bcastB = rowsB == 1; // a one-row side is the literal (strsim.rs:48-52, :61-66)
+    const bool bcastA = !COLS && rowsA == 1, bcastB = !COLS && rowsB == 1; // a one-row side is the literal (strsim.rs:48-52, :61-66)
     const uint32_t litA0 = bcastA ? load_invariant(offA) : 0u, litB0 = bcastB ? load_invariant(offB) : 0u;
     const uint32_t litAlen = bcastA ? totalA - litA0 : 0u, litBlen = bcastB ? totalB - litB0 : 0u;
     if (wv == 0u) {
@@ -524,6 +556,9 @@ lane_stage_body(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ v
 
     uint64_t prev_row0 = 0;           // the block whose results are waiting in LDS
     uint32_t prev_rows = 0;
+    // STRSIM_STAGE_CUT_CARRY: the end offsets of the last block, which are the base offsets of the next one while the range lasts
+    uint32_t carryA = 0u, carryB = 0u;
+    bool carried = false;
     if (row0 < row_end) dma_offsets(row0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     lds_barrier();
@@ -533,13 +568,13 @@ lane_stage_body(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ v
     // arithmetic and the stores: left to itself hipcc sinks each load into the branch that stores its row and waits for it
     // there (s_waitcnt vmcnt(0) per row: the L2 round trips of a thread's rows one after the other, each behind the previous
     // row's store).  `pin` keeps a loaded value outside those branches.
+    // The phase comes in two parts so that the block cut, which touches LDS and SGPRs only, can run between them under the
+    // L2 round trip of the table loads (STRSIM_STAGE_CUT_UNDER_STORE): store_fetch, the first two passes, and store_finish.
     auto pin = [](double &x) { asm volatile("" : "+v"(x)); };
-    auto store_block = [&](uint64_t r0, uint32_t rows) {
-        unsigned long long *__restrict__ const maskb = slowmask + (r0 >> 6);
-        constexpr int M1 = (MEASURE == ALL_MEASURES || MEASURE == LEVENSHTEIN) ? JARO : MEASURE;
-        constexpr bool JARO_LIKE = ALL || M1 == JARO || M1 == JARO_WINKLER;
-        unsigned long long pk[RPT]; // (rows of the block behind `rows` hold all-ones: nobody computed them)
-        double t0[RPT], t1[RPT], t2[RPT], t3[RPT];
+    constexpr int M1 = (MEASURE == ALL_MEASURES || MEASURE == LEVENSHTEIN) ? JARO : MEASURE;
+    constexpr bool JARO_LIKE = ALL || M1 == JARO || M1 == JARO_WINKLER;
+    auto store_fetch = [&](uint64_t r0, unsigned long long (&pk)[RPT], double (&t0)[RPT], double (&t1)[RPT], double (&t2)[RPT], double (&t3)[RPT]) {
+        (void)r0; // (named by the lab build's bounds checks only)
 #pragma unroll
         for (int q = 0; q < RPT; ++q) {
             const uint32_t i = (uint32_t)q * STAGE_BLOCK + tid;
@@ -580,6 +615,9 @@ lane_stage_body(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ v
                 }
             }
         }
+    };
+    auto store_finish = [&](uint64_t r0, uint32_t rows, unsigned long long (&pk)[RPT], double (&t0)[RPT], double (&t1)[RPT], double (&t2)[RPT], double (&t3)[RPT]) {
+        unsigned long long *__restrict__ const maskb = slowmask + (r0 >> 6);
 #pragma unroll
         for (int q = 0; q < RPT; ++q) {
             if (LEV || JARO_LIKE) pin(t0[q]);
@@ -621,6 +659,12 @@ lane_stage_body(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ v
             }
         }
     };
+    auto store_block = [&](uint64_t r0, uint32_t rows) { // the phase in one piece
+        unsigned long long pk[RPT]; // (rows of the block behind `rows` hold all-ones: nobody computed them)
+        double t0[RPT], t1[RPT], t2[RPT], t3[RPT];
+        store_fetch(r0, pk, t0, t1, t2, t3);
+        store_finish(r0, rows, pk, t0, t1, t2, t3);
+    };
 
 #if defined(STRSIM_LAB) && defined(STRSIM_STAGE_STAMPS)
     unsigned long long st_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -637,27 +681,56 @@ lane_stage_body(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ v
         }
         // ---- B: store(j-1).  Before the bytes DMA of this block is issued: a wave's vector-memory results return in order,
         //         so the table loads of the store phase would otherwise sit behind its share of the DMA (HBM latency).
-        if (prev_rows) store_block(prev_row0, prev_rows);
+        //         With STRSIM_STAGE_CUT_UNDER_STORE only its loads are issued here and the block cut runs under them.
+        unsigned long long pk[RPT]; // (UNDER: the store phase's registers across the cut)
+        double t0[RPT], t1[RPT], t2[RPT], t3[RPT];
+        if constexpr (UNDER) {
+            if (prev_rows) store_fetch(prev_row0, pk, t0, t1, t2, t3);
+        } else {
+            if (prev_rows) store_block(prev_row0, prev_rows);
+        }
         STAGE_STAMP(1);
         // ---- the block: as many of the next 64-row chunks (at most B / 64) as have their bytes inside the staging areas
         const uint32_t avail = (uint32_t)(row_end - row0 < (uint64_t)B ? row_end - row0 : (uint64_t)B); // rows whose offsets are in s_off
-        const uint32_t baseA = bcastA ? litA0 : uniform(s_off[0][0]), baseB = bcastB ? litB0 : uniform(s_off[1][0]);
+        // lane c < B / 64: does the block still fit if it ends behind chunk c?
+        const uint32_t e = (lane + 1u) * 64u < avail ? (lane + 1u) * 64u : avail; // rows if the block ends behind chunk `lane`
+        const bool exists = lane * 64u < avail && lane < (uint32_t)(B / 64);
+        uint32_t laneEndA = 0u, laneEndB = 0u; // s_off[side][e]; a literal side: its base
+        uint32_t baseA, baseB;
+        if constexpr (CARRY) {
+            // (issued in front of the wait for the bases: one LDS round trip for both when the bases are read at all)
+            laneEndA = bcastA ? litA0 : s_off[0][exists ? e : 0u];
+            laneEndB = bcastB ? litB0 : s_off[1][exists ? e : 0u];
+        }
+        if (CARRY && carried) { // (uniform) the previous block of this range ended where this one starts
+            baseA = carryA;
+            baseB = carryB;
+        } else {
+            baseA = bcastA ? litA0 : uniform(s_off[0][0]);
+            baseB = bcastB ? litB0 : uniform(s_off[1][0]);
+        }
         const uint32_t misA = (uint32_t)(reinterpret_cast<uintptr_t>(valA + baseA) & 15u);
         const uint32_t misB = (uint32_t)(reinterpret_cast<uintptr_t>(valB + baseB) & 15u);
-        uint32_t rows;
-        {
-            // lane c < B / 64: does the block still fit if it ends behind chunk c?
-            const uint32_t e = (lane + 1u) * 64u < avail ? (lane + 1u) * 64u : avail; // rows if the block ends behind chunk `lane`
-            const bool exists = lane * 64u < avail && lane < (uint32_t)(B / 64);
-            const uint32_t endA = bcastA ? baseA : s_off[0][exists ? e : 0u], endB = bcastB ? baseB : s_off[1][exists ? e : 0u];
-            const bool fits = exists && endA - baseA + misA <= (uint32_t)STAGE_CAP && endB - baseB + misB <= (uint32_t)STAGE_CAP;
-            const unsigned long long okm = __ballot(fits);
-            // chunks 0 .. k-1 fit: k = number of trailing ones; at least one chunk is taken even if it overflows
-            uint32_t k = (uint32_t)__builtin_ctzll(~okm);
-            if (k == 0u) k = 1u;
-            rows = uniform(k * 64u < avail ? k * 64u : avail);
+        if constexpr (!CARRY) {
+            laneEndA = bcastA ? baseA : s_off[0][exists ? e : 0u];
+            laneEndB = bcastB ? baseB : s_off[1][exists ? e : 0u];
         }
-        const uint32_t endA = bcastA ? baseA : uniform(s_off[0][rows]), endB = bcastB ? baseB : uniform(s_off[1][rows]);
+        const bool fits = exists && laneEndA - baseA + misA <= (uint32_t)STAGE_CAP && laneEndB - baseB + misB <= (uint32_t)STAGE_CAP;
+        const unsigned long long okm = __ballot(fits);
+        // chunks 0 .. k-1 fit: k = number of trailing ones; at least one chunk is taken even if it overflows
+        uint32_t k = (uint32_t)__builtin_ctzll(~okm);
+        if (k == 0u) k = 1u;
+        const uint32_t rows = uniform(k * 64u < avail ? k * 64u : avail);
+        uint32_t endA, endB;
+        if constexpr (CARRY) {
+            // lane k - 1 exists (chunks that fit exist, and so does chunk 0) and its e is min(k * 64, avail) = rows: it holds
+            // s_off[side][rows] already
+            endA = (uint32_t)__builtin_amdgcn_readlane((int)laneEndA, (int)(k - 1u));
+            endB = (uint32_t)__builtin_amdgcn_readlane((int)laneEndB, (int)(k - 1u));
+        } else {
+            endA = bcastA ? baseA : uniform(s_off[0][rows]);
+            endB = bcastB ? baseB : uniform(s_off[1][rows]);
+        }
         // ---- A: bytes DMA(j).  Column side X: the 16-byte chunks from the aligned address below the block's first byte
         //         up to the block's last byte, at most STAGE_CAP bytes -> s_bytes[X]
         const uint32_t spanA = endA - baseA + misA, spanB = endB - baseB + misB;
@@ -674,6 +747,13 @@ lane_stage_body(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ v
         else if (tid < 4u) STRSIM_CHECK_RANGE(K_STAGE, 21, row0, COLB + (chunksB << 4) + (tid - 2u) * 16u + 16u, 0, sizeof(s_bytes));
         if (tid < 2u) *reinterpret_cast<uint4 *>(s_bytes + (chunksA << 4) + tid * 16u) = make_uint4(0u, 0u, 0u, 0u);
         else if (tid < 4u) *reinterpret_cast<uint4 *>(s_bytes + COLB + (chunksB << 4) + (tid - 2u) * 16u) = make_uint4(0u, 0u, 0u, 0u);
+        if (UNDER && prev_rows) {
+            // the rest of store(j-1): its table loads went out in front of the cut and are waited for here, still in front of this
+            // block's DMA (never behind it, and never with a counted wait: the DMA instructions of a wave vary with its branches)
+            STAGE_STAMP(0);
+            store_finish(prev_row0, prev_rows, pk, t0, t1, t2, t3);
+            STAGE_STAMP(1);
+        }
         {
             const uint8_t *__restrict__ const gA = valA + baseA - misA, *__restrict__ const gB = valB + baseB - misB;
 #pragma unroll
@@ -764,6 +844,12 @@ lane_stage_body(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ v
         if (tid < 32u) s_cnt[tid] = 0u; // read by sortB above, next used by sortA behind barrier G
         // ---- E: offsets DMA(j+1), in flight during the rounds
         uint64_t next_row0 = row0 + rows;
+        // (literal sides carry their constant base: harmless)
+        if constexpr (CARRY) {
+            carryA = endA;
+            carryB = endB;
+            carried = next_row0 < row_end; // the next block continues this range: its base offsets are this block's end offsets
+        }
         if (next_row0 >= row_end) { // this range is done: move to the next one and ask for the one after it
             const uint64_t lo = uniform(s_sched[0]), hi = lo + uniform(s_sched[1]); // (uniform: row counters live in SGPRs)
             next_row0 = lo * 64u < n ? lo * 64u : n;
@@ -863,15 +949,16 @@ template <int MEASURE, bool TABLES, bool LONG = false> constexpr int stage_waves
 }
 
 // TABLES: match masks from the LDS tables (a measure whose bit is set in STRSIM_STAGE_LUT); LONG: the long-row geometry
-// (StageGeom), without tables -- what the kernel does on such frames is mostly staging.
-template <int MEASURE, bool TABLES, bool LONG = false>
+// (StageGeom), without tables -- what the kernel does on such frames is mostly staging.  COLS: the twin for calls without a literal
+// (stage_has_cols_only); the launcher takes it when both sides have more than one row.
+template <int MEASURE, bool TABLES, bool LONG = false, bool COLS = false>
 __global__ __launch_bounds__(STAGE_BLOCK) __attribute__((amdgpu_waves_per_eu(stage_waves_per_eu<MEASURE, TABLES, LONG>()))) void
 k_lane_stage(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ valA, uint64_t rowsA,
              const uint32_t *__restrict__ offB, const uint8_t *__restrict__ valB, uint64_t rowsB, OutPtrs outs, uint64_t n,
              unsigned long long *__restrict__ slowmask, DevStatus *__restrict__ status, const double *__restrict__ qtab,
              uint32_t *__restrict__ sched, DevStatus *__restrict__ publish, uint32_t ticket)
 {
-    lane_stage_body<MEASURE, TABLES, LONG>(offA, valA, rowsA, offB, valB, rowsB, outs, n, slowmask, status, qtab, sched, publish, ticket);
+    lane_stage_body<MEASURE, TABLES, LONG, COLS>(offA, valA, rowsA, offB, valB, rowsB, outs, n, slowmask, status, qtab, sched, publish, ticket);
 }
 
 // The five-output instantiation keeps the matching state of three cores alive at once and stages 64 bits per row.

@@ -1,0 +1,163 @@
+"""k_lane_stage<levenshtein>: the block cut (base offsets carried from block to block inside a range, end offsets taken from the
+lanes of the fit test), the store phase split around it and the instantiation without literal code, bit for bit against the oracle.
+
+A workgroup takes ranges of at least two blocks of up to 512 rows; a block is cut to the 64-row chunks whose bytes fit the staging
+area of 10 240 bytes per column.  The first block of a range reads its base offsets from LDS, every later one takes the previous
+block's end offsets, so the frames put full blocks, cut blocks, cuts of changing length, a forced one-chunk block and one-row and
+one-chunk last blocks behind one another.  Frames are a few thousand rows through strsim_pairs_device on a fresh one-launch context.
+
+The carried offsets and the split store phase are compile-time knobs of strsim_lane_stage.h (STRSIM_STAGE_CUT_CARRY,
+STRSIM_STAGE_CUT_UNDER_STORE) that ship switched off (LAB_NOTES 3.1c); the column-only instantiation (STRSIM_STAGE_COLS_ONLY) ships
+on.  The frames hold for any setting of the three: the results do not depend on them.
+"""
+import functools
+import random
+
+import numpy as np
+import pytest
+
+import gen
+import oracle_lib as O
+
+pytestmark = pytest.mark.gpu
+
+ROWS = 4096
+
+
+@pytest.fixture(scope="module")
+def S():
+    import strsim_amd
+    return strsim_amd
+
+
+def _partner(rng, a, lo, hi):
+    r = rng.random()
+    b = gen.edit(rng, a, gen.ASCII_LOWER, rng.randint(1, 3)) if r < 0.5 else (a if r < 0.55 else gen.rand_string(rng, gen.ASCII_LOWER, lo, hi))
+    b = b[:hi]
+    while len(b) < lo:
+        b += rng.choice(gen.ASCII_LOWER)
+    return b
+
+
+def _frame(seed, n, lo, hi):
+    rng = random.Random(seed)
+    A = [gen.rand_string(rng, gen.ASCII_LOWER, lo, hi) for _ in range(n)]
+    B = [_partner(rng, a, lo, hi) for a in A]
+    return A, B
+
+
+@functools.lru_cache(maxsize=None)
+def _uniform():
+    """frame (a): U{0..32} on both sides, 4 096 rows, with its expected results (shared, never changed)"""
+    A, B = _frame(31, ROWS, 0, 32)
+    exp = O.batch_strings("levenshtein", A, B, 8)
+    exp.setflags(write=False)
+    return tuple(A), tuple(B), exp
+
+
+def _column(S, strings, dev, shift=0):
+    """(offsets, values) on the device; the value buffer starts `shift` bytes behind a 16-byte boundary, 64 readable bytes follow it"""
+    import torch
+    off, val = S.pack_strings(list(strings))
+    buf = np.concatenate([np.full(shift, 0xE9, dtype=np.uint8), val.view(np.uint8), np.zeros(64, dtype=np.uint8)])
+    values = torch.from_numpy(buf).to(dev)[shift:]
+    assert values.data_ptr() % 16 == shift % 16
+    return torch.from_numpy(off.view(np.int32)).to(dev), values
+
+
+def _run(S, A, B, exp=None, late=0, shifts=(0, 0), one_op=True):
+    import torch
+    dev = torch.device("cuda", 0)
+    cols = _column(S, A, dev, shifts[0]) + _column(S, B, dev, shifts[1])
+    torch.cuda.synchronize()
+    n = max(len(A), len(B))
+    if exp is None:
+        exp = O.batch_strings("levenshtein", list(A) * (n if len(A) == 1 else 1), list(B) * (n if len(B) == 1 else 1), 8)
+    with S.Context(0, one_launch=True) as ctx:
+        before = ctx.enqueued_ops
+        out = ctx.pairs_device("levenshtein", *cols)
+        ops = ctx.enqueued_ops - before
+        ctx.synchronize()
+        got_late = ctx.last_late_rows
+        got = out.cpu().numpy()
+    bad = np.nonzero(got.view(np.uint64) != exp.view(np.uint64))[0]
+    assert bad.size == 0, "%d / %d rows differ; first row %d: a=%r b=%r got=%r exp=%r" % (
+        bad.size, n, bad[0], A[bad[0] % len(A)], B[bad[0] % len(B)], got[bad[0]], exp[bad[0]])
+    if one_op:
+        assert ops == 1  # a fresh one-launch context enqueues the stage kernel alone; flagged rows are finished at retirement
+    assert got_late == late
+
+
+def test_full_blocks(S):
+    """(a) full blocks of 512 rows: the base carried behind a full block, re-read at the start of a range."""
+    A, B, exp = _uniform()
+    _run(S, A, B, exp)
+
+
+def test_every_block_cut(S):
+    """(b) every string 28..32 bytes: 512 rows overflow the staging area, every block is cut to about five chunks; the carried base is
+    the cut block's end, not the end of the rows whose offsets were loaded."""
+    A, B = _frame(32, ROWS, 28, 32)
+    _run(S, A, B)
+
+
+def test_cuts_of_changing_length(S):
+    """(c) runs of 200 rows of 30..32-byte strings and of 0..4-byte strings: cuts of different lengths follow one another inside a
+    range, and in half of the runs column a is long where column b is short, so either column decides the cut."""
+    rng = random.Random(33)
+    A, B = [], []
+    for i in range(4160):
+        run = (i // 200) % 4
+        la, lb = ((30, 32), (30, 32)) if run == 0 else ((0, 4), (0, 4)) if run == 1 else ((30, 32), (0, 4)) if run == 2 else ((0, 4), (30, 32))
+        A.append(gen.rand_string(rng, gen.ASCII_LOWER, *la))
+        B.append(gen.rand_string(rng, gen.ASCII_LOWER, *lb) if run >= 2 or rng.random() < 0.5 else _partner(rng, A[-1], *lb))
+    _run(S, A, B)
+
+
+@pytest.mark.parametrize("n", [70, 1024 + 1, 1088])
+def test_small_frames(S, n):
+    """(d) one block that is not full; a one-row last block at the start of a range; a last block of a single chunk."""
+    A, B = _frame(34 + n, n, 0, 32)
+    _run(S, A, B)
+
+
+def test_one_chunk_overflows_alone(S):
+    """(e) 64 rows of 200-byte strings inside frame (a), one chunk behind the start of a block: that block is cut behind its first
+    chunk, the next one is the chunk that overflows alone (at least one chunk is taken), the one behind it starts from the forced
+    block's end.  The 64 rows are longer than 32 bytes: the later kernels finish them."""
+    A, B, _ = _uniform()
+    A, B = list(A), list(B)
+    rng = random.Random(35)
+    for i in range(2048 + 64, 2048 + 128):
+        A[i] = gen.rand_string(rng, gen.ASCII_LOWER, 200, 200)
+        B[i] = gen.edit(rng, A[i], gen.ASCII_LOWER, 3)[:200]
+    _run(S, A, B, late=64)
+
+
+LITERALS = ["", "abcdefghijklmnopqrstuvwxyzabcdef", "kitten"]
+
+
+@pytest.mark.parametrize("stage_kernel", [True, False])
+@pytest.mark.parametrize("side", ["a", "b"])
+def test_literal_on_either_side(S, monkeypatch, side, stage_kernel):
+    """(f) a one-row side against frame (a)'s other column: an empty literal, a 32-byte one and a short one.  With
+    STRSIM_NO_LITERAL_PATH the call takes the stage kernel's instantiation that keeps the literal's code; without it the literal
+    kernel, which this change does not touch."""
+    if stage_kernel:
+        monkeypatch.setenv("STRSIM_NO_LITERAL_PATH", "1")
+    else:
+        monkeypatch.delenv("STRSIM_NO_LITERAL_PATH", raising=False)
+    A, B, _ = _uniform()
+    for lit in LITERALS:
+        if side == "a":
+            _run(S, [lit], B, one_op=stage_kernel)
+        else:
+            _run(S, A, [lit], one_op=stage_kernel)
+
+
+@pytest.mark.parametrize("shift", [1, 7, 15])
+def test_misaligned_value_buffers(S, shift):
+    """(g) frame (a) with the value buffers 1, 7 and 15 bytes behind a 16-byte boundary (column b: 15, 9 and 1): the alignment of a
+    block's copy derives from a carried base."""
+    A, B, exp = _uniform()
+    _run(S, A, B, exp, shifts=(shift, 16 - shift))
