@@ -36,11 +36,6 @@ static_assert(WIDE_LIST >= WIDE_ROWS && WIDE_BLOCK * 64 <= 65536, "one span alwa
 constexpr int U8_SPAN = 32;                  // ... of k_lane_utf8 (its symbol columns take the LDS: a larger span costs a workgroup per CU)
 constexpr int U8_ROWS = U8_SPAN * 64;        // 2048 rows
 constexpr int WIDE_MAXW = 4;
-#ifndef STRSIM_WIDE_ONE_WORD
-// 1: k_lane_wide also takes flagged ASCII rows whose LONGER string is <= 32 bytes (masks of one word) -- the rows k_lane_stage's LONG
-// geometry leaves behind under STRSIM_STAGE_LONG_TEXT_MAX, and short rows a staging overflow left in the mask.  Round 6's experiment.
-#define STRSIM_WIDE_ONE_WORD 0
-#endif
 
 // NDW dwords of vals[start, start + 4*NDW); bytes outside [0, total) read as 0.  start may be negative.
 template <int NDW>
@@ -105,7 +100,9 @@ struct LdsTxt {
         *reinterpret_cast<__attribute__((address_space(3))) uint32_t *>((uintptr_t)at(g)) = v;
     }
 };
-// Jaro's string of matched characters (strsim_lane_wide.h) overwrites the front of the lane's text
+// Jaro's string of matched characters (strsim_lane_wide.h) overwrites the front of the lane's text.
+// STRSIM_WIDE_ZIP_MATCHES is the last switch in the lane kernels that selects a measured-and-closed alternative path: it stays
+// because the CPU harness drives that path of jaro_wide (harness_set_zip_mode, tests/cpu_harness/lane_core_harness.cpp).
 #ifndef STRSIM_WIDE_ZIP_MATCHES
 #define STRSIM_WIDE_ZIP_MATCHES 0 // 1: Jaro's zip pass may walk the matched characters instead of b (jaro_wide): measured, off -- see DESIGN 3.3 [r5]
 #endif
@@ -300,37 +297,9 @@ __device__ __forceinline__ void wide_text(const uint8_t *__restrict__ valA, uint
     a0w = ta[0];
 }
 
-#ifndef STRSIM_WIDE_PREFETCH
-// 1: the windows of the NEXT two-word round are fetched into registers before the cores of the current two-word round run (rows two
-// rounds ahead, windows one): round 6's experiment (LAB_NOTES 9.0 "~4 % of cfg3").  See profiles/r6_rounds_ab.txt.
-#define STRSIM_WIDE_PREFETCH 0
-#endif
-// a two-word round's windows in flight: 4 x 16-byte pieces of pattern per row (coop_fetch<4>), 2 or 4 of text
-struct WidePref {
-    bool valid;
-    uint4 vp[4], vt[4];
-};
-__device__ __forceinline__ void wide_prefetch2(const uint8_t *vT, const uint8_t *vP, uint32_t tstart, uint32_t pstart, uint32_t wtw, WidePref &pf
-                                               STRSIM_COOP_RANGES)
-{
-    uint32_t lane = lane_id();
-    asm volatile("" : "+v"(lane));
-    coop_fetch<4>(vP, pstart, lane, pf.vp STRSIM_COOP_RANGES_ARG);
-    if (STRSIM_WIDE_PREFETCH == 2) { // (the pattern alone: 16 registers instead of 32; the text is fetched when its round starts)
-    } else if (wtw <= 1u) {
-        uint4 t[2];
-        coop_fetch<2>(vT, tstart, lane, t STRSIM_COOP_RANGES_ARG);
-        pf.vt[0] = t[0]; pf.vt[1] = t[1];
-    } else {
-        coop_fetch<4>(vT, tstart, lane, pf.vt STRSIM_COOP_RANGES_ARG);
-    }
-    pf.valid = true;
-}
-
 // W: words of the masks (by the round's longest PATTERN), wtw: 32-byte units of text to fetch (uniform, 1..4)
-// pf: the round's windows, already fetched (two-word rounds under STRSIM_WIDE_PREFETCH; valid implies the round is not an edge round)
 template <int MEASURE, int W>
-__device__ __forceinline__ void wide_round(const WidePref &pf, const uint8_t *__restrict__ valA, uint32_t totalA,
+__device__ __forceinline__ void wide_round(const uint8_t *__restrict__ valA, uint32_t totalA,
                                            const uint8_t *__restrict__ valB, uint32_t totalB, uint32_t firstA, uint32_t firstB, bool has, uint32_t a0,
                                            uint32_t la, uint32_t b0, uint32_t lb, uint32_t wtw, const LdsTxt &txt, bool &done, double &res WIDE_STAMP_PARAMS
                                            STRSIM_COOP_RANGES)
@@ -357,23 +326,12 @@ __device__ __forceinline__ void wide_round(const WidePref &pf, const uint8_t *__
     if (!edge) {
         // both fetches in flight together; the pattern passes through the rows first, then the text moves in
         const uint32_t pstart = has ? b0 : firstB, tstart = has ? a0 : firstA;
-        const bool have = W == 2 && STRSIM_WIDE_PREFETCH && pf.valid; // (uniform)
         uint4 vp[CoopGeom<2 * W>::ITER];
-        if (have) {
-#pragma unroll
-            for (int q = 0; q < CoopGeom<2 * W>::ITER; ++q) vp[q] = pf.vp[q & 3];
-        } else {
-            coop_fetch<2 * W>(valB, pstart, lane, vp STRSIM_COOP_RANGES_ARG);
-        }
+        coop_fetch<2 * W>(valB, pstart, lane, vp STRSIM_COOP_RANGES_ARG);
         auto text = [&](auto wt) {
             constexpr int WT = decltype(wt)::value;
             uint4 vt[CoopGeom<2 * WT>::ITER];
-            if (have && WT <= 2 && STRSIM_WIDE_PREFETCH == 1) {
-#pragma unroll
-                for (int q = 0; q < CoopGeom<2 * WT>::ITER; ++q) vt[q] = pf.vt[q & 3];
-            } else {
-                coop_fetch<2 * WT>(valA, tstart, lane, vt STRSIM_COOP_RANGES_ARG);
-            }
+            coop_fetch<2 * WT>(valA, tstart, lane, vt STRSIM_COOP_RANGES_ARG);
             coop_store_groups<2 * W>(base, lane, vp);
             wide_pattern_regs<W>(base, lane, wp);
             coop_store_text<2 * WT>(base, lane, vt);
@@ -497,7 +455,7 @@ __global__ __launch_bounds__(WIDE_BLOCK) __attribute__((amdgpu_waves_per_eu(STRS
         auto row_key = [&](uint32_t i, uint32_t la8, uint32_t lb8) -> uint32_t { // 0xFFFF: not a candidate
             if (!((s_mask[i >> 6] >> (i & 63u)) & 1ull)) return 0xFFFFu;
             const uint32_t mx = la8 > lb8 ? la8 : lb8, mn = la8 < lb8 ? la8 : lb8;
-            if (!(mx > (STRSIM_WIDE_ONE_WORD ? 0u : 32u) && mx <= 128u && mn >= 1u)) return 0xFFFFu;
+            if (!(mx > 32u && mx <= 128u && mn >= 1u)) return 0xFFFFu;
             const uint32_t steps = mn, pat = mx; // text = the shorter string, pattern = the longer one
             const uint32_t cls = (pat - 1u) >> 5; // masks of cls + 1 words: as wide as the PATTERN is long
             return (cls * 32u + ((steps - 1u) >> 2)) * 4u + (pat - 1u - 32u * cls) / 8u;
@@ -600,7 +558,7 @@ __global__ __launch_bounds__(WIDE_BLOCK) __attribute__((amdgpu_waves_per_eu(STRS
             WIDE_STAMP(0);
             // what a round's lanes fetch and how wide its masks are (uniform ballots over the round's rows)
             struct Cls {
-                const uint8_t *vT, *vP; uint32_t tT, tP, fT, fP, t0, lt, p0, lp, wtw; bool pat2, pat3, pat4;
+                const uint8_t *vT, *vP; uint32_t tT, tP, fT, fP, t0, lt, p0, lp, wtw; bool pat3, pat4;
             };
             auto classify = [&](const Rows &q) -> Cls {
                 Cls c;
@@ -609,7 +567,6 @@ __global__ __launch_bounds__(WIDE_BLOCK) __attribute__((amdgpu_waves_per_eu(STRS
                 c.tT = swap ? totalB : totalA; c.tP = swap ? totalA : totalB;
                 c.fT = swap ? firstB : firstA; c.fP = swap ? firstA : firstB; // (the columns' first bytes: offsets[0])
                 c.t0 = swap ? q.b0 : q.a0; c.lt = swap ? q.lb : q.la; c.p0 = swap ? q.a0 : q.b0; c.lp = swap ? q.la : q.lb;
-                c.pat2 = !STRSIM_WIDE_ONE_WORD || __ballot(q.has && c.lp > 32u) != 0ull;
                 c.pat3 = __ballot(q.has && c.lp > 64u) != 0ull;
                 c.pat4 = __ballot(q.has && c.lp > 96u) != 0ull;
                 c.wtw = 1u + (__ballot(q.has && c.lt > 32u) != 0ull) + (__ballot(q.has && c.lt > 64u) != 0ull) + (__ballot(q.has && c.lt > 96u) != 0ull);
@@ -625,14 +582,10 @@ __global__ __launch_bounds__(WIDE_BLOCK) __attribute__((amdgpu_waves_per_eu(STRS
                     atomicAnd(&s_mask[i >> 6], ~(1ull << (i & 63u)));
                 }
             };
-            WidePref none;
-            none.valid = false;
             Rows cur = take();
-            // ---- loop A: every round (with STRSIM_WIDE_PREFETCH: the rounds of three- and four-word masks -- they come first, the list
-            //      is dealt from its long end -- and their registers leave no room for a deeper pipeline)
+            // ---- the round loop
             while (cur.valid) {
                 const Cls c = classify(cur);
-                if (STRSIM_WIDE_PREFETCH && !c.pat3) break; // two-word rounds (and narrower) from here on: loop B
                 const Rows nxt = take();
 #if defined(STRSIM_LAB) && defined(STRSIM_WIDE_STAMPS)
                 asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -641,56 +594,17 @@ __global__ __launch_bounds__(WIDE_BLOCK) __attribute__((amdgpu_waves_per_eu(STRS
                 WIDE_STAMP(1);
                 bool done = false;
                 double res = 0.0;
-                if (!c.pat2) { // (only with STRSIM_WIDE_ONE_WORD: a round whose longest pattern fits one word)
-#if STRSIM_WIDE_ONE_WORD
-                    wide_round<MEASURE, 1>(none, c.vT, c.tT, c.vP, c.tP, c.fT, c.fP, cur.has, c.t0, c.lt, c.p0, c.lp, c.wtw, txt, done, res WIDE_STAMP_ARGS STRSIM_COOP_RANGES_ARG);
-#endif
-                } else if (!c.pat3) // (the pattern is the longer string: two words or more)
-                    wide_round<MEASURE, 2>(none, c.vT, c.tT, c.vP, c.tP, c.fT, c.fP, cur.has, c.t0, c.lt, c.p0, c.lp, c.wtw, txt, done, res WIDE_STAMP_ARGS STRSIM_COOP_RANGES_ARG);
+                if (!c.pat3) // (the pattern is the longer string: two words or more)
+                    wide_round<MEASURE, 2>(c.vT, c.tT, c.vP, c.tP, c.fT, c.fP, cur.has, c.t0, c.lt, c.p0, c.lp, c.wtw, txt, done, res WIDE_STAMP_ARGS STRSIM_COOP_RANGES_ARG);
                 else if (!c.pat4)
-                    wide_round<MEASURE, 3>(none, c.vT, c.tT, c.vP, c.tP, c.fT, c.fP, cur.has, c.t0, c.lt, c.p0, c.lp, c.wtw, txt, done, res WIDE_STAMP_ARGS STRSIM_COOP_RANGES_ARG);
+                    wide_round<MEASURE, 3>(c.vT, c.tT, c.vP, c.tP, c.fT, c.fP, cur.has, c.t0, c.lt, c.p0, c.lp, c.wtw, txt, done, res WIDE_STAMP_ARGS STRSIM_COOP_RANGES_ARG);
                 else
-                    wide_round<MEASURE, 4>(none, c.vT, c.tT, c.vP, c.tP, c.fT, c.fP, cur.has, c.t0, c.lt, c.p0, c.lp, c.wtw, txt, done, res WIDE_STAMP_ARGS STRSIM_COOP_RANGES_ARG);
+                    wide_round<MEASURE, 4>(c.vT, c.tT, c.vP, c.tP, c.fT, c.fP, cur.has, c.t0, c.lt, c.p0, c.lp, c.wtw, txt, done, res WIDE_STAMP_ARGS STRSIM_COOP_RANGES_ARG);
                 WIDE_STAMP(3);
                 finish(cur.i, done, res);
                 cur = nxt;
                 WIDE_STAMP(4);
             }
-#if STRSIM_WIDE_PREFETCH
-            // ---- loop B: the two-word rounds, one stage deeper: rows TWO rounds ahead, and the next round's windows go out into
-            //      registers before this round's cores run (they land under the cores instead of in front of the next round)
-            if (cur.valid) {
-                Rows nxt = take();
-                WidePref pf;
-                pf.valid = false;
-                while (cur.valid) {
-                    const Rows nn = nxt.valid ? take() : nxt;
-                    const Cls c = classify(cur);
-                    WidePref pn;
-                    pn.valid = false;
-                    if (nxt.valid) {
-                        const Cls cn = classify(nxt);
-                        const bool edge_n = __ballot((nxt.has && ((uint64_t)cn.p0 + 64u > cn.tP || (uint64_t)cn.t0 + 32u * cn.wtw > cn.tT)) ||
-                                                     cn.tP - cn.fP < 64u || cn.tT - cn.fT < 32u * cn.wtw) != 0ull;
-                        if (cn.pat2 && !edge_n)
-                            wide_prefetch2(cn.vT, cn.vP, nxt.has ? cn.t0 : cn.fT, nxt.has ? cn.p0 : cn.fP, cn.wtw, pn STRSIM_COOP_RANGES_ARG);
-                    }
-                    bool done = false;
-                    double res = 0.0;
-                    if (!c.pat2) {
-#if STRSIM_WIDE_ONE_WORD
-                        wide_round<MEASURE, 1>(none, c.vT, c.tT, c.vP, c.tP, c.fT, c.fP, cur.has, c.t0, c.lt, c.p0, c.lp, c.wtw, txt, done, res WIDE_STAMP_ARGS STRSIM_COOP_RANGES_ARG);
-#endif
-                    } else {
-                        wide_round<MEASURE, 2>(pf, c.vT, c.tT, c.vP, c.tP, c.fT, c.fP, cur.has, c.t0, c.lt, c.p0, c.lp, c.wtw, txt, done, res WIDE_STAMP_ARGS STRSIM_COOP_RANGES_ARG);
-                    }
-                    finish(cur.i, done, res);
-                    cur = nxt;
-                    nxt = nn;
-                    pf = pn;
-                }
-            }
-#endif
         }
         lds_barrier();
         WIDE_STAMP(5);

@@ -92,9 +92,6 @@ struct OutPtrs {
 };
 
 #include "strsim_lane_stage.h"
-#if defined(STRSIM_LAB) && defined(STRSIM_STAGE_PC)
-#include "strsim_lane_stage_pc.h" // lab only: the producer / consumer form of k_lane_stage (round 6's experiment)
-#endif
 #include "strsim_lane_lit.h"
 #include "strsim_match.h"
 #include "strsim_nearest_kernels.h"
@@ -148,15 +145,6 @@ static uint64_t stage_launch_size(uint64_t nsb, uint64_t resident, uint64_t cus)
 template <int M>
 static void launch_lane_t(const LaunchArgs &a)
 {
-#if defined(STRSIM_LAB) && defined(STRSIM_STAGE_STRIP)
-    if (M == LEVENSHTEIN && a.rowsA != 1 && a.rowsB != 1) { // (lab) the strip lengths of every row, by a kernel of its own IN FRONT of the timed one
-        static uint16_t *buf = nullptr;
-        static uint64_t cap = 0;
-        if (a.n > cap) { if (buf) (void)hipFree(buf); (void)hipMalloc((void **)&buf, a.n * 2 + 64); cap = a.n; }
-        hipLaunchKernelGGL(k_strip_oracle, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, buf);
-        (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_strip_ptr), &buf, sizeof buf, 0, hipMemcpyHostToDevice, a.stream);
-    }
-#endif
     if (a.ev_lane0) (void)hipEventRecord(a.ev_lane0, a.stream);
     OutPtrs op{};
     op.p[0] = a.out;
@@ -190,14 +178,6 @@ static void launch_lane_t(const LaunchArgs &a)
                 hipLaunchKernelGGL((k_lane_stage<M, T, L>), dim3((unsigned)gs), dim3(STAGE_BLOCK), 0, a.stream, a.offA, a.valA, a.rowsA,
                                    a.offB, a.valB, a.rowsB, op, a.n, a.slowmask, a.status, a.qtab, a.sched, a.publish_host, a.publish_ticket);
         };
-#if defined(STRSIM_LAB) && defined(STRSIM_STAGE_PC)
-        if (((STRSIM_STAGE_PC >> M) & 1) != 0 && a.rowsA != 1 && a.rowsB != 1 && !a.long_rows) {
-            const uint64_t cus = (uint64_t)a.stage_grid / (uint64_t)STRSIM_STAGE_WAVES_PER_EU;
-            const uint64_t gs = stage_launch_size(nsb, cus * (uint64_t)STRSIM_PC_WG_PER_CU, cus);
-            hipLaunchKernelGGL((k_lane_stage_pc<M, STRSIM_PC_LUT != 0>), dim3((unsigned)gs), dim3(PC_THREADS), 0, a.stream, a.offA, a.valA, a.rowsA,
-                               a.offB, a.valB, a.rowsB, op, a.n, a.slowmask, a.status, a.qtab, a.sched, a.publish_host, a.publish_ticket);
-        } else
-#endif
         if (a.long_rows) go(std::false_type{}, std::true_type{});
         else if constexpr (stage_uses_lut<M>()) go(std::true_type{}, std::false_type{});
         else go(std::false_type{}, std::false_type{});

@@ -57,19 +57,12 @@ __device__ __forceinline__ uint32_t wave_max_rounded(uint32_t v)
     return C * (g + 1u);
 }
 
-#ifndef STRSIM_LANE_FULL_BARRIERS
-#define STRSIM_LANE_FULL_BARRIERS 0
-#endif
 // Workgroup barrier that orders LDS traffic only: __syncthreads() also drains the wave's global loads and STORES
 // (s_waitcnt vmcnt(0)), which k_lane_pairs does not need -- it communicates through LDS alone -- and which exposes the
 // latency of a block's result stores at the next barrier.
 __device__ __forceinline__ void lds_barrier()
 {
-#if STRSIM_LANE_FULL_BARRIERS
-    __syncthreads();
-#else
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
 }
 
 } // namespace strsim

@@ -51,15 +51,6 @@ enum Measure : int { LEVENSHTEIN = 0, JARO = 1, JARO_WINKLER = 2, JACCARD = 3, S
 #define STRSIM_COLS_PER_TEST 2
 #endif
 constexpr int COLS_PER_TEST = STRSIM_COLS_PER_TEST;
-#ifndef STRSIM_LEV_JOIN_SELECT
-// The Levenshtein cores (lev_myers32_snap, lev_myers32_ptab) from tmin on, where a lane's text may have ended.  0: such a column runs
-// under `column < lt`, i.e. the exec mask; the masked variant of a group must update (Pv, Mv) in place, the unmasked one need not, and
-// hipcc joins the two with two v_mov_b32 per group (and a chain of swaps behind the seven-plane loop).  1: the column is computed for
-// every lane and a lane whose text has ended keeps its state by two selects, so both variants may write any register.  Closed
-// experiment (LAB 3.1c): the headline kernel 5 137 -> 4 659 instructions but 79 -> 94 VGPRs, and cfg2 1.3 % slower (74.56 against 75.57
-// G pairs/s by the medians, same box, no overlap).
-#define STRSIM_LEV_JOIN_SELECT 0
-#endif
 
 STRSIM_HD uint32_t lane_byte(const uint32_t (&w)[8], int j) { return (w[j >> 2] >> ((j & 3) * 8)) & 0xFFu; }
 
@@ -289,23 +280,22 @@ STRSIM_HD uint32_t lev_myers32_snap(const uint32_t (&wt)[8], uint32_t lt, uint32
         // one straight-line block per group of columns (the match masks of the whole group are independent work the
         // scheduler can put between the dependent steps of the recurrence)
         // A lane whose text has ended keeps its (Pv, Mv): in the groups where that can happen (from tmin on) every column
-        // runs under `column < lt` -- one compare per column and the exec mask, instead of copying the state aside.
-        auto column = [&](int j, bool keep = false) { // keep (STRSIM_LEV_JOIN_SELECT): this lane's text has ended
+        // runs under `column < lt` -- one compare per column and the exec mask, instead of copying the state aside.  (The masked
+        // variant of a group updates (Pv, Mv) in place and hipcc joins it with the unmasked one by two v_mov_b32 per group; keeping
+        // the state by two selects per column instead saves those and costs 15 VGPRs: 1.3 % slower, LAB_NOTES "Retired switches".)
+        auto column = [&](int j) {
             const uint32_t Eq = eq_mask<NP>(P, 0xFFFFFFFFu, wt[j >> 2], j & 3);
             const uint32_t D0 = bitop3<0xBE>((Eq & Pv) + Pv, Pv, Eq) | Mv; // (((Eq & Pv) + Pv) ^ Pv) | Eq | Mv
             const uint32_t nHP = bitop3<0x0E>(Mv, D0, Pv);                 // ~HP = ~Mv & (D0 | Pv)
             const uint32_t nX = twice(nHP);                                 // ~((HP << 1) | 1)
             const uint32_t HN2 = twice(D0 & Pv);                            // HN << 1
-            const uint32_t nPv = bitop3<0xF2>(HN2, D0, nX);                                 // (HN << 1) | ~(D0 | X)
-            const uint32_t nMv = bitop3<0x50>(D0, D0, nX);                                  // D0 & X
-            Pv = keep ? Pv : nPv;
-            Mv = keep ? Mv : nMv;
+            Pv = bitop3<0xF2>(HN2, D0, nX);                                 // (HN << 1) | ~(D0 | X)
+            Mv = bitop3<0x50>(D0, D0, nX);                                  // D0 & X
         };
         if ((uint32_t)(COLS_PER_TEST * (g + 1)) >= tmin) {                 // (uniform) some lane's text may end in this group
 #pragma unroll
             for (int jj = 0; jj < COLS_PER_TEST; ++jj)
-                if (STRSIM_LEV_JOIN_SELECT) column(COLS_PER_TEST * g + jj, (uint32_t)(COLS_PER_TEST * g + jj) >= lt);
-                else if ((uint32_t)(COLS_PER_TEST * g + jj) < lt) column(COLS_PER_TEST * g + jj);
+                if ((uint32_t)(COLS_PER_TEST * g + jj) < lt) column(COLS_PER_TEST * g + jj);
         } else {
 #pragma unroll
             for (int jj = 0; jj < COLS_PER_TEST; ++jj) column(COLS_PER_TEST * g + jj);

@@ -79,22 +79,19 @@ STRSIM_HD uint32_t lev_myers32_ptab(const uint32_t (&wt)[8], uint32_t lt, uint32
         constexpr int g = decltype(gc)::value;
         if ((uint32_t)(COLS_PER_TEST * g) >= tmax) return false;
         if constexpr ((COLS_PER_TEST * g) % 4 == 0) ptab_masks(T, wt[(COLS_PER_TEST * g) >> 2], Eq);
-        auto column = [&](int j, bool keep = false) { // keep (STRSIM_LEV_JOIN_SELECT): this lane's text has ended
+        auto column = [&](int j) {
             const uint32_t E = Eq[j & 3];
             const uint32_t D0 = bitop3<0xBE>((E & Pv) + Pv, Pv, E) | Mv; // (((Eq & Pv) + Pv) ^ Pv) | Eq | Mv
             const uint32_t nHP = bitop3<0x0E>(Mv, D0, Pv);               // ~HP = ~Mv & (D0 | Pv)
             const uint32_t nX = twice(nHP);                               // ~((HP << 1) | 1)
             const uint32_t HN2 = twice(D0 & Pv);                          // HN << 1
-            const uint32_t nPv = bitop3<0xF2>(HN2, D0, nX);                               // (HN << 1) | ~(D0 | X)
-            const uint32_t nMv = bitop3<0x50>(D0, D0, nX);                                // D0 & X
-            Pv = keep ? Pv : nPv;
-            Mv = keep ? Mv : nMv;
+            Pv = bitop3<0xF2>(HN2, D0, nX);                               // (HN << 1) | ~(D0 | X)
+            Mv = bitop3<0x50>(D0, D0, nX);                                // D0 & X
         };
         if ((uint32_t)(COLS_PER_TEST * (g + 1)) >= tmin) {               // (uniform) some lane's text may end in this group
 #pragma unroll
             for (int jj = 0; jj < COLS_PER_TEST; ++jj)
-                if (STRSIM_LEV_JOIN_SELECT) column(COLS_PER_TEST * g + jj, (uint32_t)(COLS_PER_TEST * g + jj) >= lt);
-                else if ((uint32_t)(COLS_PER_TEST * g + jj) < lt) column(COLS_PER_TEST * g + jj);
+                if ((uint32_t)(COLS_PER_TEST * g + jj) < lt) column(COLS_PER_TEST * g + jj);
         } else {
 #pragma unroll
             for (int jj = 0; jj < COLS_PER_TEST; ++jj) column(COLS_PER_TEST * g + jj);

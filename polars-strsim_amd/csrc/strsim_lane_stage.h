@@ -10,8 +10,10 @@
 // never touches a VGPR) and the lanes then pick their windows out of LDS as nine aligned dwords + eight v_alignbyte.
 //
 //   per block of STAGE_ROWS consecutive rows (persistent 256-thread workgroup, grid-stride over blocks):
-//     A  bytes DMA(j)      both columns' byte ranges of block j -> s_bytes (in flight during B and C)
-//     B  store(j-1)        results of block j-1, staged in LDS by its rounds, leave as coalesced 8-byte stores
+//     B  store(j-1)        results of block j-1, staged in LDS by its rounds, leave as coalesced 8-byte stores (in one piece, in
+//                          front of the DMA: its table loads would otherwise return behind the wave's share of the copy)
+//        cut(j)            base and end offsets of the block from s_off, the fit test of its chunks: LDS and scalar work only
+//     A  bytes DMA(j)      both columns' byte ranges of block j -> s_bytes (in flight during C)
 //     C  sortA/sortB(j)    offsets (in LDS since the previous block's rounds) -> lengths -> bucket by the number of
 //                          DP columns -> rank by LDS atomics | barrier | wave scan of the counters -> 8-byte
 //                          descriptors in length order
@@ -54,15 +56,6 @@
 // the tables), a shorter one keeps the bit fills.  33 = never (the table core is not instantiated).
 #define STRSIM_STAGE_PTAB_MIN 12
 #endif
-#ifndef STRSIM_JARO_KEEP_EQ_FILLS
-#define STRSIM_JARO_KEEP_EQ_FILLS 1 // the bit-fill form of Jaro's cores (the long-row geometry) keeps the first pass's masks for the zip pass too
-#endif
-#ifndef STRSIM_STAGE_LONG_TEXT_MAX
-// LONG geometry only (frames of long rows, cfg3): rows whose SHORTER string exceeds this many bytes are left to k_lane_wide's one-word
-// class (STRSIM_WIDE_ONE_WORD).  32 = off.  Round 6's experiment: a block's critical path is its longest round,
-// and on Zipf lengths the 64 longest of ~275 texts run 32 columns where the next round runs 14 (LAB 3.3 [r5]).
-#define STRSIM_STAGE_LONG_TEXT_MAX 32
-#endif
 #ifndef STRSIM_STAGE_RANGE_MAX
 #define STRSIM_STAGE_RANGE_MAX 64   // chunks of 64 rows a workgroup takes from the device-wide counter at a time, at most
 #endif
@@ -73,22 +66,6 @@
 #define STRSIM_STAGE_RANGE_MIN_BLOCKS 2 // ... and at least this many blocks (1: a 3 M-row call 132 us instead of 102, cfg2 +2 %: the counter is one contended address)
 #endif
 
-// Three separable changes to the per-block skeleton (LAB 3.1c; each measured alone against the previous commit, whose ISA all three
-// switched off give back instruction for instruction):
-#ifndef STRSIM_STAGE_CUT_CARRY
-// 1: the block cut without its chain of LDS round trips -- a block that starts where the previous one ended (same range) takes its
-// base offsets from that block's end offsets, which are in SGPRs, and the end offsets come from the lane of the fit test that has
-// already loaded them (v_readlane), so the cut waits for LDS once instead of five times.  Closed experiment, cfg2, G pairs/s by the
-// medians: box A 75.45 against the parent's 75.20, box B 74.51 against 74.74, both inside the parent's spread.  0: every block reads s_off[side][0] and s_off[side][rows].
-#define STRSIM_STAGE_CUT_CARRY 0
-#endif
-#ifndef STRSIM_STAGE_CUT_UNDER_STORE
-// 1: the store phase in two parts around the cut (Levenshtein's short-row geometry) -- the staged codes leave LDS and the
-// quotient-table loads are issued, then the cut (LDS and scalar work only) runs under their L2 round trip, then the wait, the
-// arithmetic and the stores.  Closed experiment: +0.5 % on one box (every run above every parent run, by 0.01 %), nothing on the
-// other; costs 8 VGPRs.  0: the store phase in one piece.
-#define STRSIM_STAGE_CUT_UNDER_STORE 0
-#endif
 #ifndef STRSIM_STAGE_COLS_ONLY
 // Bit m set: measure m's short-row instantiation without tables exists a second time for calls where neither side is a literal (the
 // launcher knows): no literal windows, no selects on them, no uniform branches.  Default: Levenshtein (cfg2 +2 %, LAB 3.1c).
@@ -120,12 +97,6 @@ constexpr int STAGE_RPW = STAGE_NR / STAGE_WAVES;     // rounds per wave and blo
 // Jaro 41 -> 45.6 G pairs/s on cfg2's lengths.  Levenshtein, Jaccard and Dice are issue-bound at 5 workgroups per CU and
 // latency-bound at 4: 28 % fewer vector instructions bought nothing there.
 template <int MEASURE> constexpr bool stage_uses_lut() { return ((STRSIM_STAGE_LUT >> MEASURE) & 1) != 0; } // (5: five outputs)
-// Which instantiations carry the cut's offsets in registers (STRSIM_STAGE_CUT_CARRY: all of them, the other measures'
-// lines of bench_support/kernel_resources.sh do not move) / cut under the store's loads (STRSIM_STAGE_CUT_UNDER_STORE: Levenshtein's short-row
-// geometry.  The store phase's registers stay live across the cut: Jaro's three table values per row and the five-output pass's four
-// turned into spills -- k_lane_stage_all 0 -> 12, k_lane_stage<1, true> 4 -> 10, <2, true> 6 -> 11 -- and Jaccard and Dice load nothing).
-template <int MEASURE, bool TABLES, bool LONG> constexpr bool stage_cut_carry() { return STRSIM_STAGE_CUT_CARRY != 0; }
-template <int MEASURE, bool TABLES, bool LONG> constexpr bool stage_cut_under_store() { return STRSIM_STAGE_CUT_UNDER_STORE != 0 && MEASURE == LEVENSHTEIN && !TABLES && !LONG; }
 // Which instantiations have a twin for column x column calls (STRSIM_STAGE_COLS_ONLY).
 template <int MEASURE, bool TABLES, bool LONG> constexpr bool stage_has_cols_only() { return !TABLES && !LONG && MEASURE < 5 && ((STRSIM_STAGE_COLS_ONLY >> MEASURE) & 1) != 0; }
 
@@ -186,31 +157,6 @@ __device__ __forceinline__ uint32_t load_invariant(const uint32_t *p)
 // Jaro / Jaro-Winkler and the five-output pass too: the reference's greedy matching is symmetric, strsim_lane_core.h).
 constexpr uint32_t STAGE_DEAD = 1u << 31;
 
-#if defined(STRSIM_LAB) && defined(STRSIM_STAGE_STRIP)
-// LAB ONLY (round 6, LAB_NOTES "an idea priced and not built"): Levenshtein on a pair's strings with their common prefix and suffix
-// stripped (the distance does not change).  STRSIM_STAGE_STRIP = the most bytes stripped at either end.  Mode STRSIM_STAGE_STRIP_ORACLE:
-// the strip lengths come from an array that a separate, UNTIMED kernel has filled (k_strip_oracle) -- the BENEFIT side of the idea
-// alone: what the kernel gains from the shorter texts if knowing them were free.  A descriptor's y carries p + s in bits 25..30 (the
-// row index needs 9 of its 11 bits): the denominator of the result is the ORIGINAL longer length = lp + p + s.
-__device__ const uint16_t *g_strip_ptr; // per row: p | s << 8
-__global__ __launch_bounds__(256) void k_strip_oracle(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ valA, const uint32_t *__restrict__ offB,
-                                                      const uint8_t *__restrict__ valB, uint64_t n, uint16_t *__restrict__ out)
-{
-    const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (r >= n) return;
-    const uint32_t a0 = offA[r], la = offA[r + 1] - a0, b0 = offB[r], lb = offB[r + 1] - b0;
-    const uint32_t m = la < lb ? la : lb, cap = (uint32_t)STRSIM_STAGE_STRIP;
-    uint32_t p = 0, s = 0;
-    while (p < m && p < cap && valA[a0 + p] == valB[b0 + p]) ++p;
-    while (s < m - p && s < cap && valA[a0 + la - 1u - s] == valB[b0 + lb - 1u - s]) ++s;
-    if (p + s > 63u) s = 63u - p;
-    out[r] = (uint16_t)(p | (s << 8));
-}
-#define STRSIM_STRIP_ON 1
-#else
-#define STRSIM_STRIP_ON 0
-#endif
-
 // 32 bytes at byte offset `at` of `base` (an LDS array) into w[0..7]: nine dwords from the dword-aligned address below (56 LDS
 // cycles per 64 lanes) + eight v_alignbyte_b32.  (gfx950 serves a wide LDS read that is not naturally aligned one lane at a time:
 // two ds_read_b128 at the byte address cost 129 LDS cycles, bench_support/micro/lds_window.hip; cfg2 1.636 vs 1.587 ms.)
@@ -246,7 +192,7 @@ __device__ __forceinline__ uint32_t scan32_inclusive(uint32_t x)
 // Levenshtein result as an index into the table of integer quotients (dist * QTAB_N + den); 0xFFFF is never produced
 template <int NP, bool USE_LUT, bool PTAB = false> // match masks from bit fills / from the LDS tables; PTAB: register tables in long rounds
 __device__ __forceinline__ uint32_t stage_lev_code(const EqLut &lut, const uint32_t (&wa)[8], uint32_t la, const uint32_t (&wb)[8],
-                                                   uint32_t lb, uint32_t tmin, uint32_t tmax, uint32_t stripped = 0u)
+                                                   uint32_t lb, uint32_t tmin, uint32_t tmax)
 {
     uint32_t P[NP];
     build_planes<NP>(wb, P);
@@ -265,13 +211,6 @@ __device__ __forceinline__ uint32_t stage_lev_code(const EqLut &lut, const uint3
     uint32_t code = dist * (uint32_t)QTAB_N + (la1 > lb1 ? la1 : lb1);
     // both empty: 1.0 = 1 - 0/1; one side empty: 0.0 = 1 - 1/1   (strsim.rs:128, :160)
     if (!live) code = (la == 0u && lb == 0u) ? 1u : (uint32_t)QTAB_N + 1u;
-#if STRSIM_STRIP_ON
-    // (lab) la / lb are what is left of the strings behind a common prefix and in front of a common suffix of `stripped` bytes in all;
-    // the denominator is the original longer length; an empty side leaves the other side's length as the distance
-    // (the longer one is lb between two columns -- the columns walk the shorter string -- but not with a literal side)
-    const uint32_t longer = la > lb ? la : lb;
-    code = (live ? dist : longer) * (uint32_t)QTAB_N + (longer + stripped);
-#endif
     return code;
 }
 
@@ -338,7 +277,7 @@ __device__ __forceinline__ uint32_t stage_ints(const EqLut &lut, const uint32_t 
     if (USE_LUT) lut_build<NP>(tb, P, 0xFFFFFFFFu);
     if (MEASURE == JARO || MEASURE == JARO_WINKLER) {
         if (USE_LUT) lane_cores32_lut<NP, false, true, false>(tb, wa, la1, tmin, tmax, lb1, P, dist, m, t, isect);
-        else lane_cores32<NP, false, true, false, STRSIM_JARO_KEEP_EQ_FILLS != 0>(wa, la1, tmin, tmax, lb1, P, dist, m, t, isect); // (the long-row geometry: four waves per SIMD too)
+        else lane_cores32<NP, false, true, false, true>(wa, la1, tmin, tmax, lb1, P, dist, m, t, isect); // (the long-row geometry, four waves per SIMD too: the first pass's masks are kept for the zip pass)
         const uint32_t pre = MEASURE == JARO_WINKLER ? common_prefix4(wa[0], la1, wb[0], lb1) : 0u;
         return m | (t << 6) | (la << 12) | (lb << 18) | (pre << 24);
     }
@@ -369,11 +308,7 @@ __device__ __forceinline__ void stage_compute(const EqLut &lut, const uint32_t (
                                               uint32_t last, uint16_t *s_code, uint32_t *s_word, double *s_val)
 {
     bool fast = (meta & STAGE_DEAD) == 0u;
-#if STRSIM_STRIP_ON
-    const uint32_t lt = meta & 0x3Fu, lp = (meta >> 8) & 0x3Fu, idx = (meta >> 16) & 0x1FFu, stripped = (meta >> 25) & 0x3Fu;
-#else
-    const uint32_t lt = meta & 0x3Fu, lp = (meta >> 8) & 0x3Fu, idx = (meta >> 16) & 0x7FFu, stripped = 0u;
-#endif
+    const uint32_t lt = meta & 0x3Fu, lp = (meta >> 8) & 0x3Fu, idx = (meta >> 16) & 0x7FFu;
     // conservative tests on the whole 32-byte windows (bytes past a string belong to its neighbours): any high bit leaves
     // the row to the code-point kernels; the varying low bits decide how many bit-planes the match masks need
     uint32_t any;
@@ -392,8 +327,8 @@ __device__ __forceinline__ void stage_compute(const EqLut &lut, const uint32_t (
     const uint32_t tmin = (((lt0 ? lt0 : 1u) - 1u) & ~((1u << STAGE_BSH) - 1u)) + 1u;
     if (MEASURE == LEVENSHTEIN) {
         uint32_t code;
-        if (wide) code = stage_lev_code<7, LUT>(lut, wt, la, wp, lb, tmin, tmax, stripped);
-        else code = stage_lev_code<5, LUT, PTAB>(lut, wt, la, wp, lb, tmin, tmax, stripped);
+        if (wide) code = stage_lev_code<7, LUT>(lut, wt, la, wp, lb, tmin, tmax);
+        else code = stage_lev_code<5, LUT, PTAB>(lut, wt, la, wp, lb, tmin, tmax);
         if (fast) STRSIM_CHECK_INDEX(K_STAGE, 42, ~0ull, idx, STAGE_ROWS);
         if (fast) s_code[idx] = (uint16_t)code;
     } else if (MEASURE == ALL_MEASURES) {
@@ -426,7 +361,6 @@ lane_stage_body(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ v
     constexpr int STAGE_CAP = StageGeom<LUT, LONG>::CAP, STAGE_COL = StageGeom<LUT, LONG>::COL;
     constexpr int STAGE_DMA_ITERS = StageGeom<LUT, LONG>::DMA_ITERS;
     constexpr uint32_t COLB = STAGE_COL, LIT = 2u * STAGE_COL; // s_bytes: column a | column b | the literals' windows
-    constexpr bool CARRY = stage_cut_carry<MEASURE, LUT, LONG>(), UNDER = stage_cut_under_store<MEASURE, LUT, LONG>();
     // Match-mask tables (strsim_lane_lut.h), for the measures that use them: per wave 3 KB at a 4 KB boundary -- entry e of
     // lane l at e * 256 + l * 4, and the boundary makes (table base >> 8) | e the address byte.
     // The 1 KB behind each wave's tables holds 128 of the block's row descriptors (without tables: an array of their own).
@@ -556,9 +490,6 @@ lane_stage_body(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ v
 
     uint64_t prev_row0 = 0;           // the block whose results are waiting in LDS
     uint32_t prev_rows = 0;
-    // STRSIM_STAGE_CUT_CARRY: the end offsets of the last block, which are the base offsets of the next one while the range lasts
-    uint32_t carryA = 0u, carryB = 0u;
-    bool carried = false;
     if (row0 < row_end) dma_offsets(row0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     lds_barrier();
@@ -567,9 +498,8 @@ lane_stage_body(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ v
     // Three straight-line passes -- staged integers out of LDS, every table load of every row of the thread, then the
     // arithmetic and the stores: left to itself hipcc sinks each load into the branch that stores its row and waits for it
     // there (s_waitcnt vmcnt(0) per row: the L2 round trips of a thread's rows one after the other, each behind the previous
-    // row's store).  `pin` keeps a loaded value outside those branches.
-    // The phase comes in two parts so that the block cut, which touches LDS and SGPRs only, can run between them under the
-    // L2 round trip of the table loads (STRSIM_STAGE_CUT_UNDER_STORE): store_fetch, the first two passes, and store_finish.
+    // row's store).  `pin` keeps a loaded value outside those branches.  store_fetch: the first two passes; store_finish: the third
+    // (two lambdas: written as one body the same phase compiles to different code, profiles/retire_switches_isa.txt).
     auto pin = [](double &x) { asm volatile("" : "+v"(x)); };
     constexpr int M1 = (MEASURE == ALL_MEASURES || MEASURE == LEVENSHTEIN) ? JARO : MEASURE;
     constexpr bool JARO_LIKE = ALL || M1 == JARO || M1 == JARO_WINKLER;
@@ -659,7 +589,7 @@ lane_stage_body(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ v
             }
         }
     };
-    auto store_block = [&](uint64_t r0, uint32_t rows) { // the phase in one piece
+    auto store_block = [&](uint64_t r0, uint32_t rows) {
         unsigned long long pk[RPT]; // (rows of the block behind `rows` hold all-ones: nobody computed them)
         double t0[RPT], t1[RPT], t2[RPT], t3[RPT];
         store_fetch(r0, pk, t0, t1, t2, t3);
@@ -681,56 +611,27 @@ lane_stage_body(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ v
         }
         // ---- B: store(j-1).  Before the bytes DMA of this block is issued: a wave's vector-memory results return in order,
         //         so the table loads of the store phase would otherwise sit behind its share of the DMA (HBM latency).
-        //         With STRSIM_STAGE_CUT_UNDER_STORE only its loads are issued here and the block cut runs under them.
-        unsigned long long pk[RPT]; // (UNDER: the store phase's registers across the cut)
-        double t0[RPT], t1[RPT], t2[RPT], t3[RPT];
-        if constexpr (UNDER) {
-            if (prev_rows) store_fetch(prev_row0, pk, t0, t1, t2, t3);
-        } else {
-            if (prev_rows) store_block(prev_row0, prev_rows);
-        }
+        if (prev_rows) store_block(prev_row0, prev_rows);
         STAGE_STAMP(1);
         // ---- the block: as many of the next 64-row chunks (at most B / 64) as have their bytes inside the staging areas
         const uint32_t avail = (uint32_t)(row_end - row0 < (uint64_t)B ? row_end - row0 : (uint64_t)B); // rows whose offsets are in s_off
         // lane c < B / 64: does the block still fit if it ends behind chunk c?
         const uint32_t e = (lane + 1u) * 64u < avail ? (lane + 1u) * 64u : avail; // rows if the block ends behind chunk `lane`
         const bool exists = lane * 64u < avail && lane < (uint32_t)(B / 64);
-        uint32_t laneEndA = 0u, laneEndB = 0u; // s_off[side][e]; a literal side: its base
-        uint32_t baseA, baseB;
-        if constexpr (CARRY) {
-            // (issued in front of the wait for the bases: one LDS round trip for both when the bases are read at all)
-            laneEndA = bcastA ? litA0 : s_off[0][exists ? e : 0u];
-            laneEndB = bcastB ? litB0 : s_off[1][exists ? e : 0u];
-        }
-        if (CARRY && carried) { // (uniform) the previous block of this range ended where this one starts
-            baseA = carryA;
-            baseB = carryB;
-        } else {
-            baseA = bcastA ? litA0 : uniform(s_off[0][0]);
-            baseB = bcastB ? litB0 : uniform(s_off[1][0]);
-        }
+        const uint32_t baseA = bcastA ? litA0 : uniform(s_off[0][0]);
+        const uint32_t baseB = bcastB ? litB0 : uniform(s_off[1][0]);
         const uint32_t misA = (uint32_t)(reinterpret_cast<uintptr_t>(valA + baseA) & 15u);
         const uint32_t misB = (uint32_t)(reinterpret_cast<uintptr_t>(valB + baseB) & 15u);
-        if constexpr (!CARRY) {
-            laneEndA = bcastA ? baseA : s_off[0][exists ? e : 0u];
-            laneEndB = bcastB ? baseB : s_off[1][exists ? e : 0u];
-        }
+        const uint32_t laneEndA = bcastA ? baseA : s_off[0][exists ? e : 0u]; // s_off[side][e]; a literal side: its base
+        const uint32_t laneEndB = bcastB ? baseB : s_off[1][exists ? e : 0u];
         const bool fits = exists && laneEndA - baseA + misA <= (uint32_t)STAGE_CAP && laneEndB - baseB + misB <= (uint32_t)STAGE_CAP;
         const unsigned long long okm = __ballot(fits);
         // chunks 0 .. k-1 fit: k = number of trailing ones; at least one chunk is taken even if it overflows
         uint32_t k = (uint32_t)__builtin_ctzll(~okm);
         if (k == 0u) k = 1u;
         const uint32_t rows = uniform(k * 64u < avail ? k * 64u : avail);
-        uint32_t endA, endB;
-        if constexpr (CARRY) {
-            // lane k - 1 exists (chunks that fit exist, and so does chunk 0) and its e is min(k * 64, avail) = rows: it holds
-            // s_off[side][rows] already
-            endA = (uint32_t)__builtin_amdgcn_readlane((int)laneEndA, (int)(k - 1u));
-            endB = (uint32_t)__builtin_amdgcn_readlane((int)laneEndB, (int)(k - 1u));
-        } else {
-            endA = bcastA ? baseA : uniform(s_off[0][rows]);
-            endB = bcastB ? baseB : uniform(s_off[1][rows]);
-        }
+        const uint32_t endA = bcastA ? baseA : uniform(s_off[0][rows]);
+        const uint32_t endB = bcastB ? baseB : uniform(s_off[1][rows]);
         // ---- A: bytes DMA(j).  Column side X: the 16-byte chunks from the aligned address below the block's first byte
         //         up to the block's last byte, at most STAGE_CAP bytes -> s_bytes[X]
         const uint32_t spanA = endA - baseA + misA, spanB = endB - baseB + misB;
@@ -747,13 +648,6 @@ lane_stage_body(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ v
         else if (tid < 4u) STRSIM_CHECK_RANGE(K_STAGE, 21, row0, COLB + (chunksB << 4) + (tid - 2u) * 16u + 16u, 0, sizeof(s_bytes));
         if (tid < 2u) *reinterpret_cast<uint4 *>(s_bytes + (chunksA << 4) + tid * 16u) = make_uint4(0u, 0u, 0u, 0u);
         else if (tid < 4u) *reinterpret_cast<uint4 *>(s_bytes + COLB + (chunksB << 4) + (tid - 2u) * 16u) = make_uint4(0u, 0u, 0u, 0u);
-        if (UNDER && prev_rows) {
-            // the rest of store(j-1): its table loads went out in front of the cut and are waited for here, still in front of this
-            // block's DMA (never behind it, and never with a counted wait: the DMA instructions of a wave vary with its branches)
-            STAGE_STAMP(0);
-            store_finish(prev_row0, prev_rows, pk, t0, t1, t2, t3);
-            STAGE_STAMP(1);
-        }
         {
             const uint8_t *__restrict__ const gA = valA + baseA - misA, *__restrict__ const gB = valB + baseB - misB;
 #pragma unroll
@@ -785,31 +679,15 @@ lane_stage_body(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ v
                 const uint32_t lb8 = bcastB ? litBlen : s_off[1][i + 1u] - s_off[1][i];
                 // mine: both strings <= 32 bytes and inside what was copied to the staging areas (the literal has its own copy)
                 const bool stA = bcastA || misA + a0 + la8 <= stagedA, stB = bcastB || misB + b0 + lb8 <= stagedB;
-                bool mine = have && la8 <= 32u && lb8 <= 32u && stA && stB;
-                if (LONG && STRSIM_STAGE_LONG_TEXT_MAX < 32 && !bcastA && !bcastB) mine = mine && (la8 < lb8 ? la8 : lb8) <= (uint32_t)STRSIM_STAGE_LONG_TEXT_MAX;
+                const bool mine = have && la8 <= 32u && lb8 <= 32u && stA && stB;
                 const uint32_t wa = bcastA ? LIT : misA + a0, wb = bcastB ? LIT + 32u : COLB + misB + b0;
                 const bool swap = !bcastA && !bcastB && la8 > lb8; // the columns walk the shorter string (every measure is symmetric: strsim_lane_core.h)
-#if STRSIM_STRIP_ON
-                // (lab, Levenshtein, two columns) the strings behind their common prefix and in front of their common suffix
-                uint32_t sp = 0u, ss = 0u;
-                if (LEV && !bcastA && !bcastB && have) {
-                    const uint32_t ps = g_strip_ptr[row0 + i];
-                    sp = ps & 0xFFu; ss = ps >> 8;
-                }
-                const uint32_t lt = (swap ? lb8 : la8) - sp - ss, lp = (swap ? la8 : lb8) - sp - ss;
-                const uint32_t key = mine ? (((lt ? lt : 1u) - 1u) >> STAGE_BSH) : (uint32_t)(NBK - 1);
-                skey[q] = key;
-                srank[q] = atomicAdd(&s_cnt[key], 1u);
-                sd0[q] = mine ? (swap ? ((wb + sp) | ((wa + sp) << 16)) : ((wa + sp) | ((wb + sp) << 16))) : 0u;
-                sd1[q] = mine ? (lt | (lp << 8) | (i << 16) | ((sp + ss) << 25)) : STAGE_DEAD;
-#else
                 const uint32_t lt = swap ? lb8 : la8, lp = swap ? la8 : lb8;
                 const uint32_t key = mine ? (((lt ? lt : 1u) - 1u) >> STAGE_BSH) : (uint32_t)(NBK - 1);
                 skey[q] = key;
                 srank[q] = atomicAdd(&s_cnt[key], 1u);
                 sd0[q] = mine ? (swap ? (wb | (wa << 16)) : (wa | (wb << 16))) : 0u;
                 sd1[q] = mine ? (lt | (lp << 8) | (i << 16)) : STAGE_DEAD;
-#endif
             }
         }
         STAGE_STAMP(2);
@@ -844,12 +722,6 @@ lane_stage_body(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ v
         if (tid < 32u) s_cnt[tid] = 0u; // read by sortB above, next used by sortA behind barrier G
         // ---- E: offsets DMA(j+1), in flight during the rounds
         uint64_t next_row0 = row0 + rows;
-        // (literal sides carry their constant base: harmless)
-        if constexpr (CARRY) {
-            carryA = endA;
-            carryB = endB;
-            carried = next_row0 < row_end; // the next block continues this range: its base offsets are this block's end offsets
-        }
         if (next_row0 >= row_end) { // this range is done: move to the next one and ask for the one after it
             const uint64_t lo = uniform(s_sched[0]), hi = lo + uniform(s_sched[1]); // (uniform: row counters live in SGPRs)
             next_row0 = lo * 64u < n ? lo * 64u : n;

@@ -1,14 +1,14 @@
-"""k_lane_stage<levenshtein>: the block cut (base offsets carried from block to block inside a range, end offsets taken from the
-lanes of the fit test), the store phase split around it and the instantiation without literal code, bit for bit against the oracle.
+"""k_lane_stage<levenshtein>: the block cut, the store phase behind it and the instantiation without literal code, bit for bit
+against the oracle.
 
 A workgroup takes ranges of at least two blocks of up to 512 rows; a block is cut to the 64-row chunks whose bytes fit the staging
-area of 10 240 bytes per column.  The first block of a range reads its base offsets from LDS, every later one takes the previous
-block's end offsets, so the frames put full blocks, cut blocks, cuts of changing length, a forced one-chunk block and one-row and
+area of 10 240 bytes per column.  A block's base offsets are the previous block's end offsets while the range lasts, so the frames
+put full blocks, cut blocks, cuts of changing length, a forced one-chunk block and one-row and
 one-chunk last blocks behind one another.  Frames are a few thousand rows through strsim_pairs_device on a fresh one-launch context.
 
-The carried offsets and the split store phase are compile-time knobs of strsim_lane_stage.h (STRSIM_STAGE_CUT_CARRY,
-STRSIM_STAGE_CUT_UNDER_STORE) that ship switched off (LAB_NOTES 3.1c); the column-only instantiation (STRSIM_STAGE_COLS_ONLY) ships
-on.  The frames hold for any setting of the three: the results do not depend on them.
+The column-only instantiation is a compile-time knob of strsim_lane_stage.h (STRSIM_STAGE_COLS_ONLY) that ships on; the results do
+not depend on it.  (The frames were built when the cut could also carry its offsets from block to block and the store phase could
+be split around it: LAB_NOTES 3.1c, 3.1d.)
 """
 import functools
 import random
