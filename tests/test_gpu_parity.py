@@ -5,6 +5,7 @@ reference's IEEE operation order with contraction off).  north_star allows 1 ulp
 we hold it to 0.
 """
 import struct
+import zlib
 
 import numpy as np
 import pytest
@@ -75,7 +76,7 @@ def test_readme_table(S):
 @pytest.mark.parametrize("alphabet,lo,hi", [("ab", 0, 32), (gen.ASCII_LOWER, 0, 32), (gen.ASCII_LOWER, 1, 12),
                                              ("".join(chr(c) for c in range(1, 128)), 0, 32)])
 def test_lane_path_random(S, ctx, measure, alphabet, lo, hi):
-    A, B = gen.pairs(hash((measure, alphabet, hi)) & 0xFFFF, 20000, alphabet, lo, hi, max_bytes=32)
+    A, B = gen.pairs(zlib.crc32(repr((measure, alphabet, hi)).encode()) & 0xFFFF, 20000, alphabet, lo, hi, max_bytes=32)
     got = gpu(S, ctx, measure, A, B)
     assert_bit_exact(got, O.batch_strings(measure, A, B, 8), A, B, measure)
     assert ctx.last_wave_rows <= 64  # only rows whose 32-byte window crosses the end of the buffer
@@ -85,7 +86,7 @@ def test_lane_path_random(S, ctx, measure, alphabet, lo, hi):
 @pytest.mark.parametrize("alphabet", ["абвгдежзийклмнопрстуфхцчшщыэюя ", "abcdeéèüñöçß-'", "日本語中文字漢한국어テキスト", "αβγ abc жзи 語"])
 def test_short_non_ascii_lane_path(S, ctx, measure, alphabet):
     """<= 32 scalar values per string in any BMP script: decoded per lane (k_lane_utf8), not one wave per pair."""
-    A, B = gen.pairs(hash((measure, alphabet)) & 0xFFFF, 12000, alphabet, 0, 30)
+    A, B = gen.pairs(zlib.crc32(repr((measure, alphabet)).encode()) & 0xFFFF, 12000, alphabet, 0, 30)
     got = gpu(S, ctx, measure, A, B)
     assert_bit_exact(got, O.batch_strings(measure, A, B, 8), A, B, measure)
     leftovers = sum(1 for a, b in zip(A, B) if not a or not b or len(a) > 32 or len(b) > 32
@@ -131,7 +132,7 @@ def test_wave_path_unicode_and_long(S, ctx, measure):
                                             (20, 128, "".join(chr(c) for c in range(1, 128)))])
 def test_wide_lane_path_random(S, ctx, measure, lo, hi, alphabet):
     """33..128-byte ASCII strings: the W = 2 / W = 4 lane kernel (k_lane_wide)."""
-    A, B = gen.pairs(hash((measure, lo, hi)) & 0xFFFF, 6000, alphabet, lo, hi, max_bytes=128)
+    A, B = gen.pairs(zlib.crc32(repr((measure, lo, hi)).encode()) & 0xFFFF, 6000, alphabet, lo, hi, max_bytes=128)
     got = gpu(S, ctx, measure, A, B)
     assert_bit_exact(got, O.batch_strings(measure, A, B, 8), A, B, measure)
     assert ctx.last_wave_rows <= 64 + sum(1 for a, b in zip(A, B) if not a or not b)
@@ -299,9 +300,9 @@ def test_literal_broadcast(S, ctx, measure):
 
 @pytest.mark.parametrize("measure", O.MEASURES)
 def test_literal_against_every_row_class(S, ctx, measure):
-    """The column-x-literal kernel (k_lane_lit<M>; for Jaro / Jaro-Winkler only a literal a goes there, a literal b runs in
-    k_lane_stage) on a frame that mixes everything: short ASCII, empty strings, non-ASCII, 33..900-byte rows (blocks get cut to
-    the staging area), more rows than one range; literal on either side; empty, long and non-ASCII literals."""
+    """The column-x-literal kernel (k_lane_lit<M>: the launcher sends a one-row side there for every measure, on either side;
+    the kernel trace of profiles/stage_routes_kernels.txt shows it) on a frame that mixes everything: short ASCII, empty strings,
+    non-ASCII, 33..900-byte rows (blocks get cut to the staging area), more rows than one range; literal on either side; empty, long and non-ASCII literals."""
     A, _ = gen.pairs(61, 150_000, gen.ASCII_LOWER, 0, 32)
     A2, _ = gen.pairs(62, 3000, gen.MIXED, 0, 120)
     A3, _ = gen.pairs(63, 300, gen.ASCII_LOWER, 200, 900)

@@ -8,6 +8,7 @@ import os
 import random
 import struct
 import subprocess
+import zlib
 
 import pytest
 
@@ -110,7 +111,7 @@ def _rand_pairs(rng, n, alphabet, maxlen=32):
 @pytest.mark.parametrize("measure", O.MEASURES)
 @pytest.mark.parametrize("alphabet", [b"ab", b"abcdefghijklmnopqrstuvwxyz", bytes(range(1, 128))])
 def test_lane_core_random_bit_exact(harness, measure, alphabet):
-    rng = random.Random(hash((measure, len(alphabet))) & 0xFFFF)
+    rng = random.Random(zlib.crc32(repr((measure, len(alphabet))).encode()) & 0xFFFF)
     for n, (a, b) in enumerate(_rand_pairs(rng, 3000, alphabet)):
         exp = O.pair(measure, a, b)
         # planes chosen like the kernel does, with window filler from the same alphabet ...

@@ -6,22 +6,22 @@ area of 10 240 bytes per column.  A block's base offsets are the previous block'
 put full blocks, cut blocks, cuts of changing length, a forced one-chunk block and one-row and
 one-chunk last blocks behind one another.  Frames are a few thousand rows through strsim_pairs_device on a fresh one-launch context.
 
+These are the Levenshtein cases the frames were first built for: k_lane_stage<levenshtein, 0, 0, 1>, its literal-keeping sibling
+and k_lane_lit<levenshtein>.  The frames themselves live in tests/stage_frames.py, built once and shared;
+tests/test_stage_routes_gpu.py runs them, and the frames whose block fits its staging area exactly or misses it by a byte, over
+every first kernel of a pairwise call (tests/stage_routes.py: 17 kernels, four staging sizes, three geometries).
+
 The column-only instantiation is a compile-time knob of strsim_lane_stage.h (STRSIM_STAGE_COLS_ONLY) that ships on; the results do
 not depend on it.  (The frames were built when the cut could also carry its offsets from block to block and the store phase could
 be split around it: LAB_NOTES 3.1c, 3.1d.)
 """
-import functools
-import random
-
 import numpy as np
 import pytest
 
-import gen
 import oracle_lib as O
+import stage_frames as F
 
 pytestmark = pytest.mark.gpu
-
-ROWS = 4096
 
 
 @pytest.fixture(scope="module")
@@ -30,29 +30,10 @@ def S():
     return strsim_amd
 
 
-def _partner(rng, a, lo, hi):
-    r = rng.random()
-    b = gen.edit(rng, a, gen.ASCII_LOWER, rng.randint(1, 3)) if r < 0.5 else (a if r < 0.55 else gen.rand_string(rng, gen.ASCII_LOWER, lo, hi))
-    b = b[:hi]
-    while len(b) < lo:
-        b += rng.choice(gen.ASCII_LOWER)
-    return b
-
-
-def _frame(seed, n, lo, hi):
-    rng = random.Random(seed)
-    A = [gen.rand_string(rng, gen.ASCII_LOWER, lo, hi) for _ in range(n)]
-    B = [_partner(rng, a, lo, hi) for a in A]
-    return A, B
-
-
-@functools.lru_cache(maxsize=None)
 def _uniform():
     """frame (a): U{0..32} on both sides, 4 096 rows, with its expected results (shared, never changed)"""
-    A, B = _frame(31, ROWS, 0, 32)
-    exp = O.batch_strings("levenshtein", A, B, 8)
-    exp.setflags(write=False)
-    return tuple(A), tuple(B), exp
+    f = F.frame("a")
+    return f.A, f.B, F.expected("a", "levenshtein")
 
 
 def _column(S, strings, dev, shift=0):
@@ -97,44 +78,34 @@ def test_full_blocks(S):
 def test_every_block_cut(S):
     """(b) every string 28..32 bytes: 512 rows overflow the staging area, every block is cut to about five chunks; the carried base is
     the cut block's end, not the end of the rows whose offsets were loaded."""
-    A, B = _frame(32, ROWS, 28, 32)
-    _run(S, A, B)
+    f = F.frame("b")
+    _run(S, f.A, f.B, F.expected("b", "levenshtein"))
 
 
 def test_cuts_of_changing_length(S):
     """(c) runs of 200 rows of 30..32-byte strings and of 0..4-byte strings: cuts of different lengths follow one another inside a
-    range, and in half of the runs column a is long where column b is short, so either column decides the cut."""
-    rng = random.Random(33)
-    A, B = [], []
-    for i in range(4160):
-        run = (i // 200) % 4
-        la, lb = ((30, 32), (30, 32)) if run == 0 else ((0, 4), (0, 4)) if run == 1 else ((30, 32), (0, 4)) if run == 2 else ((0, 4), (30, 32))
-        A.append(gen.rand_string(rng, gen.ASCII_LOWER, *la))
-        B.append(gen.rand_string(rng, gen.ASCII_LOWER, *lb) if run >= 2 or rng.random() < 0.5 else _partner(rng, A[-1], *lb))
-    _run(S, A, B)
+    range, and in half of the runs column a is long where column b is short.  (At 10 240 bytes column b decides every cut of this
+    frame, at 8 960 either column does: tests/test_stage_frames_cpu.py.  The edge frames put either column at every cut.)"""
+    f = F.frame("c")
+    _run(S, f.A, f.B, F.expected("c", "levenshtein"))
 
 
 @pytest.mark.parametrize("n", [70, 1024 + 1, 1088])
 def test_small_frames(S, n):
     """(d) one block that is not full; a one-row last block at the start of a range; a last block of a single chunk."""
-    A, B = _frame(34 + n, n, 0, 32)
-    _run(S, A, B)
+    f = F.frame("d%d" % n)
+    _run(S, f.A, f.B, F.expected(f.name, "levenshtein"))
 
 
 def test_one_chunk_overflows_alone(S):
     """(e) 64 rows of 200-byte strings inside frame (a), one chunk behind the start of a block: that block is cut behind its first
     chunk, the next one is the chunk that overflows alone (at least one chunk is taken), the one behind it starts from the forced
     block's end.  The 64 rows are longer than 32 bytes: the later kernels finish them."""
-    A, B, _ = _uniform()
-    A, B = list(A), list(B)
-    rng = random.Random(35)
-    for i in range(2048 + 64, 2048 + 128):
-        A[i] = gen.rand_string(rng, gen.ASCII_LOWER, 200, 200)
-        B[i] = gen.edit(rng, A[i], gen.ASCII_LOWER, 3)[:200]
-    _run(S, A, B, late=64)
+    f = F.frame("e")
+    _run(S, f.A, f.B, F.expected("e", "levenshtein"), late=64)
 
 
-LITERALS = ["", "abcdefghijklmnopqrstuvwxyzabcdef", "kitten"]
+LITERALS = F.LITERALS
 
 
 @pytest.mark.parametrize("stage_kernel", [True, False])
@@ -149,10 +120,11 @@ def test_literal_on_either_side(S, monkeypatch, side, stage_kernel):
         monkeypatch.delenv("STRSIM_NO_LITERAL_PATH", raising=False)
     A, B, _ = _uniform()
     for lit in LITERALS:
+        exp = F.expected("a", "levenshtein", side, lit)
         if side == "a":
-            _run(S, [lit], B, one_op=stage_kernel)
+            _run(S, [lit], B, exp, one_op=stage_kernel)
         else:
-            _run(S, A, [lit], one_op=stage_kernel)
+            _run(S, A, [lit], exp, one_op=stage_kernel)
 
 
 @pytest.mark.parametrize("shift", [1, 7, 15])
