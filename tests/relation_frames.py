@@ -91,6 +91,23 @@ def token_search_frame(nq=128, nc=300):
     return T.token_search_frame(8, nq, nc)
 
 
+def frame_of(m):
+    import relation_checks as RC
+    return token_frame() if m in RC.TOKEN else pair_frame()
+
+
+def mixed_frame(m):
+    """Rows of every tier in one frame: lane class, 2- and 4-byte relabelled, padded to 65 and 129 bytes, and a few beyond WAVE_CAP."""
+    A, B = frame_of(m)
+    X, Y = A[:1500], B[:1500]
+    X += [T.relabel(s, 0x400) for s in A[1500:2000]] + [T.relabel(s, 0x1F600) for s in A[2000:2500]]
+    Y += [T.relabel(s, 0x400) for s in B[1500:2000]] + [T.relabel(s, 0x1F600) for s in B[2000:2500]]
+    for longest, n in ((65, 300), (129, 300), (1025, 40)):
+        P, Q = padded_frame(longest, n)
+        X, Y = X + P, Y + Q
+    return X, Y
+
+
 SEARCH_PREFIX = "x" * 33  # one byte past the 32-byte lane class of the searches
 # cutoffs that drop some candidates of a query and keep others (test_relations_cpu.py asserts that on the models)
 NEAREST_CUTOFF = 3

@@ -102,8 +102,7 @@ def check_tiers(be):
     return seen
 
 
-def frame_of(m):
-    return F.token_frame() if m in RC.TOKEN else F.pair_frame()
+frame_of = F.frame_of
 
 
 # ---- relabel ----
@@ -239,16 +238,7 @@ def test_token_sort_ratio_is_indel_of_the_sorted_strings(be):
 KINDS = [("sim", m) for m in RC.SIMILARITIES] + [("dist", m) for m in RC.DISTANCES]
 
 
-def mixed_frame(m):
-    """Rows of every tier in one frame: lane class, 2- and 4-byte relabelled, padded to 65 and 129 bytes, and a few beyond WAVE_CAP."""
-    A, B = frame_of(m)
-    X, Y = A[:1500], B[:1500]
-    X += [T.relabel(s, 0x400) for s in A[1500:2000]] + [T.relabel(s, 0x1F600) for s in A[2000:2500]]
-    Y += [T.relabel(s, 0x400) for s in B[1500:2000]] + [T.relabel(s, 0x1F600) for s in B[2000:2500]]
-    for longest, n in ((65, 300), (129, 300), (1025, 40)):
-        P, Q = F.padded_frame(longest, n)
-        X, Y = X + P, Y + Q
-    return X, Y
+mixed_frame = F.mixed_frame
 
 
 def cutoff_of(kind, m):
