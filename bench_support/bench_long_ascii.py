@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Levenshtein on long ASCII strings (cfg5 lengths): a-z (five-plane batches) vs mixed case (seven planes)."""
+"""k_wave_pairs on long ASCII strings (cfg5 lengths): a-z (Levenshtein: five-plane batches) vs mixed case (seven planes).
+    bench_long_ascii.py [rows [measure ...]]   (default: 1 000 000 rows, levenshtein)"""
 import os
 import sys
 import time
@@ -14,6 +15,7 @@ import strsim_amd as S
 from bench_support import workload as W
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
+measures = sys.argv[2:] or ["levenshtein"]
 oa, va, ob, vb = W.host_columns(5, W.UNIFORM, 1, 1024, 0, n)
 
 
@@ -33,11 +35,12 @@ cells = float((np.diff(oa.astype(np.int64)) * np.diff(ob.astype(np.int64))).sum(
 # the same upper-casing pattern on both sides keeps edited copies close
 for label, (xa, xb) in (("a-z", (va, vb)), ("mixed case", (mixed(va, 1), mixed(vb, 2)))):
     args = (t(oa, np.int32), t(np.concatenate([xa, pad]), np.uint8), t(ob, np.int32), t(np.concatenate([xb, pad]), np.uint8))
-    out = ctx.pairs_device("levenshtein", *args)
-    ctx.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(3):
-        ctx.pairs_device("levenshtein", *args, out=out)
-    ctx.synchronize()
-    dt = (time.perf_counter() - t0) / 3
-    print(f"{label:10s}: {dt*1e3:8.3f} ms  {n/dt/1e6:7.2f} M pairs/s  {cells/dt/1e12:6.2f} TCUPS  (wave-kernel rows: {ctx.last_wave_rows})")
+    for m in measures:
+        out = ctx.pairs_device(m, *args)
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(3):
+            ctx.pairs_device(m, *args, out=out)
+        ctx.synchronize()
+        dt = (time.perf_counter() - t0) / 3
+        print(f"{label:10s} {m:13s}: {dt*1e3:8.3f} ms  {n/dt/1e6:7.2f} M pairs/s  {cells/dt/1e12:6.2f} TCUPS  (wave-kernel rows: {ctx.last_wave_rows})")

@@ -17,10 +17,6 @@ constexpr int WAVE_CAP = 1024; // wave-per-pair kernels: max bytes (hence scalar
 #define STRSIM_LEV_JOBS 16
 #endif
 constexpr int LEV_JOBS = STRSIM_LEV_JOBS;
-#ifndef STRSIM_LEV_BYTES_ROWS
-#define STRSIM_LEV_BYTES_ROWS 64 // pattern rows per lane of an ASCII batch of k_wave_pairs<levenshtein>: 64 (two mask words) or 32
-#endif
-constexpr int LEV_BYTES_ROWS = STRSIM_LEV_BYTES_ROWS;
 #ifndef STRSIM_LEV_POOL
 #define STRSIM_LEV_POOL 384 // rows ranked together before they are dealt into batches, at most (a multiple of 64; 16 bits of LDS per row)
 #endif

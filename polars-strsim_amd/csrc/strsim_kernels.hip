@@ -16,7 +16,8 @@
 //                     windows fetched by the wave together through its LDS rows, where the text stays.
 //   k_lane_utf8<M>    ONE PAIR PER LANE, short non-ASCII strings (<= 32 scalar values, BMP): per-lane UTF-8 decode
 //                     into 16-bit symbols in LDS, then the same cores on symbols (strsim_lane_sym.h).
-//   k_wave_pairs<M>   the rest, up to WAVE_CAP bytes, any UTF-8, taken chunk by chunk from a work list k_lane_utf8 builds.
+//   k_wave_pairs<M>   the rest, up to WAVE_CAP bytes, any UTF-8, taken chunk by chunk from a work list k_lane_utf8 builds
+//                     (strsim_kernel_wave.h; what only Levenshtein uses: strsim_wave_lev.h).
 //                     Levenshtein: up to 16 pairs per wave in runs of lanes, block-parallel Myers (one 64-row block per
 //                     lane, DPP hand-off), match masks from a per-lane LDS table, texts in a global arena; on bytes
 //                     (ASCII) or on 16-bit scalar values (the reference works on `char`s, strsim.rs:133,189,297).
@@ -186,25 +187,30 @@ static void launch_lane_t(const LaunchArgs &a)
 }
 
 template <int M>
-static void launch_slow_t(const LaunchArgs &a)
+static void launch_slow_kernels(const LaunchArgs &a, double *out)
 {
     const uint64_t nchunks = (a.n + 63u) >> 6;
+    uint32_t sps, sps8;
+    unsigned g3, g8;
+    wide_geometry(a, WIDE_SPAN, sps, g3);
+    wide_geometry(a, U8_SPAN, sps8, g8);
     // waves per CU: Levenshtein by its 8 KB table; Jaro by its 12.4 KB of LDS (12); Jaccard / Dice 16 (a.wave_grid)
     const uint64_t wg = M == LEVENSHTEIN ? (uint64_t)a.wave_grid_lev
                         : (M == JARO || M == JARO_WINKLER) ? (uint64_t)a.wave_grid * 3u / 4u : (uint64_t)a.wave_grid;
     const uint64_t g2 = nchunks < wg ? nchunks : wg;
-    {
-        uint32_t sps, sps8;
-        unsigned g3, g8;
-        wide_geometry(a, WIDE_SPAN, sps, g3);
-        wide_geometry(a, U8_SPAN, sps8, g8);
-        hipLaunchKernelGGL((k_lane_wide<M>), dim3(g3), dim3(WIDE_BLOCK), 0, a.stream, a.offA, a.valA, a.rowsA,
-                           a.offB, a.valB, a.rowsB, a.out, a.n, a.slowmask, sps);
-        hipLaunchKernelGGL((k_lane_utf8<M>), dim3(g8), dim3(WIDE_BLOCK), 0, a.stream, a.offA, a.valA, a.rowsA,
-                           a.offB, a.valB, a.rowsB, a.out, a.n, a.slowmask, sps8, a.worklist, a.status);
-    }
+    hipLaunchKernelGGL((k_lane_wide<M>), dim3(g3), dim3(WIDE_BLOCK), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB,
+                       a.valB, a.rowsB, out, a.n, a.slowmask, sps);
+    hipLaunchKernelGGL((k_lane_utf8<M>), dim3(g8), dim3(WIDE_BLOCK), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB,
+                       a.valB, a.rowsB, out, a.n, a.slowmask, sps8, a.worklist, a.status);
     hipLaunchKernelGGL((k_wave_pairs<M>), dim3((unsigned)g2), dim3(64), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB,
-                       a.valB, a.rowsB, a.out, a.n, a.slowmask, a.worklist, a.status, a.lev_ws);
+                       a.valB, a.rowsB, out, a.n, a.slowmask, a.worklist, a.status, a.lev_ws);
+}
+
+// one measure: the slow-row kernels into the call's output column
+template <int M>
+static void launch_slow_t(const LaunchArgs &a)
+{
+    launch_slow_kernels<M>(a, a.out);
     if (a.ev_wave1) (void)hipEventRecord(a.ev_wave1, a.stream);
 }
 
@@ -234,26 +240,6 @@ hipError_t launch_huge(int measure, const LaunchArgs &a, uint32_t *ws, uint32_t 
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
-}
-
-template <int M>
-static void launch_slow_kernels(const LaunchArgs &a, double *out)
-{
-    const uint64_t nchunks = (a.n + 63u) >> 6;
-    uint32_t sps, sps8;
-    unsigned g3, g8;
-    wide_geometry(a, WIDE_SPAN, sps, g3);
-    wide_geometry(a, U8_SPAN, sps8, g8);
-    // waves per CU: Levenshtein by its 8 KB table; Jaro by its 12.4 KB of LDS (12); Jaccard / Dice 16 (a.wave_grid)
-    const uint64_t wg = M == LEVENSHTEIN ? (uint64_t)a.wave_grid_lev
-                        : (M == JARO || M == JARO_WINKLER) ? (uint64_t)a.wave_grid * 3u / 4u : (uint64_t)a.wave_grid;
-    const uint64_t g2 = nchunks < wg ? nchunks : wg;
-    hipLaunchKernelGGL((k_lane_wide<M>), dim3(g3), dim3(WIDE_BLOCK), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB,
-                       a.valB, a.rowsB, out, a.n, a.slowmask, sps);
-    hipLaunchKernelGGL((k_lane_utf8<M>), dim3(g8), dim3(WIDE_BLOCK), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB,
-                       a.valB, a.rowsB, out, a.n, a.slowmask, sps8, a.worklist, a.status);
-    hipLaunchKernelGGL((k_wave_pairs<M>), dim3((unsigned)g2), dim3(64), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB,
-                       a.valB, a.rowsB, out, a.n, a.slowmask, a.worklist, a.status, a.lev_ws);
 }
 
 // All five measures of one frame: one fused lane kernel (five outputs), then the slow-row kernels per measure,
