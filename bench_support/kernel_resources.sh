@@ -19,6 +19,8 @@
 #                    scan kernels they reuse
 #         qgram   -- the kernels of q-gram similarity (strsim_qgram.h), and below them the Indel / edit-distance kernels whose headers
 #                    it includes (their figures must not move when strsim_qgram.h changes)
+#         qgram_join -- the twelve k_qgram_join_lane kernels of strsim_qgram_join_device and k_qgram_join_first, k_qgram_lane and
+#                    k_match_join_lane beside them (the same gram masks per pair; the same skeleton) and the join kernels around the sweep
 ROOT=$(cd "$(dirname "$0")/.." && pwd); OUT=${TMPDIR:-/tmp}/strsim_co; mkdir -p $OUT
 case "$1" in
     qgram) FILTER='k_qgram_|k_indel_|k_dist_' ;;
@@ -29,6 +31,7 @@ case "$1" in
     cdist) FILTER='k_cdist_|k_match_pack|k_match_lane' ;;
     join) FILTER='k_join_|k_extract_|k_nearest_hist|k_nearest_scan|k_nearest_scatter|k_match_pack' ;;
     match_join) FILTER='k_match_join_|k_match_lane|k_join_|k_nearest_hist|k_nearest_scan|k_nearest_scatter|k_match_pack' ;;
+    qgram_join) FILTER='k_qgram_join_|k_qgram_lane|k_match_join_|k_join_|k_nearest_hist|k_nearest_scan|k_nearest_scatter|k_match_pack' ;;
     cluster) FILTER='k_components_|k_join_scan_' ;;
     nearest) FILTER='k_nearest_|k_match_pack|k_match_clear|k_match_fold|k_match_merge' ;;
     *) FILTER=${1:-.} ;;

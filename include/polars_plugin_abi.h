@@ -226,6 +226,21 @@ POLARS_PLUGIN_DECLARE(qgram_sorensen_dice)
 POLARS_PLUGIN_DECLARE(qgram_overlap)
 POLARS_PLUGIN_DECLARE(qgram_cosine)
 
+/* qgram_join: match_join by q-gram similarity (strsim_qgram_join_host): every candidate whose q-gram score of the kind is at least
+ * min_score.  Inputs 0 and 1 are the queries and the candidates as for join_ratio; input 2 is q and input 3 the set flag, as for
+ * qgram_jaccard (both required here); an optional input 4 is min_score (parsed as join's score_cutoff).  The null rules and the
+ * LargeList<Struct{index: UInt32, score: Float64}> result are join_ratio's.
+ * qgram_cluster: cluster by q-gram similarity (strsim_qgram_cluster_host).  Input 0 is the column, input 1 q, input 2 the set flag,
+ * input 3 the Float64 literal min_score (required); the UInt32 result and the null rule are cluster_ratio's. */
+POLARS_PLUGIN_DECLARE(qgram_join_jaccard)
+POLARS_PLUGIN_DECLARE(qgram_join_sorensen_dice)
+POLARS_PLUGIN_DECLARE(qgram_join_overlap)
+POLARS_PLUGIN_DECLARE(qgram_join_cosine)
+POLARS_PLUGIN_DECLARE(qgram_cluster_jaccard)
+POLARS_PLUGIN_DECLARE(qgram_cluster_sorensen_dice)
+POLARS_PLUGIN_DECLARE(qgram_cluster_overlap)
+POLARS_PLUGIN_DECLARE(qgram_cluster_cosine)
+
 /* ---- diagnostics of this implementation (not part of the polars-ffi contract; the engine never calls them) ----
  * The plugin's staging -- pinned host memory and its device mirrors, per pipeline set -- is leased per call from one process-wide
  * pool under POLARS_STRSIM_STAGING_BUDGET_MB (csrc/plugin_pack.h: StagingPool; reference counterpart: the per-call scratch of

@@ -692,6 +692,56 @@ STRSIM_API int strsim_cluster_device(strsim_ctx_t *ctx, int measure, const uint3
 STRSIM_API int strsim_cluster_host(strsim_ctx_t *ctx, int measure, const uint32_t *offsets, const uint8_t *values, uint64_t rows,
                                    double min_score, uint32_t *out_root, uint32_t *out_cluster, uint64_t *out_count, uint64_t *out_nnz);
 
+/*
+ * Threshold join by q-gram similarity: every pair (query i, candidate j) whose q-gram score is >= min_score, as CSR -- "which rows
+ * of this column look like which rows of that one, at trigram similarity 0.8 or better" (found by dlsym, like strsim_join_*: the
+ * ABI version stays 1.7, there is no new measure id and strsim_measure_supported does not describe these entry points).  `kind`,
+ * `q` and `qflags` are the kind, q and flags of strsim_qgram_device (STRSIM_QGRAM_JACCARD .. _COSINE, 1 .. 3, STRSIM_QGRAM_SET);
+ * score(i, j) is bit for bit what strsim_qgram_device(kind, q, qflags, queries[i], candidates[j]) returns, and a hit is the f64
+ * comparison score >= min_score.
+ *
+ * Everything else is the contract of strsim_match_join_device, word for word: STRSIM_JOIN_UPPER in `flags` keeps only j > i; the
+ * result is CSR with every row in ascending candidate index; *out_nnz (host memory) and all of out_indptr are always written, and
+ * exact; out_index and out_score (capacity elements each) are written iff nnz <= capacity, otherwise not one element of either is
+ * touched and the call still returns STRSIM_OK; capacity == 0 with NULL out_index / out_score is the count-only form.  min_score =
+ * -INFINITY or 0.0 reports every pair, a value above 1.0 nothing (no sweep is launched, one clear of out_indptr is enqueued); NaN
+ * is STRSIM_ERR_ARG.  kind, q and qflags are checked first, in strsim_qgram_device's words, then the arguments of
+ * strsim_match_join_device in its order, the context last: no argument error needs a device.
+ *
+ * Device-resident: strings of at most 32 ASCII bytes are swept one query per lane in length order.  In multiset mode only the
+ * candidate lengths are visited at which the kind's own best score for the two gram counts reaches min_score (Jaccard,
+ * Sorensen-Dice, cosine; the overlap coefficient reaches 1.0 at every pair of lengths and is never pruned).  In set mode the counts
+ * are those of distinct grams, which lengths do not bound: every length with a gram is visited.  Every pair with a longer or
+ * non-ASCII side goes through strsim_qgram_device's kernels with that string as the literal; those internal calls leave
+ * strsim_ctx_last_wave_rows as the caller's last pairwise call set it.
+ */
+STRSIM_API int strsim_qgram_join_device(strsim_ctx_t *ctx, int kind, uint32_t q, uint32_t qflags,
+                                        const uint32_t *q_offsets, const uint8_t *q_values, uint64_t q_rows,
+                                        const uint32_t *c_offsets, const uint8_t *c_values, uint64_t c_rows,
+                                        double min_score, uint32_t flags, uint64_t capacity,
+                                        uint64_t *out_indptr, uint32_t *out_index, double *out_score, uint64_t *out_nnz);
+
+/* The same with HOST-RESIDENT buffers (the column layout of strsim_pairs_host, every output included); synchronous. */
+STRSIM_API int strsim_qgram_join_host(strsim_ctx_t *ctx, int kind, uint32_t q, uint32_t qflags,
+                                      const uint32_t *q_offsets, const uint8_t *q_values, uint64_t q_rows,
+                                      const uint32_t *c_offsets, const uint8_t *c_values, uint64_t c_rows,
+                                      double min_score, uint32_t flags, uint64_t capacity,
+                                      uint64_t *out_indptr, uint32_t *out_index, double *out_score, uint64_t *out_nnz);
+
+/*
+ * The duplicate groups of one column by q-gram similarity: strsim_cluster_device with the STRSIM_JOIN_UPPER self-join made by
+ * strsim_qgram_join_device(kind, q, qflags).  Outputs, the range of min_score, the limits and the waits are strsim_cluster_device's;
+ * kind, q and qflags are checked first, then its remaining arguments in its order, the context last.
+ */
+STRSIM_API int strsim_qgram_cluster_device(strsim_ctx_t *ctx, int kind, uint32_t q, uint32_t qflags,
+                                           const uint32_t *offsets, const uint8_t *values, uint64_t rows, double min_score,
+                                           uint32_t *out_root, uint32_t *out_cluster, uint64_t *out_count, uint64_t *out_nnz);
+
+/* The same with HOST-RESIDENT buffers; synchronous. */
+STRSIM_API int strsim_qgram_cluster_host(strsim_ctx_t *ctx, int kind, uint32_t q, uint32_t qflags,
+                                         const uint32_t *offsets, const uint8_t *values, uint64_t rows, double min_score,
+                                         uint32_t *out_root, uint32_t *out_cluster, uint64_t *out_count, uint64_t *out_nnz);
+
 /* Row partition used to shard a column over `n` GPUs/ranks: the reference's split_offsets
  * (strsim.rs:21-39).  Writes n (offset,len) pairs into out_offset_len[2*n]. */
 STRSIM_API void strsim_split_offsets(uint64_t len, uint64_t n, uint64_t *out_offset_len);

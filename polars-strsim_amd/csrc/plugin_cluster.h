@@ -37,13 +37,15 @@ struct ClusterOwned {
     ~ClusterOwned() { free(root); free(valid); }
 };
 
-void run_cluster(int measure, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret)
+// cluster_host(ctx, offsets, values, rows, min_score, out_root, &count): the family's host entry point with its measure bound.
+// The column is input 0, min_score the Float64 literal `min_score_input`.
+template <class ClusterHost>
+void run_cluster_call(ClusterHost cluster_host, SeriesExport *inputs, const SeriesExport &min_score_input, SeriesExport *ret)
 {
-    if (n_inputs != 2) fail(CLUSTER_NO_LITERAL + std::to_string(n_inputs));
     Column col;
     describe(inputs[0], col);
     if (col.rows > 0xFFFFFFFEull) fail("cluster: more than 2^32 - 2 rows");
-    const double min_score = cluster_min_score(inputs[1]);
+    const double min_score = cluster_min_score(min_score_input);
     const uint64_t n = col.rows;
     std::vector<uint32_t> off, pos;
     std::vector<uint8_t> val;
@@ -58,8 +60,7 @@ void run_cluster(int measure, SeriesExport *inputs, size_t n_inputs, SeriesExpor
         // staging, the join's workspace (as run_join), its CSR at the first capacity, parent, the flags' scan and the labels
         PipeLease lease(4 * (val.size() + 4 * off.size()) + 16 * m + 2 * 84 * m + 4 * 65 * m + 16 * 8 * m + 12 * (4 * m + 1024) + 24 * m);
         uint64_t count = 0;
-        if (strsim_cluster_host(leased_context(lease), measure, off.data(), val.data(), m, min_score, root, nullptr, &count, nullptr) != STRSIM_OK)
-            fail(strsim_last_error_message());
+        if (cluster_host(leased_context(lease), off.data(), val.data(), m, min_score, root, &count) != STRSIM_OK) fail(strsim_last_error_message());
     }
     // packed row x -> row pos[x] of the column, back to front: pos[x] >= x, so no root is overwritten before it is read
     int64_t nulls = 0;
@@ -72,4 +73,14 @@ void run_cluster(int measure, SeriesExport *inputs, size_t n_inputs, SeriesExpor
     }
     export_primitive("I", col.name.c_str(), n, own.root, valid, nulls, false, ret);
     own.root = own.valid = nullptr;
+}
+
+void run_cluster(int measure, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret)
+{
+    if (n_inputs != 2) fail(CLUSTER_NO_LITERAL + std::to_string(n_inputs));
+    run_cluster_call(
+        [=](strsim_ctx_t *ctx, const uint32_t *off, const uint8_t *val, uint64_t rows, double min_score, uint32_t *root, uint64_t *count) {
+            return strsim_cluster_host(ctx, measure, off, val, rows, min_score, root, nullptr, count, nullptr);
+        },
+        inputs, inputs[1], ret);
 }

@@ -9,7 +9,8 @@
 // a hit gives an empty one.  The call is strsim_join_host: once to count (capacity 0), once more with exactly nnz slots.
 //
 // The match_join_<measure> functions (the five reference measures; input 2 is min_score) are the same flow over
-// strsim_match_join_host: run_join takes the host entry point to call.
+// strsim_match_join_host: run_join takes the host entry point to call.  The qgram_join_<kind> functions (plugin_qgram_join.h) are
+// the same flow again over strsim_qgram_join_host: run_join_call takes the call itself, with whatever the family binds to it.
 #pragma once
 
 // the nullable LargeList<Struct{index, score}> named `name` (its child: "item")
@@ -115,7 +116,10 @@ void export_list_struct(JoinOwned &own, uint64_t n, uint64_t nnz, int64_t list_n
 typedef int (*JoinHostFn)(strsim_ctx_t *, int, const uint32_t *, const uint8_t *, uint64_t, const uint32_t *, const uint8_t *, uint64_t, double, uint32_t,
                           uint64_t, uint64_t *, uint32_t *, double *, uint64_t *);
 
-void run_join(JoinHostFn join_host, int scorer, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret)
+// join_host(ctx, q_off, q_val, q_rows, c_off, c_val, c_rows, cutoff, capacity, indptr, index, score, &nnz): the family's host entry
+// point with its scorer bound and no flags
+template <class JoinHost>
+void run_join_call(JoinHost join_host, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret)
 {
     if (n_inputs != 2 && n_inputs != 3)
         fail("join: expected 2 input series (queries, candidates) and an optional score_cutoff, got " + std::to_string(n_inputs));
@@ -132,11 +136,11 @@ void run_join(JoinHostFn join_host, int scorer, SeriesExport *inputs, size_t n_i
         // counts, the fallback's columns; the outputs once nnz is known
         PipeLease lease(2 * p.staged_bytes() + 16 * n + 84 * (n + m) + 4 * 65 * n + 16 * 8 * std::max(n, m));
         strsim_ctx_t *const ctx = leased_context(lease);
-        if (join_host(ctx, scorer, p.ao.data(), p.av.data(), n, p.bo.data(), p.bv.data(), m, cutoff, 0u, 0, indptr.data(), nullptr, nullptr, &nnz) !=
-            STRSIM_OK)
+        if (join_host(ctx, p.ao.data(), p.av.data(), n, p.bo.data(), p.bv.data(), m, cutoff, (uint64_t)0, indptr.data(), (uint32_t *)nullptr,
+                      (double *)nullptr, &nnz) != STRSIM_OK)
             fail(strsim_last_error_message());
         own.room(nnz);
-        if (nnz && join_host(ctx, scorer, p.ao.data(), p.av.data(), n, p.bo.data(), p.bv.data(), m, cutoff, 0u, nnz, indptr.data(),
+        if (nnz && join_host(ctx, p.ao.data(), p.av.data(), n, p.bo.data(), p.bv.data(), m, cutoff, nnz, indptr.data(),
                              static_cast<uint32_t *>(own.index), static_cast<double *>(own.score), &nnz) != STRSIM_OK)
             fail(strsim_last_error_message());
     } else {
@@ -164,4 +168,14 @@ void run_join(JoinHostFn join_host, int scorer, SeriesExport *inputs, size_t n_i
         off[r + 1] = (int64_t)at;
     }
     export_list_struct(own, n, at, list_nulls, in.q.name.c_str(), ret);
+}
+
+void run_join(JoinHostFn join_host, int scorer, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret)
+{
+    run_join_call(
+        [=](strsim_ctx_t *ctx, const uint32_t *qo, const uint8_t *qv, uint64_t n, const uint32_t *co, const uint8_t *cv, uint64_t m, double cutoff,
+            uint64_t capacity, uint64_t *indptr, uint32_t *index, double *score, uint64_t *nnz) {
+            return join_host(ctx, scorer, qo, qv, n, co, cv, m, cutoff, 0u, capacity, indptr, index, score, nnz);
+        },
+        inputs, n_inputs, ret);
 }

@@ -31,6 +31,7 @@
 #include "strsim_cdist.h"
 #include "strsim_join.h"
 #include "strsim_match_join.h"
+#include "strsim_qgram_join.h"
 #include "strsim_components.h"
 
 namespace strsim {
@@ -185,6 +186,8 @@ struct strsim_ctx {
     // buffers of its own, for the same reason; it reads extract_tab (the rank table, never rewritten) and scorer 14 normalises into
     // extract_off / extract_val, which no flow inside a join call uses
     DevBuf join_ws, join_scratch;
+    // strsim_qgram_join_device in set mode: one word per candidate in length order (its first occurrences, strsim_qgram_join.h)
+    DevBuf qgram_join_first;
     // strsim_components_device: parent[], the root flags and their scan, and the status words {count, indices out of range} with
     // their pinned read-back; strsim_cluster_device: the CSR of its self-join, which never reaches the host -- buffers of their own,
     // for the same reason (the join inside a cluster call uses every buffer above freely)
@@ -1802,8 +1805,8 @@ int strsim_distance_host(strsim_ctx_t *c, int measure, const uint32_t *a_off, co
 
 // ---- q-gram similarity (strsim_qgram.h) ----
 
-static int qgram_check(const char *who, strsim_ctx_t *c, int kind, uint32_t q, uint32_t flags, const Col &a, const Col &b, const double *out,
-                       uint64_t out_rows)
+// kind, q and the mode flags of every q-gram entry point
+static int qgram_kind_check(const char *who, int kind, uint32_t q, uint32_t flags)
 {
     if (kind < STRSIM_QGRAM_JACCARD || kind > STRSIM_QGRAM_COSINE) {
         set_error("%s: unknown kind %d (STRSIM_QGRAM_JACCARD, _SORENSEN_DICE, _OVERLAP or _COSINE: 0..3)", who, kind);
@@ -1814,6 +1817,14 @@ static int qgram_check(const char *who, strsim_ctx_t *c, int kind, uint32_t q, u
         set_error("%s: unknown flag bits 0x%x (STRSIM_QGRAM_SET is the only flag)", who, flags & ~STRSIM_QGRAM_SET);
         return STRSIM_ERR_ARG;
     }
+    return STRSIM_OK;
+}
+
+static int qgram_check(const char *who, strsim_ctx_t *c, int kind, uint32_t q, uint32_t flags, const Col &a, const Col &b, const double *out,
+                       uint64_t out_rows)
+{
+    const int rc = qgram_kind_check(who, kind, q, flags);
+    if (rc) return rc;
     return elementwise_check(who, c, a.rows, b.rows, out_rows, a.off && a.val && b.off && b.val && out);
 }
 
@@ -2509,15 +2520,11 @@ static const JoinWords JOIN_WORDS = {[](int id) { return id == STRSIM_INDEL || i
 static const JoinWords MATCH_JOIN_WORDS = {[](int id) { return id >= STRSIM_LEVENSHTEIN && id <= STRSIM_SORENSEN_DICE; },
                                            "%s: measure %d is not a measure of match_join (the reference measures 0 .. 4)", "min_score"};
 
-static int join_check(const JoinWords &words, const char *who, strsim_ctx_t *c, int scorer, const Col &q, const Col &cnd, double score_cutoff,
-                      uint32_t flags, uint64_t capacity, const uint64_t *out_indptr, const uint32_t *out_index, const double *out_score,
-                      const uint64_t *out_nnz)
+// What every join entry point checks behind its scorer (or kind, q and flags), the context last; `cutoff`: the name of the cutoff.
+static int join_rest_check(const char *cutoff, const char *who, strsim_ctx_t *c, const Col &q, const Col &cnd, double score_cutoff, uint32_t flags,
+                           uint64_t capacity, const uint64_t *out_indptr, const uint32_t *out_index, const double *out_score, const uint64_t *out_nnz)
 {
-    if (!words.accepts(scorer)) {
-        set_error(words.refusal, who, scorer);
-        return STRSIM_ERR_ARG;
-    }
-    if (score_cutoff != score_cutoff) { set_error("%s: %s is NaN", who, words.cutoff); return STRSIM_ERR_ARG; }
+    if (score_cutoff != score_cutoff) { set_error("%s: %s is NaN", who, cutoff); return STRSIM_ERR_ARG; }
     if (flags & ~STRSIM_JOIN_UPPER) { set_error("%s: unknown flags 0x%x (STRSIM_JOIN_UPPER = 1)", who, flags); return STRSIM_ERR_ARG; }
     int rc = search_rows_check(who, q, cnd);
     if (rc) return rc;
@@ -2534,17 +2541,30 @@ static int join_check(const JoinWords &words, const char *who, strsim_ctx_t *c, 
     return STRSIM_OK;
 }
 
+static int join_check(const JoinWords &words, const char *who, strsim_ctx_t *c, int scorer, const Col &q, const Col &cnd, double score_cutoff,
+                      uint32_t flags, uint64_t capacity, const uint64_t *out_indptr, const uint32_t *out_index, const double *out_score,
+                      const uint64_t *out_nnz)
+{
+    if (!words.accepts(scorer)) {
+        set_error(words.refusal, who, scorer);
+        return STRSIM_ERR_ARG;
+    }
+    return join_rest_check(words.cutoff, who, c, q, cnd, score_cutoff, flags, capacity, out_indptr, out_index, out_score, out_nnz);
+}
+
 // The join over two columns, q.rows >= 1, by the scores of one pairwise measure.  What a family of entry points brings: `who` (for
 // the fallback's errors), `nothing` (the cutoff is above every score: no sweep), ready() (the sweep's table on the device; called
-// only when there is a sweep to come), sweep(fill, args) (the launcher of its lane sweep) and slow_measure (of the fallback's
-// strsim_pairs_device calls).  strsim_join_*: Indel ranks (for STRSIM_TOKEN_SORT_RATIO over the normalised columns);
-// strsim_match_join_*: the f64 score of a reference measure.  Waits for the stream: once for the slow counts (search_pack), once
+// only when there is a sweep to come), sweep(fill, args) (the launcher of its lane sweep) and slow_score(lit, other, to) (the
+// fallback's pairwise call: the scores of the literal `lit` against the column `other` into `to`, complete in stream order).
+// strsim_join_*: Indel ranks (for STRSIM_TOKEN_SORT_RATIO over the normalised columns); strsim_match_join_*: the f64 score of a
+// reference measure, both with strsim_pairs_device behind slow_score; strsim_qgram_join_*: the f64 q-gram score, with
+// strsim_qgram_device's flow behind it.  Waits for the stream: once for the slow counts (search_pack), once
 // for nnz; the fallback waits for every batch of its pairwise calls (in the count pass, and again in the fill when their scores
 // were too many to keep).
-template <class Ready, class Sweep>
+template <class Ready, class Sweep, class SlowScore>
 static int join_pairs(strsim_ctx *c, const char *who, const Col &q, const Col &cnd, double cutoff, uint32_t flags, uint64_t capacity,
                       uint64_t *out_indptr, uint32_t *out_index, double *out_score, uint64_t *out_nnz, bool nothing, Ready ready, Sweep sweep,
-                      int slow_measure)
+                      SlowScore slow_score)
 {
     hipStream_t st = c->stream;
     const uint32_t nq = (uint32_t)q.rows, nc = (uint32_t)cnd.rows;
@@ -2587,7 +2607,7 @@ static int join_pairs(strsim_ctx *c, const char *who, const Col &q, const Col &c
                     (uint32_t *)(p.tail + o_map), map_words, map_shift, out_indptr, out_index, out_score, st};
     JoinSlowArgs sa{c->join_scratch.as<double>(), nullptr, 0u, p.qm, nq, nc, cutoff, upper, fb, cur, out_indptr, out_index, out_score, st};
     const uint64_t calls = fallback_calls(nq, nc);
-    // every pair with a slow side: strsim_pairs_device(slow_measure) with that side as the literal, batch by batch (slow_walk), a batch
+    // every pair with a slow side: slow_score with that side as the literal, batch by batch (slow_walk), a batch
     // waited for and then counted into the fallback's list.  The columns of scores are kept for the fill when they fit
     // JOIN_KEEP_SCORES doubles (the slow queries' columns first, then the slow candidates'); otherwise a batch reuses the scratch and
     // the fill walks, scores and waits again.
@@ -2615,7 +2635,7 @@ static int join_pairs(strsim_ctx *c, const char *who, const Col &q, const Col &c
             c, who, p, calls,
             [&](int side, const Col &lit, const Col &other, uint32_t b) {
                 double *const to = keep ? kept_column(side, walked[side] + b) : c->join_scratch.as<double>() + (size_t)b * other.rows;
-                return pairs_device(c, slow_measure, lit, other, to, other.rows);
+                return slow_score(lit, other, to);
             },
             [&](int side, uint32_t b0, uint32_t nb) -> int {
                 const int r = strsim_ctx_synchronize(c);
@@ -2671,14 +2691,16 @@ static int join_pairs(strsim_ctx *c, const char *who, const Col &q, const Col &c
     return STRSIM_OK;
 }
 
-// The host-resident form of a join entry point: the columns staged, `device_call` on them, the results copied back.
+// The host-resident form of a join entry point behind its check (`checked`: what the check returned): the columns staged,
+// device_call(queries, candidates, indptr, index, score) -- the family's *_device entry point on the staged columns with the
+// caller's cutoff, flags, capacity and out_nnz --, the results copied back.
 typedef int (*JoinDeviceFn)(strsim_ctx_t *, int, const uint32_t *, const uint8_t *, uint64_t, const uint32_t *, const uint8_t *, uint64_t, double, uint32_t,
                             uint64_t, uint64_t *, uint32_t *, double *, uint64_t *);
-static int join_host(JoinDeviceFn device_call, const JoinWords &words, const char *who, strsim_ctx_t *c, int scorer, const Col &q, const Col &cnd,
-                     double score_cutoff, uint32_t flags, uint64_t capacity, uint64_t *out_indptr, uint32_t *out_index, double *out_score,
-                     uint64_t *out_nnz)
+template <class DeviceCall>
+static int join_host(int checked, DeviceCall device_call, strsim_ctx_t *c, const Col &q, const Col &cnd, uint64_t capacity, uint64_t *out_indptr,
+                     uint32_t *out_index, double *out_score, uint64_t *out_nnz)
 {
-    int rc = join_check(words, who, c, scorer, q, cnd, score_cutoff, flags, capacity, out_indptr, out_index, out_score, out_nnz);
+    int rc = checked;
     if (rc) return rc;
     *out_nnz = 0;
     out_indptr[0] = 0;
@@ -2692,7 +2714,7 @@ static int join_host(JoinDeviceFn device_call, const JoinWords &words, const cha
     uint64_t *const d_ptr = reinterpret_cast<uint64_t *>(s.out);
     uint32_t *const d_idx = capacity ? reinterpret_cast<uint32_t *>(s.out + ptr_bytes) : nullptr;
     double *const d_score = capacity ? reinterpret_cast<double *>(s.out + ptr_bytes + idx_bytes) : nullptr;
-    rc = device_call(c, scorer, s.a.off, s.a.val, q.rows, s.b.off, s.b.val, cnd.rows, score_cutoff, flags, capacity, d_ptr, d_idx, d_score, out_nnz);
+    rc = device_call(Col{s.a.off, s.a.val, q.rows}, Col{s.b.off, s.b.val, cnd.rows}, d_ptr, d_idx, d_score);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(out_indptr, d_ptr, ((size_t)q.rows + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     if (*out_nnz && *out_nnz <= capacity) {
@@ -2733,15 +2755,21 @@ int strsim_join_device(strsim_ctx_t *c, int scorer, const uint32_t *q_off, const
             return STRSIM_OK;
         },
         [&](bool fill, const JoinLaneArgs &a) { return launch_join_lane(fill, a, c->extract_tab.as<ExtractTable>(), rlimit); },
-        STRSIM_INDEL);
+        [&](const Col &lit, const Col &other, double *to) { return pairs_device(c, STRSIM_INDEL, lit, other, to, other.rows); });
 }
 
 int strsim_join_host(strsim_ctx_t *c, int scorer, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows, const uint32_t *c_off,
                      const uint8_t *c_val, uint64_t c_rows, double score_cutoff, uint32_t flags, uint64_t capacity, uint64_t *out_indptr,
                      uint32_t *out_index, double *out_score, uint64_t *out_nnz)
 {
-    return join_host(strsim_join_device, JOIN_WORDS, "strsim_join_host", c, scorer, Col{q_off, q_val, q_rows}, Col{c_off, c_val, c_rows}, score_cutoff,
-                     flags, capacity, out_indptr, out_index, out_score, out_nnz);
+    const Col q{q_off, q_val, q_rows}, cnd{c_off, c_val, c_rows};
+    return join_host(
+        join_check(JOIN_WORDS, "strsim_join_host", c, scorer, q, cnd, score_cutoff, flags, capacity, out_indptr, out_index, out_score, out_nnz),
+        [&](const Col &dq, const Col &dc, uint64_t *d_ptr, uint32_t *d_idx, double *d_score) {
+            return strsim_join_device(c, scorer, dq.off, dq.val, dq.rows, dc.off, dc.val, dc.rows, score_cutoff, flags, capacity, d_ptr, d_idx, d_score,
+                                      out_nnz);
+        },
+        c, q, cnd, capacity, out_indptr, out_index, out_score, out_nnz);
 }
 
 // ---- threshold join by the five reference measures (strsim_match_join.h, strsim_match_join_kernels.h): join_pairs with another sweep ----
@@ -2766,15 +2794,22 @@ int strsim_match_join_device(strsim_ctx_t *c, int measure, const uint32_t *q_off
     return join_pairs(
         c, "strsim_match_join_device", q, cnd, min_score, flags, capacity, out_indptr, out_index, out_score, out_nnz, !some,
         []() -> int { return STRSIM_OK; }, // (the quotient table is the context's, on the device since the context was made)
-        [&](bool fill, const JoinLaneArgs &a) { return launch_match_join_lane(measure, fill, a, c->qtab, need, min_score); }, measure);
+        [&](bool fill, const JoinLaneArgs &a) { return launch_match_join_lane(measure, fill, a, c->qtab, need, min_score); },
+        [&](const Col &lit, const Col &other, double *to) { return pairs_device(c, measure, lit, other, to, other.rows); });
 }
 
 int strsim_match_join_host(strsim_ctx_t *c, int measure, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows, const uint32_t *c_off,
                            const uint8_t *c_val, uint64_t c_rows, double min_score, uint32_t flags, uint64_t capacity, uint64_t *out_indptr,
                            uint32_t *out_index, double *out_score, uint64_t *out_nnz)
 {
-    return join_host(strsim_match_join_device, MATCH_JOIN_WORDS, "strsim_match_join_host", c, measure, Col{q_off, q_val, q_rows},
-                     Col{c_off, c_val, c_rows}, min_score, flags, capacity, out_indptr, out_index, out_score, out_nnz);
+    const Col q{q_off, q_val, q_rows}, cnd{c_off, c_val, c_rows};
+    return join_host(
+        join_check(MATCH_JOIN_WORDS, "strsim_match_join_host", c, measure, q, cnd, min_score, flags, capacity, out_indptr, out_index, out_score, out_nnz),
+        [&](const Col &dq, const Col &dc, uint64_t *d_ptr, uint32_t *d_idx, double *d_score) {
+            return strsim_match_join_device(c, measure, dq.off, dq.val, dq.rows, dc.off, dc.val, dc.rows, min_score, flags, capacity, d_ptr, d_idx,
+                                            d_score, out_nnz);
+        },
+        c, q, cnd, capacity, out_indptr, out_index, out_score, out_nnz);
 }
 
 } // extern "C"
@@ -2836,14 +2871,18 @@ static JoinDeviceFn cluster_join(int measure)
     return nullptr;
 }
 
-static int cluster_check(const char *who, strsim_ctx_t *c, int measure, const Col &col, double min_score, const uint32_t *out_root,
-                         const uint64_t *out_count)
+// The self-join of strsim_cluster_*: the join flow of `measure` over one column under STRSIM_JOIN_UPPER.
+static auto cluster_self_join(strsim_ctx *c, int measure)
 {
-    if (!cluster_join(measure)) {
-        set_error("%s: measure %d is not a measure of cluster (the reference measures 0 .. 4, STRSIM_INDEL = 8 or STRSIM_TOKEN_SORT_RATIO = 14)",
-                  who, measure);
-        return STRSIM_ERR_ARG;
-    }
+    const JoinDeviceFn join = cluster_join(measure);
+    return [=](const Col &col, double min_score, uint64_t cap, uint64_t *indptr, uint32_t *index, double *score, uint64_t *nnz) {
+        return join(c, measure, col.off, col.val, col.rows, col.off, col.val, col.rows, min_score, STRSIM_JOIN_UPPER, cap, indptr, index, score, nnz);
+    };
+}
+
+// What every cluster entry point checks behind its measure (or kind, q and flags), the context last.
+static int cluster_rest_check(const char *who, strsim_ctx_t *c, const Col &col, double min_score, const uint32_t *out_root, const uint64_t *out_count)
+{
     if (min_score != min_score) { set_error("%s: min_score is NaN", who); return STRSIM_ERR_ARG; }
     if (col.rows > 0xFFFFFFFEull) { set_error("%s: %llu rows (at most 2^32 - 2)", who, (unsigned long long)col.rows); return STRSIM_ERR_ARG; }
     if (col.rows && (!col.off || !col.val)) { set_error("%s: NULL column buffer", who); return STRSIM_ERR_ARG; }
@@ -2853,13 +2892,24 @@ static int cluster_check(const char *who, strsim_ctx_t *c, int measure, const Co
     return STRSIM_OK;
 }
 
+static int cluster_check(const char *who, strsim_ctx_t *c, int measure, const Col &col, double min_score, const uint32_t *out_root,
+                         const uint64_t *out_count)
+{
+    if (!cluster_join(measure)) {
+        set_error("%s: measure %d is not a measure of cluster (the reference measures 0 .. 4, STRSIM_INDEL = 8 or STRSIM_TOKEN_SORT_RATIO = 14)",
+                  who, measure);
+        return STRSIM_ERR_ARG;
+    }
+    return cluster_rest_check(who, c, col, min_score, out_root, out_count);
+}
+
 // The STRSIM_JOIN_UPPER self-join of a device-resident column, rows >= 1, into the context's cluster_pairs under the capacity
 // protocol (4 * rows + 1024 slots, or what the buffer already holds; when the hits do not fit, exactly nnz and one more call), then
-// the components of its CSR.
-static int cluster_labels(strsim_ctx *c, const char *who, int measure, const Col &col, double min_score, uint32_t *out_root,
+// the components of its CSR.  join(col, min_score, capacity, indptr, index, score, &nnz): the self-join of a family of entry points.
+template <class Join>
+static int cluster_labels(strsim_ctx *c, const char *who, Join join, const Col &col, double min_score, uint32_t *out_root,
                           uint32_t *out_cluster, uint64_t *out_count, uint64_t *out_nnz)
 {
-    const JoinDeviceFn join = cluster_join(measure);
     const size_t ptr_bytes = up256(((size_t)col.rows + 1) * sizeof(uint64_t));
     uint64_t cap = 4u * col.rows + 1024u, nnz = 0;
     if (c->cluster_pairs.cap > ptr_bytes + 256) { // the buffer only grows: what an earlier call left is the first capacity when it is more
@@ -2875,8 +2925,7 @@ static int cluster_labels(strsim_ctx *c, const char *who, int measure, const Col
         uint8_t *const b = c->cluster_pairs.as<uint8_t>();
         d_ptr = reinterpret_cast<uint64_t *>(b);
         d_idx = reinterpret_cast<uint32_t *>(b + ptr_bytes);
-        rc = join(c, measure, col.off, col.val, col.rows, col.off, col.val, col.rows, min_score, STRSIM_JOIN_UPPER, cap, d_ptr, d_idx,
-                  reinterpret_cast<double *>(b + ptr_bytes + idx_bytes), &nnz);
+        rc = join(col, min_score, cap, d_ptr, d_idx, reinterpret_cast<double *>(b + ptr_bytes + idx_bytes), &nnz);
         if (rc) return rc;
         if (nnz <= cap) break;
         if (call) {
@@ -2945,7 +2994,7 @@ int strsim_cluster_device(strsim_ctx_t *c, int measure, const uint32_t *offsets,
     if (rows == 0) return STRSIM_OK;
     rc = ctx_set_device(c);
     if (rc) return rc;
-    return cluster_labels(c, "strsim_cluster_device", measure, col, min_score, out_root, out_cluster, out_count, out_nnz);
+    return cluster_labels(c, "strsim_cluster_device", cluster_self_join(c, measure), col, min_score, out_root, out_cluster, out_count, out_nnz);
 }
 
 int strsim_cluster_host(strsim_ctx_t *c, int measure, const uint32_t *offsets, const uint8_t *values, uint64_t rows, double min_score,
@@ -2962,8 +3011,142 @@ int strsim_cluster_host(strsim_ctx_t *c, int measure, const uint32_t *offsets, c
     Staged s;
     rc = ctx_stage(c, col, NO_COL, 2 * up256((size_t)rows * 4), &s);
     if (rc) return rc;
-    rc = cluster_labels(c, "strsim_cluster_host", measure, s.a, min_score, reinterpret_cast<uint32_t *>(s.out),
+    rc = cluster_labels(c, "strsim_cluster_host", cluster_self_join(c, measure), s.a, min_score, reinterpret_cast<uint32_t *>(s.out),
                         out_cluster ? reinterpret_cast<uint32_t *>(s.out + up256((size_t)rows * 4)) : nullptr, out_count, out_nnz);
+    if (rc) return rc;
+    return labels_to_host(c, rows, s.out, out_root, out_cluster);
+}
+
+} // extern "C"
+
+// ---- threshold join and cluster by q-gram similarity (strsim_qgram_join.h, strsim_qgram_join_kernels.h): join_pairs with a third sweep ----
+
+static int qgram_join_check(const char *who, strsim_ctx_t *c, int kind, uint32_t q, uint32_t qflags, const Col &qc, const Col &cnd, double min_score,
+                            uint32_t flags, uint64_t capacity, const uint64_t *out_indptr, const uint32_t *out_index, const double *out_score,
+                            const uint64_t *out_nnz)
+{
+    const int rc = qgram_kind_check(who, kind, q, qflags);
+    if (rc) return rc;
+    return join_rest_check("min_score", who, c, qc, cnd, min_score, flags, capacity, out_indptr, out_index, out_score, out_nnz);
+}
+
+// strsim_qgram_join_device behind its check.  Multiset mode enqueues what strsim_match_join_device enqueues; set mode one kernel
+// more, behind the length order: the candidates' first occurrences.
+static int qgram_join_device_impl(strsim_ctx_t *c, const char *who, int kind, uint32_t q, uint32_t qflags, const Col &qc, const Col &cnd,
+                                  double min_score, uint32_t flags, uint64_t capacity, uint64_t *out_indptr, uint32_t *out_index, double *out_score,
+                                  uint64_t *out_nnz)
+{
+    int rc = ctx_set_device(c);
+    if (rc) return rc;
+    if (qc.rows == 0) {
+        *out_nnz = 0;
+        HIP_TRY(hipMemsetAsync(out_indptr, 0, sizeof(uint64_t), c->stream));
+        return STRSIM_OK;
+    }
+    const bool set = (qflags & STRSIM_QGRAM_SET) != 0u;
+    MatchJoinNeed need; // which candidate lengths a query of each length visits: 33 words, a kernel argument
+    const bool some = qgram_join_need_mask(kind, q, set, min_score, need);
+    return join_pairs(
+        c, who, qc, cnd, min_score, flags, capacity, out_indptr, out_index, out_score, out_nnz, !some,
+        [&]() -> int { return set ? c->qgram_join_first.reserve((size_t)cnd.rows * sizeof(uint32_t)) : STRSIM_OK; },
+        [&](bool fill, const JoinLaneArgs &a) -> hipError_t {
+            uint32_t *const first = set ? c->qgram_join_first.as<uint32_t>() : nullptr;
+            if (set && !fill) { // (the fill reads what the count's launch left)
+                const hipError_t e = launch_qgram_join_first(q, a, (uint32_t)cnd.rows, first);
+                if (e != hipSuccess) return e;
+                c->enqueued_ops += 1u;
+            }
+            return launch_qgram_join_lane(kind, q, set, fill, a, first, need, min_score);
+        },
+        [&](const Col &lit, const Col &other, double *to) {
+            // (strsim_ctx_last_wave_rows describes the caller's last pairwise q-gram or distance call: a fallback batch leaves it alone)
+            const uint64_t wave_rows = c->last_wave_rows;
+            const int r = qgram_device_impl(c, kind, q, qflags, lit, other, to, other.rows);
+            c->last_wave_rows = wave_rows;
+            return r;
+        });
+}
+
+extern "C" {
+
+int strsim_qgram_join_device(strsim_ctx_t *c, int kind, uint32_t q, uint32_t qflags, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows,
+                             const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, double min_score, uint32_t flags, uint64_t capacity,
+                             uint64_t *out_indptr, uint32_t *out_index, double *out_score, uint64_t *out_nnz)
+{
+    const Col qc{q_off, q_val, q_rows}, cnd{c_off, c_val, c_rows};
+    const int rc = qgram_join_check("strsim_qgram_join_device", c, kind, q, qflags, qc, cnd, min_score, flags, capacity, out_indptr, out_index,
+                                    out_score, out_nnz);
+    if (rc) return rc;
+    return qgram_join_device_impl(c, "strsim_qgram_join_device", kind, q, qflags, qc, cnd, min_score, flags, capacity, out_indptr, out_index,
+                                  out_score, out_nnz);
+}
+
+int strsim_qgram_join_host(strsim_ctx_t *c, int kind, uint32_t q, uint32_t qflags, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows,
+                           const uint32_t *c_off, const uint8_t *c_val, uint64_t c_rows, double min_score, uint32_t flags, uint64_t capacity,
+                           uint64_t *out_indptr, uint32_t *out_index, double *out_score, uint64_t *out_nnz)
+{
+    const Col qc{q_off, q_val, q_rows}, cnd{c_off, c_val, c_rows};
+    return join_host(
+        qgram_join_check("strsim_qgram_join_host", c, kind, q, qflags, qc, cnd, min_score, flags, capacity, out_indptr, out_index, out_score, out_nnz),
+        [&](const Col &dq, const Col &dc, uint64_t *d_ptr, uint32_t *d_idx, double *d_score) {
+            return qgram_join_device_impl(c, "strsim_qgram_join_host", kind, q, qflags, dq, dc, min_score, flags, capacity, d_ptr, d_idx, d_score,
+                                          out_nnz);
+        },
+        c, qc, cnd, capacity, out_indptr, out_index, out_score, out_nnz);
+}
+
+} // extern "C"
+
+static int qgram_cluster_check(const char *who, strsim_ctx_t *c, int kind, uint32_t q, uint32_t qflags, const Col &col, double min_score,
+                               const uint32_t *out_root, const uint64_t *out_count)
+{
+    const int rc = qgram_kind_check(who, kind, q, qflags);
+    if (rc) return rc;
+    return cluster_rest_check(who, c, col, min_score, out_root, out_count);
+}
+
+// The self-join of strsim_qgram_cluster_*: the q-gram join of one column under STRSIM_JOIN_UPPER, kind, q and the mode bound.
+static auto qgram_cluster_self_join(strsim_ctx *c, const char *who, int kind, uint32_t q, uint32_t qflags)
+{
+    return [=](const Col &col, double min_score, uint64_t cap, uint64_t *indptr, uint32_t *index, double *score, uint64_t *nnz) {
+        return qgram_join_device_impl(c, who, kind, q, qflags, col, col, min_score, STRSIM_JOIN_UPPER, cap, indptr, index, score, nnz);
+    };
+}
+
+extern "C" {
+
+int strsim_qgram_cluster_device(strsim_ctx_t *c, int kind, uint32_t q, uint32_t qflags, const uint32_t *offsets, const uint8_t *values, uint64_t rows,
+                                double min_score, uint32_t *out_root, uint32_t *out_cluster, uint64_t *out_count, uint64_t *out_nnz)
+{
+    const Col col{offsets, values, rows};
+    int rc = qgram_cluster_check("strsim_qgram_cluster_device", c, kind, q, qflags, col, min_score, out_root, out_count);
+    if (rc) return rc;
+    *out_count = 0;
+    if (out_nnz) *out_nnz = 0;
+    if (rows == 0) return STRSIM_OK;
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    return cluster_labels(c, "strsim_qgram_cluster_device", qgram_cluster_self_join(c, "strsim_qgram_cluster_device", kind, q, qflags), col, min_score,
+                          out_root, out_cluster, out_count, out_nnz);
+}
+
+int strsim_qgram_cluster_host(strsim_ctx_t *c, int kind, uint32_t q, uint32_t qflags, const uint32_t *offsets, const uint8_t *values, uint64_t rows,
+                              double min_score, uint32_t *out_root, uint32_t *out_cluster, uint64_t *out_count, uint64_t *out_nnz)
+{
+    const Col col{offsets, values, rows};
+    int rc = qgram_cluster_check("strsim_qgram_cluster_host", c, kind, q, qflags, col, min_score, out_root, out_count);
+    if (rc) return rc;
+    *out_count = 0;
+    if (out_nnz) *out_nnz = 0;
+    if (rows == 0) return STRSIM_OK;
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    Staged s;
+    rc = ctx_stage(c, col, NO_COL, 2 * up256((size_t)rows * 4), &s);
+    if (rc) return rc;
+    rc = cluster_labels(c, "strsim_qgram_cluster_host", qgram_cluster_self_join(c, "strsim_qgram_cluster_host", kind, q, qflags), s.a, min_score,
+                        reinterpret_cast<uint32_t *>(s.out), out_cluster ? reinterpret_cast<uint32_t *>(s.out + up256((size_t)rows * 4)) : nullptr,
+                        out_count, out_nnz);
     if (rc) return rc;
     return labels_to_host(c, rows, s.out, out_root, out_cluster);
 }

@@ -75,8 +75,8 @@ __device__ __forceinline__ void join_lane_start(const JoinSweep &s, JoinLane &L)
 }
 
 // One slice: the candidates of length lc that this split takes.  `need` is the lane's own (of (lq, lc) alone: out of the candidate
-// loop); the caller has seen that some lane of the wave needs the length.  R.core<NP>(wt, lc, P, w0, lq) is the kernel's scoring call
-// on this lane's planes and the candidate text wt, R.value(c) what the pair yields, R.hit(v, upper, i, j) whether it is reported,
+// loop); the caller has seen that some lane of the wave needs the length.  R.core<NP>(wt, lc, P, w0, lq, x) is the kernel's scoring call
+// on this lane's planes and the candidate text wt (x: its position in the length order, uniform), R.value(c) what the pair yields, R.hit(v, upper, i, j) whether it is reported,
 // R.score(v) the f64 that is stored.
 template <bool FILL, class Rule>
 __device__ __forceinline__ void join_lane_slice(const JoinSweep &s, JoinLane &L, uint32_t lc, bool need, const Rule &R)
@@ -100,9 +100,9 @@ __device__ __forceinline__ void join_lane_slice(const JoinSweep &s, JoinLane &L,
         uint32_t wt[8];
 #pragma unroll
         for (int w = 0; w < 8; ++w) wt[w] = s.sw[(size_t)x * 8u + w];
-        decltype(R.template core<5>(wt, lc, L.q.P5, L.q.w0, L.lq)) c;
-        if (match_five_planes(L.q.wcls | ((cm >> 8) & 15u))) c = R.template core<5>(wt, lc, L.q.P5, L.q.w0, L.lq);
-        else c = R.template core<7>(wt, lc, L.q.P, L.q.w0, L.lq);
+        decltype(R.template core<5>(wt, lc, L.q.P5, L.q.w0, L.lq, x)) c;
+        if (match_five_planes(L.q.wcls | ((cm >> 8) & 15u))) c = R.template core<5>(wt, lc, L.q.P5, L.q.w0, L.lq, x);
+        else c = R.template core<7>(wt, lc, L.q.P, L.q.w0, L.lq, x);
         const auto v = R.value(c);
         const bool hit = need && R.hit(v, s.upper, L.i, j);
         if (FILL) {
@@ -124,7 +124,7 @@ __device__ __forceinline__ void join_lane_end(const JoinSweep &s, const JoinLane
 // JoinRankRule with the rank join's scoring call: the Indel distance of the pair.
 struct JoinRankSweep : JoinRankRule {
     template <int NP>
-    __device__ __forceinline__ uint32_t core(const uint32_t (&wt)[8], uint32_t lc, const uint32_t (&P)[NP], uint32_t, uint32_t lq) const
+    __device__ __forceinline__ uint32_t core(const uint32_t (&wt)[8], uint32_t lc, const uint32_t (&P)[NP], uint32_t, uint32_t lq, uint32_t) const
     {
         return extract_indel_uniform_text<NP>(wt, lc, P, lq);
     }

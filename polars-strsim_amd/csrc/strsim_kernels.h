@@ -281,6 +281,13 @@ hipError_t launch_join_sort_rows(const uint64_t *indptr, uint32_t nq, uint32_t n
 struct MatchJoinNeed;
 hipError_t launch_match_join_lane(int measure, bool fill, const JoinLaneArgs &a, const double *qtab, const MatchJoinNeed &need, double min_score);
 
+// Threshold join by q-gram similarity (strsim_qgram_join_kernels.h; the rule is in strsim_qgram_join.h): the sweep that stands where
+// launch_join_lane stands.  kind: STRSIM_QGRAM_*, q: 1..3, set: the set mode.  Set mode reads `first`, one word per candidate in
+// length order (nc words), which launch_qgram_join_first fills behind launch_nearest_order; multiset mode takes nullptr.
+hipError_t launch_qgram_join_first(uint32_t q, const JoinLaneArgs &a, uint32_t nc, uint32_t *first);
+hipError_t launch_qgram_join_lane(int kind, uint32_t q, bool set, bool fill, const JoinLaneArgs &a, const uint32_t *first, const MatchJoinNeed &need,
+                                  double min_score);
+
 // Connected components of a CSR graph (strsim_components_kernels.h; the rules are in strsim_components.h).
 // launch_components_identity: the labels of a graph without edges, one launch.  launch_components: init, link, compress, the join's
 // three scan kernels over the root flags and the rank -- seven launches whatever the graph holds.  parent: rows words; scan: rows

@@ -50,6 +50,8 @@
 //                     through a rank table in LDS (ExtractRules, strsim_extract.h; strsim_extract_kernels.h).
 //   k_cdist_lane<M>   the full score matrix (strsim_cdist.h, strsim_cdist_kernels.h): k_match_lane's sweep with every score kept,
 //                     staged per wave in a tile of LDS and written out row-wise; k_cdist_put_col / k_cdist_cutoff close its fallback.
+//   k_qgram_join_lane<Q, SET, FILL>  the threshold join by q-gram similarity (strsim_qgram_join.h, strsim_qgram_join_kernels.h): the
+//                     join's lane sweep with the q-gram gram masks as its scoring call, the candidate as the wave-uniform text.
 //   k_huge_pairs<M>   strings beyond WAVE_CAP, scratch in global memory, launched from strsim_ctx_synchronize() only
 //                     when such rows were counted; Levenshtein: the block step in stripes of 64 blocks, any length.
 //
@@ -82,6 +84,7 @@
 #include "strsim_cdist.h"
 #include "strsim_join.h"
 #include "strsim_match_join.h"
+#include "strsim_qgram_join.h"
 #include "strsim_components.h"
 
 namespace strsim {
@@ -100,6 +103,7 @@ struct OutPtrs {
 #include "strsim_cdist_kernels.h"
 #include "strsim_join_kernels.h"
 #include "strsim_match_join_kernels.h"
+#include "strsim_qgram_join_kernels.h"
 #include "strsim_components_kernels.h"
 
 #include "strsim_kernel_wide.h"
@@ -767,6 +771,31 @@ hipError_t launch_qgram_wave(const LaunchArgs &a, int kind, uint32_t q, bool set
         else
             hipLaunchKernelGGL((k_qgram_wave<QGRAM_WAVE_LDS_GRAMS, decltype(Q)::value, decltype(SET)::value>), dim3((unsigned)grid), dim3(64), 0,
                                a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB, a.rowsB, kind, a.out, worklist, a.status, scratch, slot_words, slots);
+    });
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// threshold join by q-gram similarity (strsim_qgram_join_kernels.h)
+// ------------------------------------------------------------------------------------------------
+hipError_t launch_qgram_join_first(uint32_t q, const JoinLaneArgs &a, uint32_t nc, uint32_t *first)
+{
+    with_qgram(q, true, [&](auto Q, auto) {
+        hipLaunchKernelGGL(k_qgram_join_first<decltype(Q)::value>, dim3(match_grid(nc)), dim3(MATCH_BLOCK), 0, a.stream, a.swords, a.smeta, a.cstart,
+                           nc, first);
+    });
+    return hipGetLastError();
+}
+
+hipError_t launch_qgram_join_lane(int kind, uint32_t q, bool set, bool fill, const JoinLaneArgs &a, const uint32_t *first, const MatchJoinNeed &need,
+                                  double min_score)
+{
+    with_qgram(q, set, [&](auto Q, auto SET) {
+        with_fill(fill, [&](auto FILL) {
+            hipLaunchKernelGGL((k_qgram_join_lane<decltype(Q)::value, decltype(SET)::value, decltype(FILL)::value>), dim3(match_grid(a.nq), a.splits),
+                               dim3(MATCH_BLOCK), 0, a.stream, a.qwords, a.qmeta, a.qperm, a.qstart, a.nq, a.swords, a.smeta, a.sidx, a.cstart, kind,
+                               first, need, min_score, a.upper, a.cnt, a.map, a.map_words, a.map_shift, a.indptr, a.out_index, a.out_score);
+        });
     });
     return hipGetLastError();
 }

@@ -17,7 +17,7 @@ template <int MEASURE>
 struct MatchJoinSweep : MatchJoinRule {
     const double *s_q;
     template <int NP>
-    __device__ __forceinline__ double core(const uint32_t (&wt)[8], uint32_t lc, const uint32_t (&P)[NP], uint32_t w0, uint32_t lq) const
+    __device__ __forceinline__ double core(const uint32_t (&wt)[8], uint32_t lc, const uint32_t (&P)[NP], uint32_t w0, uint32_t lq, uint32_t) const
     {
         return match_score<MEASURE, NP>(s_q, wt, lc, P, w0, lq);
     }

@@ -73,6 +73,30 @@ STRSIM_HD T qgram_eq(const uint32_t (&Plo)[7], const uint32_t (&Phi)[7], uint32_
     }
 }
 
+// The step of every walk, in two halves.  With E the positions of the pattern that hold the text's byte j: gram(E) is the set of
+// pattern grams equal to the text gram that byte j completes (the one that starts at j - Q + 1), and push(E) then takes E into the
+// two masks behind it.  Before the text's first gram is complete the masks behind are empty, and so is gram(E).
+template <typename T, int Q>
+struct QgramGrams {
+    T acc1 = 0, acc2 = 0;
+    STRSIM_HD T gram(T E) const { return Q == 1 ? E : (Q == 2 ? (T)(acc1 & (E >> 1)) : (T)(acc2 & (E >> 2))); }
+    STRSIM_HD void push(T E)
+    {
+        if constexpr (Q == 3) acc2 = acc1 & (E >> 1);
+        if constexpr (Q >= 2) acc1 = E;
+    }
+};
+
+// The greedy of the multiset intersection: the text gram whose equal pattern grams are M takes the lowest of them that is still
+// free (M is already cut to the pattern's grams) -> 1 when it found one.
+template <typename T>
+STRSIM_HD uint32_t qgram_take(T M, T &used)
+{
+    const T m = M & ~used;
+    used |= m & ((T)0 - m);
+    return m != 0 ? 1u : 0u;
+}
+
 enum QgramWalk : int {
     QGRAM_GREEDY = 0, // -> the number of text grams that found a free equal gram among the pattern's first gp
     QGRAM_HIT = 1,    // -> bit i: text gram i equals one of the pattern's first gp grams
@@ -89,7 +113,8 @@ STRSIM_HD uint64_t qgram_walk(const uint32_t (&wt)[16], uint32_t lt, uint32_t tm
 {
     const uint32_t vm[2] = {low_ones(lt), low_ones(lt > 32u ? lt - 32u : 0u)};
     const T rows = qgram_low<T>(gp);
-    T acc1 = 0, acc2 = 0, used = 0;
+    QgramGrams<T, Q> grams;
+    T used = 0;
     uint64_t res = 0ull;
     unrolled_until<0, (int)(8 * sizeof(T))>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
@@ -97,18 +122,15 @@ STRSIM_HD uint64_t qgram_walk(const uint32_t (&wt)[16], uint32_t lt, uint32_t tm
         const T E = qgram_eq<T>(Plo, Phi, bit_fill(vm[j >> 5], j & 31), wt[j >> 2], j & 3);
         if constexpr (j >= Q - 1) {
             constexpr int i = j - (Q - 1);
-            T M = Q == 1 ? E : (Q == 2 ? (T)(acc1 & (E >> 1)) : (T)(acc2 & (E >> 2)));
+            T M = grams.gram(E);
             if constexpr (MODE == QGRAM_GREEDY) {
-                const T m = M & rows & ~used;
-                used |= m & ((T)0 - m);
-                res += m != 0 ? 1u : 0u;
+                res += qgram_take<T>(M & rows, used);
             } else {
                 M &= MODE == QGRAM_HIT ? rows : qgram_low<T>((uint32_t)i);
                 res |= M != 0 ? (1ull << i) : 0ull;
             }
         }
-        if constexpr (Q == 3) acc2 = acc1 & (E >> 1);
-        if constexpr (Q >= 2) acc1 = E;
+        grams.push(E);
         return true;
     });
     return res;

@@ -423,15 +423,21 @@ __all__ += ["qgram_jaccard", "qgram_sorensen_dice", "qgram_overlap", "qgram_cosi
 _QGRAM_KINDS = ("jaccard", "sorensen_dice", "overlap", "cosine")
 
 
-def _qgram(kind: str, expr: IntoExpr, other: IntoExpr, q: int, multiset: bool) -> pl.Expr:
+def _qgram_mode(kind: str, q: int, multiset: bool) -> list:
+    """q and the set flag as the plugin takes them, two UInt32 literals; ValueError for an unknown kind or a q outside 1 .. 3"""
     if kind not in _QGRAM_KINDS:
         raise ValueError(f"unknown q-gram kind {kind!r}; expected one of {_QGRAM_KINDS}")
     if isinstance(q, bool) or not isinstance(q, int) or not 1 <= q <= 3:
         raise ValueError(f"q={q!r} is outside 1 .. 3")
+    return [pl.lit(q, dtype=pl.UInt32), pl.lit(0 if multiset else 1, dtype=pl.UInt32)]
+
+
+def _qgram(kind: str, expr: IntoExpr, other: IntoExpr, q: int, multiset: bool) -> pl.Expr:
+    mode = _qgram_mode(kind, q, multiset)
     return register_plugin_function(
         plugin_path=_PLUGIN_DIR,
         function_name="qgram_" + kind,
-        args=[parse_into_expr(expr), other, pl.lit(q, dtype=pl.UInt32), pl.lit(0 if multiset else 1, dtype=pl.UInt32)],
+        args=[parse_into_expr(expr), other] + mode,
         is_elementwise=True,
     )
 
@@ -462,3 +468,40 @@ def qgram_cosine(expr: IntoExpr, other: IntoExpr, q: int = 2, multiset: bool = T
     """Cosine (Ochiai) coefficient over q-grams: I / sqrt(na nb); q, multiset and the edge cases as in `qgram_jaccard`.  Not in the
     upstream polars-strsim."""
     return _qgram("cosine", expr, other, q, multiset)
+
+
+# (a statement of its own again)
+__all__ += ["qgram_join", "qgram_cluster"]
+
+
+def qgram_join(expr: IntoExpr, candidates: IntoExpr, kind: str = "sorensen_dice", q: int = 2, multiset: bool = True,
+               min_score: float | None = None) -> pl.Expr:
+    """Every row of `candidates` (any length) whose q-gram similarity to the row of `expr` is at least min_score -- `kind` is
+    "jaccard", "sorensen_dice", "overlap" or "cosine", q and multiset as in `qgram_jaccard`: a List(Struct{index: UInt32, score:
+    Float64}) per row, in ascending candidate index, nothing truncated; None reports every candidate.  A null row gives a null list,
+    a row without a hit an empty one; null candidates are never matched.  The score is the pairwise qgram_<kind> function's, bit for
+    bit.  Not in the upstream polars-strsim."""
+    args = [parse_into_expr(expr, dtype=pl.Utf8), parse_into_expr(candidates, dtype=pl.Utf8)] + _qgram_mode(kind, q, multiset)
+    if min_score is not None:
+        args.append(pl.lit(min_score, dtype=pl.Float64))
+    return register_plugin_function(
+        plugin_path=_PLUGIN_DIR,
+        function_name="qgram_join_" + kind,
+        args=args,
+        is_elementwise=False,
+    )
+
+
+def qgram_cluster(expr: IntoExpr, kind: str = "sorensen_dice", q: int = 2, multiset: bool = True, min_score: float | None = None) -> pl.Expr:
+    """The duplicate groups of a column by q-gram similarity: `cluster` with the rows linked whose qgram_<kind> score (q and
+    multiset as in `qgram_jaccard`) is at least min_score.  Every row gets the row number of the first member of its group, as
+    UInt32; groups chain, a null row gives null, min_score is required.  Not in the upstream polars-strsim."""
+    mode = _qgram_mode(kind, q, multiset)
+    if min_score is None:
+        raise ValueError("qgram_cluster: min_score is required (None would put every row in one group)")
+    return register_plugin_function(
+        plugin_path=_PLUGIN_DIR,
+        function_name="qgram_cluster_" + kind,
+        args=[parse_into_expr(expr, dtype=pl.Utf8)] + mode + [pl.lit(min_score, dtype=pl.Float64)],
+        is_elementwise=False,
+    )

@@ -441,6 +441,26 @@ def match_dedupe_pairs(measure, column, min_score, ctx=None, processor=None):
     return np.repeat(np.arange(len(column), dtype=np.int64), np.diff(indptr)), index, score
 
 
+def qgram_join(kind, queries, candidates, min_score, q=2, multiset=True, upper=False, ctx=None, processor=None):
+    """Threshold join by q-gram similarity: every pair (query i, candidate j) whose qgram(kind, q, multiset) score is >= min_score,
+    as CSR: (indptr int64 [N + 1], index int64 [nnz], score f64 [nnz]) -- "which rows look like which, at bigram Dice 0.8 or
+    better" (pg_trgm's similarity join, strsim's sorensen_dice over a whole column).  kind is one of QGRAM_KINDS, q is 1, 2 or 3,
+    multiset=False compares the sets of grams.  The hits of query i are index / score[indptr[i]:indptr[i + 1]], in ascending
+    candidate position; the score is bit for bit qgram()'s.  min_score=None reports every pair.  upper, the nulls and
+    processor="default_process" are join()'s."""
+    qgram_args(kind, q, multiset)
+    call = lambda c: lambda _, qo, qv, co, cv, cut, up: c.qgram_join(kind, qo, qv, co, cv, cut, up, q=q, multiset=multiset)
+    return _join_lists(call, kind, queries, candidates, min_score, upper, ctx, processor)
+
+
+def qgram_dedupe_pairs(kind, column, min_score, q=2, multiset=True, ctx=None, processor=None):
+    """The near-duplicates of one column by q-gram similarity: the self-join qgram_join(kind, column, column, min_score, q,
+    multiset, upper=True) as COO -- (i int64 [nnz], j int64 [nnz], score f64 [nnz]) with i < j, ordered by i, then j."""
+    column = list(column)
+    indptr, index, score = qgram_join(kind, column, column, min_score, q, multiset, upper=True, ctx=ctx, processor=processor)
+    return np.repeat(np.arange(len(column), dtype=np.int64), np.diff(indptr)), index, score
+
+
 CLUSTER_MEASURES = MEASURES + ("ratio", "token_sort_ratio")
 _CLUSTER_MEASURE = {**{m: m for m in MEASURES}, "ratio": "indel", "indel": "indel", "token_sort_ratio": "token_sort_ratio"}
 
@@ -463,6 +483,11 @@ def cluster(measure, column, min_score, ctx=None, processor=None):
     min_score=None is refused (it would put every row in one cluster).  processor="default_process" as in join()."""
     if not isinstance(measure, str) or measure not in _CLUSTER_MEASURE:
         raise ValueError(f"no cluster by measure {measure!r} (one of {CLUSTER_MEASURES})")
+    return _cluster_column(lambda c, o, v: c.cluster(_CLUSTER_MEASURE[measure], o, v, min_score), column, min_score, ctx, processor)
+
+
+def _cluster_column(call, column, min_score, ctx, processor):
+    """cluster() and qgram_cluster() over a Python list: call(ctx, offsets, values) is the context's method with its measure bound"""
     if min_score is None:
         raise ValueError("cluster: min_score=None would put every row in one cluster; pass a score in [0, 1]")
     if processor is not None:
@@ -477,10 +502,18 @@ def cluster(measure, column, min_score, ctx=None, processor=None):
     o, v = pack_strings([column[j] for j in pos])
     if processor is not None:
         o, v = ctx.default_process_host(o, v)
-    r, c, count = ctx.cluster(_CLUSTER_MEASURE[measure], o, v, min_score)
+    r, c, count = call(ctx, o, v)
     root[pos] = pos[np.asarray(r).astype(np.int64)]
     label[pos] = np.asarray(c).astype(np.int64)
     return root, label, count
+
+
+def qgram_cluster(kind, column, min_score, q=2, multiset=True, ctx=None, processor=None):
+    """The duplicate groups of one column by q-gram similarity: cluster() with the rows linked that score >= min_score by
+    qgram(kind, q, multiset) -> (root int64 [n], cluster int64 [n], count).  Components chain, a null row is -1 and not counted,
+    min_score=None is refused, processor="default_process" as in join()."""
+    qgram_args(kind, q, multiset)
+    return _cluster_column(lambda c, o, v: c.qgram_cluster(kind, o, v, min_score, q=q, multiset=multiset), column, min_score, ctx, processor)
 
 
 __all__ = ["default_process", "PROCESSORS", "best_match", "nearest", "Codec", "Context", "device_count", "pack_strings", "split_offsets", "similarity", "levenshtein", "jaro",
@@ -491,4 +524,4 @@ __all__ = ["default_process", "PROCESSORS", "best_match", "nearest", "Codec", "C
            "DISTANCE_MEASURES", "DISTANCE_UNBOUNDED", "MEASURES", "EXTRA_MEASURES", "MEASURE_ID", "STATUS", "ShapeMismatch", "StrsimError",
            "extract", "EXTRACT_SCORERS", "cdist", "CDIST_MEASURES", "join", "dedupe_pairs", "JOIN_SCORERS",
            "match_join", "match_dedupe_pairs", "MATCH_JOIN_MEASURES", "components", "cluster", "CLUSTER_MEASURES",
-           "qgram", "QGRAM_KINDS", "QGRAM_MAX_Q"]
+           "qgram", "QGRAM_KINDS", "QGRAM_MAX_Q", "qgram_join", "qgram_dedupe_pairs", "qgram_cluster"]

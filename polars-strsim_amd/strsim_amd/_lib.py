@@ -191,6 +191,14 @@ def lib():
         f = getattr(L, name)
         f.restype = i32
         f.argtypes = [vp, i32, vp, vp, u64, vp, vp, u64, C.c_double, C.c_uint32, u64, vp, vp, vp, C.POINTER(u64)]
+    for name in ("strsim_qgram_join_device", "strsim_qgram_join_host"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, i32, C.c_uint32, C.c_uint32, vp, vp, u64, vp, vp, u64, C.c_double, C.c_uint32, u64, vp, vp, vp, C.POINTER(u64)]
+    for name in ("strsim_qgram_cluster_device", "strsim_qgram_cluster_host"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, i32, C.c_uint32, C.c_uint32, vp, vp, u64, C.c_double, vp, vp, C.POINTER(u64), C.POINTER(u64)]
     for name in ("strsim_components_device", "strsim_components_host"):
         f = getattr(L, name)
         f.restype = i32

@@ -465,8 +465,19 @@ class Context:
         result, `upper`, the capacity protocol and count_only are join()'s."""
         return self._join("strsim_match_join", measure, q_offsets, q_values, c_offsets, c_values, min_score, upper, capacity, count_only)
 
+    def qgram_join(self, kind, q_offsets, q_values, c_offsets, c_values, min_score=None, upper=False, q=2, multiset=True, capacity=None,
+                   count_only=False):
+        """Threshold join by q-gram similarity (strsim_qgram_join_host for numpy columns, strsim_qgram_join_device for torch tensors
+        on this context's device): every pair (i, j) whose score by `kind` (one of QGRAM_KINDS) over q-grams (q: 1, 2 or 3;
+        multiset=False compares the sets of grams) is >= min_score (None: every pair), as CSR; the score is bit for bit
+        qgram_device's.  The result, `upper`, the capacity protocol and count_only are join()'s."""
+        return self._join("strsim_qgram_join", qgram_args(kind, q, multiset), q_offsets, q_values, c_offsets, c_values, min_score, upper, capacity,
+                          count_only)
+
     def _join(self, entry, scorer, q_offsets, q_values, c_offsets, c_values, score_cutoff, upper, capacity, count_only):
-        """join() and match_join(): the entry points `entry`_device / `entry`_host under the capacity protocol"""
+        """join(), match_join() and qgram_join(): the entry points `entry`_device / `entry`_host under the capacity protocol.  scorer: a
+        measure, or the (kind id, q, flags) of a q-gram call"""
+        what = scorer if isinstance(scorer, tuple) else (measure_id(scorer),)
         cut = -np.inf if score_cutoff is None else float(score_cutoff)
         flags = JOIN_UPPER if upper else 0
         nnz = C.c_uint64(0)
@@ -489,12 +500,12 @@ class Context:
             new = lambda n, dt: np.empty(n, dtype={"i": np.uint32, "f": np.float64}[dt])
             ptr = lambda a: a.ctypes.data
         if count_only:
-            check(fn(self._h, measure_id(scorer), *cols, cut, flags, 0, ptr(indptr), None, None, C.byref(nnz)))
+            check(fn(self._h, *what, *cols, cut, flags, 0, ptr(indptr), None, None, C.byref(nnz)))
             return indptr
         cap = 4 * nq + 1024 if capacity is None else int(capacity)
         for _ in range(2):
             index, score = new(cap, "i"), new(cap, "f")
-            check(fn(self._h, measure_id(scorer), *cols, cut, flags, cap, ptr(indptr), ptr(index) if cap else None,
+            check(fn(self._h, *what, *cols, cut, flags, cap, ptr(indptr), ptr(index) if cap else None,
                      ptr(score) if cap else None, C.byref(nnz)))
             if nnz.value <= cap:
                 return indptr, index[:nnz.value], score[:nnz.value]
@@ -548,6 +559,30 @@ class Context:
             root, cluster = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32)
             check(lib().strsim_cluster_host(self._h, measure_id(measure), o.ctypes.data, v.ctypes.data, n, float(min_score),
                                             root.ctypes.data if n else None, cluster.ctypes.data if n else None, C.byref(count), C.byref(nnz)))
+        out = (root, cluster, int(count.value))
+        return out + (int(nnz.value),) if with_nnz else out
+
+    def qgram_cluster(self, kind, offsets, values, min_score, q=2, multiset=True, with_nnz=False):
+        """The duplicate groups of one column by q-gram similarity (strsim_qgram_cluster_host for numpy columns,
+        strsim_qgram_cluster_device for torch tensors on this context's device): cluster() with the self-join of qgram_join(kind, q,
+        multiset)."""
+        kid, q, flags = qgram_args(kind, q, multiset)
+        count, nnz = C.c_uint64(0), C.c_uint64(0)
+        if not isinstance(offsets, np.ndarray) and hasattr(offsets, "data_ptr"):
+            import torch
+            n = max(offsets.numel() - 1, 0)
+            root = torch.empty(n, dtype=torch.int32, device=offsets.device)
+            cluster = torch.empty(n, dtype=torch.int32, device=offsets.device)
+            check(lib().strsim_qgram_cluster_device(self._h, kid, q, flags, offsets.data_ptr(), values.data_ptr(), n, float(min_score),
+                                                    root.data_ptr() if n else None, cluster.data_ptr() if n else None, C.byref(count),
+                                                    C.byref(nnz)))
+        else:
+            o, v, n = _host_column(offsets, values)
+            n = max(n, 0)
+            root, cluster = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32)
+            check(lib().strsim_qgram_cluster_host(self._h, kid, q, flags, o.ctypes.data, v.ctypes.data, n, float(min_score),
+                                                  root.ctypes.data if n else None, cluster.ctypes.data if n else None, C.byref(count),
+                                                  C.byref(nnz)))
         out = (root, cluster, int(count.value))
         return out + (int(nnz.value),) if with_nnz else out
 
