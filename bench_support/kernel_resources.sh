@@ -21,8 +21,11 @@
 #                    it includes (their figures must not move when strsim_qgram.h changes)
 #         qgram_join -- the twelve k_qgram_join_lane kernels of strsim_qgram_join_device and k_qgram_join_first, k_qgram_lane and
 #                    k_match_join_lane beside them (the same gram masks per pair; the same skeleton) and the join kernels around the sweep
+#         damerau -- the kernels of the unrestricted Damerau-Levenshtein calls (strsim_damerau.h), and below them the edit-distance
+#                    kernels whose header it includes (their figures must not move when strsim_damerau.h changes)
 ROOT=$(cd "$(dirname "$0")/.." && pwd); OUT=${TMPDIR:-/tmp}/strsim_co; mkdir -p $OUT
 case "$1" in
+    damerau) FILTER='k_dl_|k_dist_' ;;
     qgram) FILTER='k_qgram_|k_indel_|k_dist_' ;;
     wratio) FILTER='k_wratio_|k_take_|k_max_f64|k_token_|k_partial_|k_indel_|k_dist_' ;;
     token) FILTER='k_token_|k_partial_|k_indel_|k_dist_' ;;

@@ -216,6 +216,13 @@ POLARS_PLUGIN_DECLARE(cluster_sorensen_dice)
  * belong to the array's release callback. */
 POLARS_PLUGIN_DECLARE(default_process)
 
+/* Unrestricted Damerau-Levenshtein (not in the reference module; strsim::damerau_levenshtein of the crate, strsim_damerau_host and
+ * strsim_damerau_distance_host of strsim_amd.h): the similarity, Float64 named after input 0 like the similarities above, and the
+ * integer distance, UInt32 with the optional max_distance input 2 of the *_distance functions above.  Null where either input is
+ * null.  These calls bypass the small-call combiner. */
+POLARS_PLUGIN_DECLARE(damerau_levenshtein)
+POLARS_PLUGIN_DECLARE(damerau_levenshtein_distance)
+
 /* q-gram similarity (not in the reference; strsim_qgram_host of strsim_amd.h): Jaccard, Sorensen-Dice, overlap and cosine over the
  * q-grams of the two strings.  Inputs 0 and 1 as for the similarities (shape rule, literal broadcast, nulls); input 2 is q, a
  * length-1 non-null UInt32 series holding 1, 2 or 3 (required: without it the call fails with "q is missing: ..."); an optional

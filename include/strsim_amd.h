@@ -341,6 +341,43 @@ STRSIM_API int strsim_qgram_host(strsim_ctx_t *ctx, int kind, uint32_t q, uint32
                                  double *out, uint64_t out_rows);
 
 /*
+ * Unrestricted Damerau-Levenshtein similarity and distance (found by dlsym, like the distance calls: the ABI version stays 1.7, and
+ * no measure id is added).  Strings are sequences of Unicode scalar values.  d(a, b) is the smallest number of insertions,
+ * deletions, substitutions and swaps of two adjacent characters that turns a into b, where a substring may be edited any number of
+ * times (Lowrance and Wagner 1975): ("ca", "abc") is 2, where STRSIM_OSA's restricted distance is 3.  Unlike that one, d is a metric;
+ * levenshtein >= osa >= d >= | |a| - |b| | for every pair.  A NUL byte is a character like any other.
+ *   strsim_damerau_*           1.0 when a == b bytewise or both are empty, else 1.0 - d / max(|a|, |b|) (STRSIM_OSA's two f64
+ *                              operations; strsim::normalized_damerau_levenshtein)
+ *   strsim_damerau_distance_*  d when d <= max_distance, else max_distance + 1; STRSIM_DISTANCE_UNBOUNDED: no cutoff, 0: an equality
+ *                              test (strsim_distance_device's convention)
+ * Shape rule, literal broadcast and out_rows as strsim_pairs_device; zero rows is a no-op.  The arguments are checked first and the
+ * context last (a NULL ctx is STRSIM_ERR_ARG too): no argument error needs a device.  Rows where both strings are ASCII and at most
+ * 32 bytes are one pair per lane, every other row one pair per wave (any length; pairs whose shorter string has more than 2048
+ * bytes use a scratch buffer the context grows), and strsim_ctx_last_wave_rows counts the latter when the call returns.  The cost is
+ * that of a cell DP, |a| |b| cells a pair: there is no bit-parallel form of this distance.  Every row is complete in stream order;
+ * the call waits once for the stream after its first kernel (to size the second), so everything enqueued before it has completed
+ * when it returns.  It is not a pending call of strsim_ctx_synchronize and adds nothing to strsim_ctx_last_long_rows /
+ * _last_late_rows.  Its kernels read only the bytes the offsets describe.  The host variants stage the columns (strsim_pairs_host's
+ * copy path) and are synchronous.
+ */
+STRSIM_API int strsim_damerau_device(strsim_ctx_t *ctx,
+                                     const uint32_t *a_offsets, const uint8_t *a_values, uint64_t a_rows,
+                                     const uint32_t *b_offsets, const uint8_t *b_values, uint64_t b_rows,
+                                     double *out, uint64_t out_rows);
+STRSIM_API int strsim_damerau_host(strsim_ctx_t *ctx,
+                                   const uint32_t *a_offsets, const uint8_t *a_values, uint64_t a_rows,
+                                   const uint32_t *b_offsets, const uint8_t *b_values, uint64_t b_rows,
+                                   double *out, uint64_t out_rows);
+STRSIM_API int strsim_damerau_distance_device(strsim_ctx_t *ctx,
+                                              const uint32_t *a_offsets, const uint8_t *a_values, uint64_t a_rows,
+                                              const uint32_t *b_offsets, const uint8_t *b_values, uint64_t b_rows,
+                                              uint32_t max_distance, uint32_t *out, uint64_t out_rows);
+STRSIM_API int strsim_damerau_distance_host(strsim_ctx_t *ctx,
+                                            const uint32_t *a_offsets, const uint8_t *a_values, uint64_t a_rows,
+                                            const uint32_t *b_offsets, const uint8_t *b_values, uint64_t b_rows,
+                                            uint32_t max_distance, uint32_t *out, uint64_t out_rows);
+
+/*
  * Partial ratio with its alignment (found by dlsym, like the distance calls: the ABI version stays 1.7).  out_score[i] is bit for
  * bit what strsim_pairs_device(STRSIM_PARTIAL_RATIO) returns for row i.  out_span is out_rows x 4 uint32, row-major: a_start, a_end,
  * b_start, b_end -- half open, in Unicode scalar values (not bytes).  The needle (the shorter string; a when the lengths are equal,

@@ -568,6 +568,9 @@ POLARS_PLUGIN_EXPORT(partial_ratio_alignment, run_partial_alignment(inputs, n_in
 POLARS_PLUGIN_DEFINE_DISTANCE(levenshtein, STRSIM_LEVENSHTEIN)
 POLARS_PLUGIN_DEFINE_DISTANCE(osa, STRSIM_OSA)
 POLARS_PLUGIN_DEFINE_DISTANCE(indel, STRSIM_INDEL)
+POLARS_PLUGIN_EXPORT(damerau_levenshtein, run_damerau(inputs, n_inputs, return_value), field_entry(input_fields, n_fields, return_value))
+POLARS_PLUGIN_EXPORT(damerau_levenshtein_distance, run_damerau_distance(inputs, n_inputs, return_value),
+                     field_named_after_input0(input_fields, n_fields, return_value, [](ArrowSchema *s, const char *n) { fill_named_schema(s, "I", n); }))
 POLARS_PLUGIN_DEFINE_QGRAM(jaccard, STRSIM_QGRAM_JACCARD)
 POLARS_PLUGIN_DEFINE_QGRAM(sorensen_dice, STRSIM_QGRAM_SORENSEN_DICE)
 POLARS_PLUGIN_DEFINE_QGRAM(overlap, STRSIM_QGRAM_OVERLAP)

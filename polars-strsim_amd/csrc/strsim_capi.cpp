@@ -22,6 +22,7 @@
 #include "strsim_distance.h"
 #include "strsim_indel.h"
 #include "strsim_qgram.h"
+#include "strsim_damerau.h"
 #include "strsim_partial.h"
 #include "strsim_token.h"
 #include "strsim_wratio.h"
@@ -712,20 +713,22 @@ static int dist_report(strsim_ctx *c)
 static constexpr size_t OSA_SCRATCH_BUDGET = (size_t)1 << 30; // the wave kernel runs fewer waves rather than use more scratch
 
 // Which pair of kernels a call runs, and what they take beside the LaunchArgs.
-enum TwoPassKind { TP_DIST, TP_INDEL, TP_PARTIAL, TP_QGRAM };
+enum TwoPassKind { TP_DIST, TP_INDEL, TP_PARTIAL, TP_QGRAM, TP_DAMERAU };
 struct TwoPassCall {
     TwoPassKind kind;
     int measure;     // TP_DIST: STRSIM_LEVENSHTEIN or STRSIM_OSA; TP_QGRAM: the kind (STRSIM_QGRAM_*)
-    uint32_t k;      // TP_DIST, TP_INDEL: the cutoff (DIST_UNBOUNDED: none)
-    uint32_t *out32; // TP_DIST, TP_INDEL: the distances, or nullptr for the similarity in la.out (TP_DIST: of STRSIM_OSA)
+    uint32_t k;      // TP_DIST, TP_INDEL, TP_DAMERAU: the cutoff (DIST_UNBOUNDED: none)
+    uint32_t *out32; // TP_DIST, TP_INDEL, TP_DAMERAU: the distances, or nullptr for the similarity in la.out (TP_DIST: of STRSIM_OSA)
     uint32_t *span;  // TP_PARTIAL: the alignment, or nullptr for the score alone
     uint32_t q = 0u;     // TP_QGRAM: 1..3
     uint32_t flags = 0u; // TP_QGRAM: STRSIM_QGRAM_SET
 };
 static const char *const TWO_PASS_LANE[] = {"kernel launch (k_dist_lane)", "kernel launch (k_indel_lane)",
-                                            "kernel launch (k_partial_lane)", "kernel launch (k_qgram_lane)"};
+                                            "kernel launch (k_partial_lane)", "kernel launch (k_qgram_lane)",
+                                            "kernel launch (k_dl_lane)"};
 static const char *const TWO_PASS_WAVE[] = {"kernel launch (k_dist_wave)", "kernel launch (k_indel_wave)",
-                                            "kernel launch (k_partial_wave)", "kernel launch (k_qgram_wave)"};
+                                            "kernel launch (k_partial_wave)", "kernel launch (k_qgram_wave)",
+                                            "kernel launch (k_dl_wave)"};
 
 static hipError_t two_pass_lane(const TwoPassCall &t, const LaunchArgs &la, uint32_t *list)
 {
@@ -733,6 +736,7 @@ static hipError_t two_pass_lane(const TwoPassCall &t, const LaunchArgs &la, uint
     case TP_DIST: return launch_dist_lane(t.measure, la, t.k, t.out32, list);
     case TP_INDEL: return launch_indel_lane(la, t.k, t.out32, list);
     case TP_QGRAM: return launch_qgram_lane(la, t.measure, t.q, (t.flags & STRSIM_QGRAM_SET) != 0u, list);
+    case TP_DAMERAU: return launch_dl_lane(la, t.k, t.out32, list);
     default: return launch_partial_lane(la, t.span, list);
     }
 }
@@ -747,6 +751,7 @@ static hipError_t two_pass_wave(const TwoPassCall &t, const LaunchArgs &la, cons
     case TP_DIST: return launch_dist_wave(t.measure, la, t.k, t.out32, list, grid, scratch, words);
     case TP_INDEL: return launch_indel_wave(la, t.k, t.out32, list, grid, scratch, words);
     case TP_QGRAM: return launch_qgram_wave(la, t.measure, t.q, (t.flags & STRSIM_QGRAM_SET) != 0u, qgram_grams_bound(st), list, grid, scratch, words);
+    case TP_DAMERAU: return launch_dl_wave(la, t.k, t.out32, st.max_len, list, grid, scratch, words);
     default: return launch_partial_wave(la, t.span, list, grid, scratch, words);
     }
 }
@@ -763,6 +768,8 @@ static uint64_t two_pass_slot_words(TwoPassKind kind, const DevStatus &st)
         const uint64_t grams = qgram_grams_bound(st);
         return grams > QGRAM_WAVE_LDS_GRAMS ? qgram_wave_slot_words(grams, st.pad1[0]) : 0u;
     }
+    if (kind == TP_DAMERAU) // the columns and the boundary row of the shorter string (max_len: bytes, hence scalar values)
+        return st.max_len > DL_WAVE_LDS_COLS ? dl_wave_slot_words(st.max_len) : 0u;
     if (st.max_len <= OSA_WAVE_LDS_CPS) return 0u; // (max_len bounds the pattern in scalar values: it is a byte length)
     return kind == TP_DIST ? dist_wave_slot_words(st.max_len) : indel_wave_slot_words(st.max_len);
 }
@@ -1858,6 +1865,68 @@ int strsim_qgram_host(strsim_ctx_t *c, int kind, uint32_t q, uint32_t flags, con
     return elementwise_host(
         c, qgram_check("strsim_qgram_host", c, kind, q, flags, a, b, out, out_rows), a, b, out_rows, out, out_rows * 8, nullptr, 0,
         [&](const Staged &s, uint8_t *d_out, uint8_t *) { return qgram_device_impl(c, kind, q, flags, s.a, s.b, (double *)d_out, out_rows); },
+        nothing_to_settle);
+}
+
+} // extern "C"
+
+// ---- unrestricted Damerau-Levenshtein similarity and distance (strsim_damerau.h) ----
+
+// k_dl_lane, then k_dl_wave: the distances under the cutoff k into out32, or with out32 == nullptr the similarity into out.  The
+// size of the work list is what strsim_ctx_last_wave_rows reports (two_pass has waited for it).
+static int damerau_device_impl(strsim_ctx_t *c, const Col &a, const Col &b, uint32_t k, double *out, uint32_t *out32, uint64_t n)
+{
+    int rc = dist_prepare(c, n);
+    if (rc) return rc;
+    const LaunchArgs la = two_pass_args(c, a, b, out, n, c->dist_status);
+    rc = two_pass(c, la, TwoPassCall{TP_DAMERAU, 0, k, out32, nullptr}, -1);
+    if (rc) return rc;
+    c->last_wave_rows = c->dist_status_host->wave_rows;
+    return STRSIM_OK;
+}
+
+static int damerau_check(const char *who, strsim_ctx_t *c, const Col &a, const Col &b, const void *out, uint64_t out_rows)
+{
+    return elementwise_check(who, c, a.rows, b.rows, out_rows, a.off && a.val && b.off && b.val && out);
+}
+
+extern "C" {
+
+int strsim_damerau_device(strsim_ctx_t *c, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
+                          const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t out_rows)
+{
+    const Col a{a_off, a_val, a_rows}, b{b_off, b_val, b_rows};
+    int rc = damerau_check("strsim_damerau_device", c, a, b, out, out_rows);
+    if (rc || out_rows == 0) return rc;
+    return damerau_device_impl(c, a, b, DIST_UNBOUNDED, out, nullptr, out_rows);
+}
+
+int strsim_damerau_host(strsim_ctx_t *c, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
+                        const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t out_rows)
+{
+    const Col a{a_off, a_val, a_rows}, b{b_off, b_val, b_rows};
+    return elementwise_host(
+        c, damerau_check("strsim_damerau_host", c, a, b, out, out_rows), a, b, out_rows, out, out_rows * 8, nullptr, 0,
+        [&](const Staged &s, uint8_t *d_out, uint8_t *) { return damerau_device_impl(c, s.a, s.b, DIST_UNBOUNDED, (double *)d_out, nullptr, out_rows); },
+        nothing_to_settle);
+}
+
+int strsim_damerau_distance_device(strsim_ctx_t *c, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
+                                   const uint8_t *b_val, uint64_t b_rows, uint32_t max_distance, uint32_t *out, uint64_t out_rows)
+{
+    const Col a{a_off, a_val, a_rows}, b{b_off, b_val, b_rows};
+    int rc = damerau_check("strsim_damerau_distance_device", c, a, b, out, out_rows);
+    if (rc || out_rows == 0) return rc;
+    return damerau_device_impl(c, a, b, max_distance, nullptr, out, out_rows);
+}
+
+int strsim_damerau_distance_host(strsim_ctx_t *c, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
+                                 const uint8_t *b_val, uint64_t b_rows, uint32_t max_distance, uint32_t *out, uint64_t out_rows)
+{
+    const Col a{a_off, a_val, a_rows}, b{b_off, b_val, b_rows};
+    return elementwise_host(
+        c, damerau_check("strsim_damerau_distance_host", c, a, b, out, out_rows), a, b, out_rows, out, out_rows * 4, nullptr, 0,
+        [&](const Staged &s, uint8_t *d_out, uint8_t *) { return damerau_device_impl(c, s.a, s.b, max_distance, nullptr, (uint32_t *)d_out, out_rows); },
         nothing_to_settle);
 }
 

@@ -144,6 +144,14 @@ hipError_t launch_qgram_lane(const LaunchArgs &a, int kind, uint32_t q, bool set
 hipError_t launch_qgram_wave(const LaunchArgs &a, int kind, uint32_t q, bool set, uint64_t grams, const uint32_t *worklist, int grid,
                              uint32_t *scratch, uint64_t slot_words);
 
+// Unrestricted Damerau-Levenshtein similarity / distance (strsim_damerau.h): the same two-kernel protocol.  out32 == nullptr: the
+// f64 similarity into a.out (k is not looked at).  k_dl_lane leaves a bound of the work list's shorter strings (bytes) in
+// a.status->max_len; cols: that bound, which picks the wave kernel's LDS boundary row and lays out a scratch slot (slot_words =
+// dl_wave_slot_words(cols), for pairs of more than DL_WAVE_LDS_COLS columns; nullptr without any).
+hipError_t launch_dl_lane(const LaunchArgs &a, uint32_t k, uint32_t *out32, uint32_t *worklist);
+hipError_t launch_dl_wave(const LaunchArgs &a, uint32_t k, uint32_t *out32, uint64_t cols, const uint32_t *worklist, int grid, uint32_t *scratch,
+                          uint64_t slot_words);
+
 // Token transforms (strsim_token.h), measure ids 14 and 16.  launch_token_bounds leaves a column's longest row and its first and
 // last offset in st (side 0 or 1; max_len zeroed first).  A form is a measuring pass (write = false: the bytes of row i into
 // out_off[i + 1], out_off[0] = 0, the rows the lane kernel cannot take onto `list`, counted in *count, zeroed first), then

@@ -31,6 +31,9 @@
 //   k_qgram_lane / k_qgram_wave  q-gram Jaccard, Dice, overlap and cosine (strsim_qgram.h; q = 1..3, multiset or set): one pair per
 //                     lane for ASCII strings of up to 64 bytes (gram masks from shifted match masks), one pair per wave through a
 //                     hash table of the grams of both strings for the rest; in stream order.
+//   k_dl_lane / k_dl_wave  unrestricted Damerau-Levenshtein similarity and distance (strsim_damerau.h): a cell DP, not a bit-parallel
+//                     step.  One pair per lane for ASCII strings of up to 32 bytes, the column state packed into one dword a
+//                     column in LDS; one pair per wave for the rest, systolic over strips of 64 rows; in stream order.
 //   k_partial_lane / k_partial_wave  partial ratio and its alignment (measure 10, strsim_partial.h): the best window of the longer
 //                     string against the shorter one, match masks built once per pair; ASCII strings of up to 32 bytes per lane,
 //                     the rest one pair per wave; in stream order.
@@ -76,6 +79,7 @@
 #include "strsim_indel.h"
 #include "strsim_partial.h"
 #include "strsim_qgram.h"
+#include "strsim_damerau.h"
 #include "strsim_token.h"
 #include "strsim_wratio.h"
 #include "strsim_process.h"
@@ -735,6 +739,43 @@ hipError_t launch_indel_wave(const LaunchArgs &a, uint32_t k, uint32_t *out32, c
 {
     hipLaunchKernelGGL(k_indel_wave, dim3((unsigned)grid), dim3(64), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB, a.rowsB, k,
                        a.out, out32, worklist, a.status, scratch, slot_words);
+    return hipGetLastError();
+}
+
+// OUT = uint32_t: the distance into out32; OUT = double: the similarity into a.out
+template <typename OUT>
+static void launch_dl_lane_as(const LaunchArgs &a, uint32_t k, OUT *out, uint32_t *worklist)
+{
+    with_literal(a, [&](auto LIT) {
+        hipLaunchKernelGGL((k_dl_lane<decltype(LIT)::value, OUT>), lane_grid(a), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n, k,
+                           out, worklist, a.status);
+    });
+}
+
+template <typename OUT>
+static void launch_dl_wave_as(const LaunchArgs &a, uint32_t k, OUT *out, uint64_t cols, const uint32_t *worklist, int grid, uint32_t *scratch,
+                              uint64_t slot_words)
+{
+    if (cols <= DL_WAVE_SMALL_COLS)
+        hipLaunchKernelGGL((k_dl_wave<DL_WAVE_SMALL_COLS, OUT>), dim3((unsigned)grid), dim3(64), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB,
+                           a.valB, a.rowsB, k, out, worklist, a.status, scratch, slot_words);
+    else
+        hipLaunchKernelGGL((k_dl_wave<DL_WAVE_LDS_COLS, OUT>), dim3((unsigned)grid), dim3(64), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB,
+                           a.valB, a.rowsB, k, out, worklist, a.status, scratch, slot_words);
+}
+
+hipError_t launch_dl_lane(const LaunchArgs &a, uint32_t k, uint32_t *out32, uint32_t *worklist)
+{
+    if (out32) launch_dl_lane_as(a, k, out32, worklist);
+    else launch_dl_lane_as(a, k, a.out, worklist);
+    return hipGetLastError();
+}
+
+hipError_t launch_dl_wave(const LaunchArgs &a, uint32_t k, uint32_t *out32, uint64_t cols, const uint32_t *worklist, int grid, uint32_t *scratch,
+                          uint64_t slot_words)
+{
+    if (out32) launch_dl_wave_as(a, k, out32, cols, worklist, grid, scratch, slot_words);
+    else launch_dl_wave_as(a, k, a.out, cols, worklist, grid, scratch, slot_words);
     return hipGetLastError();
 }
 

@@ -82,7 +82,7 @@ def osa(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
     """Optimal string alignment: the restricted Damerau-Levenshtein (OSA) similarity.
 
     Levenshtein with one more edit: a swap of two adjacent characters costs 1 ("jonh" / "john" is 0.75, not 0.5).  Restricted:
-    no substring is edited twice, so ("ca", "abc") is 3 edits, where the unrestricted Damerau-Levenshtein distance is 2.
+    no substring is edited twice, so ("ca", "abc") is 3 edits, where the unrestricted Damerau-Levenshtein distance (`damerau_levenshtein`) is 2.
     Normalised like levenshtein: 1 - distance / max(len), over characters; 1.0 when both strings are empty.  Not a measure of
     the upstream polars-strsim.
     """
@@ -215,6 +215,23 @@ def indel_distance(expr: IntoExpr, other: IntoExpr, max_distance: int | None = N
     return _distance("indel_distance", expr, other, max_distance)
 
 
+def damerau_levenshtein(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
+    """Unrestricted Damerau-Levenshtein similarity (strsim's `normalized_damerau_levenshtein`, rapidfuzz's
+    `DamerauLevenshtein.normalized_similarity`).
+
+    Like `osa`, a swap of two adjacent characters costs 1; unlike it, a substring may be edited again after a swap, so
+    ("ca", "abc") is 2 edits, not 3, and the distance is a metric.  Normalised like levenshtein: 1 - distance / max(len), over
+    characters; 1.0 when both strings are empty.  A cell DP on the GPU, slower than `osa`.  Not in the upstream polars-strsim.
+    """
+    return _similarity("damerau_levenshtein", expr, other)
+
+
+def damerau_levenshtein_distance(expr: IntoExpr, other: IntoExpr, max_distance: int | None = None) -> pl.Expr:
+    """Unrestricted Damerau-Levenshtein distance as UInt32 (see damerau_levenshtein); never more than osa_distance.
+    max_distance as in levenshtein_distance.  Not in the upstream polars-strsim."""
+    return _distance("damerau_levenshtein_distance", expr, other, max_distance)
+
+
 def default_process(expr: IntoExpr) -> pl.Expr:
     """rapidfuzz `utils.default_process` on the GPU, String in and String out: every character that is neither alphanumeric nor
     "_" becomes a space, the others are lower-cased, and spaces are removed from both ends (inner runs of spaces stay:
@@ -236,6 +253,8 @@ __all__ = [
     "levenshtein_distance",
     "osa_distance",
     "osa",
+    "damerau_levenshtein_distance",
+    "damerau_levenshtein",
     "indel_distance",
     "indel",
     "partial_ratio",

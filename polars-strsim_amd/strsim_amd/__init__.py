@@ -94,8 +94,8 @@ def sorensen_dice(a, b, ctx=None):
 
 def osa(a, b, ctx=None):
     """Optimal string alignment: the restricted Damerau-Levenshtein similarity.  Like levenshtein, with a swap of two adjacent
-    characters counted as one edit; no substring is edited twice (("ca", "abc") is 3 edits, not the unrestricted variant's 2).
-    1.0 - d / max(len(a), len(b)) over characters, 1.0 when both are empty."""
+    characters counted as one edit; no substring is edited twice (("ca", "abc") is 3 edits, not the unrestricted variant's 2:
+    damerau_levenshtein).  1.0 - d / max(len(a), len(b)) over characters, 1.0 when both are empty."""
     return similarity("osa", a, b, ctx)
 
 
@@ -259,6 +259,40 @@ def osa_distance(a, b, max_distance=None, ctx=None):
 def indel_distance(a, b, max_distance=None, ctx=None):
     """Indel distance: len(a) + len(b) - 2 LCS(a, b) over characters (insert and delete, a substitution costs 2); see distance()."""
     return distance("indel", a, b, max_distance, ctx)
+
+
+def _damerau_columns(a, b, max_distance=None):
+    """The packed columns and validities of a damerau call; every ValueError of its arguments, before a context is touched."""
+    from .context import _max_distance
+    _max_distance(max_distance)
+    A, va = _as_column(a)
+    B, vb = _as_column(b)
+    if len(A) != len(B) and len(A) != 1 and len(B) != 1:
+        raise ShapeMismatch(1, f"Inputs must have the same length or one of them must be a literal (got {len(A)} and {len(B)} rows)")
+    return pack_strings(A), pack_strings(B), va, vb
+
+
+def damerau_levenshtein(a, b, ctx=None):
+    """Unrestricted Damerau-Levenshtein similarity (strsim's normalized_damerau_levenshtein, rapidfuzz's
+    DamerauLevenshtein.normalized_similarity) of two columns / a column and a literal -> f64 numpy array, NaN where either input
+    is null.  d is the smallest number of insertions, deletions, substitutions and swaps of two adjacent characters, where a
+    substring may be edited again after a swap: ("ca", "abc") is 2, where osa() counts 3.  Unlike osa's, this distance is a metric.
+    1.0 - d / max(len(a), len(b)) over characters, 1.0 when both are empty."""
+    (ao, av), (bo, bv), va, vb = _damerau_columns(a, b)
+    ctx = ctx or default_context()
+    out = ctx.damerau_host(ao, av, bo, bv)
+    out[_null_mask(out.size, va, vb)] = np.nan
+    return out
+
+
+def damerau_levenshtein_distance(a, b, max_distance=None, ctx=None):
+    """Unrestricted Damerau-Levenshtein distance over characters (see damerau_levenshtein) -> numpy.ma.MaskedArray of uint32,
+    masked where either input is null.  max_distance as for distance().  levenshtein_distance >= osa_distance >= this >= the
+    difference of the lengths, row by row."""
+    (ao, av), (bo, bv), va, vb = _damerau_columns(a, b, max_distance)
+    ctx = ctx or default_context()
+    out = ctx.damerau_distance_host(ao, av, bo, bv, max_distance)
+    return np.ma.MaskedArray(out, mask=_null_mask(out.size, va, vb))
 
 
 def best_match(measure, queries, candidates, k=1, min_score=None, ctx=None):
@@ -524,4 +558,4 @@ __all__ = ["default_process", "PROCESSORS", "best_match", "nearest", "Codec", "C
            "DISTANCE_MEASURES", "DISTANCE_UNBOUNDED", "MEASURES", "EXTRA_MEASURES", "MEASURE_ID", "STATUS", "ShapeMismatch", "StrsimError",
            "extract", "EXTRACT_SCORERS", "cdist", "CDIST_MEASURES", "join", "dedupe_pairs", "JOIN_SCORERS",
            "match_join", "match_dedupe_pairs", "MATCH_JOIN_MEASURES", "components", "cluster", "CLUSTER_MEASURES",
-           "qgram", "QGRAM_KINDS", "QGRAM_MAX_Q", "qgram_join", "qgram_dedupe_pairs", "qgram_cluster"]
+           "damerau_levenshtein", "damerau_levenshtein_distance", "qgram", "QGRAM_KINDS", "QGRAM_MAX_Q", "qgram_join", "qgram_dedupe_pairs", "qgram_cluster"]

@@ -149,6 +149,14 @@ def lib():
         f = getattr(L, name)
         f.restype = i32
         f.argtypes = [vp, i32, C.c_uint32, C.c_uint32, vp, vp, u64, vp, vp, u64, vp, u64]
+    for name in ("strsim_damerau_device", "strsim_damerau_host"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, u64]
+    for name in ("strsim_damerau_distance_device", "strsim_damerau_distance_host"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, vp, vp, u64, vp, vp, u64, C.c_uint32, vp, u64]
     for name in ("strsim_partial_alignment_device", "strsim_partial_alignment_host"):
         f = getattr(L, name)
         f.restype = i32

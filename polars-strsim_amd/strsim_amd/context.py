@@ -221,6 +221,37 @@ class Context:
                                         b_offsets.data_ptr(), b_values.data_ptr(), rb, out.data_ptr(), out.numel()))
         return out
 
+    def damerau_device(self, a_offsets, a_values, b_offsets, b_values, out=None):
+        """Unrestricted Damerau-Levenshtein similarity (strsim_damerau_device) of device tensors laid out as for pairs_device -> f64
+        tensor.  Complete in stream order; last_wave_rows counts the rows that took the one-pair-per-wave tier."""
+        import torch
+        ra, rb = a_offsets.numel() - 1, b_offsets.numel() - 1
+        n = rb if ra == 1 else ra
+        _check_device_column(a_offsets, a_values)
+        _check_device_column(b_offsets, b_values)
+        if out is None:
+            out = torch.empty(n if (ra == rb or ra == 1 or rb == 1) else 0, dtype=torch.float64, device=a_offsets.device)
+        check(lib().strsim_damerau_device(self._h, a_offsets.data_ptr(), a_values.data_ptr(), ra, b_offsets.data_ptr(), b_values.data_ptr(),
+                                          rb, out.data_ptr(), out.numel()))
+        return out
+
+    def damerau_distance_device(self, a_offsets, a_values, b_offsets, b_values, max_distance=None, out=None):
+        """Unrestricted Damerau-Levenshtein distance (strsim_damerau_distance_device) of device tensors -> uint32 values in an int32
+        tensor, as distance_device returns them.  max_distance=None is no cutoff, else rows beyond it hold max_distance + 1."""
+        import torch
+        k = _max_distance(max_distance)
+        ra, rb = a_offsets.numel() - 1, b_offsets.numel() - 1
+        n = rb if ra == 1 else ra
+        _check_device_column(a_offsets, a_values)
+        _check_device_column(b_offsets, b_values)
+        if out is None:
+            out = torch.empty(n if (ra == rb or ra == 1 or rb == 1) else 0, dtype=torch.int32, device=a_offsets.device)
+        assert out.is_cuda and out.device == a_offsets.device and out.element_size() == 4 and out.is_contiguous() \
+            and not out.is_floating_point(), "out must be a contiguous 4-byte integer tensor on the inputs' device"
+        check(lib().strsim_damerau_distance_device(self._h, a_offsets.data_ptr(), a_values.data_ptr(), ra, b_offsets.data_ptr(),
+                                                   b_values.data_ptr(), rb, k, out.data_ptr(), out.numel()))
+        return out
+
     def partial_alignment_device(self, a_offsets, a_values, b_offsets, b_values, score=None, span=None):
         """Partial ratio with its alignment (strsim_partial_alignment_device) of device tensors laid out as for pairs_device ->
         (score f64 [n], span int32 [n, 4] holding uint32 a_start, a_end, b_start, b_end in characters).  Complete in stream order."""
@@ -355,6 +386,28 @@ class Context:
         out = np.empty(n, dtype=np.float64)
         check(lib().strsim_qgram_host(self._h, kid, q, flags, ao.ctypes.data, av.ctypes.data, ra, bo.ctypes.data, bv.ctypes.data, rb,
                                       out.ctypes.data, n))
+        return out
+
+    def damerau_host(self, a_offsets, a_values, b_offsets, b_values):
+        """Synchronous unrestricted Damerau-Levenshtein similarity (strsim_damerau_host): numpy uint32 offsets + uint8 values in,
+        numpy f64 out."""
+        ao, av, ra = _host_column(a_offsets, a_values)
+        bo, bv, rb = _host_column(b_offsets, b_values)
+        n = _rows_out(ra, rb)
+        out = np.empty(n, dtype=np.float64)
+        check(lib().strsim_damerau_host(self._h, ao.ctypes.data, av.ctypes.data, ra, bo.ctypes.data, bv.ctypes.data, rb, out.ctypes.data, n))
+        return out
+
+    def damerau_distance_host(self, a_offsets, a_values, b_offsets, b_values, max_distance=None):
+        """Synchronous unrestricted Damerau-Levenshtein distance (strsim_damerau_distance_host): numpy uint32 offsets + uint8 values
+        in, numpy uint32 out."""
+        k = _max_distance(max_distance)
+        ao, av, ra = _host_column(a_offsets, a_values)
+        bo, bv, rb = _host_column(b_offsets, b_values)
+        n = _rows_out(ra, rb)
+        out = np.empty(n, dtype=np.uint32)
+        check(lib().strsim_damerau_distance_host(self._h, ao.ctypes.data, av.ctypes.data, ra, bo.ctypes.data, bv.ctypes.data, rb, k,
+                                                 out.ctypes.data, n))
         return out
 
     def partial_alignment_host(self, a_offsets, a_values, b_offsets, b_values):
