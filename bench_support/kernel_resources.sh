@@ -23,6 +23,8 @@
 #                    k_match_join_lane beside them (the same gram masks per pair; the same skeleton) and the join kernels around the sweep
 #         damerau -- the kernels of the unrestricted Damerau-Levenshtein calls (strsim_damerau.h), and below them the edit-distance
 #                    kernels whose header it includes (their figures must not move when strsim_damerau.h changes)
+#         distance_join -- the six k_distance_join_lane kernels of strsim_distance_join_device and k_distance_join_finish, k_nearest_lane,
+#                    k_dl_lane and k_match_join_lane beside them (the same cores; the same skeleton) and the join kernels around the sweep
 ROOT=$(cd "$(dirname "$0")/.." && pwd); OUT=${TMPDIR:-/tmp}/strsim_co; mkdir -p $OUT
 case "$1" in
     damerau) FILTER='k_dl_|k_dist_' ;;
@@ -35,6 +37,7 @@ case "$1" in
     join) FILTER='k_join_|k_extract_|k_nearest_hist|k_nearest_scan|k_nearest_scatter|k_match_pack' ;;
     match_join) FILTER='k_match_join_|k_match_lane|k_join_|k_nearest_hist|k_nearest_scan|k_nearest_scatter|k_match_pack' ;;
     qgram_join) FILTER='k_qgram_join_|k_qgram_lane|k_match_join_|k_join_|k_nearest_hist|k_nearest_scan|k_nearest_scatter|k_match_pack' ;;
+    distance_join) FILTER='k_distance_join_|k_nearest_lane|k_nearest_scores|k_dl_lane|k_match_join_|k_join_|k_nearest_hist|k_nearest_scan|k_nearest_scatter|k_match_pack' ;;
     cluster) FILTER='k_components_|k_join_scan_' ;;
     nearest) FILTER='k_nearest_|k_match_pack|k_match_clear|k_match_fold|k_match_merge' ;;
     *) FILTER=${1:-.} ;;

@@ -248,6 +248,19 @@ POLARS_PLUGIN_DECLARE(qgram_cluster_sorensen_dice)
 POLARS_PLUGIN_DECLARE(qgram_cluster_overlap)
 POLARS_PLUGIN_DECLARE(qgram_cluster_cosine)
 
+/* distance_join: the join by integer edit distance (strsim_distance_join_host): every candidate within max_distance edits of the
+ * query, by Levenshtein, OSA or the unrestricted Damerau-Levenshtein distance.  Inputs 0 and 1 are the queries and the candidates as
+ * for join_ratio; an optional input 2 is max_distance, a length-1 UInt32 series (null or absent: every pair).  The null rules are
+ * join_ratio's; the result is a LargeList<Struct{index: UInt32, distance: UInt32}>, the hits in ascending candidate index.
+ * distance_cluster: cluster by edit distance (strsim_distance_cluster_host).  Input 0 is the column, input 1 the UInt32 literal
+ * max_distance (required, not null); the UInt32 result and the null rule are cluster_ratio's. */
+POLARS_PLUGIN_DECLARE(distance_join_levenshtein)
+POLARS_PLUGIN_DECLARE(distance_join_osa)
+POLARS_PLUGIN_DECLARE(distance_join_damerau_levenshtein)
+POLARS_PLUGIN_DECLARE(distance_cluster_levenshtein)
+POLARS_PLUGIN_DECLARE(distance_cluster_osa)
+POLARS_PLUGIN_DECLARE(distance_cluster_damerau_levenshtein)
+
 /* ---- diagnostics of this implementation (not part of the polars-ffi contract; the engine never calls them) ----
  * The plugin's staging -- pinned host memory and its device mirrors, per pipeline set -- is leased per call from one process-wide
  * pool under POLARS_STRSIM_STAGING_BUDGET_MB (csrc/plugin_pack.h: StagingPool; reference counterpart: the per-call scratch of

@@ -779,6 +779,61 @@ STRSIM_API int strsim_qgram_cluster_host(strsim_ctx_t *ctx, int kind, uint32_t q
                                          const uint32_t *offsets, const uint8_t *values, uint64_t rows, double min_score,
                                          uint32_t *out_root, uint32_t *out_cluster, uint64_t *out_count, uint64_t *out_nnz);
 
+/*
+ * Join by integer edit distance: every pair (query i, candidate j) with d(i, j) <= max_distance, as CSR -- "which rows are within
+ * two edits of which" (found by dlsym, like strsim_join_*: the ABI version stays 1.7, there is no new measure id and
+ * strsim_measure_supported does not describe these entry points).  `kind` is one of STRSIM_EDIT_*: d(i, j) is exactly what
+ * strsim_distance_device(STRSIM_LEVENSHTEIN or STRSIM_OSA, ..., STRSIM_DISTANCE_UNBOUNDED) returns for the pair, and for
+ * STRSIM_EDIT_DAMERAU what strsim_damerau_distance_device(..., STRSIM_DISTANCE_UNBOUNDED) returns: the unrestricted
+ * Damerau-Levenshtein distance, the one of the three that is a metric.  max_distance = 0 is the exact-duplicate join,
+ * STRSIM_DISTANCE_UNBOUNDED reports every pair.  Any other kind is STRSIM_ERR_ARG.
+ *
+ * Everything else is the contract of strsim_match_join_device, word for word, with out_distance (uint32, capacity elements) where
+ * out_score stands: STRSIM_JOIN_UPPER in `flags` keeps only j > i; the result is CSR with every row in ascending candidate index;
+ * *out_nnz (host memory) and all of out_indptr are always written, and exact; out_index and out_distance are written iff
+ * nnz <= capacity, otherwise not one element of either is touched and the call still returns STRSIM_OK; capacity == 0 with NULL
+ * out_index / out_distance is the count-only form.  The kind is checked first, then the arguments of strsim_match_join_device in
+ * its order, the context last: no argument error needs a device.
+ *
+ * Device-resident: strings of at most 32 ASCII bytes are swept one query per lane in length order; d >= | |a| - |b| | by all three
+ * measures, so only the candidate lengths within max_distance of a query's are visited.  Levenshtein and OSA run their
+ * bit-parallel column.  Damerau-Levenshtein runs the OSA column and decides by it wherever it can (osa <= 2: d = osa; osa >
+ * 2 max_distance: no hit) and runs its cell DP only for the rest: at max_distance <= 1 never.  Every pair with a longer or
+ * non-ASCII side goes through strsim_distance_device / strsim_damerau_distance_device at max_distance with that string as the
+ * literal; those internal calls leave strsim_ctx_last_wave_rows as the caller's last pairwise call set it.  The hits travel as
+ * f64 inside the call: a context-owned buffer of min(capacity, q_rows * c_rows) doubles.
+ */
+enum { STRSIM_EDIT_LEVENSHTEIN = 0, STRSIM_EDIT_OSA = 1, STRSIM_EDIT_DAMERAU = 2 };
+
+STRSIM_API int strsim_distance_join_device(strsim_ctx_t *ctx, int kind,
+                                           const uint32_t *q_offsets, const uint8_t *q_values, uint64_t q_rows,
+                                           const uint32_t *c_offsets, const uint8_t *c_values, uint64_t c_rows,
+                                           uint32_t max_distance, uint32_t flags, uint64_t capacity,
+                                           uint64_t *out_indptr, uint32_t *out_index, uint32_t *out_distance, uint64_t *out_nnz);
+
+/* The same with HOST-RESIDENT buffers (the column layout of strsim_pairs_host, every output included); synchronous. */
+STRSIM_API int strsim_distance_join_host(strsim_ctx_t *ctx, int kind,
+                                         const uint32_t *q_offsets, const uint8_t *q_values, uint64_t q_rows,
+                                         const uint32_t *c_offsets, const uint8_t *c_values, uint64_t c_rows,
+                                         uint32_t max_distance, uint32_t flags, uint64_t capacity,
+                                         uint64_t *out_indptr, uint32_t *out_index, uint32_t *out_distance, uint64_t *out_nnz);
+
+/*
+ * The duplicate groups of one column by edit distance: strsim_cluster_device with the STRSIM_JOIN_UPPER self-join made by
+ * strsim_distance_join_device(kind, max_distance): rows within max_distance edits are linked and the links chain ("a" ~ "b" ~ "c"
+ * is one group even when "a" and "c" are further apart).  Outputs, the limits and the waits are strsim_cluster_device's;
+ * STRSIM_DISTANCE_UNBOUNDED gives one cluster, as min_score = -INFINITY does there.  The kind is checked first, then the remaining
+ * arguments in strsim_cluster_device's order, the context last.
+ */
+STRSIM_API int strsim_distance_cluster_device(strsim_ctx_t *ctx, int kind, const uint32_t *offsets, const uint8_t *values, uint64_t rows,
+                                              uint32_t max_distance, uint32_t *out_root, uint32_t *out_cluster, uint64_t *out_count,
+                                              uint64_t *out_nnz);
+
+/* The same with HOST-RESIDENT buffers; synchronous. */
+STRSIM_API int strsim_distance_cluster_host(strsim_ctx_t *ctx, int kind, const uint32_t *offsets, const uint8_t *values, uint64_t rows,
+                                            uint32_t max_distance, uint32_t *out_root, uint32_t *out_cluster, uint64_t *out_count,
+                                            uint64_t *out_nnz);
+
 /* Row partition used to shard a column over `n` GPUs/ranks: the reference's split_offsets
  * (strsim.rs:21-39).  Writes n (offset,len) pairs into out_offset_len[2*n]. */
 STRSIM_API void strsim_split_offsets(uint64_t len, uint64_t n, uint64_t *out_offset_len);

@@ -37,15 +37,15 @@ struct ClusterOwned {
     ~ClusterOwned() { free(root); free(valid); }
 };
 
-// cluster_host(ctx, offsets, values, rows, min_score, out_root, &count): the family's host entry point with its measure bound.
-// The column is input 0, min_score the Float64 literal `min_score_input`.
-template <class ClusterHost>
-void run_cluster_call(ClusterHost cluster_host, SeriesExport *inputs, const SeriesExport &min_score_input, SeriesExport *ret)
+// cluster_host(ctx, offsets, values, rows, cutoff, out_root, &count): the family's host entry point with its measure bound.  The
+// column is input 0; cutoff() parses the family's cutoff (behind the column's own check, as the messages are ordered).
+template <class ClusterHost, class Cutoff>
+void run_cluster_cut(ClusterHost cluster_host, SeriesExport *inputs, Cutoff cutoff, SeriesExport *ret)
 {
     Column col;
     describe(inputs[0], col);
     if (col.rows > 0xFFFFFFFEull) fail("cluster: more than 2^32 - 2 rows");
-    const double min_score = cluster_min_score(min_score_input);
+    const auto min_score = cutoff();
     const uint64_t n = col.rows;
     std::vector<uint32_t> off, pos;
     std::vector<uint8_t> val;
@@ -73,6 +73,13 @@ void run_cluster_call(ClusterHost cluster_host, SeriesExport *inputs, const Seri
     }
     export_primitive("I", col.name.c_str(), n, own.root, valid, nulls, false, ret);
     own.root = own.valid = nullptr;
+}
+
+// The families that cut by an f64 score: min_score is the Float64 literal `min_score_input`.
+template <class ClusterHost>
+void run_cluster_call(ClusterHost cluster_host, SeriesExport *inputs, const SeriesExport &min_score_input, SeriesExport *ret)
+{
+    run_cluster_cut(cluster_host, inputs, [&] { return cluster_min_score(min_score_input); }, ret);
 }
 
 void run_cluster(int measure, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret)

@@ -10,11 +10,13 @@
 //
 // The match_join_<measure> functions (the five reference measures; input 2 is min_score) are the same flow over
 // strsim_match_join_host: run_join takes the host entry point to call.  The qgram_join_<kind> functions (plugin_qgram_join.h) are
-// the same flow again over strsim_qgram_join_host: run_join_call takes the call itself, with whatever the family binds to it.
+// the same flow again over strsim_qgram_join_host: run_join_call takes the call itself, with whatever the family binds to it.  The
+// distance_join_<kind> functions (plugin_distance_join.h) carry a UInt32 distance where the score stands: run_join_values takes the
+// type of the value, the struct's shape and the cutoff as the family parsed it.
 #pragma once
 
-// the nullable LargeList<Struct{index, score}> named `name` (its child: "item")
-void fill_list_struct_schema(ArrowSchema *s, const char *name)
+// the nullable LargeList<Struct `shape`> named `name` (its child: "item")
+void fill_list_struct_schema_of(ArrowSchema *s, const char *name, const StructShape &shape)
 {
     memset(s, 0, sizeof *s);
     std::unique_ptr<ListSchemaPriv> p(new ListSchemaPriv{});
@@ -22,7 +24,7 @@ void fill_list_struct_schema(ArrowSchema *s, const char *name)
     p->child = static_cast<ArrowSchema *>(calloc(1, sizeof(ArrowSchema)));
     if (!p->name || !p->child) { free(p->name); free(p->child); throw std::bad_alloc(); }
     try {
-        fill_struct_schema(p->child, "item", MATCH_STRUCT);
+        fill_struct_schema(p->child, "item", shape);
     } catch (...) {
         free(p->name); free(p->child);
         throw;
@@ -37,6 +39,9 @@ void fill_list_struct_schema(ArrowSchema *s, const char *name)
     s->private_data = p.release();
 }
 
+// the nullable LargeList<Struct{index, score}> named `name`
+void fill_list_struct_schema(ArrowSchema *s, const char *name) { fill_list_struct_schema_of(s, name, MATCH_STRUCT); }
+
 // Every buffer and box of a join result, allocated before any of it is handed over; until then the destructor frees them.
 struct JoinOwned {
     void *index = nullptr, *score = nullptr, *offsets = nullptr, *valid = nullptr;
@@ -49,10 +54,10 @@ struct JoinOwned {
             if (!(box[b] = calloc(1, sizeof(ArrowArray)))) throw std::bad_alloc();
         if (!(box[4] = calloc(1, sizeof(ArrowSchema))) || !(box[5] = calloc(1, sizeof(ArrowArray *)))) throw std::bad_alloc();
     }
-    void room(uint64_t nnz)
+    void room(uint64_t nnz, size_t value_bytes = sizeof(double)) // (score: the hits' values, f64 scores or uint32 distances)
     {
         index = alloc64(nnz * sizeof(uint32_t));
-        score = alloc64(nnz * sizeof(double));
+        score = alloc64(nnz * value_bytes);
     }
     ~JoinOwned()
     {
@@ -61,8 +66,9 @@ struct JoinOwned {
     }
 };
 
-// Hands the buffers of `own` to `ret` as one LargeList<Struct{index, score}> chunk of n lists (nnz structs in the child) named `name`.
-void export_list_struct(JoinOwned &own, uint64_t n, uint64_t nnz, int64_t list_nulls, const char *name, SeriesExport *ret)
+// Hands the buffers of `own` to `ret` as one LargeList<Struct `shape`> chunk of n lists (nnz structs in the child) named `name`.
+void export_list_struct(JoinOwned &own, uint64_t n, uint64_t nnz, int64_t list_nulls, const char *name, SeriesExport *ret,
+                        const StructShape &shape = MATCH_STRUCT)
 {
     ArrowSchema *const schema = static_cast<ArrowSchema *>(own.box[4]);
     ArrowArray **const arrays = static_cast<ArrowArray **>(own.box[5]);
@@ -71,7 +77,7 @@ void export_list_struct(JoinOwned &own, uint64_t n, uint64_t nnz, int64_t list_n
     std::unique_ptr<StructPriv> st(new StructPriv{2, {}, nullptr, {nullptr}});
     std::unique_ptr<ListPriv> lp(new ListPriv{own.offsets, own.valid, nullptr, {}, {own.valid, own.offsets}});
     std::unique_ptr<SeriesPriv> sp(new SeriesPriv{schema, arrays, 1});
-    fill_list_struct_schema(schema, name); // (the last step that may throw)
+    fill_list_struct_schema_of(schema, name, shape); // (the last step that may throw)
     // ---- from here on nothing allocates or throws: hand every buffer and box to the result
     ChildPriv *const cp[2] = {ci.release(), cs.release()};
     for (int i = 0; i < 2; ++i) {
@@ -116,15 +122,14 @@ void export_list_struct(JoinOwned &own, uint64_t n, uint64_t nnz, int64_t list_n
 typedef int (*JoinHostFn)(strsim_ctx_t *, int, const uint32_t *, const uint8_t *, uint64_t, const uint32_t *, const uint8_t *, uint64_t, double, uint32_t,
                           uint64_t, uint64_t *, uint32_t *, double *, uint64_t *);
 
-// join_host(ctx, q_off, q_val, q_rows, c_off, c_val, c_rows, cutoff, capacity, indptr, index, score, &nnz): the family's host entry
-// point with its scorer bound and no flags
-template <class JoinHost>
-void run_join_call(JoinHost join_host, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret)
+// join_host(ctx, q_off, q_val, q_rows, c_off, c_val, c_rows, cutoff, capacity, indptr, index, value, &nnz): the family's host entry
+// point with its scorer bound and no flags.  T: the type of a hit's value (the second child of `shape`); parse_cutoff() gives the
+// family's cutoff (behind the columns' own checks, as the messages are ordered).
+template <class T, class ParseCutoff, class JoinHost>
+void run_join_values(JoinHost join_host, ParseCutoff parse_cutoff, const StructShape &shape, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret)
 {
-    if (n_inputs != 2 && n_inputs != 3)
-        fail("join: expected 2 input series (queries, candidates) and an optional score_cutoff, got " + std::to_string(n_inputs));
     const SearchInputs in("join", inputs, n_inputs, false);
-    const double cutoff = extract_cutoff(inputs, n_inputs);
+    const auto cutoff = parse_cutoff();
     const uint64_t n = in.q.rows;
     const Packed p(in.q, in.c, true);
     const uint64_t m = p.b_rows();
@@ -137,18 +142,18 @@ void run_join_call(JoinHost join_host, SeriesExport *inputs, size_t n_inputs, Se
         PipeLease lease(2 * p.staged_bytes() + 16 * n + 84 * (n + m) + 4 * 65 * n + 16 * 8 * std::max(n, m));
         strsim_ctx_t *const ctx = leased_context(lease);
         if (join_host(ctx, p.ao.data(), p.av.data(), n, p.bo.data(), p.bv.data(), m, cutoff, (uint64_t)0, indptr.data(), (uint32_t *)nullptr,
-                      (double *)nullptr, &nnz) != STRSIM_OK)
+                      (T *)nullptr, &nnz) != STRSIM_OK)
             fail(strsim_last_error_message());
-        own.room(nnz);
+        own.room(nnz, sizeof(T));
         if (nnz && join_host(ctx, p.ao.data(), p.av.data(), n, p.bo.data(), p.bv.data(), m, cutoff, nnz, indptr.data(),
-                             static_cast<uint32_t *>(own.index), static_cast<double *>(own.score), &nnz) != STRSIM_OK)
+                             static_cast<uint32_t *>(own.index), static_cast<T *>(own.score), &nnz) != STRSIM_OK)
             fail(strsim_last_error_message());
     } else {
-        own.room(0);
+        own.room(0, sizeof(T));
     }
     // the hits of a null query (scored as the empty string) are dropped: the lists are compacted in place
     uint32_t *const index = static_cast<uint32_t *>(own.index);
-    double *const score = static_cast<double *>(own.score);
+    T *const score = static_cast<T *>(own.score);
     int64_t *const off = static_cast<int64_t *>(own.offsets);
     uint8_t *const valid = static_cast<uint8_t *>(own.valid);
     if (valid) memset(valid, 0, (n + 63) / 64 * 8);
@@ -167,7 +172,16 @@ void run_join_call(JoinHost join_host, SeriesExport *inputs, size_t n_inputs, Se
         }
         off[r + 1] = (int64_t)at;
     }
-    export_list_struct(own, n, at, list_nulls, in.q.name.c_str(), ret);
+    export_list_struct(own, n, at, list_nulls, in.q.name.c_str(), ret, shape);
+}
+
+// The families whose hits carry an f64 score: an optional input 2 is the cutoff (extract_cutoff).
+template <class JoinHost>
+void run_join_call(JoinHost join_host, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret)
+{
+    if (n_inputs != 2 && n_inputs != 3)
+        fail("join: expected 2 input series (queries, candidates) and an optional score_cutoff, got " + std::to_string(n_inputs));
+    run_join_values<double>(join_host, [&] { return extract_cutoff(inputs, n_inputs); }, MATCH_STRUCT, inputs, n_inputs, ret);
 }
 
 void run_join(JoinHostFn join_host, int scorer, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret)

@@ -158,6 +158,7 @@ void export_primitive(const char *format, const char *name, uint64_t n, void *da
 #include "plugin_join.h"
 #include "plugin_cluster.h"
 #include "plugin_qgram_join.h"
+#include "plugin_distance_join.h"
 #include "plugin_process.h"
 
 void run(int measure, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret, bool engine_parallel)
@@ -284,6 +285,11 @@ void _polars_plugin_strsim_coalesce_stats(uint64_t out[4]) { if (out) combiner()
     POLARS_PLUGIN_EXPORT(qgram_join_##name, run_qgram_join(kind, inputs, n_inputs, return_value),      \
                          field_named_after_input0(input_fields, n_fields, return_value, fill_list_struct_schema)) \
     POLARS_PLUGIN_EXPORT(qgram_cluster_##name, run_qgram_cluster(kind, inputs, n_inputs, return_value), \
+                         field_named_after_input0(input_fields, n_fields, return_value, [](ArrowSchema *s, const char *n) { fill_named_schema(s, "I", n); }))
+#define POLARS_PLUGIN_DEFINE_DISTANCE_JOIN(name, kind)                                                       \
+    POLARS_PLUGIN_EXPORT(distance_join_##name, run_distance_join(kind, inputs, n_inputs, return_value),      \
+                         field_named_after_input0(input_fields, n_fields, return_value, fill_list_distance_schema)) \
+    POLARS_PLUGIN_EXPORT(distance_cluster_##name, run_distance_cluster(kind, inputs, n_inputs, return_value), \
                          field_named_after_input0(input_fields, n_fields, return_value, [](ArrowSchema *s, const char *n) { fill_named_schema(s, "I", n); }))
 #define POLARS_PLUGIN_DEFINE_MATCH(name, id) \
     POLARS_PLUGIN_EXPORT(best_match_##name, run_best_match(id, inputs, n_inputs, return_value), STRUCT_FIELD(MATCH_STRUCT))
@@ -604,6 +610,9 @@ POLARS_PLUGIN_DEFINE_QGRAM_JOIN(jaccard, STRSIM_QGRAM_JACCARD)
 POLARS_PLUGIN_DEFINE_QGRAM_JOIN(sorensen_dice, STRSIM_QGRAM_SORENSEN_DICE)
 POLARS_PLUGIN_DEFINE_QGRAM_JOIN(overlap, STRSIM_QGRAM_OVERLAP)
 POLARS_PLUGIN_DEFINE_QGRAM_JOIN(cosine, STRSIM_QGRAM_COSINE)
+POLARS_PLUGIN_DEFINE_DISTANCE_JOIN(levenshtein, STRSIM_EDIT_LEVENSHTEIN)
+POLARS_PLUGIN_DEFINE_DISTANCE_JOIN(osa, STRSIM_EDIT_OSA)
+POLARS_PLUGIN_DEFINE_DISTANCE_JOIN(damerau_levenshtein, STRSIM_EDIT_DAMERAU)
 POLARS_PLUGIN_EXPORT(default_process, run_default_process(inputs, n_inputs, return_value),
                      field_named_after_input0(input_fields, n_fields, return_value, [](ArrowSchema *s, const char *n) { fill_named_schema(s, "u", n); }))
 POLARS_PLUGIN_DEFINE_MATCH(levenshtein, STRSIM_LEVENSHTEIN)

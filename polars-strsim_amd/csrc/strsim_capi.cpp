@@ -33,6 +33,7 @@
 #include "strsim_join.h"
 #include "strsim_match_join.h"
 #include "strsim_qgram_join.h"
+#include "strsim_distance_join.h"
 #include "strsim_components.h"
 
 namespace strsim {
@@ -189,6 +190,9 @@ struct strsim_ctx {
     DevBuf join_ws, join_scratch;
     // strsim_qgram_join_device in set mode: one word per candidate in length order (its first occurrences, strsim_qgram_join.h)
     DevBuf qgram_join_first;
+    // strsim_distance_join_device: the hits' f64 values -(double)d until the finishing kernel has written the caller's uint32 column,
+    // and one uint32 column of the fallback's pairwise distances (strsim_distance_join.h)
+    DevBuf distance_join_score, distance_join_col;
     // strsim_components_device: parent[], the root flags and their scan, and the status words {count, indices out of range} with
     // their pinned read-back; strsim_cluster_device: the CSR of its self-join, which never reaches the host -- buffers of their own,
     // for the same reason (the join inside a cluster call uses every buffer above freely)
@@ -3216,6 +3220,183 @@ int strsim_qgram_cluster_host(strsim_ctx_t *c, int kind, uint32_t q, uint32_t qf
     rc = cluster_labels(c, "strsim_qgram_cluster_host", qgram_cluster_self_join(c, "strsim_qgram_cluster_host", kind, q, qflags), s.a, min_score,
                         reinterpret_cast<uint32_t *>(s.out), out_cluster ? reinterpret_cast<uint32_t *>(s.out + up256((size_t)rows * 4)) : nullptr,
                         out_count, out_nnz);
+    if (rc) return rc;
+    return labels_to_host(c, rows, s.out, out_root, out_cluster);
+}
+
+} // extern "C"
+
+// ---- join and cluster by integer edit distance (strsim_distance_join.h, strsim_distance_join_kernels.h): join_pairs with a fourth sweep ----
+
+static int edit_kind_check(const char *who, int kind)
+{
+    if (kind < STRSIM_EDIT_LEVENSHTEIN || kind > STRSIM_EDIT_DAMERAU) {
+        set_error("%s: unknown kind %d (STRSIM_EDIT_LEVENSHTEIN, _OSA or _DAMERAU: 0..2)", who, kind);
+        return STRSIM_ERR_ARG;
+    }
+    return STRSIM_OK;
+}
+
+static int distance_join_check(const char *who, strsim_ctx_t *c, int kind, const Col &qc, const Col &cnd, uint32_t flags, uint64_t capacity,
+                               const uint64_t *out_indptr, const uint32_t *out_index, const uint32_t *out_distance, const uint64_t *out_nnz)
+{
+    const int rc = edit_kind_check(who, kind);
+    if (rc) return rc;
+    // (an integer cutoff is never NaN; the distances stand where the scores stand, looked at for NULL only)
+    return join_rest_check("max_distance", who, c, qc, cnd, 0.0, flags, capacity, out_indptr, out_index,
+                           reinterpret_cast<const double *>(out_distance), out_nnz);
+}
+
+// The join by edit distance in the join's own terms, qc.rows >= 1: the hits carry -(double)d in out_score.  It enqueues what
+// strsim_match_join_device enqueues, and in the fallback one conversion behind every pairwise call.
+static int distance_join_scores(strsim_ctx *c, const char *who, int kind, const Col &qc, const Col &cnd, uint32_t k, uint32_t flags,
+                                uint64_t capacity, uint64_t *out_indptr, uint32_t *out_index, double *out_score, uint64_t *out_nnz)
+{
+    MatchJoinNeed need; // which candidate lengths a query of each length visits: 33 words, a kernel argument
+    distance_join_need_mask(k, need);
+    return join_pairs(
+        c, who, qc, cnd, distance_join_cutoff(k), flags, capacity, out_indptr, out_index, out_score, out_nnz, false,
+        [&]() -> int { return c->distance_join_col.reserve((size_t)std::max(qc.rows, cnd.rows) * sizeof(uint32_t)); },
+        [&](bool fill, const JoinLaneArgs &a) { return launch_distance_join_lane(kind, fill, a, need, k); },
+        [&](const Col &lit, const Col &other, double *to) -> int {
+            // the pairwise call under the cutoff (its length prefilter applies; k + 1 stands for every longer distance and is no
+            // hit), then the column as k_join_slow reads it.  One uint32 column serves every call: they run in stream order.
+            // (strsim_ctx_last_wave_rows describes the caller's last pairwise call: a fallback batch leaves it alone)
+            uint32_t *const d32 = c->distance_join_col.as<uint32_t>();
+            const uint64_t wave_rows = c->last_wave_rows;
+            const int r = kind == STRSIM_EDIT_DAMERAU
+                              ? damerau_device_impl(c, lit, other, k, nullptr, d32, other.rows)
+                              : distance_device_impl(c, kind == STRSIM_EDIT_OSA ? STRSIM_OSA : STRSIM_LEVENSHTEIN, lit, other, k, d32, other.rows);
+            c->last_wave_rows = wave_rows;
+            if (r) return r;
+            HIP_TRY(launch_nearest_scores(d32, other.rows, to, c->stream));
+            c->enqueued_ops += 1u;
+            return STRSIM_OK;
+        });
+}
+
+// strsim_distance_join_device behind its check: the join into the context's f64 column, then the distances of the hits that were
+// stored.
+static int distance_join_device_impl(strsim_ctx_t *c, const char *who, int kind, const Col &qc, const Col &cnd, uint32_t k, uint32_t flags,
+                                     uint64_t capacity, uint64_t *out_indptr, uint32_t *out_index, uint32_t *out_distance, uint64_t *out_nnz)
+{
+    int rc = ctx_set_device(c);
+    if (rc) return rc;
+    if (qc.rows == 0) {
+        *out_nnz = 0;
+        HIP_TRY(hipMemsetAsync(out_indptr, 0, sizeof(uint64_t), c->stream));
+        return STRSIM_OK;
+    }
+    // (a hit is stored only when all of them fit, and there are at most q_rows * c_rows)
+    const uint64_t slots = std::min(capacity, qc.rows * cnd.rows);
+    rc = c->distance_join_score.reserve((size_t)slots * sizeof(double));
+    if (rc) return rc;
+    double *const score = slots ? c->distance_join_score.as<double>() : nullptr;
+    rc = distance_join_scores(c, who, kind, qc, cnd, k, flags, capacity, out_indptr, out_index, score, out_nnz);
+    if (rc) return rc;
+    if (*out_nnz && *out_nnz <= capacity) {
+        HIP_TRY(launch_distance_join_finish(score, *out_nnz, out_distance, c->stream));
+        c->enqueued_ops += 1u;
+    }
+    return STRSIM_OK;
+}
+
+extern "C" {
+
+int strsim_distance_join_device(strsim_ctx_t *c, int kind, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows, const uint32_t *c_off,
+                                const uint8_t *c_val, uint64_t c_rows, uint32_t max_distance, uint32_t flags, uint64_t capacity,
+                                uint64_t *out_indptr, uint32_t *out_index, uint32_t *out_distance, uint64_t *out_nnz)
+{
+    const Col qc{q_off, q_val, q_rows}, cnd{c_off, c_val, c_rows};
+    const int rc = distance_join_check("strsim_distance_join_device", c, kind, qc, cnd, flags, capacity, out_indptr, out_index, out_distance, out_nnz);
+    if (rc) return rc;
+    return distance_join_device_impl(c, "strsim_distance_join_device", kind, qc, cnd, max_distance, flags, capacity, out_indptr, out_index,
+                                     out_distance, out_nnz);
+}
+
+// (join_host with a uint32 column where its f64 column stands)
+int strsim_distance_join_host(strsim_ctx_t *c, int kind, const uint32_t *q_off, const uint8_t *q_val, uint64_t q_rows, const uint32_t *c_off,
+                              const uint8_t *c_val, uint64_t c_rows, uint32_t max_distance, uint32_t flags, uint64_t capacity,
+                              uint64_t *out_indptr, uint32_t *out_index, uint32_t *out_distance, uint64_t *out_nnz)
+{
+    const Col qc{q_off, q_val, q_rows}, cnd{c_off, c_val, c_rows};
+    int rc = distance_join_check("strsim_distance_join_host", c, kind, qc, cnd, flags, capacity, out_indptr, out_index, out_distance, out_nnz);
+    if (rc) return rc;
+    *out_nnz = 0;
+    out_indptr[0] = 0;
+    if (q_rows == 0) return STRSIM_OK;
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    const size_t ptr_bytes = up256(((size_t)q_rows + 1) * sizeof(uint64_t)), idx_bytes = up256((size_t)capacity * sizeof(uint32_t));
+    Staged s;
+    rc = ctx_stage(c, qc, cnd, ptr_bytes + 2 * idx_bytes + 256, &s);
+    if (rc) return rc;
+    uint64_t *const d_ptr = reinterpret_cast<uint64_t *>(s.out);
+    uint32_t *const d_idx = capacity ? reinterpret_cast<uint32_t *>(s.out + ptr_bytes) : nullptr;
+    uint32_t *const d_dist = capacity ? reinterpret_cast<uint32_t *>(s.out + ptr_bytes + idx_bytes) : nullptr;
+    rc = distance_join_device_impl(c, "strsim_distance_join_host", kind, Col{s.a.off, s.a.val, q_rows}, Col{s.b.off, s.b.val, c_rows}, max_distance,
+                                   flags, capacity, d_ptr, d_idx, d_dist, out_nnz);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out_indptr, d_ptr, ((size_t)q_rows + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (*out_nnz && *out_nnz <= capacity) {
+        HIP_TRY(hipMemcpyAsync(out_index, d_idx, (size_t)*out_nnz * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(out_distance, d_dist, (size_t)*out_nnz * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    return strsim_ctx_synchronize(c);
+}
+
+} // extern "C"
+
+static int distance_cluster_check(const char *who, strsim_ctx_t *c, int kind, const Col &col, const uint32_t *out_root, const uint64_t *out_count)
+{
+    const int rc = edit_kind_check(who, kind);
+    if (rc) return rc;
+    return cluster_rest_check(who, c, col, 0.0, out_root, out_count);
+}
+
+// The self-join of strsim_distance_cluster_*: the join by edit distance of one column under STRSIM_JOIN_UPPER, kind and cutoff
+// bound.  cluster_labels reads the CSR alone, so the f64 column of its buffer is never turned into distances.
+static auto distance_cluster_self_join(strsim_ctx *c, const char *who, int kind, uint32_t k)
+{
+    return [=](const Col &col, double, uint64_t cap, uint64_t *indptr, uint32_t *index, double *score, uint64_t *nnz) {
+        return distance_join_scores(c, who, kind, col, col, k, STRSIM_JOIN_UPPER, cap, indptr, index, score, nnz);
+    };
+}
+
+extern "C" {
+
+int strsim_distance_cluster_device(strsim_ctx_t *c, int kind, const uint32_t *offsets, const uint8_t *values, uint64_t rows, uint32_t max_distance,
+                                   uint32_t *out_root, uint32_t *out_cluster, uint64_t *out_count, uint64_t *out_nnz)
+{
+    const Col col{offsets, values, rows};
+    int rc = distance_cluster_check("strsim_distance_cluster_device", c, kind, col, out_root, out_count);
+    if (rc) return rc;
+    *out_count = 0;
+    if (out_nnz) *out_nnz = 0;
+    if (rows == 0) return STRSIM_OK;
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    return cluster_labels(c, "strsim_distance_cluster_device", distance_cluster_self_join(c, "strsim_distance_cluster_device", kind, max_distance),
+                          col, distance_join_cutoff(max_distance), out_root, out_cluster, out_count, out_nnz);
+}
+
+int strsim_distance_cluster_host(strsim_ctx_t *c, int kind, const uint32_t *offsets, const uint8_t *values, uint64_t rows, uint32_t max_distance,
+                                 uint32_t *out_root, uint32_t *out_cluster, uint64_t *out_count, uint64_t *out_nnz)
+{
+    const Col col{offsets, values, rows};
+    int rc = distance_cluster_check("strsim_distance_cluster_host", c, kind, col, out_root, out_count);
+    if (rc) return rc;
+    *out_count = 0;
+    if (out_nnz) *out_nnz = 0;
+    if (rows == 0) return STRSIM_OK;
+    rc = ctx_set_device(c);
+    if (rc) return rc;
+    Staged s;
+    rc = ctx_stage(c, col, NO_COL, 2 * up256((size_t)rows * 4), &s);
+    if (rc) return rc;
+    rc = cluster_labels(c, "strsim_distance_cluster_host", distance_cluster_self_join(c, "strsim_distance_cluster_host", kind, max_distance), s.a,
+                        distance_join_cutoff(max_distance), reinterpret_cast<uint32_t *>(s.out),
+                        out_cluster ? reinterpret_cast<uint32_t *>(s.out + up256((size_t)rows * 4)) : nullptr, out_count, out_nnz);
     if (rc) return rc;
     return labels_to_host(c, rows, s.out, out_root, out_cluster);
 }

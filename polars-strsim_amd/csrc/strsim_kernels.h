@@ -296,6 +296,12 @@ hipError_t launch_qgram_join_first(uint32_t q, const JoinLaneArgs &a, uint32_t n
 hipError_t launch_qgram_join_lane(int kind, uint32_t q, bool set, bool fill, const JoinLaneArgs &a, const uint32_t *first, const MatchJoinNeed &need,
                                   double min_score);
 
+// Join by integer edit distance (strsim_distance_join_kernels.h; the rules are in strsim_distance_join.h): the sweep that stands
+// where launch_join_lane stands.  kind: EDIT_LEVENSHTEIN, EDIT_OSA or EDIT_DAMERAU; need: |lq - lc| <= max_distance.  The hits carry
+// -(double)d in a.out_score; launch_distance_join_finish turns n of them into the uint32 distances.
+hipError_t launch_distance_join_lane(int kind, bool fill, const JoinLaneArgs &a, const MatchJoinNeed &need, uint32_t max_distance);
+hipError_t launch_distance_join_finish(const double *score, uint64_t n, uint32_t *dist, hipStream_t stream);
+
 // Connected components of a CSR graph (strsim_components_kernels.h; the rules are in strsim_components.h).
 // launch_components_identity: the labels of a graph without edges, one launch.  launch_components: init, link, compress, the join's
 // three scan kernels over the root flags and the rank -- seven launches whatever the graph holds.  parent: rows words; scan: rows

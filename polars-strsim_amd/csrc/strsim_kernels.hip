@@ -55,6 +55,9 @@
 //                     staged per wave in a tile of LDS and written out row-wise; k_cdist_put_col / k_cdist_cutoff close its fallback.
 //   k_qgram_join_lane<Q, SET, FILL>  the threshold join by q-gram similarity (strsim_qgram_join.h, strsim_qgram_join_kernels.h): the
 //                     join's lane sweep with the q-gram gram masks as its scoring call, the candidate as the wave-uniform text.
+//   k_distance_join_lane<KIND, FILL>  the join by integer edit distance (strsim_distance_join.h, strsim_distance_join_kernels.h): the
+//                     join's lane sweep with the Levenshtein / OSA column as its scoring call; Damerau-Levenshtein filters by the
+//                     OSA distance and runs dl_lane_core for the wave when a lane is left undecided.
 //   k_huge_pairs<M>   strings beyond WAVE_CAP, scratch in global memory, launched from strsim_ctx_synchronize() only
 //                     when such rows were counted; Levenshtein: the block step in stripes of 64 blocks, any length.
 //
@@ -89,6 +92,7 @@
 #include "strsim_join.h"
 #include "strsim_match_join.h"
 #include "strsim_qgram_join.h"
+#include "strsim_distance_join.h"
 #include "strsim_components.h"
 
 namespace strsim {
@@ -108,6 +112,7 @@ struct OutPtrs {
 #include "strsim_join_kernels.h"
 #include "strsim_match_join_kernels.h"
 #include "strsim_qgram_join_kernels.h"
+#include "strsim_distance_join_kernels.h"
 #include "strsim_components_kernels.h"
 
 #include "strsim_kernel_wide.h"
@@ -838,6 +843,36 @@ hipError_t launch_qgram_join_lane(int kind, uint32_t q, bool set, bool fill, con
                                first, need, min_score, a.upper, a.cnt, a.map, a.map_words, a.map_shift, a.indptr, a.out_index, a.out_score);
         });
     });
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// join by integer edit distance (strsim_distance_join_kernels.h)
+// ------------------------------------------------------------------------------------------------
+template <int KIND>
+static void launch_distance_join_lane_k(bool fill, const JoinLaneArgs &a, const MatchJoinNeed &need, uint32_t max_distance)
+{
+    with_fill(fill, [&](auto FILL) {
+        hipLaunchKernelGGL((k_distance_join_lane<KIND, decltype(FILL)::value>), dim3(match_grid(a.nq), a.splits), dim3(MATCH_BLOCK), 0, a.stream,
+                           a.qwords, a.qmeta, a.qperm, a.qstart, a.nq, a.swords, a.smeta, a.sidx, a.cstart, need, max_distance, a.upper, a.cnt, a.map,
+                           a.map_words, a.map_shift, a.indptr, a.out_index, a.out_score);
+    });
+}
+
+hipError_t launch_distance_join_lane(int kind, bool fill, const JoinLaneArgs &a, const MatchJoinNeed &need, uint32_t max_distance)
+{
+    switch (kind) {
+    case EDIT_LEVENSHTEIN: launch_distance_join_lane_k<EDIT_LEVENSHTEIN>(fill, a, need, max_distance); break;
+    case EDIT_OSA: launch_distance_join_lane_k<EDIT_OSA>(fill, a, need, max_distance); break;
+    default: launch_distance_join_lane_k<EDIT_DAMERAU>(fill, a, need, max_distance); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_distance_join_finish(const double *score, uint64_t n, uint32_t *dist, hipStream_t stream)
+{
+    if (n == 0u) return hipSuccess;
+    hipLaunchKernelGGL(k_distance_join_finish, dim3(match_grid(n)), dim3(MATCH_BLOCK), 0, stream, score, n, dist);
     return hipGetLastError();
 }
 

@@ -524,3 +524,50 @@ def qgram_cluster(expr: IntoExpr, kind: str = "sorensen_dice", q: int = 2, multi
         args=[parse_into_expr(expr, dtype=pl.Utf8)] + mode + [pl.lit(min_score, dtype=pl.Float64)],
         is_elementwise=False,
     )
+
+
+# (a statement of its own again)
+__all__ += ["distance_join", "distance_cluster"]
+
+_DISTANCE_JOIN_MEASURES = ("levenshtein", "osa", "damerau_levenshtein")
+
+
+def _distance_join_measure(measure: str, max_distance) -> None:
+    """ValueError for an unknown measure or a max_distance that is not None or an int in 0 .. 2^32 - 2"""
+    if measure not in _DISTANCE_JOIN_MEASURES:
+        raise ValueError(f"unknown measure {measure!r}; expected one of {_DISTANCE_JOIN_MEASURES}")
+    if max_distance is not None and (isinstance(max_distance, bool) or not isinstance(max_distance, int) or not 0 <= max_distance < 0xFFFFFFFF):
+        raise ValueError(f"max_distance={max_distance!r} is not None or an int in 0 .. 2^32 - 2")
+
+
+def distance_join(expr: IntoExpr, candidates: IntoExpr, measure: str = "levenshtein", max_distance: int | None = None) -> pl.Expr:
+    """Every row of `candidates` (any length) within max_distance edits of the row of `expr` by `measure` ("levenshtein", "osa" or
+    "damerau_levenshtein", the unrestricted distance): a List(Struct{index: UInt32, distance: UInt32}) per row, in ascending
+    candidate index, nothing truncated; max_distance=0 lists the exact duplicates, None every candidate.  A null row gives a null
+    list, a row without a hit an empty one; null candidates are never matched.  The distance is the pairwise
+    <measure>_distance function's.  Not in the upstream polars-strsim."""
+    _distance_join_measure(measure, max_distance)
+    args = [parse_into_expr(expr, dtype=pl.Utf8), parse_into_expr(candidates, dtype=pl.Utf8)]
+    if max_distance is not None:
+        args.append(pl.lit(max_distance, dtype=pl.UInt32))
+    return register_plugin_function(
+        plugin_path=_PLUGIN_DIR,
+        function_name="distance_join_" + measure,
+        args=args,
+        is_elementwise=False,
+    )
+
+
+def distance_cluster(expr: IntoExpr, measure: str = "levenshtein", max_distance: int | None = None) -> pl.Expr:
+    """The duplicate groups of a column by edit distance: `cluster` with the rows linked that are within max_distance edits by
+    `measure` (as in `distance_join`) -- "group all spellings within 2 edits".  Every row gets the row number of the first member
+    of its group, as UInt32; groups chain, a null row gives null, max_distance is required.  Not in the upstream polars-strsim."""
+    _distance_join_measure(measure, max_distance)
+    if max_distance is None:
+        raise ValueError("distance_cluster: max_distance is required (None would put every row in one group)")
+    return register_plugin_function(
+        plugin_path=_PLUGIN_DIR,
+        function_name="distance_cluster_" + measure,
+        args=[parse_into_expr(expr, dtype=pl.Utf8), pl.lit(max_distance, dtype=pl.UInt32)],
+        is_elementwise=False,
+    )

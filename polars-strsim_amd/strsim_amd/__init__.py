@@ -8,7 +8,7 @@ validity mask), as in README.md:69-70.
 """
 import numpy as np
 
-from ._lib import PROCESSORS, QGRAM_KINDS, QGRAM_MAX_Q, qgram_args, DISTANCE_MEASURES, DISTANCE_UNBOUNDED, ENTRY_POINT_ID, EXTRA_MEASURES, INDEL_MEASURES, MEASURES, MEASURE_ID, PARTIAL_MEASURES, TOKEN_MEASURES, WEIGHTED_MEASURES, LIB_PATH, STATUS, ShapeMismatch, StrsimError, lib, processor_id
+from ._lib import EDIT_KINDS, edit_kind_id, PROCESSORS, QGRAM_KINDS, QGRAM_MAX_Q, qgram_args, DISTANCE_MEASURES, DISTANCE_UNBOUNDED, ENTRY_POINT_ID, EXTRA_MEASURES, INDEL_MEASURES, MEASURES, MEASURE_ID, PARTIAL_MEASURES, TOKEN_MEASURES, WEIGHTED_MEASURES, LIB_PATH, STATUS, ShapeMismatch, StrsimError, lib, processor_id
 from .context import Codec, Context, device_count, pack_strings, split_offsets
 
 _default_ctx = None
@@ -410,8 +410,9 @@ def join(scorer, queries, candidates, score_cutoff, upper=False, ctx=None, proce
     return _join_lists(lambda c: c.join, _JOIN_SCORER_MEASURE[scorer], queries, candidates, score_cutoff, upper, ctx, processor)
 
 
-def _join_lists(call, measure, queries, candidates, cutoff, upper, ctx, processor):
-    """join() and match_join() over Python lists: call(ctx) is the context's method; nulls, `upper` and the processor alike"""
+def _join_lists(call, measure, queries, candidates, cutoff, upper, ctx, processor, value_dtype=np.float64):
+    """join(), match_join(), qgram_join() and distance_join() over Python lists: call(ctx) is the context's method; nulls, `upper`
+    and the processor alike.  value_dtype: of the value a hit carries (the f64 score, or the uint32 distance)"""
     if processor is not None:
         processor_id(processor)
     ctx = ctx or default_context()
@@ -432,7 +433,7 @@ def _join_lists(call, measure, queries, candidates, cutoff, upper, ctx, processo
     indptr, idx, score = call(ctx)(measure, qo, qv, co, cv, cutoff, upper)
     indptr = np.asarray(indptr).astype(np.int64)
     index = pos[np.asarray(idx).astype(np.int64)] if len(idx) else np.zeros(0, dtype=np.int64)
-    score = np.asarray(score, dtype=np.float64)
+    score = np.asarray(score, dtype=value_dtype)
     keep = np.ones(index.size, dtype=bool)
     rows = np.repeat(np.arange(len(Q), dtype=np.int64), np.diff(indptr))
     if vq is not None:
@@ -520,10 +521,11 @@ def cluster(measure, column, min_score, ctx=None, processor=None):
     return _cluster_column(lambda c, o, v: c.cluster(_CLUSTER_MEASURE[measure], o, v, min_score), column, min_score, ctx, processor)
 
 
-def _cluster_column(call, column, min_score, ctx, processor):
-    """cluster() and qgram_cluster() over a Python list: call(ctx, offsets, values) is the context's method with its measure bound"""
+def _cluster_column(call, column, min_score, ctx, processor, cutoff="min_score", advice="a score in [0, 1]"):
+    """cluster(), qgram_cluster() and distance_cluster() over a Python list: call(ctx, offsets, values) is the context's method with
+    its measure bound; min_score is only looked at for None (cutoff: its name in the refusal, advice: what to pass instead)"""
     if min_score is None:
-        raise ValueError("cluster: min_score=None would put every row in one cluster; pass a score in [0, 1]")
+        raise ValueError(f"cluster: {cutoff}=None would put every row in one cluster; pass {advice}")
     if processor is not None:
         processor_id(processor)
     ctx = ctx or default_context()
@@ -550,6 +552,38 @@ def qgram_cluster(kind, column, min_score, q=2, multiset=True, ctx=None, process
     return _cluster_column(lambda c, o, v: c.qgram_cluster(kind, o, v, min_score, q=q, multiset=multiset), column, min_score, ctx, processor)
 
 
+DISTANCE_JOIN_MEASURES = EDIT_KINDS
+
+
+def distance_join(measure, queries, candidates, max_distance, upper=False, ctx=None, processor=None):
+    """Join by integer edit distance: every pair (query i, candidate j) within max_distance edits by `measure` ("levenshtein",
+    "osa" or "damerau_levenshtein": DISTANCE_JOIN_MEASURES), as CSR: (indptr int64 [N + 1], index int64 [nnz], distance uint32
+    [nnz]) -- "which rows are within 2 edits of which".  The hits of query i are index / distance[indptr[i]:indptr[i + 1]], in
+    ascending candidate position; the distance is exactly levenshtein_distance() / osa_distance() /
+    damerau_levenshtein_distance() of the pair.  max_distance=0 is the exact-duplicate join, None reports every pair.  upper, the
+    nulls and processor="default_process" are join()'s."""
+    edit_kind_id(measure)
+    call = lambda c: lambda kind, qo, qv, co, cv, k, up: c.distance_join(kind, qo, qv, co, cv, k, up)
+    return _join_lists(call, measure, queries, candidates, max_distance, upper, ctx, processor, value_dtype=np.uint32)
+
+
+def distance_dedupe_pairs(measure, column, max_distance, ctx=None, processor=None):
+    """The near-duplicates of one column by edit distance: the self-join distance_join(measure, column, column, max_distance,
+    upper=True) as COO -- (i int64 [nnz], j int64 [nnz], distance uint32 [nnz]) with i < j, ordered by i, then j."""
+    column = list(column)
+    indptr, index, dist = distance_join(measure, column, column, max_distance, upper=True, ctx=ctx, processor=processor)
+    return np.repeat(np.arange(len(column), dtype=np.int64), np.diff(indptr)), index, dist
+
+
+def distance_cluster(measure, column, max_distance, ctx=None, processor=None):
+    """The duplicate groups of one column by edit distance: cluster() with the rows linked that are within max_distance edits by
+    `measure` (DISTANCE_JOIN_MEASURES) -> (root int64 [n], cluster int64 [n], count) -- "group all spellings within 2 edits".
+    Components chain, a null row is -1 and not counted, max_distance=None is refused, processor="default_process" as in join()."""
+    edit_kind_id(measure)
+    return _cluster_column(lambda c, o, v: c.distance_cluster(measure, o, v, max_distance), column, max_distance, ctx, processor,
+                           cutoff="max_distance", advice="a number of edits")
+
+
 __all__ = ["default_process", "PROCESSORS", "best_match", "nearest", "Codec", "Context", "device_count", "pack_strings", "split_offsets", "similarity", "levenshtein", "jaro",
            "jaro_winkler", "jaccard", "sorensen_dice", "osa", "indel", "measure_supported", "distance", "levenshtein_distance", "osa_distance",
            "indel_distance", "INDEL_MEASURES", "partial_ratio", "partial_ratio_alignment", "PARTIAL_MEASURES",
@@ -558,4 +592,5 @@ __all__ = ["default_process", "PROCESSORS", "best_match", "nearest", "Codec", "C
            "DISTANCE_MEASURES", "DISTANCE_UNBOUNDED", "MEASURES", "EXTRA_MEASURES", "MEASURE_ID", "STATUS", "ShapeMismatch", "StrsimError",
            "extract", "EXTRACT_SCORERS", "cdist", "CDIST_MEASURES", "join", "dedupe_pairs", "JOIN_SCORERS",
            "match_join", "match_dedupe_pairs", "MATCH_JOIN_MEASURES", "components", "cluster", "CLUSTER_MEASURES",
-           "damerau_levenshtein", "damerau_levenshtein_distance", "qgram", "QGRAM_KINDS", "QGRAM_MAX_Q", "qgram_join", "qgram_dedupe_pairs", "qgram_cluster"]
+           "damerau_levenshtein", "damerau_levenshtein_distance", "qgram", "QGRAM_KINDS", "QGRAM_MAX_Q", "qgram_join", "qgram_dedupe_pairs", "qgram_cluster",
+           "distance_join", "distance_dedupe_pairs", "distance_cluster", "DISTANCE_JOIN_MEASURES"]

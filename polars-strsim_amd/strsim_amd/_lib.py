@@ -59,6 +59,17 @@ QGRAM_MAX_Q = 3
 QGRAM_SET = 1
 
 
+# The kinds of strsim_distance_join_* and strsim_distance_cluster_* (STRSIM_EDIT_*), in the order of their ids.
+EDIT_KINDS = ("levenshtein", "osa", "damerau_levenshtein")
+
+
+def edit_kind_id(kind):
+    """STRSIM_EDIT_* of a kind; ValueError for one that is not in EDIT_KINDS."""
+    if not isinstance(kind, str) or kind not in EDIT_KINDS:
+        raise ValueError(f"unknown edit distance {kind!r} (one of {EDIT_KINDS})")
+    return EDIT_KINDS.index(kind)
+
+
 def qgram_args(kind, q, multiset=True):
     """(kind id, q, flags) of a q-gram call; ValueError for a kind that is not one of QGRAM_KINDS or a q outside 1 .. QGRAM_MAX_Q."""
     if not isinstance(kind, str) or kind not in QGRAM_KINDS:
@@ -207,6 +218,14 @@ def lib():
         f = getattr(L, name)
         f.restype = i32
         f.argtypes = [vp, i32, C.c_uint32, C.c_uint32, vp, vp, u64, C.c_double, vp, vp, C.POINTER(u64), C.POINTER(u64)]
+    for name in ("strsim_distance_join_device", "strsim_distance_join_host"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, i32, vp, vp, u64, vp, vp, u64, C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.POINTER(u64)]
+    for name in ("strsim_distance_cluster_device", "strsim_distance_cluster_host"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, i32, vp, vp, u64, C.c_uint32, vp, vp, C.POINTER(u64), C.POINTER(u64)]
     for name in ("strsim_components_device", "strsim_components_host"):
         f = getattr(L, name)
         f.restype = i32

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import DISTANCE_UNBOUNDED, JOIN_UPPER, StrsimError, check, lib, measure_id, processor_id, qgram_args
+from ._lib import DISTANCE_UNBOUNDED, JOIN_UPPER, StrsimError, check, edit_kind_id, lib, measure_id, processor_id, qgram_args
 
 
 def split_offsets(length, n):
@@ -527,11 +527,20 @@ class Context:
         return self._join("strsim_qgram_join", qgram_args(kind, q, multiset), q_offsets, q_values, c_offsets, c_values, min_score, upper, capacity,
                           count_only)
 
-    def _join(self, entry, scorer, q_offsets, q_values, c_offsets, c_values, score_cutoff, upper, capacity, count_only):
-        """join(), match_join() and qgram_join(): the entry points `entry`_device / `entry`_host under the capacity protocol.  scorer: a
-        measure, or the (kind id, q, flags) of a q-gram call"""
+    def distance_join(self, kind, q_offsets, q_values, c_offsets, c_values, max_distance=None, upper=False, capacity=None, count_only=False):
+        """Join by integer edit distance (strsim_distance_join_host for numpy columns, strsim_distance_join_device for torch tensors
+        on this context's device): every pair (i, j) with d(i, j) <= max_distance (None: every pair) by `kind` (one of EDIT_KINDS),
+        as CSR -> (indptr [rows + 1], index [nnz], distance uint32 [nnz]; device tensors: int32); d is exactly the pairwise
+        distance call's.  `upper`, the capacity protocol and count_only are join()'s."""
+        return self._join("strsim_distance_join", (edit_kind_id(kind),), q_offsets, q_values, c_offsets, c_values, _max_distance(max_distance), upper,
+                          capacity, count_only, values="u")
+
+    def _join(self, entry, scorer, q_offsets, q_values, c_offsets, c_values, score_cutoff, upper, capacity, count_only, values="f"):
+        """join(), match_join(), qgram_join() and distance_join(): the entry points `entry`_device / `entry`_host under the capacity
+        protocol.  scorer: a measure, or the (kind id, q, flags) of a q-gram call, or the (kind id,) of a distance join, whose cutoff
+        is the integer itself and whose values are uint32 (values="u")"""
         what = scorer if isinstance(scorer, tuple) else (measure_id(scorer),)
-        cut = -np.inf if score_cutoff is None else float(score_cutoff)
+        cut = score_cutoff if values == "u" else -np.inf if score_cutoff is None else float(score_cutoff)
         flags = JOIN_UPPER if upper else 0
         nnz = C.c_uint64(0)
         device = not isinstance(q_offsets, np.ndarray) and hasattr(q_offsets, "data_ptr")
@@ -541,7 +550,7 @@ class Context:
             cols = (q_offsets.data_ptr(), q_values.data_ptr(), nq, c_offsets.data_ptr(), c_values.data_ptr(), nc)
             fn = getattr(lib(), entry + "_device")
             indptr = torch.empty(nq + 1, dtype=torch.int64, device=q_offsets.device)
-            new = lambda n, dt: torch.empty(n, dtype={"i": torch.int32, "f": torch.float64}[dt], device=q_offsets.device)
+            new = lambda n, dt: torch.empty(n, dtype={"i": torch.int32, "u": torch.int32, "f": torch.float64}[dt], device=q_offsets.device)
             ptr = lambda t: t.data_ptr()
         else:
             qo, qv, nq = _host_column(q_offsets, q_values)
@@ -550,14 +559,14 @@ class Context:
             cols = (qo.ctypes.data, qv.ctypes.data, nq, co.ctypes.data, cv.ctypes.data, nc)
             fn = getattr(lib(), entry + "_host")
             indptr = np.empty(nq + 1, dtype=np.uint64)
-            new = lambda n, dt: np.empty(n, dtype={"i": np.uint32, "f": np.float64}[dt])
+            new = lambda n, dt: np.empty(n, dtype={"i": np.uint32, "u": np.uint32, "f": np.float64}[dt])
             ptr = lambda a: a.ctypes.data
         if count_only:
             check(fn(self._h, *what, *cols, cut, flags, 0, ptr(indptr), None, None, C.byref(nnz)))
             return indptr
         cap = 4 * nq + 1024 if capacity is None else int(capacity)
         for _ in range(2):
-            index, score = new(cap, "i"), new(cap, "f")
+            index, score = new(cap, "i"), new(cap, values)
             check(fn(self._h, *what, *cols, cut, flags, cap, ptr(indptr), ptr(index) if cap else None,
                      ptr(score) if cap else None, C.byref(nnz)))
             if nnz.value <= cap:
@@ -636,6 +645,28 @@ class Context:
             check(lib().strsim_qgram_cluster_host(self._h, kid, q, flags, o.ctypes.data, v.ctypes.data, n, float(min_score),
                                                   root.ctypes.data if n else None, cluster.ctypes.data if n else None, C.byref(count),
                                                   C.byref(nnz)))
+        out = (root, cluster, int(count.value))
+        return out + (int(nnz.value),) if with_nnz else out
+
+    def distance_cluster(self, kind, offsets, values, max_distance, with_nnz=False):
+        """The duplicate groups of one column by edit distance (strsim_distance_cluster_host for numpy columns,
+        strsim_distance_cluster_device for torch tensors on this context's device): cluster() with the self-join of
+        distance_join(kind, max_distance); None is no cutoff (one cluster)."""
+        kid, k = edit_kind_id(kind), _max_distance(max_distance)
+        count, nnz = C.c_uint64(0), C.c_uint64(0)
+        if not isinstance(offsets, np.ndarray) and hasattr(offsets, "data_ptr"):
+            import torch
+            n = max(offsets.numel() - 1, 0)
+            root = torch.empty(n, dtype=torch.int32, device=offsets.device)
+            cluster = torch.empty(n, dtype=torch.int32, device=offsets.device)
+            check(lib().strsim_distance_cluster_device(self._h, kid, offsets.data_ptr(), values.data_ptr(), n, k, root.data_ptr() if n else None,
+                                                       cluster.data_ptr() if n else None, C.byref(count), C.byref(nnz)))
+        else:
+            o, v, n = _host_column(offsets, values)
+            n = max(n, 0)
+            root, cluster = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32)
+            check(lib().strsim_distance_cluster_host(self._h, kid, o.ctypes.data, v.ctypes.data, n, k, root.ctypes.data if n else None,
+                                                     cluster.ctypes.data if n else None, C.byref(count), C.byref(nnz)))
         out = (root, cluster, int(count.value))
         return out + (int(nnz.value),) if with_nnz else out
 
