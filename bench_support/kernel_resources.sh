@@ -25,8 +25,11 @@
 #                    kernels whose header it includes (their figures must not move when strsim_damerau.h changes)
 #         distance_join -- the six k_distance_join_lane kernels of strsim_distance_join_device and k_distance_join_finish, k_nearest_lane,
 #                    k_dl_lane and k_match_join_lane beside them (the same cores; the same skeleton) and the join kernels around the sweep
+#         common  -- the kernels of the Hamming / prefix / postfix / LCSseq calls (strsim_common.h), and below them the Indel and
+#                    edit-distance kernels whose headers it includes (their figures must not move when strsim_common.h changes)
 ROOT=$(cd "$(dirname "$0")/.." && pwd); OUT=${TMPDIR:-/tmp}/strsim_co; mkdir -p $OUT
 case "$1" in
+    common) FILTER='k_common_|k_indel_|k_dist_' ;;
     damerau) FILTER='k_dl_|k_dist_' ;;
     qgram) FILTER='k_qgram_|k_indel_|k_dist_' ;;
     wratio) FILTER='k_wratio_|k_take_|k_max_f64|k_token_|k_partial_|k_indel_|k_dist_' ;;

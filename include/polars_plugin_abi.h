@@ -223,6 +223,25 @@ POLARS_PLUGIN_DECLARE(default_process)
 POLARS_PLUGIN_DECLARE(damerau_levenshtein)
 POLARS_PLUGIN_DECLARE(damerau_levenshtein_distance)
 
+/* Hamming, prefix, postfix and LCSseq (not in the reference module; strsim_common_host, strsim_common_distance_host and
+ * strsim_common_count_host of strsim_amd.h; rapidfuzz.distance.{Hamming, Prefix, Postfix, LCSseq}), three functions a kind: the
+ * normalised similarity, Float64 named after input 0 like the similarities above; <kind>_distance, UInt32 with the optional
+ * max_distance input 2 of the *_distance functions above (Hamming pads: the difference of the lengths counts); <kind>_similarity,
+ * the count of common characters, UInt32, two inputs only.  Null where either input is null.  These calls bypass the small-call
+ * combiner. */
+POLARS_PLUGIN_DECLARE(hamming)
+POLARS_PLUGIN_DECLARE(hamming_distance)
+POLARS_PLUGIN_DECLARE(hamming_similarity)
+POLARS_PLUGIN_DECLARE(prefix)
+POLARS_PLUGIN_DECLARE(prefix_distance)
+POLARS_PLUGIN_DECLARE(prefix_similarity)
+POLARS_PLUGIN_DECLARE(postfix)
+POLARS_PLUGIN_DECLARE(postfix_distance)
+POLARS_PLUGIN_DECLARE(postfix_similarity)
+POLARS_PLUGIN_DECLARE(lcs_seq)
+POLARS_PLUGIN_DECLARE(lcs_seq_distance)
+POLARS_PLUGIN_DECLARE(lcs_seq_similarity)
+
 /* q-gram similarity (not in the reference; strsim_qgram_host of strsim_amd.h): Jaccard, Sorensen-Dice, overlap and cosine over the
  * q-grams of the two strings.  Inputs 0 and 1 as for the similarities (shape rule, literal broadcast, nulls); input 2 is q, a
  * length-1 non-null UInt32 series holding 1, 2 or 3 (required: without it the call fails with "q is missing: ..."); an optional

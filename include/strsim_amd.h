@@ -378,6 +378,56 @@ STRSIM_API int strsim_damerau_distance_host(strsim_ctx_t *ctx,
                                             uint32_t max_distance, uint32_t *out, uint64_t out_rows);
 
 /*
+ * Hamming, prefix, postfix and LCSseq similarity, distance and count (found by dlsym, like the distance calls: the ABI version stays
+ * 1.7, and no measure id is added).  Strings are sequences of Unicode scalar values; a NUL byte is a character like any other.  Each
+ * kind is a count c(a, b) of what the two strings share, at most min(|a|, |b|):
+ *   STRSIM_COMMON_HAMMING  positions i < min(|a|, |b|) with a_i == b_i
+ *   STRSIM_COMMON_PREFIX   length of the longest common prefix
+ *   STRSIM_COMMON_POSTFIX  length of the longest common suffix
+ *   STRSIM_COMMON_LCSSEQ   length of the longest common subsequence
+ * and the three calls derive their output from it as rapidfuzz.distance.{Hamming, Prefix, Postfix, LCSseq} do:
+ *   strsim_common_count_*     c (the similarity of rapidfuzz)
+ *   strsim_common_distance_*  d = max(|a|, |b|) - c (Hamming: mismatches plus the difference of the lengths, rapidfuzz's pad=True)
+ *                             when d <= max_distance, else max_distance + 1; STRSIM_DISTANCE_UNBOUNDED: no cutoff, 0: an equality
+ *                             test (strsim_distance_device's convention)
+ *   strsim_common_*           1.0 - d / max(|a|, |b|), and 1.0 when both are empty (STRSIM_OSA's two f64 operations)
+ * An unknown kind is STRSIM_ERR_ARG.  Shape rule, literal broadcast and out_rows as strsim_pairs_device; zero rows is a no-op.  The
+ * arguments are checked first and the context last (a NULL ctx is STRSIM_ERR_ARG too): no argument error needs a device.  For the
+ * three positional kinds, rows where both strings are ASCII and at most 32 bytes are one pair per lane, every other row one pair per
+ * wave (any length, streamed: no scratch); STRSIM_COMMON_LCSSEQ has STRSIM_INDEL's tiers (ASCII and at most 128 bytes per lane).
+ * strsim_ctx_last_wave_rows counts the rows of the wave tier when the call returns.  Every row is complete in stream order; the call
+ * waits once for the stream after its first kernel (to size the second), so everything enqueued before it has completed when it
+ * returns.  It is not a pending call of strsim_ctx_synchronize and adds nothing to strsim_ctx_last_long_rows / _last_late_rows.  Its
+ * kernels read only the bytes the offsets describe.  The host variants stage the columns (strsim_pairs_host's copy path) and are
+ * synchronous.
+ */
+enum { STRSIM_COMMON_HAMMING = 0, STRSIM_COMMON_PREFIX = 1, STRSIM_COMMON_POSTFIX = 2, STRSIM_COMMON_LCSSEQ = 3 };
+STRSIM_API int strsim_common_device(strsim_ctx_t *ctx, int kind,
+                                    const uint32_t *a_offsets, const uint8_t *a_values, uint64_t a_rows,
+                                    const uint32_t *b_offsets, const uint8_t *b_values, uint64_t b_rows,
+                                    double *out, uint64_t out_rows);
+STRSIM_API int strsim_common_host(strsim_ctx_t *ctx, int kind,
+                                  const uint32_t *a_offsets, const uint8_t *a_values, uint64_t a_rows,
+                                  const uint32_t *b_offsets, const uint8_t *b_values, uint64_t b_rows,
+                                  double *out, uint64_t out_rows);
+STRSIM_API int strsim_common_distance_device(strsim_ctx_t *ctx, int kind,
+                                             const uint32_t *a_offsets, const uint8_t *a_values, uint64_t a_rows,
+                                             const uint32_t *b_offsets, const uint8_t *b_values, uint64_t b_rows,
+                                             uint32_t max_distance, uint32_t *out, uint64_t out_rows);
+STRSIM_API int strsim_common_distance_host(strsim_ctx_t *ctx, int kind,
+                                           const uint32_t *a_offsets, const uint8_t *a_values, uint64_t a_rows,
+                                           const uint32_t *b_offsets, const uint8_t *b_values, uint64_t b_rows,
+                                           uint32_t max_distance, uint32_t *out, uint64_t out_rows);
+STRSIM_API int strsim_common_count_device(strsim_ctx_t *ctx, int kind,
+                                          const uint32_t *a_offsets, const uint8_t *a_values, uint64_t a_rows,
+                                          const uint32_t *b_offsets, const uint8_t *b_values, uint64_t b_rows,
+                                          uint32_t *out, uint64_t out_rows);
+STRSIM_API int strsim_common_count_host(strsim_ctx_t *ctx, int kind,
+                                        const uint32_t *a_offsets, const uint8_t *a_values, uint64_t a_rows,
+                                        const uint32_t *b_offsets, const uint8_t *b_values, uint64_t b_rows,
+                                        uint32_t *out, uint64_t out_rows);
+
+/*
  * Partial ratio with its alignment (found by dlsym, like the distance calls: the ABI version stays 1.7).  out_score[i] is bit for
  * bit what strsim_pairs_device(STRSIM_PARTIAL_RATIO) returns for row i.  out_span is out_rows x 4 uint32, row-major: a_start, a_end,
  * b_start, b_end -- half open, in Unicode scalar values (not bytes).  The needle (the shorter string; a when the lengths are equal,

@@ -56,8 +56,10 @@ void run_damerau_distance(SeriesExport *inputs, size_t n_inputs, SeriesExport *r
     run_distance_by(strsim_damerau_distance_host, inputs, n_inputs, ret);
 }
 
-// damerau_levenshtein: the similarity through strsim_damerau_host, one Float64 chunk named after input 0.
-void run_damerau(SeriesExport *inputs, size_t n_inputs, SeriesExport *ret)
+// A similarity that has no measure id, one Float64 chunk named after input 0.
+// host(ctx, a_off, a_val, a_rows, b_off, b_val, b_rows, out, n): the C ABI call that fills the similarities
+template <class Host>
+void run_similarity_by(Host &&host, SeriesExport *inputs, size_t n_inputs, SeriesExport *ret)
 {
     if (n_inputs != 2) fail("expected 2 input series, got " + std::to_string(n_inputs));
     const Elementwise e(inputs);
@@ -72,8 +74,7 @@ void run_damerau(SeriesExport *inputs, size_t n_inputs, SeriesExport *ret)
     if (n != 0 && !e.all_null) {
         const Packed p(e.col[0], e.col[1], false);
         PipeLease lease(p.staged_bytes() + 12 * n); // + the outputs and the work list
-        if (strsim_damerau_host(leased_context(lease), p.ao.data(), p.av.data(), p.a_rows(), p.bo.data(), p.bv.data(), p.b_rows(), out, n) !=
-            STRSIM_OK)
+        if (host(leased_context(lease), p.ao.data(), p.av.data(), p.a_rows(), p.bo.data(), p.bv.data(), p.b_rows(), out, n) != STRSIM_OK)
             fail(strsim_last_error_message());
     } else {
         for (uint64_t r = 0; r < n; ++r) out[r] = 0.0;
@@ -86,4 +87,10 @@ void run_damerau(SeriesExport *inputs, size_t n_inputs, SeriesExport *ret)
     }
     export_primitive("g", e.col[0].name.c_str(), n, out, validity, null_count, false, ret);
     cleanup.armed = false;
+}
+
+// damerau_levenshtein: the similarity through strsim_damerau_host
+void run_damerau(SeriesExport *inputs, size_t n_inputs, SeriesExport *ret)
+{
+    run_similarity_by(strsim_damerau_host, inputs, n_inputs, ret);
 }

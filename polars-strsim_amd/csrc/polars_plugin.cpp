@@ -150,6 +150,7 @@ void export_primitive(const char *format, const char *name, uint64_t n, void *da
 }
 #include "plugin_match.h"
 #include "plugin_distance.h"
+#include "plugin_common.h"
 #include "plugin_qgram.h"
 #include "plugin_partial.h"
 #include "plugin_nearest.h"
@@ -262,6 +263,12 @@ void _polars_plugin_strsim_coalesce_stats(uint64_t out[4]) { if (out) combiner()
     POLARS_PLUGIN_EXPORT(name, run(id, inputs, n_inputs, return_value, cc && (cc->bitflags & 1u)), field_entry(input_fields, n_fields, return_value))
 #define POLARS_PLUGIN_DEFINE_DISTANCE(name, id)                                                \
     POLARS_PLUGIN_EXPORT(name##_distance, run_distance(id, inputs, n_inputs, return_value), \
+                         field_named_after_input0(input_fields, n_fields, return_value, [](ArrowSchema *s, const char *n) { fill_named_schema(s, "I", n); }))
+#define POLARS_PLUGIN_DEFINE_COMMON(name, kind)                                                                                   \
+    POLARS_PLUGIN_EXPORT(name, run_common(kind, inputs, n_inputs, return_value), field_entry(input_fields, n_fields, return_value)) \
+    POLARS_PLUGIN_EXPORT(name##_distance, run_common_distance(kind, inputs, n_inputs, return_value),                             \
+                         field_named_after_input0(input_fields, n_fields, return_value, [](ArrowSchema *s, const char *n) { fill_named_schema(s, "I", n); })) \
+    POLARS_PLUGIN_EXPORT(name##_similarity, run_common_count(kind, inputs, n_inputs, return_value),                              \
                          field_named_after_input0(input_fields, n_fields, return_value, [](ArrowSchema *s, const char *n) { fill_named_schema(s, "I", n); }))
 #define POLARS_PLUGIN_DEFINE_QGRAM(name, kind) \
     POLARS_PLUGIN_EXPORT(qgram_##name, run_qgram(kind, inputs, n_inputs, return_value), field_entry(input_fields, n_fields, return_value))
@@ -577,6 +584,10 @@ POLARS_PLUGIN_DEFINE_DISTANCE(indel, STRSIM_INDEL)
 POLARS_PLUGIN_EXPORT(damerau_levenshtein, run_damerau(inputs, n_inputs, return_value), field_entry(input_fields, n_fields, return_value))
 POLARS_PLUGIN_EXPORT(damerau_levenshtein_distance, run_damerau_distance(inputs, n_inputs, return_value),
                      field_named_after_input0(input_fields, n_fields, return_value, [](ArrowSchema *s, const char *n) { fill_named_schema(s, "I", n); }))
+POLARS_PLUGIN_DEFINE_COMMON(hamming, STRSIM_COMMON_HAMMING)
+POLARS_PLUGIN_DEFINE_COMMON(prefix, STRSIM_COMMON_PREFIX)
+POLARS_PLUGIN_DEFINE_COMMON(postfix, STRSIM_COMMON_POSTFIX)
+POLARS_PLUGIN_DEFINE_COMMON(lcs_seq, STRSIM_COMMON_LCSSEQ)
 POLARS_PLUGIN_DEFINE_QGRAM(jaccard, STRSIM_QGRAM_JACCARD)
 POLARS_PLUGIN_DEFINE_QGRAM(sorensen_dice, STRSIM_QGRAM_SORENSEN_DICE)
 POLARS_PLUGIN_DEFINE_QGRAM(overlap, STRSIM_QGRAM_OVERLAP)

@@ -24,7 +24,7 @@ struct Record {
     unsigned long long lo, hi; //   the inclusive range it had to lie in
 };
 static __device__ Record g_rec; // (one per translation unit: no relocatable device code in this build)
-enum Kernel : uint32_t { K_STAGE = 1, K_LIT = 2, K_WIDE = 3, K_UTF8 = 4, K_WAVE = 5, K_VIEWS = 6, K_DAMERAU = 7 };
+enum Kernel : uint32_t { K_STAGE = 1, K_LIT = 2, K_WIDE = 3, K_UTF8 = 4, K_WAVE = 5, K_VIEWS = 6, K_DAMERAU = 7, K_COMMON = 8 };
 __device__ __forceinline__ void hit(uint32_t kernel, uint32_t site, unsigned long long row, unsigned long long v, unsigned long long lo,
                                     unsigned long long hi)
 {

@@ -23,6 +23,7 @@
 #include "strsim_indel.h"
 #include "strsim_qgram.h"
 #include "strsim_damerau.h"
+#include "strsim_common.h"
 #include "strsim_partial.h"
 #include "strsim_token.h"
 #include "strsim_wratio.h"
@@ -717,22 +718,24 @@ static int dist_report(strsim_ctx *c)
 static constexpr size_t OSA_SCRATCH_BUDGET = (size_t)1 << 30; // the wave kernel runs fewer waves rather than use more scratch
 
 // Which pair of kernels a call runs, and what they take beside the LaunchArgs.
-enum TwoPassKind { TP_DIST, TP_INDEL, TP_PARTIAL, TP_QGRAM, TP_DAMERAU };
+enum TwoPassKind { TP_DIST, TP_INDEL, TP_PARTIAL, TP_QGRAM, TP_DAMERAU, TP_COMMON };
 struct TwoPassCall {
     TwoPassKind kind;
-    int measure;     // TP_DIST: STRSIM_LEVENSHTEIN or STRSIM_OSA; TP_QGRAM: the kind (STRSIM_QGRAM_*)
-    uint32_t k;      // TP_DIST, TP_INDEL, TP_DAMERAU: the cutoff (DIST_UNBOUNDED: none)
+    int measure;     // TP_DIST: STRSIM_LEVENSHTEIN or STRSIM_OSA; TP_QGRAM: the kind (STRSIM_QGRAM_*); TP_COMMON: STRSIM_COMMON_*
+    uint32_t k;      // TP_DIST, TP_INDEL, TP_DAMERAU, TP_COMMON: the cutoff (DIST_UNBOUNDED: none)
     uint32_t *out32; // TP_DIST, TP_INDEL, TP_DAMERAU: the distances, or nullptr for the similarity in la.out (TP_DIST: of STRSIM_OSA)
     uint32_t *span;  // TP_PARTIAL: the alignment, or nullptr for the score alone
     uint32_t q = 0u;     // TP_QGRAM: 1..3
     uint32_t flags = 0u; // TP_QGRAM: STRSIM_QGRAM_SET
+    int mode = 0;        // TP_COMMON: what `out` holds (a CommonOut of strsim_common.h)
+    void *out = nullptr; // TP_COMMON: the f64 similarities, the uint32 distances or the uint32 counts
 };
 static const char *const TWO_PASS_LANE[] = {"kernel launch (k_dist_lane)", "kernel launch (k_indel_lane)",
                                             "kernel launch (k_partial_lane)", "kernel launch (k_qgram_lane)",
-                                            "kernel launch (k_dl_lane)"};
+                                            "kernel launch (k_dl_lane)", "kernel launch (k_common_lane)"};
 static const char *const TWO_PASS_WAVE[] = {"kernel launch (k_dist_wave)", "kernel launch (k_indel_wave)",
                                             "kernel launch (k_partial_wave)", "kernel launch (k_qgram_wave)",
-                                            "kernel launch (k_dl_wave)"};
+                                            "kernel launch (k_dl_wave)", "kernel launch (k_common_wave)"};
 
 static hipError_t two_pass_lane(const TwoPassCall &t, const LaunchArgs &la, uint32_t *list)
 {
@@ -741,6 +744,7 @@ static hipError_t two_pass_lane(const TwoPassCall &t, const LaunchArgs &la, uint
     case TP_INDEL: return launch_indel_lane(la, t.k, t.out32, list);
     case TP_QGRAM: return launch_qgram_lane(la, t.measure, t.q, (t.flags & STRSIM_QGRAM_SET) != 0u, list);
     case TP_DAMERAU: return launch_dl_lane(la, t.k, t.out32, list);
+    case TP_COMMON: return launch_common_lane(la, t.measure, t.mode, t.k, t.out, list);
     default: return launch_partial_lane(la, t.span, list);
     }
 }
@@ -756,13 +760,16 @@ static hipError_t two_pass_wave(const TwoPassCall &t, const LaunchArgs &la, cons
     case TP_INDEL: return launch_indel_wave(la, t.k, t.out32, list, grid, scratch, words);
     case TP_QGRAM: return launch_qgram_wave(la, t.measure, t.q, (t.flags & STRSIM_QGRAM_SET) != 0u, qgram_grams_bound(st), list, grid, scratch, words);
     case TP_DAMERAU: return launch_dl_wave(la, t.k, t.out32, st.max_len, list, grid, scratch, words);
+    case TP_COMMON: return launch_common_wave(la, t.measure, t.mode, t.k, t.out, list, grid, scratch, words);
     default: return launch_partial_wave(la, t.span, list, grid, scratch, words);
     }
 }
 
 // Words of global scratch one wave needs for the work list `st` describes; 0 when LDS holds its tables.
-static uint64_t two_pass_slot_words(TwoPassKind kind, const DevStatus &st)
+static uint64_t two_pass_slot_words(TwoPassKind kind, const DevStatus &st, int measure = 0)
 {
+    if (kind == TP_COMMON) // (only LCSseq's wave kernel holds a pattern: Indel's)
+        return measure == STRSIM_COMMON_LCSSEQ && st.max_len > OSA_WAVE_LDS_CPS ? indel_wave_slot_words(st.max_len) : 0u;
     if (kind == TP_PARTIAL) { // max_len / pad1[0] bound the needles and haystacks (bytes, hence scalar values)
         // (partial_wave_words grows with both arguments: the larger of the two forms at the bounds covers every pair)
         const uint64_t w = std::max(partial_wave_words(64u, st.pad1[0]), partial_wave_words(std::max(st.max_len, 65u), st.pad1[0]));
@@ -796,7 +803,7 @@ static int two_pass(strsim_ctx *c, const LaunchArgs &la, const TwoPassCall &t, i
     int grid = c->num_cu * 16;
     if ((uint64_t)grid > rows) grid = (int)rows;
     uint32_t *scratch = nullptr;
-    const uint64_t words = two_pass_slot_words(t.kind, st);
+    const uint64_t words = two_pass_slot_words(t.kind, st, t.measure);
     if (words) {
         const size_t per = (size_t)words * sizeof(uint32_t);
         if ((size_t)grid * per > OSA_SCRATCH_BUDGET) grid = (int)std::max<size_t>(1, OSA_SCRATCH_BUDGET / per);
@@ -1932,6 +1939,98 @@ int strsim_damerau_distance_host(strsim_ctx_t *c, const uint32_t *a_off, const u
         c, damerau_check("strsim_damerau_distance_host", c, a, b, out, out_rows), a, b, out_rows, out, out_rows * 4, nullptr, 0,
         [&](const Staged &s, uint8_t *d_out, uint8_t *) { return damerau_device_impl(c, s.a, s.b, max_distance, nullptr, (uint32_t *)d_out, out_rows); },
         nothing_to_settle);
+}
+
+} // extern "C"
+
+// ---- Hamming, prefix, postfix and LCSseq (strsim_common.h) ----
+
+static int common_check(const char *who, strsim_ctx_t *c, int kind, const Col &a, const Col &b, const void *out, uint64_t out_rows)
+{
+    if (kind < STRSIM_COMMON_HAMMING || kind > STRSIM_COMMON_LCSSEQ) {
+        set_error("%s: unknown kind %d (STRSIM_COMMON_HAMMING, _PREFIX, _POSTFIX or _LCSSEQ: 0..3)", who, kind);
+        return STRSIM_ERR_ARG;
+    }
+    return elementwise_check(who, c, a.rows, b.rows, out_rows, a.off && a.val && b.off && b.val && out);
+}
+
+// k_common_lane, then k_common_wave (LCSseq: k_common_lcs_lane / _wave): `out` holds what mode says (a CommonOut).  The size of the
+// work list is what strsim_ctx_last_wave_rows reports (two_pass has waited for it).
+static int common_device_impl(strsim_ctx_t *c, int kind, int mode, const Col &a, const Col &b, uint32_t k, void *out, uint64_t n)
+{
+    int rc = dist_prepare(c, n);
+    if (rc) return rc;
+    const LaunchArgs la = two_pass_args(c, a, b, nullptr, n, c->dist_status);
+    TwoPassCall t{TP_COMMON, kind, k, nullptr, nullptr};
+    t.mode = mode;
+    t.out = out;
+    rc = two_pass(c, la, t, -1);
+    if (rc) return rc;
+    c->last_wave_rows = c->dist_status_host->wave_rows;
+    return STRSIM_OK;
+}
+
+static int common_device(const char *who, strsim_ctx_t *c, int kind, int mode, const Col &a, const Col &b, uint32_t k, void *out,
+                         uint64_t out_rows)
+{
+    int rc = common_check(who, c, kind, a, b, out, out_rows);
+    if (rc || out_rows == 0) return rc;
+    return common_device_impl(c, kind, mode, a, b, k, out, out_rows);
+}
+
+static int common_host(const char *who, strsim_ctx_t *c, int kind, int mode, const Col &a, const Col &b, uint32_t k, void *out,
+                       uint64_t out_rows)
+{
+    return elementwise_host(
+        c, common_check(who, c, kind, a, b, out, out_rows), a, b, out_rows, out, out_rows * (mode == COMMON_OUT_SIM ? 8u : 4u), nullptr, 0,
+        [&](const Staged &s, uint8_t *d_out, uint8_t *) { return common_device_impl(c, kind, mode, s.a, s.b, k, d_out, out_rows); },
+        nothing_to_settle);
+}
+
+extern "C" {
+
+int strsim_common_device(strsim_ctx_t *c, int kind, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
+                         const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t out_rows)
+{
+    return common_device("strsim_common_device", c, kind, COMMON_OUT_SIM, Col{a_off, a_val, a_rows}, Col{b_off, b_val, b_rows}, DIST_UNBOUNDED,
+                         out, out_rows);
+}
+
+int strsim_common_host(strsim_ctx_t *c, int kind, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
+                       const uint8_t *b_val, uint64_t b_rows, double *out, uint64_t out_rows)
+{
+    return common_host("strsim_common_host", c, kind, COMMON_OUT_SIM, Col{a_off, a_val, a_rows}, Col{b_off, b_val, b_rows}, DIST_UNBOUNDED, out,
+                       out_rows);
+}
+
+int strsim_common_distance_device(strsim_ctx_t *c, int kind, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
+                                  const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, uint32_t max_distance, uint32_t *out,
+                                  uint64_t out_rows)
+{
+    return common_device("strsim_common_distance_device", c, kind, COMMON_OUT_DIST, Col{a_off, a_val, a_rows}, Col{b_off, b_val, b_rows},
+                         max_distance, out, out_rows);
+}
+
+int strsim_common_distance_host(strsim_ctx_t *c, int kind, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
+                                const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, uint32_t max_distance, uint32_t *out,
+                                uint64_t out_rows)
+{
+    return common_host("strsim_common_distance_host", c, kind, COMMON_OUT_DIST, Col{a_off, a_val, a_rows}, Col{b_off, b_val, b_rows},
+                       max_distance, out, out_rows);
+}
+
+int strsim_common_count_device(strsim_ctx_t *c, int kind, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows,
+                               const uint32_t *b_off, const uint8_t *b_val, uint64_t b_rows, uint32_t *out, uint64_t out_rows)
+{
+    return common_device("strsim_common_count_device", c, kind, COMMON_OUT_COUNT, Col{a_off, a_val, a_rows}, Col{b_off, b_val, b_rows},
+                         DIST_UNBOUNDED, out, out_rows);
+}
+
+int strsim_common_count_host(strsim_ctx_t *c, int kind, const uint32_t *a_off, const uint8_t *a_val, uint64_t a_rows, const uint32_t *b_off,
+                             const uint8_t *b_val, uint64_t b_rows, uint32_t *out, uint64_t out_rows)
+{
+    return common_host("strsim_common_count_host", c, kind, COMMON_OUT_COUNT, Col{a_off, a_val, a_rows}, Col{b_off, b_val, b_rows},
+                       DIST_UNBOUNDED, out, out_rows);
 }
 
 } // extern "C"

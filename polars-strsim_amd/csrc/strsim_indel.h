@@ -192,6 +192,7 @@ __device__ __forceinline__ uint32_t indel_lane_run(const uint8_t *__restrict__ p
 // literal is the text, read through a wave-uniform address; the row is the pattern).  k: the distance cutoff (DIST_UNBOUNDED for
 // the similarity); a pair of ASCII strings whose lengths differ by more than k is k + 1 without any column.  Rows this kernel
 // cannot take are appended to `worklist` (worklist_append of strsim_wave_util.h); the status block is zeroed before the launch.
+// (k_common_lcs_lane of strsim_common.h is this kernel under another epilogue: a change of the tier selection here belongs there too.)
 template <int LIT>
 __global__ __launch_bounds__(256) void k_indel_lane(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ valA,
                                                     const uint32_t *__restrict__ offB, const uint8_t *__restrict__ valB, uint64_t n,
@@ -263,6 +264,7 @@ __device__ __forceinline__ uint32_t indel_wave_reg(const uint32_t *pat, uint32_t
 // One pair per wave (blockDim.x = 64) for the rows k_indel_lane put on the work list (st->wave_rows of them).  The shorter string
 // (in scalar values) is the pattern.  scratch: gridDim.x slots of slot_words words, for patterns of more than OSA_WAVE_LDS_CPS
 // values (nullptr when the call has none).
+// (k_common_lcs_wave of strsim_common.h is this kernel under another epilogue: a change of the forms here belongs there too.)
 __global__ __launch_bounds__(64) void k_indel_wave(const uint32_t *__restrict__ offA, const uint8_t *__restrict__ valA, uint64_t rowsA,
                                                    const uint32_t *__restrict__ offB, const uint8_t *__restrict__ valB, uint64_t rowsB,
                                                    uint32_t k, double *__restrict__ out64, uint32_t *__restrict__ out32,

@@ -152,6 +152,13 @@ hipError_t launch_dl_lane(const LaunchArgs &a, uint32_t k, uint32_t *out32, uint
 hipError_t launch_dl_wave(const LaunchArgs &a, uint32_t k, uint32_t *out32, uint64_t cols, const uint32_t *worklist, int grid, uint32_t *scratch,
                           uint64_t slot_words);
 
+// Hamming, prefix, postfix and LCSseq (strsim_common.h): the same two-kernel protocol.  kind: a CommonKind; mode: a CommonOut, which
+// says what `out` holds (f64 similarity, uint32 distance under the cutoff k, uint32 count; k is looked at for the distance alone).
+// Only COMMON_LCSSEQ's wave kernel takes scratch (slot_words = indel_wave_slot_words of a.status->max_len beyond OSA_WAVE_LDS_CPS).
+hipError_t launch_common_lane(const LaunchArgs &a, int kind, int mode, uint32_t k, void *out, uint32_t *worklist);
+hipError_t launch_common_wave(const LaunchArgs &a, int kind, int mode, uint32_t k, void *out, const uint32_t *worklist, int grid,
+                              uint32_t *scratch, uint64_t slot_words);
+
 // Token transforms (strsim_token.h), measure ids 14 and 16.  launch_token_bounds leaves a column's longest row and its first and
 // last offset in st (side 0 or 1; max_len zeroed first).  A form is a measuring pass (write = false: the bytes of row i into
 // out_off[i + 1], out_off[0] = 0, the rows the lane kernel cannot take onto `list`, counted in *count, zeroed first), then

@@ -34,6 +34,10 @@
 //   k_dl_lane / k_dl_wave  unrestricted Damerau-Levenshtein similarity and distance (strsim_damerau.h): a cell DP, not a bit-parallel
 //                     step.  One pair per lane for ASCII strings of up to 32 bytes, the column state packed into one dword a
 //                     column in LDS; one pair per wave for the rest, systolic over strips of 64 rows; in stream order.
+//   k_common_lane / k_common_wave  Hamming, prefix and postfix similarity, distance and count (strsim_common.h): one pair per lane
+//                     for ASCII strings of up to 32 bytes, a mask of the differing bytes of the two windows; one pair per wave for
+//                     the rest, streamed 64 bytes at a time.  k_common_lcs_lane / k_common_lcs_wave: LCSseq on strsim_indel.h's
+//                     bit-parallel step.  In stream order.
 //   k_partial_lane / k_partial_wave  partial ratio and its alignment (measure 10, strsim_partial.h): the best window of the longer
 //                     string against the shorter one, match masks built once per pair; ASCII strings of up to 32 bytes per lane,
 //                     the rest one pair per wave; in stream order.
@@ -83,6 +87,7 @@
 #include "strsim_partial.h"
 #include "strsim_qgram.h"
 #include "strsim_damerau.h"
+#include "strsim_common.h"
 #include "strsim_token.h"
 #include "strsim_wratio.h"
 #include "strsim_process.h"
@@ -781,6 +786,66 @@ hipError_t launch_dl_wave(const LaunchArgs &a, uint32_t k, uint32_t *out32, uint
 {
     if (out32) launch_dl_wave_as(a, k, out32, cols, worklist, grid, scratch, slot_words);
     else launch_dl_wave_as(a, k, a.out, cols, worklist, grid, scratch, slot_words);
+    return hipGetLastError();
+}
+
+// f(std::integral_constant<int, MODE>): the output of a strsim_common call
+template <class F>
+static void with_common_out(int mode, F f)
+{
+    if (mode == COMMON_OUT_SIM) f(std::integral_constant<int, COMMON_OUT_SIM>{});
+    else if (mode == COMMON_OUT_DIST) f(std::integral_constant<int, COMMON_OUT_DIST>{});
+    else f(std::integral_constant<int, COMMON_OUT_COUNT>{});
+}
+
+template <int KIND>
+static void launch_common_lane_as(const LaunchArgs &a, int mode, uint32_t k, void *out, uint32_t *worklist)
+{
+    with_common_out(mode, [&](auto OUT) {
+        with_literal(a, [&](auto LIT) {
+            hipLaunchKernelGGL((k_common_lane<KIND, decltype(LIT)::value, decltype(OUT)::value>), lane_grid(a), dim3(256), 0, a.stream, a.offA,
+                               a.valA, a.offB, a.valB, a.n, k, out, worklist, a.status);
+        });
+    });
+}
+
+template <int KIND>
+static void launch_common_wave_as(const LaunchArgs &a, int mode, uint32_t k, void *out, const uint32_t *worklist, int grid)
+{
+    with_common_out(mode, [&](auto OUT) {
+        hipLaunchKernelGGL((k_common_wave<KIND, decltype(OUT)::value>), dim3((unsigned)grid), dim3(64), 0, a.stream, a.offA, a.valA, a.rowsA,
+                           a.offB, a.valB, a.rowsB, k, out, worklist, a.status);
+    });
+}
+
+hipError_t launch_common_lane(const LaunchArgs &a, int kind, int mode, uint32_t k, void *out, uint32_t *worklist)
+{
+    if (mode != COMMON_OUT_DIST) k = DIST_UNBOUNDED;
+    switch (kind) {
+    case COMMON_HAMMING: launch_common_lane_as<COMMON_HAMMING>(a, mode, k, out, worklist); break;
+    case COMMON_PREFIX: launch_common_lane_as<COMMON_PREFIX>(a, mode, k, out, worklist); break;
+    case COMMON_POSTFIX: launch_common_lane_as<COMMON_POSTFIX>(a, mode, k, out, worklist); break;
+    default:
+        with_literal(a, [&](auto LIT) {
+            hipLaunchKernelGGL(k_common_lcs_lane<decltype(LIT)::value>, lane_grid(a), dim3(256), 0, a.stream, a.offA, a.valA, a.offB, a.valB, a.n,
+                               k, mode, out, worklist, a.status);
+        });
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_common_wave(const LaunchArgs &a, int kind, int mode, uint32_t k, void *out, const uint32_t *worklist, int grid,
+                              uint32_t *scratch, uint64_t slot_words)
+{
+    if (mode != COMMON_OUT_DIST) k = DIST_UNBOUNDED;
+    switch (kind) {
+    case COMMON_HAMMING: launch_common_wave_as<COMMON_HAMMING>(a, mode, k, out, worklist, grid); break;
+    case COMMON_PREFIX: launch_common_wave_as<COMMON_PREFIX>(a, mode, k, out, worklist, grid); break;
+    case COMMON_POSTFIX: launch_common_wave_as<COMMON_POSTFIX>(a, mode, k, out, worklist, grid); break;
+    default:
+        hipLaunchKernelGGL(k_common_lcs_wave, dim3((unsigned)grid), dim3(64), 0, a.stream, a.offA, a.valA, a.rowsA, a.offB, a.valB, a.rowsB, k,
+                           mode, out, worklist, a.status, scratch, slot_words);
+    }
     return hipGetLastError();
 }
 

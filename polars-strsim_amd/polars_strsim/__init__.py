@@ -232,6 +232,82 @@ def damerau_levenshtein_distance(expr: IntoExpr, other: IntoExpr, max_distance: 
     return _distance("damerau_levenshtein_distance", expr, other, max_distance)
 
 
+def hamming(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
+    """Normalised Hamming similarity (rapidfuzz's `Hamming.normalized_similarity`): 1 - hamming_distance / max(len) over
+    characters, 1.0 when both strings are empty.  Strings of different lengths are padded: the difference of the lengths counts
+    as mismatches.  To have nulls there instead, compose:
+    `pl.when(a.str.len_chars() == b.str.len_chars()).then(hamming(a, b))`.  Not in the upstream polars-strsim."""
+    return _similarity("hamming", expr, other)
+
+
+def hamming_distance(expr: IntoExpr, other: IntoExpr, max_distance: int | None = None) -> pl.Expr:
+    """Hamming distance as UInt32 (strsim's `hamming`, DuckDB's `hamming` / `mismatches`): the positions at which the two strings
+    differ, over characters, plus the difference of their lengths (rapidfuzz's pad=True).  For equal lengths only:
+    `pl.when(a.str.len_chars() == b.str.len_chars()).then(hamming_distance(a, b))`.  max_distance as in levenshtein_distance.
+    Not in the upstream polars-strsim."""
+    return _distance("hamming_distance", expr, other, max_distance)
+
+
+def hamming_similarity(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
+    """The positions at which the two strings agree, as UInt32 (rapidfuzz's `Hamming.similarity`).  Not in the upstream polars-strsim."""
+    return _distance("hamming_similarity", expr, other, None)
+
+
+def lcs_seq(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
+    """Normalised LCSseq similarity (rapidfuzz's `LCSseq.normalized_similarity`): the length of the longest common subsequence over
+    characters, divided by max(len); 1.0 when both strings are empty.  Not `indel`, which divides twice that length by the sum of
+    the lengths.  Not in the upstream polars-strsim."""
+    return _similarity("lcs_seq", expr, other)
+
+
+def lcs_seq_distance(expr: IntoExpr, other: IntoExpr, max_distance: int | None = None) -> pl.Expr:
+    """max(len) minus the length of the longest common subsequence, as UInt32 (rapidfuzz's `LCSseq.distance`).  max_distance as in
+    levenshtein_distance.  Not in the upstream polars-strsim."""
+    return _distance("lcs_seq_distance", expr, other, max_distance)
+
+
+def lcs_seq_similarity(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
+    """The length of the longest common subsequence over characters, as UInt32 (rapidfuzz's `LCSseq.similarity`).  Not in the
+    upstream polars-strsim."""
+    return _distance("lcs_seq_similarity", expr, other, None)
+
+
+def prefix(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
+    """Normalised common-prefix similarity (rapidfuzz's `Prefix.normalized_similarity`): the length of the longest common prefix
+    over characters, divided by max(len); 1.0 when both strings are empty.  Not in the upstream polars-strsim."""
+    return _similarity("prefix", expr, other)
+
+
+def prefix_distance(expr: IntoExpr, other: IntoExpr, max_distance: int | None = None) -> pl.Expr:
+    """max(len) minus the length of the longest common prefix, as UInt32 (rapidfuzz's `Prefix.distance`).  max_distance as in
+    levenshtein_distance.  Not in the upstream polars-strsim."""
+    return _distance("prefix_distance", expr, other, max_distance)
+
+
+def prefix_similarity(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
+    """The length of the longest common prefix over characters, as UInt32 (rapidfuzz's `Prefix.similarity`).  Not in the upstream
+    polars-strsim."""
+    return _distance("prefix_similarity", expr, other, None)
+
+
+def postfix(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
+    """Normalised common-suffix similarity (rapidfuzz's `Postfix.normalized_similarity`): the length of the longest common suffix
+    over characters, divided by max(len); 1.0 when both strings are empty.  Not in the upstream polars-strsim."""
+    return _similarity("postfix", expr, other)
+
+
+def postfix_distance(expr: IntoExpr, other: IntoExpr, max_distance: int | None = None) -> pl.Expr:
+    """max(len) minus the length of the longest common suffix, as UInt32 (rapidfuzz's `Postfix.distance`).  max_distance as in
+    levenshtein_distance.  Not in the upstream polars-strsim."""
+    return _distance("postfix_distance", expr, other, max_distance)
+
+
+def postfix_similarity(expr: IntoExpr, other: IntoExpr) -> pl.Expr:
+    """The length of the longest common suffix over characters, as UInt32 (rapidfuzz's `Postfix.similarity`).  Not in the upstream
+    polars-strsim."""
+    return _distance("postfix_similarity", expr, other, None)
+
+
 def default_process(expr: IntoExpr) -> pl.Expr:
     """rapidfuzz `utils.default_process` on the GPU, String in and String out: every character that is neither alphanumeric nor
     "_" becomes a space, the others are lower-cased, and spaces are removed from both ends (inner runs of spaces stay:
@@ -255,6 +331,10 @@ __all__ = [
     "osa",
     "damerau_levenshtein_distance",
     "damerau_levenshtein",
+    "hamming", "hamming_distance", "hamming_similarity",
+    "lcs_seq", "lcs_seq_distance", "lcs_seq_similarity",
+    "prefix", "prefix_distance", "prefix_similarity",
+    "postfix", "postfix_distance", "postfix_similarity",
     "indel_distance",
     "indel",
     "partial_ratio",

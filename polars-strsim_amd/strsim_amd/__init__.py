@@ -8,7 +8,7 @@ validity mask), as in README.md:69-70.
 """
 import numpy as np
 
-from ._lib import EDIT_KINDS, edit_kind_id, PROCESSORS, QGRAM_KINDS, QGRAM_MAX_Q, qgram_args, DISTANCE_MEASURES, DISTANCE_UNBOUNDED, ENTRY_POINT_ID, EXTRA_MEASURES, INDEL_MEASURES, MEASURES, MEASURE_ID, PARTIAL_MEASURES, TOKEN_MEASURES, WEIGHTED_MEASURES, LIB_PATH, STATUS, ShapeMismatch, StrsimError, lib, processor_id
+from ._lib import COMMON_KINDS, common_kind_id, EDIT_KINDS, edit_kind_id, PROCESSORS, QGRAM_KINDS, QGRAM_MAX_Q, qgram_args, DISTANCE_MEASURES, DISTANCE_UNBOUNDED, ENTRY_POINT_ID, EXTRA_MEASURES, INDEL_MEASURES, MEASURES, MEASURE_ID, PARTIAL_MEASURES, TOKEN_MEASURES, WEIGHTED_MEASURES, LIB_PATH, STATUS, ShapeMismatch, StrsimError, lib, processor_id
 from .context import Codec, Context, device_count, pack_strings, split_offsets
 
 _default_ctx = None
@@ -293,6 +293,105 @@ def damerau_levenshtein_distance(a, b, max_distance=None, ctx=None):
     ctx = ctx or default_context()
     out = ctx.damerau_distance_host(ao, av, bo, bv, max_distance)
     return np.ma.MaskedArray(out, mask=_null_mask(out.size, va, vb))
+
+
+def _char_lengths(offsets, values):
+    """Unicode scalar values of every row of a packed column: the bytes that are not continuation bytes."""
+    starts = np.concatenate(([0], np.cumsum((values & 0xC0) != 0x80, dtype=np.int64)))
+    return starts[offsets[1:].astype(np.int64)] - starts[offsets[:-1].astype(np.int64)]
+
+
+def _common(kind, out, a, b, max_distance=None, pad=True, ctx=None):
+    """One of the twelve functions below: out is "similarity" (f64, NaN under nulls), "distance" or "count" (masked uint32).
+    pad=False (Hamming): rows whose character counts differ are nulls too, decided here from the inputs."""
+    common_kind_id(kind)
+    (ao, av), (bo, bv), va, vb = _damerau_columns(a, b, max_distance)
+    ctx = ctx or default_context()
+    if out == "similarity":
+        res = ctx.common_host(kind, ao, av, bo, bv)
+    elif out == "distance":
+        res = ctx.common_distance_host(kind, ao, av, bo, bv, max_distance)
+    else:
+        res = ctx.common_count_host(kind, ao, av, bo, bv)
+    mask = _null_mask(res.size, va, vb)
+    if not pad:
+        mask = mask | np.broadcast_to(_char_lengths(ao, av) != _char_lengths(bo, bv), mask.shape)
+    if out == "similarity":
+        res[mask] = np.nan
+        return res
+    return np.ma.MaskedArray(res, mask=mask)
+
+
+def hamming(a, b, pad=True, ctx=None):
+    """Normalised Hamming similarity (rapidfuzz's Hamming.normalized_similarity) of two columns / a column and a literal -> f64
+    numpy array, NaN where either input is null: 1 - hamming_distance / max(len(a), len(b)) over characters, 1.0 when both are
+    empty.  pad=True (rapidfuzz's default) counts the difference of the lengths as mismatches; with pad=False a row whose strings
+    differ in length is NaN (rapidfuzz raises there, which a column call cannot do per row)."""
+    return _common("hamming", "similarity", a, b, None, pad, ctx)
+
+
+def hamming_distance(a, b, max_distance=None, pad=True, ctx=None):
+    """Hamming distance (strsim's hamming, rapidfuzz's Hamming.distance): the positions at which the two strings differ, over
+    characters, plus the difference of their lengths -> numpy.ma.MaskedArray of uint32, masked where either input is null and,
+    with pad=False, where the lengths differ.  max_distance as for distance()."""
+    return _common("hamming", "distance", a, b, max_distance, pad, ctx)
+
+
+def hamming_similarity(a, b, pad=True, ctx=None):
+    """The positions at which the two strings agree (rapidfuzz's Hamming.similarity) -> masked uint32, as hamming_distance."""
+    return _common("hamming", "count", a, b, None, pad, ctx)
+
+
+def lcs_seq(a, b, ctx=None):
+    """Normalised LCSseq similarity (rapidfuzz's LCSseq.normalized_similarity): l / max(len(a), len(b)) written as
+    1 - (max(len) - l) / max(len), with l the length of the longest common subsequence over characters; 1.0 when both are empty.
+    Not indel(), which is 2 l / (len(a) + len(b)).  f64, NaN where either input is null."""
+    return _common("lcs_seq", "similarity", a, b, ctx=ctx)
+
+
+def lcs_seq_distance(a, b, max_distance=None, ctx=None):
+    """max(len(a), len(b)) minus the length of the longest common subsequence (rapidfuzz's LCSseq.distance) -> masked uint32.
+    max_distance as for distance().  hamming_distance >= levenshtein_distance >= this, row by row."""
+    return _common("lcs_seq", "distance", a, b, max_distance, ctx=ctx)
+
+
+def lcs_seq_similarity(a, b, ctx=None):
+    """The length of the longest common subsequence over characters (rapidfuzz's LCSseq.similarity) -> masked uint32."""
+    return _common("lcs_seq", "count", a, b, ctx=ctx)
+
+
+def prefix(a, b, ctx=None):
+    """Normalised common-prefix similarity (rapidfuzz's Prefix.normalized_similarity): the length of the longest common prefix
+    over characters, divided by max(len(a), len(b)); 1.0 when both are empty.  f64, NaN where either input is null."""
+    return _common("prefix", "similarity", a, b, ctx=ctx)
+
+
+def prefix_distance(a, b, max_distance=None, ctx=None):
+    """max(len(a), len(b)) minus the length of the longest common prefix (rapidfuzz's Prefix.distance) -> masked uint32.
+    max_distance as for distance()."""
+    return _common("prefix", "distance", a, b, max_distance, ctx=ctx)
+
+
+def prefix_similarity(a, b, ctx=None):
+    """The length of the longest common prefix over characters (rapidfuzz's Prefix.similarity) -> masked uint32."""
+    return _common("prefix", "count", a, b, ctx=ctx)
+
+
+def postfix(a, b, ctx=None):
+    """Normalised common-suffix similarity (rapidfuzz's Postfix.normalized_similarity): the length of the longest common suffix
+    over characters, divided by max(len(a), len(b)); 1.0 when both are empty.  f64, NaN where either input is null."""
+    return _common("postfix", "similarity", a, b, ctx=ctx)
+
+
+def postfix_distance(a, b, max_distance=None, ctx=None):
+    """max(len(a), len(b)) minus the length of the longest common suffix (rapidfuzz's Postfix.distance) -> masked uint32.
+    max_distance as for distance()."""
+    return _common("postfix", "distance", a, b, max_distance, ctx=ctx)
+
+
+def postfix_similarity(a, b, ctx=None):
+    """The length of the longest common suffix over characters (rapidfuzz's Postfix.similarity) -> masked uint32."""
+    return _common("postfix", "count", a, b, ctx=ctx)
 
 
 def best_match(measure, queries, candidates, k=1, min_score=None, ctx=None):
@@ -592,5 +691,7 @@ __all__ = ["default_process", "PROCESSORS", "best_match", "nearest", "Codec", "C
            "DISTANCE_MEASURES", "DISTANCE_UNBOUNDED", "MEASURES", "EXTRA_MEASURES", "MEASURE_ID", "STATUS", "ShapeMismatch", "StrsimError",
            "extract", "EXTRACT_SCORERS", "cdist", "CDIST_MEASURES", "join", "dedupe_pairs", "JOIN_SCORERS",
            "match_join", "match_dedupe_pairs", "MATCH_JOIN_MEASURES", "components", "cluster", "CLUSTER_MEASURES",
+           "COMMON_KINDS", "hamming", "hamming_distance", "hamming_similarity", "lcs_seq", "lcs_seq_distance", "lcs_seq_similarity",
+           "prefix", "prefix_distance", "prefix_similarity", "postfix", "postfix_distance", "postfix_similarity",
            "damerau_levenshtein", "damerau_levenshtein_distance", "qgram", "QGRAM_KINDS", "QGRAM_MAX_Q", "qgram_join", "qgram_dedupe_pairs", "qgram_cluster",
            "distance_join", "distance_dedupe_pairs", "distance_cluster", "DISTANCE_JOIN_MEASURES"]

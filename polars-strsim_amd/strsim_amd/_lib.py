@@ -70,6 +70,17 @@ def edit_kind_id(kind):
     return EDIT_KINDS.index(kind)
 
 
+# The kinds of strsim_common_* (STRSIM_COMMON_*), in the order of their ids.
+COMMON_KINDS = ("hamming", "prefix", "postfix", "lcs_seq")
+
+
+def common_kind_id(kind):
+    """STRSIM_COMMON_* of a kind; ValueError for one that is not in COMMON_KINDS."""
+    if not isinstance(kind, str) or kind not in COMMON_KINDS:
+        raise ValueError(f"unknown kind {kind!r} (one of {COMMON_KINDS})")
+    return COMMON_KINDS.index(kind)
+
+
 def qgram_args(kind, q, multiset=True):
     """(kind id, q, flags) of a q-gram call; ValueError for a kind that is not one of QGRAM_KINDS or a q outside 1 .. QGRAM_MAX_Q."""
     if not isinstance(kind, str) or kind not in QGRAM_KINDS:
@@ -168,6 +179,14 @@ def lib():
         f = getattr(L, name)
         f.restype = i32
         f.argtypes = [vp, vp, vp, u64, vp, vp, u64, C.c_uint32, vp, u64]
+    for name in ("strsim_common_device", "strsim_common_host", "strsim_common_count_device", "strsim_common_count_host"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, i32, vp, vp, u64, vp, vp, u64, vp, u64]
+    for name in ("strsim_common_distance_device", "strsim_common_distance_host"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, i32, vp, vp, u64, vp, vp, u64, C.c_uint32, vp, u64]
     for name in ("strsim_partial_alignment_device", "strsim_partial_alignment_host"):
         f = getattr(L, name)
         f.restype = i32

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import DISTANCE_UNBOUNDED, JOIN_UPPER, StrsimError, check, edit_kind_id, lib, measure_id, processor_id, qgram_args
+from ._lib import DISTANCE_UNBOUNDED, JOIN_UPPER, StrsimError, check, common_kind_id, edit_kind_id, lib, measure_id, processor_id, qgram_args
 
 
 def split_offsets(length, n):
@@ -252,6 +252,42 @@ class Context:
                                                    b_values.data_ptr(), rb, k, out.data_ptr(), out.numel()))
         return out
 
+    def _common_device(self, call, kind, a_offsets, a_values, b_offsets, b_values, out, dtype, *extra):
+        import torch
+        kid = common_kind_id(kind)
+        ra, rb = a_offsets.numel() - 1, b_offsets.numel() - 1
+        n = rb if ra == 1 else ra
+        _check_device_column(a_offsets, a_values)
+        _check_device_column(b_offsets, b_values)
+        if out is None:
+            out = torch.empty(n if (ra == rb or ra == 1 or rb == 1) else 0, dtype=dtype, device=a_offsets.device)
+        if dtype != torch.float64:
+            assert out.is_cuda and out.device == a_offsets.device and out.element_size() == 4 and out.is_contiguous() \
+                and not out.is_floating_point(), "out must be a contiguous 4-byte integer tensor on the inputs' device"
+        check(call(self._h, kid, a_offsets.data_ptr(), a_values.data_ptr(), ra, b_offsets.data_ptr(), b_values.data_ptr(), rb, *extra,
+                   out.data_ptr(), out.numel()))
+        return out
+
+    def common_device(self, kind, a_offsets, a_values, b_offsets, b_values, out=None):
+        """Normalised similarity of a COMMON_KINDS kind ("hamming", "prefix", "postfix", "lcs_seq"; strsim_common_device) of device
+        tensors laid out as for pairs_device -> f64 tensor: 1 - distance / max(len), 1.0 when both are empty.  Complete in stream
+        order; last_wave_rows counts the rows that took the one-pair-per-wave tier."""
+        import torch
+        return self._common_device(lib().strsim_common_device, kind, a_offsets, a_values, b_offsets, b_values, out, torch.float64)
+
+    def common_distance_device(self, kind, a_offsets, a_values, b_offsets, b_values, max_distance=None, out=None):
+        """Distance of a COMMON_KINDS kind (strsim_common_distance_device): max(len) - count, uint32 values in an int32 tensor, as
+        distance_device returns them.  max_distance=None is no cutoff, else rows beyond it hold max_distance + 1."""
+        import torch
+        k = _max_distance(max_distance)
+        return self._common_device(lib().strsim_common_distance_device, kind, a_offsets, a_values, b_offsets, b_values, out, torch.int32, k)
+
+    def common_count_device(self, kind, a_offsets, a_values, b_offsets, b_values, out=None):
+        """Count of common characters of a COMMON_KINDS kind (strsim_common_count_device; rapidfuzz's similarity) -> uint32 values
+        in an int32 tensor."""
+        import torch
+        return self._common_device(lib().strsim_common_count_device, kind, a_offsets, a_values, b_offsets, b_values, out, torch.int32)
+
     def partial_alignment_device(self, a_offsets, a_values, b_offsets, b_values, score=None, span=None):
         """Partial ratio with its alignment (strsim_partial_alignment_device) of device tensors laid out as for pairs_device ->
         (score f64 [n], span int32 [n, 4] holding uint32 a_start, a_end, b_start, b_end in characters).  Complete in stream order."""
@@ -409,6 +445,29 @@ class Context:
         check(lib().strsim_damerau_distance_host(self._h, ao.ctypes.data, av.ctypes.data, ra, bo.ctypes.data, bv.ctypes.data, rb, k,
                                                  out.ctypes.data, n))
         return out
+
+    def _common_host(self, call, kind, a_offsets, a_values, b_offsets, b_values, dtype, *extra):
+        kid = common_kind_id(kind)
+        ao, av, ra = _host_column(a_offsets, a_values)
+        bo, bv, rb = _host_column(b_offsets, b_values)
+        n = _rows_out(ra, rb)
+        out = np.empty(n, dtype=dtype)
+        check(call(self._h, kid, ao.ctypes.data, av.ctypes.data, ra, bo.ctypes.data, bv.ctypes.data, rb, *extra, out.ctypes.data, n))
+        return out
+
+    def common_host(self, kind, a_offsets, a_values, b_offsets, b_values):
+        """Synchronous normalised similarity of a COMMON_KINDS kind (strsim_common_host): numpy uint32 offsets + uint8 values in,
+        numpy f64 out."""
+        return self._common_host(lib().strsim_common_host, kind, a_offsets, a_values, b_offsets, b_values, np.float64)
+
+    def common_distance_host(self, kind, a_offsets, a_values, b_offsets, b_values, max_distance=None):
+        """Synchronous distance of a COMMON_KINDS kind (strsim_common_distance_host): numpy uint32 out."""
+        k = _max_distance(max_distance)
+        return self._common_host(lib().strsim_common_distance_host, kind, a_offsets, a_values, b_offsets, b_values, np.uint32, k)
+
+    def common_count_host(self, kind, a_offsets, a_values, b_offsets, b_values):
+        """Synchronous count of common characters of a COMMON_KINDS kind (strsim_common_count_host): numpy uint32 out."""
+        return self._common_host(lib().strsim_common_count_host, kind, a_offsets, a_values, b_offsets, b_values, np.uint32)
 
     def partial_alignment_host(self, a_offsets, a_values, b_offsets, b_values):
         """Synchronous partial ratio with its alignment (strsim_partial_alignment_host): numpy uint32 offsets + uint8 values in ->
